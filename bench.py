@@ -1,23 +1,28 @@
 """Benchmark of the hot path: images/sec end-to-end (det + cls + rec) at 960x960 on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's results when `--dump-outputs DIR` is given and
+prints the result line.  Everything else the line can carry - the single-chain roofline and kernel table, the host-input,
+two-batches-in-flight, two-workers, wait-mode, fp16 and configs[4] legs, the single-image latency, the CPU baseline and the
+neighbour re-check of an N > 1 gather - runs only with `--full` (each still switched off by its own `--no-*` option).
 
 `--gpus N` without a launcher starts the N ranks itself (before anything touches the GPU); under a launcher
 (WORLD_SIZE set) `--gpus` must equal the world size.  One rank = one process = one GPU.
 
 One step = one pass of the whole pipeline (OCRWorker::processRequest, batched) over one batch of 64
 synthetic 960x960 card images per GPU (BASELINE.json configs[1]); inputs are resident in HBM when
-the timed region starts (`value`; the same batch handed over as HOST buffers every step is `host_input`).
+the timed region starts (`value`; with `--full`, the same batch handed over as HOST buffers every step is `host_input`).
 The pipeline runs a batch as two chains on two parts of it (ocr_pipe_cfg.phases = 2, the default); the per-kernel
-`roofline` comes from a second timed region on a single-chain pipeline (phases = 1: one kernel at a time owns the
+`roofline` of `--full` comes from a second timed region on a single-chain pipeline (phases = 1: one kernel at a time owns the
 device, so a launch's HIP-event duration is that kernel's), reported with its own images/sec as `single_chain`.  det/rec weights are seeded synthetic (the reference ships none), so the
 SURVEY.md section-8d protocol applies: the det network runs in full and is timed, while
 thresholding/box extraction/recognition consume a synthetic probability map rendered from the same
 text-line layout so that box counts and rec batch shapes are controlled.  cls uses the real weights.
 Whole images are sharded over ranks (image i -> rank i mod N, gpu_worker_pool.cpp:46-59); there is no
 data-path collective (weak scaling).  After the timed region every rank's results travel to all ranks as
-fixed-size records in ONE all_gather (RCCL over xGMI) and each rank re-computes a few images of its
+fixed-size records in ONE all_gather (RCCL over xGMI); with `--full` each rank re-computes a few images of its
 neighbour's shard to check the gathered records against what a single rank produces for the same seeds.
 """
 import argparse
@@ -424,21 +429,61 @@ def parse_args(argv=None):
                          "sharded i mod N, host inputs through the double-buffered staging)")
     ap.add_argument("--images", type=int, default=0, help="cfg3: images per GPU (default 512); cfg4: stream length (default 10000)")
     ap.add_argument("--precision", choices=["fp32", "fp16"], default="fp32",
-                    help="the stages' precision parameter for EVERY leg of this run (exploration; the default line measures fp32 and "
-                         "reports the opt-in fp16 mode under its own key)")
-    ap.add_argument("--no-fp16", action="store_true", help="skip the fp16 leg of the default line")
+                    help="the stages' precision parameter for EVERY leg of this run (exploration; the default line measures fp32, and "
+                         "with --full reports the opt-in fp16 mode under its own key)")
+    ap.add_argument("--no-fp16", action="store_true", help="skip the fp16 leg of the --full line")
     ap.add_argument("--no-cfg5", action="store_true", help="skip the BASELINE configs[4] leg (server det + SVTR-large rec, fp16, batch 32; NOT a "
-                                                            "reference artifact) that the default line carries as an extra key")
+                                                            "reference artifact) that the --full line carries as an extra key")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-request latency calls (profiling runs)")
     ap.add_argument("--no-host-input", action="store_true", help="skip the host-input (PCIe-inclusive) leg")
     ap.add_argument("--no-two-workers", action="store_true", help="skip the two-workers-per-GPU leg")
     ap.add_argument("--verify-images", type=int, default=4,
-                    help="images of the neighbour rank's shard each rank re-computes to check the gathered records")
+                    help="images of the neighbour rank's shard each rank re-computes to check the gathered records (--full)")
     ap.add_argument("--stub-pipeline", action="store_true",
                     help="CPU rehearsal of launcher + sharding + gather with a stub pipeline and gloo (no measurement)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra leg of the line (roofline and kernel table, host input, two batches in flight, two "
+                         "workers, wait modes, fp16, configs[4], single-image latency, CPU baseline, the N > 1 neighbour re-check); "
+                         "a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the words of the last step (rank 0) as DIR/<name>.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_words(out_dir, words):
+    """--dump-outputs: the words of one step (per image a list of {box, ids, confidence}) as float32 arrays - boxes and ids are
+    small integers and confidences f32 values, all exact in float32.  One row per word in image order: word_image (its image),
+    word_box (4 x 2 corners), word_confidence, word_ids (the id sequence, -1 after its end); words_per_image per image.  Should
+    the arrays pass 64 MB, a fixed seeded sample of the words is written (its rows in order, word_index = their positions)."""
+    flat = [(i, w) for i, ws in enumerate(words) for w in ws]
+    maxlen = max([len(w["ids"]) for _, w in flat] + [1])
+    keep = np.arange(len(flat))
+    per_word = 4 * (1 + 8 + 1 + 1 + maxlen)
+    if len(flat) * per_word > DUMP_CAP_BYTES - 4 * len(words):
+        keep = np.sort(np.random.RandomState(0).choice(len(flat), (DUMP_CAP_BYTES - 4 * len(words)) // per_word, replace=False))
+    ids = np.full((len(keep), maxlen), -1, np.float32)
+    for r, k in enumerate(keep):
+        ids[r, :len(flat[k][1]["ids"])] = flat[k][1]["ids"]
+    arrays = {"words_per_image": np.array([len(ws) for ws in words], np.float32),
+              "word_image": np.array([flat[k][0] for k in keep], np.float32),
+              "word_box": np.array([flat[k][1]["box"] for k in keep], np.float32).reshape(len(keep), 4, 2),
+              "word_confidence": np.array([flat[k][1]["confidence"] for k in keep], np.float32),
+              "word_ids": ids}
+    if len(keep) < len(flat):
+        arrays["word_index"] = keep.astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def under_profiler():
@@ -558,8 +603,29 @@ def cfg5_line(args):
     elapsed = time.perf_counter() - t0
     cpu_s = time.process_time() - cpu0
     stage_ms = list(pipe.times)
+    if args.dump_outputs:
+        # the same call on the same resident batch and handle as the last timed step (the pipeline is deterministic), collected
+        dump_words(args.dump_outputs, pipe.run_device(d_imgs, H, W, batch, d_probs, collect=True))
     pipe.close()
-    # ---- roofline leg: one chain, HIP events around every network launch of one step
+    line = {
+        "metric": "images/sec end-to-end (det+cls+rec) at 960x960", "value": batch * args.steps / elapsed, "unit": "images/sec",
+        "n_gpus": 1, "steps": args.steps, "warmup": max(1, args.warmup), "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f16" if precision == "fp16" else "f32", "data": "synthetic",
+        "reference_artifact": False,
+        "config": {"workload": "BASELINE configs[4]: batch=32 synthetic 960x960 images, server det (ResNet50-vd + DBFPN + DB head) + SVTR-large "
+                               "rec (48x320 lines, 6625 classes) + the reference's cls model, precision %s, 32 text lines per image, 1xMI355X; "
+                               "hand-written plans (tools/make_server_plans.py) and seeded weights - the reference ships no such graph "
+                               "(SURVEY.md section 8d cfg5); probability-map protocol of section 8d" % precision,
+                   "global_batch": batch, "parallelism": "1 GPU"},
+        "words_last_step": int(nwords), "stage_ms_last_step": dict(zip(("det", "cls", "rec"), stage_ms)),
+        "p50_step_ms": statistics.median(step_ms),
+        "host": {"cpu_s_per_step": cpu_s / args.steps, "what": "user + system CPU seconds of this process (all its threads) per timed step"},
+        "parity": "tests/test_gpu_round6.py: every plan tensor of both networks - the f32 twin of the same launch list == the oracle bit for "
+                  "bit, the f16 build within stated tolerances of the oracle; the pipeline's f16 words against the f32 twin's",
+    }
+    if not args.full:
+        return line
+    # ---- roofline leg (--full): one chain, HIP events around every network launch of one step
     pipe1 = mk(1)
     run1 = lambda: pipe1.run_device(d_imgs, H, W, batch, d_probs, collect=False)
     run1(); run1()
@@ -597,42 +663,26 @@ def cfg5_line(args):
     roof_ms = sum(max(v["flops"] / (FP16_MFMA_PEAK_TFLOPS * 1e9), v["bytes"] / (HBM_PEAK_GBS * 1e6)) for v in groups.values()) / rsteps
     table = sorted(((v["ms"] / rsteps, net + "." + key, v) for (net, key), v in groups.items()), reverse=True)[:12]
     det = per_net.get("det", {})
-    line = {
-        "metric": "images/sec end-to-end (det+cls+rec) at 960x960", "value": batch * args.steps / elapsed, "unit": "images/sec",
-        "n_gpus": 1, "steps": args.steps, "warmup": max(1, args.warmup), "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f16" if precision == "fp16" else "f32", "data": "synthetic",
-        "reference_artifact": False,
-        "config": {"workload": "BASELINE configs[4]: batch=32 synthetic 960x960 images, server det (ResNet50-vd + DBFPN + DB head) + SVTR-large "
-                               "rec (48x320 lines, 6625 classes) + the reference's cls model, precision %s, 32 text lines per image, 1xMI355X; "
-                               "hand-written plans (tools/make_server_plans.py) and seeded weights - the reference ships no such graph "
-                               "(SURVEY.md section 8d cfg5); probability-map protocol of section 8d" % precision,
-                   "global_batch": batch, "parallelism": "1 GPU"},
-        "words_last_step": int(nwords), "stage_ms_last_step": dict(zip(("det", "cls", "rec"), stage_ms)),
-        "p50_step_ms": statistics.median(step_ms),
-        "host": {"cpu_s_per_step": cpu_s / args.steps, "what": "user + system CPU seconds of this process (all its threads) per timed step"},
-        "roofline": {
-            "kernel": dnet + "." + dkey, "launches_per_step": dom["count"] // rsteps, "ms_per_launch": dom_ms, "bound": bound,
-            "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak, "traffic": cfg5_traffic(dnet + "." + dkey, dom_ms)[0],
-            "traffic_source": cfg5_traffic(dnet + "." + dkey, dom_ms)[1],
-            "arithmetic_intensity": ai,
-            "what": "the (kernel, shape) group with the most time in the step; duration = HIP events on the launch stream, one chain",
-            "det_conv_stack": {"tflops": det.get("conv_flops", 0) / max(det.get("conv_ms", 1e-9), 1e-9) / 1e9,
-                               "frac_of_f16_mfma_peak": det.get("conv_flops", 0) / max(det.get("conv_ms", 1e-9), 1e-9) / 1e9 / FP16_MFMA_PEAK_TFLOPS,
-                               "ms": det.get("conv_ms", 0), "gflop": det.get("conv_flops", 0) / 1e9,
-                               "what": "every conv / transposed conv launch of the server detector in one step (32 images)"},
-            "step": {"kernel_ms": tot["ms"], "tflop": tot["flops"] / 1e12, "gb": tot["bytes"] / 1e9,
-                     "frac_mfma": tot["flops"] / max(tot["ms"], 1e-9) / 1e9 / FP16_MFMA_PEAK_TFLOPS,
-                     "frac_hbm": tot["bytes"] / max(tot["ms"], 1e-9) / 1e6 / HBM_PEAK_GBS,
-                     "layer_roof_frac": roof_ms / max(tot["ms"], 1e-9),
-                     "what": "network launches of one step; layer_roof_frac = sum over launches of max(flops / 2.5 PF, bytes / 8 TB/s) "
-                             "over their measured time"},
-            "per_network_ms": {k: v["ms"] for k, v in per_net.items()},
-            "top_kernels": [{"kernel": n, "ms_per_step": ms, "launches": v["count"] // rsteps,
-                             "tflops": v["flops"] / max(v["ms"], 1e-9) / 1e9, "gbs": v["bytes"] / max(v["ms"], 1e-9) / 1e6} for ms, n, v in table],
-            "single_chain_images_per_s": batch * rsteps / elr,
-        },
-        "parity": "tests/test_gpu_round6.py: every plan tensor of both networks - the f32 twin of the same launch list == the oracle bit for "
-                  "bit, the f16 build within stated tolerances of the oracle; the pipeline's f16 words against the f32 twin's",
+    line["roofline"] = {
+        "kernel": dnet + "." + dkey, "launches_per_step": dom["count"] // rsteps, "ms_per_launch": dom_ms, "bound": bound,
+        "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak, "traffic": cfg5_traffic(dnet + "." + dkey, dom_ms)[0],
+        "traffic_source": cfg5_traffic(dnet + "." + dkey, dom_ms)[1],
+        "arithmetic_intensity": ai,
+        "what": "the (kernel, shape) group with the most time in the step; duration = HIP events on the launch stream, one chain",
+        "det_conv_stack": {"tflops": det.get("conv_flops", 0) / max(det.get("conv_ms", 1e-9), 1e-9) / 1e9,
+                           "frac_of_f16_mfma_peak": det.get("conv_flops", 0) / max(det.get("conv_ms", 1e-9), 1e-9) / 1e9 / FP16_MFMA_PEAK_TFLOPS,
+                           "ms": det.get("conv_ms", 0), "gflop": det.get("conv_flops", 0) / 1e9,
+                           "what": "every conv / transposed conv launch of the server detector in one step (32 images)"},
+        "step": {"kernel_ms": tot["ms"], "tflop": tot["flops"] / 1e12, "gb": tot["bytes"] / 1e9,
+                 "frac_mfma": tot["flops"] / max(tot["ms"], 1e-9) / 1e9 / FP16_MFMA_PEAK_TFLOPS,
+                 "frac_hbm": tot["bytes"] / max(tot["ms"], 1e-9) / 1e6 / HBM_PEAK_GBS,
+                 "layer_roof_frac": roof_ms / max(tot["ms"], 1e-9),
+                 "what": "network launches of one step; layer_roof_frac = sum over launches of max(flops / 2.5 PF, bytes / 8 TB/s) "
+                         "over their measured time"},
+        "per_network_ms": {k: v["ms"] for k, v in per_net.items()},
+        "top_kernels": [{"kernel": n, "ms_per_step": ms, "launches": v["count"] // rsteps,
+                         "tflops": v["flops"] / max(v["ms"], 1e-9) / 1e9, "gbs": v["bytes"] / max(v["ms"], 1e-9) / 1e6} for ms, n, v in table],
+        "single_chain_images_per_s": batch * rsteps / elr,
     }
     if not args.no_cpu_baseline:
         line["cpu_baseline"] = cfg5_cpu_baseline()
@@ -686,7 +736,7 @@ def main(argv=None):
     if cfg == "cfg2":
         batch = 8 if stub else BATCH
         seeds = shard_seeds(rank, world, batch)
-        vcount = max(0, min(args.verify_images, batch))
+        vcount = max(0, min(args.verify_images, batch)) if args.full else 0
         vseeds = shard_seeds(nb, world, batch)[:vcount]
         if stub:
             imgs, probs = stub_inputs(seeds)
@@ -701,7 +751,7 @@ def main(argv=None):
         batch = (args.images or 512) if cfg == "cfg3" else 64
         pool_n = batch if cfg == "cfg3" else 256
         seeds = shard_seeds(rank, world, pool_n)
-        vcount = max(0, min(args.verify_images, pool_n))
+        vcount = max(0, min(args.verify_images, pool_n)) if args.full else 0
         vseeds = shard_seeds(nb, world, pool_n)[:vcount]
         img_list, prob_list = make_cfg3_inputs(seeds, workers)
         vimgs, vprobs = make_cfg3_inputs(vseeds, workers) if vcount else (None, None)
@@ -774,7 +824,7 @@ def main(argv=None):
 
     for _ in range(args.warmup):
         run_step()
-    kernel_timing = not args.no_kernel_timing and not stub and cfg in ("cfg2", "cfg3")
+    kernel_timing = args.full and not args.no_kernel_timing and not stub and cfg in ("cfg2", "cfg3")
     if cfg == "cfg4" and not stub:
         for b in range(pool_n // batch):   # every composition once, untimed: the stream's steady state has seen all its shapes
             stage_batch(0, b)
@@ -806,11 +856,16 @@ def main(argv=None):
     barrier()
     elapsed = time.perf_counter() - t0
     host_cpu_s = time.process_time() - cpu_t0
+    if args.dump_outputs and rank == 0:
+        # the last timed step's words: the same call on the same inputs and handle (the pipeline is deterministic), collected -
+        # a stream (cfg4) re-runs its last batch from the slot it was staged in
+        last = pipe.run_staged((stream_batches - 1) & 1, collect=True) if cfg == "cfg4" and not stub else run_step(collect=True)
+        dump_words(args.dump_outputs, last)
     # ---- the other way of waiting for a stream (round 6): the same timed steps with the library's host threads
     # spinning in hipStreamSynchronize (what rounds 1-5 did) instead of sleeping on a blocking event (the default since) - images/s
     # and host CPU seconds per step of both modes; rank 0 of a single-GPU resident-batch run only
     wait_modes = None
-    if not stub and world == 1 and cfg in ("cfg2", "cfg3") and hasattr(pkg.lib(), "ocr_rt_set_wait_mode"):
+    if args.full and not stub and world == 1 and cfg in ("cfg2", "cfg3") and hasattr(pkg.lib(), "ocr_rt_set_wait_mode"):
         L_ = pkg.lib()
         mode0 = L_.ocr_rt_get_wait_mode()
         wait_modes = {("block" if mode0 else "spin"): {"images_per_s": batch * steps_done / elapsed, "cpu_s_per_step": host_cpu_s / max(1, steps_done)}}
@@ -891,7 +946,7 @@ def main(argv=None):
 
     # ---- host-input leg (PCIe-inclusive), rank 0 of a single-GPU run only: same batch from host memory every step
     host_in = None
-    if not stub and cfg in ("cfg2", "cfg3") and world == 1 and not args.no_host_input:
+    if args.full and not stub and cfg in ("cfg2", "cfg3") and world == 1 and not args.no_host_input:
         hsteps = max(2, args.steps)
         hel = host_input_leg(pipe, img_list, prob_list, hsteps)
         host_in = {"value": batch * hsteps / hel, "unit": "images/sec", "ms_per_step": hel * 1e3 / hsteps, "steps": hsteps,
@@ -907,7 +962,7 @@ def main(argv=None):
     in_flight = None
     # (a handle built with ONE chain - OCR_PIPE_PHASES=1 - has no second chain to name: the leg is skipped)
     one_chain = os.environ.get("OCR_PIPE_PHASES", "") == "1"
-    if not stub and cfg == "cfg2" and world == 1 and not args.no_two_workers and hasattr(pipe, "run_device_on") and not one_chain:
+    if args.full and not stub and cfg == "cfg2" and world == 1 and not args.no_two_workers and hasattr(pipe, "run_device_on") and not one_chain:
         import threading
         for c_ in (0, 1):
             pipe.run_device_on(c_, d_imgs, H, W, BATCH, d_probs, collect=False)
@@ -934,7 +989,7 @@ def main(argv=None):
     # the tail of rec) the other one's dense kernels fill the GPU.  An extra key, never `value`: the per-kernel
     # roofline figures above are measured with one worker owning the device.
     two_workers = None
-    if not stub and cfg == "cfg2" and world == 1 and not args.no_two_workers:
+    if args.full and not stub and cfg == "cfg2" and world == 1 and not args.no_two_workers:
         import threading
         pipe2 = mk_pipe()
         pipe.stage(0, img_list, prob_list)
@@ -961,39 +1016,39 @@ def main(argv=None):
 
     # ---- the opt-in fp16 mode on the same resident batch (cfg2, one GPU): an extra key
     fp16 = None
-    if not stub and cfg == "cfg2" and world == 1 and not args.no_fp16 and args.precision == "fp32":
+    if args.full and not stub and cfg == "cfg2" and world == 1 and not args.no_fp16 and args.precision == "fp32":
         ref_words = run_step(collect=True)
         fp16 = fp16_leg(mk_pipe, lambda p_: (lambda collect=False: p_.run_device(d_imgs, H, W, BATCH, d_probs, collect=collect)),
                         ref_words, batch, max(2, args.steps), sync)
 
     # ---- BASELINE configs[4] (server det + SVTR-large rec, fp16, batch 32; hand-written plans, NOT a reference artifact): an extra
-    # key of the default line, so that the driver's record holds a number measured by the driver for it; `--config cfg5` prints the
-    # full line (roofline tables, CPU baseline).  Never `value`.
+    # key of the --full line, so that one benchmark record holds a number measured for it; `--config cfg5 --full` prints the
+    # whole line (roofline tables, CPU baseline).  Never `value`.
     cfg5 = None
-    if not stub and cfg == "cfg2" and world == 1 and not args.no_cfg5 and args.precision == "fp32" and not under_profiler():
+    if args.full and not stub and cfg == "cfg2" and world == 1 and not args.no_cfg5 and args.precision == "fp32" and not under_profiler():
         try:
             import argparse as _ap
             a5 = _ap.Namespace(**vars(args))
-            a5.steps, a5.warmup, a5.no_cpu_baseline, a5.gpus = max(2, min(args.steps, 6)), 1, True, 1
+            a5.steps, a5.warmup, a5.no_cpu_baseline, a5.gpus, a5.dump_outputs = max(2, min(args.steps, 6)), 1, True, 1, None
             l5 = cfg5_line(a5)
             r5 = l5["roofline"]
             cfg5 = {"value": l5["value"], "unit": l5["unit"], "ms_per_step": l5["ms_per_step"], "steps": l5["steps"], "dtype": l5["dtype"],
                     "reference_artifact": False, "global_batch": l5["config"]["global_batch"], "workload": l5["config"]["workload"],
                     "roofline": {k: r5[k] for k in ("kernel", "ms_per_launch", "bound", "achieved", "peak", "unit", "frac", "traffic", "det_conv_stack", "step", "per_network_ms")},
                     "what": "BASELINE configs[4] on this GPU, after the headline's timed region (its own inputs, handles and timed region); "
-                            "`python bench.py --config cfg5` prints the whole line"}
+                            "`python bench.py --config cfg5 --full` prints the whole line"}
         except Exception as e:  # (the default line must not die with its extra)
             cfg5 = {"error": repr(e)[:400], "reference_artifact": False}
 
-    # ---- result gather (after the timed region): every rank's words of one step as fixed-size records
+    # ---- result gather (after the timed region, N > 1): every rank's words of one step as fixed-size records
     gather = None
-    gcap = max(GATHER_CAP, batch * 80)
-    words = run_step(collect=True)
-    recs, nrec = G.pack_records(words, seeds[:len(words)], gcap)
-    if stub and os.environ.get("OCR_BENCH_STUB_CORRUPT") == str(rank):
-        recs[0, 2] ^= 1   # rehearsal of a rank that reports a wrong box: its neighbour's check must catch it
     if dist is not None:
         import torch
+        gcap = max(GATHER_CAP, batch * 80)
+        words = run_step(collect=True)
+        recs, nrec = G.pack_records(words, seeds[:len(words)], gcap)
+        if stub and os.environ.get("OCR_BENCH_STUB_CORRUPT") == str(rank):
+            recs[0, 2] ^= 1   # rehearsal of a rank that reports a wrong box: its neighbour's check (--full) must catch it
         sync()
         g0 = time.perf_counter()
         allrec = G.gather_records(dist, recs, device)
@@ -1034,7 +1089,7 @@ def main(argv=None):
     # one request at a time (the other half of BASELINE.json's metric, "p50 ms/image"): same protocol, one
     # resident 960x960 image with its 32 lines per call, after the timed region
     single_ms = []
-    if rank == 0 and not stub and cfg == "cfg2":
+    if args.full and rank == 0 and not stub and cfg == "cfg2":
         for i in range(0 if args.no_latency else 25):
             s0 = time.perf_counter()
             pipe.run_device(d_imgs, H, W, 1, d_probs, collect=False)
@@ -1211,7 +1266,7 @@ def main(argv=None):
                        "what": "cpu_s_per_step: user + system CPU seconds of rank 0's process (the library's chain threads included) per "
                                "timed step; cpu_cores_busy = that over the wall time; threads: tasks of the process at the end of the run; "
                                "wait_modes: the same steps with the host threads blocking on an event / spinning in hipStreamSynchronize"}
-        if n_ranks == 1 and not args.no_cpu_baseline and not stub and cfg == "cfg2":
+        if args.full and n_ranks == 1 and not args.no_cpu_baseline and not stub and cfg == "cfg2":
             out["cpu_baseline"] = cpu_baseline()
         emit_line(out)
     if dist is not None:

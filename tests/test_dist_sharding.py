@@ -65,8 +65,8 @@ def _run_bench(args, env_extra=None, timeout=300):
 def test_bench_gpus_flag_starts_that_many_ranks_and_gathers_their_results():
     """`bench.py --gpus 2` with no launcher: the same spawn, sharding, max-over-ranks timing and record gather the GPU
     run uses, on two gloo ranks with the stub pipeline.  The line must report the ranks the
-    process group saw, and every rank's neighbour check of the gathered records must pass."""
-    rc, out, err = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--stub-pipeline"])
+    process group saw, and every rank's neighbour check of the gathered records (a --full leg) must pass."""
+    rc, out, err = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--stub-pipeline", "--full"])
     assert rc == 0, err[-2000:]
     assert out["n_gpus"] == 2 and out["gather"]["ranks"] == 2 and out["gather"]["backend"] == "gloo"
     assert out["gather"]["matches_single_rank"] is True and out["gather"]["verified_images_per_rank"] == 4
@@ -113,7 +113,7 @@ def bench_cpulist_ok():
 
 
 def test_bench_gather_check_catches_a_rank_that_reports_a_wrong_box():
-    rc, out, err = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--stub-pipeline"], {"OCR_BENCH_STUB_CORRUPT": "1"})
+    rc, out, err = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--stub-pipeline", "--full"], {"OCR_BENCH_STUB_CORRUPT": "1"})
     assert rc != 0 and out is not None and "error" in out and out["gather"]["matches_single_rank"] is False
 
 

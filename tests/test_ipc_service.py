@@ -6,9 +6,11 @@ import base64
 import io
 import json
 import os
+import shutil
 import socket
 import struct
 import subprocess
+import tempfile
 import time
 
 import numpy as np
@@ -46,9 +48,18 @@ class Client:
         return b
 
 
-def _start(tmp_path, gpu_workers):
+@pytest.fixture
+def sock_dir():
+    """A short directory for the service's socket: an AF_UNIX path holds at most 107 bytes, and pytest's tmp_path under a
+    deep temporary directory is longer than that."""
+    d = tempfile.mkdtemp(prefix="ocr", dir="/tmp")
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+def _start(sock_dir, gpu_workers):
     subprocess.check_call(["make", "-s", "-C", HOST])
-    sock = str(tmp_path / "ocr.sock")
+    sock = os.path.join(sock_dir, "ocr.sock")
     proc = subprocess.Popen([os.path.join(HOST, "ocr_service"), "--model-dir", os.path.join(ROOT, "models"), "--pipe-name", sock,
                              "--gpu-workers", str(gpu_workers)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     return proc, sock
@@ -138,8 +149,8 @@ def test_device_jpeg_decode_equals_host(built, card, tmp_path):
         assert np.array_equal(np.array(Image.open(dst)), want), (name, kw)
 
 
-def test_ipc_protocol_without_workers(built, card, tmp_path):
-    proc, sock = _start(tmp_path, 0)
+def test_ipc_protocol_without_workers(built, card, sock_dir):
+    proc, sock = _start(sock_dir, 0)
     try:
         c = Client(sock)
         st = c.call({"command": "status"})
@@ -181,8 +192,8 @@ def test_ipc_protocol_without_workers(built, card, tmp_path):
 
 
 @pytest.mark.gpu
-def test_ipc_recognize_matches_pipeline(pkg, built, card, tmp_path):
-    proc, sock = _start(tmp_path, 1)
+def test_ipc_recognize_matches_pipeline(pkg, built, card, tmp_path, sock_dir):
+    proc, sock = _start(sock_dir, 1)
     try:
         c = Client(sock)
         path = tmp_path / "card.png"
@@ -219,11 +230,11 @@ def test_ipc_recognize_matches_pipeline(pkg, built, card, tmp_path):
 
 
 @pytest.mark.gpu
-def test_ipc_concurrent_requests_are_batched_with_identical_results(pkg, built, card, tmp_path):
+def test_ipc_concurrent_requests_are_batched_with_identical_results(pkg, built, card, tmp_path, sock_dir):
     """Concurrent clients: the worker takes the queued requests as one pipeline run (OCRWorker::processBatch).
     Every reply must be what the request gets alone - same boxes, text and confidence bits."""
     import threading
-    proc, sock = _start(tmp_path, 1)
+    proc, sock = _start(sock_dir, 1)
     try:
         imgs = [card, np.ascontiguousarray(card[:, ::-1]), np.ascontiguousarray(card[::2, ::2]),
                 np.ascontiguousarray(card[100:700, 50:900])]

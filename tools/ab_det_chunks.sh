@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$1; mkdir -p $O
 for l in 4 8 16 32; do
-  OCR_DET_LANES=$l OCR_DET_CHUNK_MP=32 python3 $R/bench.py --config cfg3 --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-host-input > $O/cfg3_l$l.json 2> $O/cfg3_l$l.err
+  OCR_DET_LANES=$l OCR_DET_CHUNK_MP=32 python3 $R/bench.py --full --config cfg3 --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-host-input > $O/cfg3_l$l.json 2> $O/cfg3_l$l.err
   python3 - <<PY
 import json
 try:

@@ -6,14 +6,14 @@ T=${1:-r5}
 O=gpurun_out/ev_$T
 mkdir -p $O
 # (gpurun_out/ does not travel to the box: this call makes its own bench line for the duration check of pmc_traffic.py)
-python bench.py --no-cpu-baseline --no-fp16 --no-cfg5 --no-two-workers --no-host-input --no-latency > $O/bench_cfg2_prof.json 2> $O/bench_cfg2_prof.err
+python bench.py --full --no-cpu-baseline --no-fp16 --no-cfg5 --no-two-workers --no-host-input --no-latency > $O/bench_cfg2_prof.json 2> $O/bench_cfg2_prof.err
 tools/run_profile.sh $T > $O/profile.log 2>&1
 python tools/prof_summary.py gpurun_out/prof_$T > $O/prof_summary.txt 2>&1
 python tools/pmc_traffic.py gpurun_out/prof_$T $O/pmc_traffic.json $O/bench_cfg2_prof.json dw_lds_kernel,dw_conv_kernel > $O/pmc_traffic.log 2>&1
 python tools/hbm_table.py gpurun_out/prof_$T > $O/kernel_hbm_table.txt 2>&1
 cp gpurun_out/prof_$T/trace/*/*kernel_stats.csv $O/ 2>/dev/null
 # precision "fp16": its own bench line (every leg in fp16; the line's roofline is the mode's dominant kernel), then the same passes
-python bench.py --precision fp16 --no-cpu-baseline --no-two-workers --no-host-input --no-latency > $O/bench_fp16.json 2> $O/bench_fp16.err
+python bench.py --full --precision fp16 --no-cpu-baseline --no-two-workers --no-host-input --no-latency > $O/bench_fp16.json 2> $O/bench_fp16.err
 tools/run_profile.sh $T fp16 > $O/profile_fp16.log 2>&1
 python tools/pmc_traffic.py gpurun_out/prof_${T}_fp16 $O/pmc_traffic_fp16.json $O/bench_fp16.json > $O/pmc_traffic_fp16.log 2>&1
 python tools/hbm_table.py gpurun_out/prof_${T}_fp16 > $O/kernel_hbm_table_fp16.txt 2>&1

@@ -6,7 +6,7 @@ TAG=${1:-r6}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 export OCR_PIPE_PHASES=1
-B="python3 $R/bench.py --config cfg5 --steps 2 --warmup 1 --no-cpu-baseline"
+B="python3 $R/bench.py --full --config cfg5 --steps 2 --warmup 1 --no-cpu-baseline"
 O=$R/gpurun_out/prof_${TAG}_cfg5
 rm -rf $O; mkdir -p $O
 # the tile configurations are found once, un-profiled, and kept (OCR_SRV_TUNE_FILE): the profiled runs launch the networks only
