@@ -57,7 +57,8 @@ EXPORTS = [
     "ocr_net_timing", "ocr_net_timing_report", "ocr_probe", "ocr_selftest_refuse_launch", "ocr_selftest_lds_memo",
     "ocr_selftest_unclip", "ocr_selftest_unclip_box",
     "ocr_srv_net_create", "ocr_srv_net_destroy", "ocr_srv_net_forward", "ocr_srv_net_rerun", "ocr_srv_net_num_tensors", "ocr_srv_net_fetch",
-    "ocr_srv_net_timing", "ocr_srv_net_timing_report",
+    "ocr_srv_net_timing", "ocr_srv_net_timing_report", "ocr_srv_net_num_launches", "ocr_srv_net_launch_info", "ocr_srv_net_run_launches",
+    "ocr_srv_net_upload",
 ]
 
 
@@ -106,6 +107,10 @@ class SrvNet:
         L.ocr_srv_net_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
         L.ocr_srv_net_timing.argtypes = [C.c_void_p, C.c_int]
         L.ocr_srv_net_timing_report.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        L.ocr_srv_net_num_launches.argtypes = [C.c_void_p]
+        L.ocr_srv_net_launch_info.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+        L.ocr_srv_net_run_launches.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.ocr_srv_net_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         if model_dir is None:
             root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
             model_dir = os.path.join(root, "models_server", kind)
@@ -141,6 +146,25 @@ class SrvNet:
             break
         n = dims[0] * dims[1] * dims[2] * dims[3]
         return out[:n].reshape(dims[0], dims[1], dims[2], dims[3]).copy()
+
+    def launches(self):
+        """test hook: the launch list of the last forward's binding as (name, output tid, [input tids])"""
+        out = []
+        name = C.create_string_buffer(256)
+        o, n_in, ins = C.c_int(), C.c_int(), (C.c_int * 8)()
+        for i in range(lib().ocr_srv_net_num_launches(self.h)):
+            check(lib().ocr_srv_net_launch_info(self.h, i, name, len(name), C.byref(o), ins, 8, C.byref(n_in)))
+            out.append((name.value.decode(), o.value, [ins[k] for k in range(n_in.value)]))
+        return out
+
+    def run_launches(self, first, count=1):
+        """test hook: launches [first, first + count) of the last forward's binding, alone"""
+        check(lib().ocr_srv_net_run_launches(self.h, first, count))
+
+    def upload(self, tid, x):
+        """test hook: logical NHWC data into tensor `tid` (rounded to its element type, pad channels zero)"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        check(lib().ocr_srv_net_upload(self.h, tid, x.ctypes.data, x.size))
 
     def timing(self, on=True):
         check(lib().ocr_srv_net_timing(self.h, 1 if on else 0))

@@ -129,6 +129,37 @@ int ocr_srv_net_fetch(ocr_srv_net* h, int tid, float* out, size_t cap_floats, in
   return OCR_OK;
 }
 
+int ocr_srv_net_num_launches(ocr_srv_net* h) { return h ? h->net.num_launches() : 0; }
+
+int ocr_srv_net_launch_info(ocr_srv_net* h, int i, char* name, size_t name_cap, int* out_tid, int* in_tids, int in_cap, int* n_in) {
+  if (!h || !name || !out_tid || !in_tids || !n_in || name_cap == 0) return fail(OCR_ERR_ARG, "null argument");
+  std::string nm;
+  std::vector<int> ins;
+  if (!h->net.launch_info(i, nm, *out_tid, ins)) return fail(OCR_ERR_ARG, "no such launch (or no binding yet)");
+  if (nm.size() >= name_cap || (int)ins.size() > in_cap) return fail(OCR_ERR_CAPACITY, "buffer too small");
+  memcpy(name, nm.c_str(), nm.size() + 1);
+  for (size_t k = 0; k < ins.size(); ++k) in_tids[k] = ins[k];
+  *n_in = (int)ins.size();
+  return OCR_OK;
+}
+
+int ocr_srv_net_run_launches(ocr_srv_net* h, int first, int count) {
+  if (!h) return fail(OCR_ERR_ARG, "null handle");
+  CAPI_HIP(rt_set_device(h->device));
+  std::string err;
+  if (!h->net.run_launches(first, count, h->stream, err)) return fail(OCR_ERR_ARG, err);
+  CAPI_HIP(g_stream_sync(h->stream));
+  return OCR_OK;
+}
+
+int ocr_srv_net_upload(ocr_srv_net* h, int tid, const float* data, size_t count) {
+  if (!h || !data) return fail(OCR_ERR_ARG, "null argument");
+  CAPI_HIP(rt_set_device(h->device));
+  std::string err;
+  if (!h->net.upload_logical(tid, data, count, h->stream, err)) return fail(OCR_ERR_ARG, err);
+  return OCR_OK;
+}
+
 int ocr_srv_net_timing(ocr_srv_net* h, int enable) {
   if (!h) return fail(OCR_ERR_ARG, "null handle");
   h->net.enable_timing(enable != 0);

@@ -101,6 +101,8 @@ void launch_addpos(const void* x, const float* pos, void* y, long pixels, int hw
 void launch_layernorm(const void* x, const float* g, const float* b, void* y, long rows, int C, float eps, bool half, hipStream_t s);
 // SVTR mixing: qkv [N][T][3*D] (q | k | v, head-major inside each) -> out [N][T][D]; token grid gh x gw, local window lh x lw
 // (lh = 0: global).  hd must be 32.
+// which attn_h_kernel<NWV, NH> the f16 build launches for a shape: "8x2", "16x2", "8x1" or "4x1" (OCR_SRV_ATTN_PAIR=0: no pairs)
+const char* attention_variant(int T, int heads, int gh, int gw, int lh, int lw);
 bool launch_attention(const void* qkv, void* out, int N, int T, int heads, int hd, float scale, int gh, int gw, int lh, int lw, bool half,
                       hipStream_t s, std::string& err);
 // the DB head's last layer: 2x2 stride-2 transposed conv Cin -> 1 + bias + sigmoid, output the f32 probability map [N][2H][2W]

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
+#include <cstring>
 #include <string>
 
 #include "lds_attr.h"
@@ -1804,6 +1805,17 @@ __global__ void __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : 16 / NWV) attn_h_ker
   }
 }
 
+// the attn_h_kernel instantiation a shape takes: "8x2" (T = 240 pairs), "16x2" (T = 480 pairs), "8x1", "4x1" (NWV x NH)
+const char* attention_variant(int T, int heads, int gh, int gw, int lh, int lw) {
+  const size_t lds = (size_t)(T + 32) * 64 * 2;
+  if (lh <= 0) { gh = 1; gw = T; }
+  const bool pairs = lh > 0 && lw / 2 <= 8;
+  const int nq = pairs ? ((gh + 1) / 2) * ((gw + 15) / 16) : gh * ((gw + 31) / 32);
+  static const bool pair_on = [] { const char* e = getenv("OCR_SRV_ATTN_PAIR"); return !(e && e[0] == '0'); }();
+  if (pair_on && heads % 2 == 0 && 2 * lds <= 160 * 1024) return 4 * lds <= 160 * 1024 ? "8x2" : "16x2";
+  return nq >= 12 ? "8x1" : "4x1";
+}
+
 bool launch_attention(const void* qkv, void* out, int N, int T, int heads, int hd, float scale, int gh, int gw, int lh, int lw, bool half,
                       hipStream_t s, std::string& err) {
   if (hd != 32) { err = "attention: head dimension must be 32"; return false; }
@@ -1819,15 +1831,14 @@ bool launch_attention(const void* qkv, void* out, int N, int T, int heads, int h
   // a Global mixer has no use for the grid: its tokens as ONE row of T (T = 240: 8 x 8 tile pairs instead of 9 x 9 row-aligned
   // ones whose third column tile is half empty, T = 480: 15 x 15 instead of 18 x 18)
   if (lh <= 0) { gh = 1; gw = T; }
-  const bool pairs = lh > 0 && lw / 2 <= 8;  // (the kernel's query tiling)
-  const int nq = pairs ? ((gh + 1) / 2) * ((gw + 15) / 16) : gh * ((gw + 31) / 32);
   // heads in pairs (whole-line loads) where two heads' K and V fit beside another workgroup's: T = 240 (70 KB, 8 waves, two workgroups
-  // per CU) and T = 480 (131 KB: one workgroup of 16 waves); a 960-token line (123 KB per head) keeps one head per workgroup
+  // per CU) and T = 480 (131 KB: one workgroup of 16 waves); a 960-token line (123 KB per head) keeps one head per workgroup; then
+  // 8 waves where there are at least 12 query tiles (attention_variant)
   static LdsAttrMemo memo8, memo4, memo8p, memo16p;
-  static const bool pair_on = [] { const char* e = getenv("OCR_SRV_ATTN_PAIR"); return !(e && e[0] == '0'); }();
-  if (pair_on && heads % 2 == 0 && 2 * lds <= 160 * 1024) {
+  const char* var = attention_variant(T, heads, gh, gw, lh, lw);
+  if (!strcmp(var, "8x2") || !strcmp(var, "16x2")) {
     const size_t lds2 = 2 * lds;
-    if (2 * lds2 <= 160 * 1024) {
+    if (!strcmp(var, "8x2")) {
       if (lds2 > 64 * 1024 && !raise_dynamic_lds((const void*)attn_h_kernel<8, 2>, (int)lds2, memo8p)) { err = "attention: dynamic LDS attribute refused"; return false; }
       hipLaunchKernelGGL((attn_h_kernel<8, 2>), dim3((unsigned)(N * heads / 2)), dim3(512), lds2, s, (const _Float16*)qkv, (_Float16*)out, T, heads, sl, gh, gw, lh, lw);
     } else {
@@ -1836,7 +1847,7 @@ bool launch_attention(const void* qkv, void* out, int N, int T, int heads, int h
     }
     return true;
   }
-  if (nq >= 12) {
+  if (!strcmp(var, "8x1")) {
     if (lds > 64 * 1024 && !raise_dynamic_lds((const void*)attn_h_kernel<8, 1>, (int)lds, memo8)) { err = "attention: dynamic LDS attribute refused"; return false; }
     hipLaunchKernelGGL((attn_h_kernel<8, 1>), dim3((unsigned)(N * heads)), dim3(512), lds, s, (const _Float16*)qkv, (_Float16*)out, T, heads, sl, gh, gw, lh, lw);
   } else {

@@ -41,6 +41,14 @@ class SrvNet {
   // parity tap: tensor `tid` in logical NHWC f32 (pad channels dropped)
   bool fetch_logical(int tid, std::vector<float>& host, int dims[4], hipStream_t s, std::string& err);
   void set_keep_all(bool on) { if (on != keep_all_) { keep_all_ = on; bound_n_ = -1; } }
+  // test taps on the binding `run` last made: the launch list (name, the tensor a launch writes, every tensor it reads - the pack
+  // launch reads tensor 0, the f32 input), launches [first, first + count) enqueued alone, and caller data (logical NHWC f32) written
+  // into tensor `tid` as its element type, pad channels zero.  In the arena a launch's output never shares bytes with its inputs: a
+  // tensor is released only after the op that last reads it has had its output allocated (fused pairs: after the pair's launch)
+  int num_launches() const { return bound_n_ < 0 ? 0 : (int)launches_.size(); }
+  bool launch_info(int i, std::string& name, int& out, std::vector<int>& ins) const;
+  bool run_launches(int first, int count, hipStream_t s, std::string& err);
+  bool upload_logical(int tid, const float* host, size_t count, hipStream_t s, std::string& err);
   // CTC mode of the LAST linear (f32 logits), f16 build: it leaves per-row partials in the output tensor's slot instead of the logits
   // (GemmArgs::ctc_part); the caller folds them with srv::launch_ctc_reduce(tensor_ptr(output_tid()), rows, ctc_slots(), ctc_step(), ..)
   void set_ctc_partials(bool on) { if (on != ctc_) { ctc_ = on; bound_n_ = -1; } }
@@ -81,6 +89,8 @@ class SrvNet {
   struct Launch {
     std::string name;
     double flops = 0, bytes = 0;
+    int out = -1;          // the tensor it writes
+    std::vector<int> ins;  // the tensors it reads (a residual and every source of a folded concat included)
     std::function<bool(hipStream_t, std::string&)> fn;
   };
   bool parse(const char* text, std::string& err);

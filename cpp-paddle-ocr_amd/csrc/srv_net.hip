@@ -583,6 +583,8 @@ bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
     const long px = (long)N * H * W;
     Launch L;
     L.name = "pack_input";
+    L.out = pk;
+    L.ins = {0};
     L.bytes = (double)px * (12 + 8 * esz);
     void* dst = ptr(pk);
     const bool hf = half_;
@@ -612,6 +614,8 @@ bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
       }
       snprintf(nm, sizeof nm, "%zu.concat_%dx%d@%dx%dx%d", oi, ns, cs, ot.n, ot.h, ot.w);
       L.name = nm;
+      L.out = o;
+      L.ins = op.ins;
       L.bytes = 2.0 * ot.bytes(half_);
       void* dst = ptr(o);
       const int n_ = ot.n, oh = ot.h, ow = ot.w;
@@ -632,11 +636,15 @@ bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
       in_cat.c = in_cat.cs = 64 * (int)c.ins.size();
     }
     const SrvTensor& in = cat_in ? in_cat : tensors_[itid];
+    L.out = o;
+    L.ins = cat_in ? ops_[oi - 1].ins : std::vector<int>{itid};
+    if (op.res_tid >= 0) L.ins.push_back(op.res_tid);
     if (ht_head[oi]) {
       const Op& d2 = ops_[oi + 1];
       const SrvTensor& yt = tensors_[d2.geti("o")];
       snprintf(nm, sizeof nm, "%zu.head_tail_64_64_1@%dx%dx%d", oi, yt.n, yt.h, yt.w);
       L.name = nm;
+      L.out = d2.geti("o");
       L.flops = 2.0 * in.pixels() * 64.0 * 256.0 + 2.0 * in.pixels() * 4.0 * 4.0 * 64.0;
       L.bytes = (double)in.bytes(half_) + (double)yt.bytes(half_);
       const void* xs = ptr(itid);
@@ -658,6 +666,8 @@ bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
       const int c = xt.c;
       snprintf(nm, sizeof nm, "%zu.mlp%s_%d_%d_%d@%dx%dx%d", oi, lnin ? "_ln" : "", c, 4 * c, c, yt.n, yt.h, yt.w);
       L.name = nm;
+      L.out = f2.geti("o");
+      L.ins = {xtid};  // (input and residual)
       const double M_ = (double)xt.pixels();
       L.flops = 2.0 * 2.0 * M_ * c * 4.0 * c;
       L.bytes = (double)xt.bytes(half_) + (double)yt.bytes(half_) + 2.0 * 4.0 * c * c * esz;
@@ -822,7 +832,7 @@ bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
       const int gh = op.geti("gh", in.h), gw = op.geti("gw", in.w), lh = op.geti("lh", 0), lw = op.geti("lw", 0);
       if (gh != in.h || gw != in.w) { err = "attention: the plan's token grid is " + std::to_string(gh) + "x" + std::to_string(gw) + ", the tensor's " + std::to_string(in.h) + "x" + std::to_string(in.w); return false; }
       snprintf(nm, sizeof nm, "%zu.attn_%s_h%d@%dx%dx%d", oi, lh > 0 ? "local" : "global", heads, ot.n, ot.h, ot.w);
-      L.name = nm;
+      L.name = std::string(nm) + (half_ ? std::string("[") + srv::attention_variant(T, heads, gh, gw, lh, lw) + "]" : std::string());
       // keys that take part: the window (clipped at the grid's border) or every token
       double keys = T;
       if (lh > 0) {
@@ -884,6 +894,42 @@ void SrvNet::collect_timings() {
     (void)hipEventDestroy(p.b);
   }
   ev_pending_.clear();
+}
+
+bool SrvNet::launch_info(int i, std::string& name, int& out, std::vector<int>& ins) const {
+  if (bound_n_ < 0 || i < 0 || i >= (int)launches_.size()) return false;
+  name = launches_[i].name;
+  out = launches_[i].out;
+  ins = launches_[i].ins;
+  return true;
+}
+
+bool SrvNet::run_launches(int first, int count, hipStream_t s, std::string& err) {
+  if (bound_n_ < 0 || !x_in_ || first < 0 || count < 0 || first + count > (int)launches_.size()) { err = "no such launch range"; return false; }
+  for (int i = first; i < first + count; ++i)
+    if (!launches_[i].fn(s, err)) { err = launches_[i].name + ": " + err; return false; }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { err = std::string("server network launch: ") + hipGetErrorString(e); return false; }
+  return true;
+}
+
+bool SrvNet::upload_logical(int tid, const float* host, size_t count, hipStream_t s, std::string& err) {
+  if (tid <= 0 || tid > ntensors_ || bound_n_ < 0 || tensors_[tid].n == 0) { err = "no such tensor"; return false; }
+  const SrvTensor& t = tensors_[tid];
+  const size_t px = (size_t)t.pixels();
+  if (count != px * t.c) { err = "upload: element count is not the tensor's"; return false; }
+  std::vector<unsigned char> img(t.bytes(half_), 0);
+  for (size_t p = 0; p < px; ++p)
+    for (int c = 0; c < t.c; ++c) {
+      const float v = host[p * t.c + c];
+      const size_t k = p * t.cs + c;
+      if (t.f32 || !half_) ((float*)img.data())[k] = v;
+      else ((_Float16*)img.data())[k] = (_Float16)v;
+    }
+  hipError_t e = g_stream_sync(s);
+  if (e == hipSuccess) e = g_memcpy(arena_ + t.offset, img.data(), img.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { err = std::string("upload: ") + hipGetErrorString(e); return false; }
+  return true;
 }
 
 bool SrvNet::fetch_logical(int tid, std::vector<float>& host, int dims[4], hipStream_t s, std::string& err) {

@@ -326,6 +326,16 @@ int ocr_srv_net_num_tensors(ocr_srv_net* h);
 int ocr_srv_net_fetch(ocr_srv_net* h, int tid, float* out, size_t cap_floats, int dims[4]);
 int ocr_srv_net_timing(ocr_srv_net* h, int enable);
 int ocr_srv_net_timing_report(ocr_srv_net* h, char* buf, size_t cap);
+/* test hooks on the binding the last forward made (tests/test_gpu_srv_ops.py checks every launch alone against a float64
+ * reference).  ocr_srv_net_num_launches: launches of that binding.  ocr_srv_net_launch_info: launch i's name, the tensor it
+ * writes and the tensors it reads (a residual and every source of a folded concat included; the pack launch reads tid 0, the
+ * input).  ocr_srv_net_run_launches: launches [first, first + count) enqueued alone (on the input the last forward uploaded)
+ * and waited for.  ocr_srv_net_upload: caller data, logical NHWC f32 of the tensor's element count, written into tensor `tid`
+ * as its element type (f16 / f32), pad channels zero.  A launch's output never shares arena bytes with its inputs. */
+int ocr_srv_net_num_launches(ocr_srv_net* h);
+int ocr_srv_net_launch_info(ocr_srv_net* h, int i, char* name, size_t name_cap, int* out_tid, int* in_tids, int in_cap, int* n_in);
+int ocr_srv_net_run_launches(ocr_srv_net* h, int first, int count);
+int ocr_srv_net_upload(ocr_srv_net* h, int tid, const float* data, size_t count);
 
 /* self-tests / fault injection (tests): ocr_selftest_refuse_launch - a network launch whose name contains `substr` is
  * refused as if its launcher had rejected the shape (NULL or "" switches it off): the run must fail with OCR_ERR_DEVICE

@@ -43,80 +43,9 @@ def test_erf_of_the_gelu(built):
 
 
 def _torch_run(plan_text, params, x):
-    """float64 torch interpretation of a server plan, op by op, written from the plan grammar alone"""
-    import torch
-    import torch.nn.functional as F
-    t = {0: torch.from_numpy(x.astype(np.float64)).permute(0, 3, 1, 2)}
-    P = {k: torch.from_numpy(np.asarray(v, np.float64)) for k, v in params.items()}
-
-    def ep(y, stages):
-        for st in stages:
-            k, _, a = st.partition(":")
-            a = a.split(",")
-            if k == "bias":
-                y = y + P[a[0]].view(1, -1, 1, 1)
-            elif k == "bn":
-                g, b, m, v = (P[n] for n in a[:4])
-                y = (y - m.view(1, -1, 1, 1)) / torch.sqrt(v.view(1, -1, 1, 1) + float(a[4])) * g.view(1, -1, 1, 1) + b.view(1, -1, 1, 1)
-            elif k == "addt":
-                y = y + t[int(a[0])]
-            elif k == "addup":
-                y = y + F.interpolate(t[int(a[0])], scale_factor=int(a[1]), mode="nearest")
-            elif k == "addpos":
-                n, c, h, w = y.shape
-                y = y + P[a[0]].view(1, h, w, c).permute(0, 3, 1, 2)
-            elif k == "act":
-                y = {"relu": F.relu, "gelu": lambda z: F.gelu(z), "hswish": F.hardswish, "sigmoid": torch.sigmoid}[a[0]](y)
-            else:
-                raise ValueError(k)
-        return y
-
-    out = None
-    for line in plan_text.splitlines():
-        if not line or line[0] == "#" or line.startswith("plan "):
-            continue
-        toks = line.split()
-        kind, kv = toks[0], dict(tk.split("=", 1) for tk in toks[1:])
-        stages = kv.get("ep", "").split("|") if kv.get("ep") else []
-        gi = lambda k, d=0: int(kv.get(k, d))
-        if kind == "output":
-            out = t[gi("i")]
-            continue
-        o = gi("o")
-        if kind == "conv":
-            y = F.conv2d(t[gi("i")], P[kv["w"]], stride=(gi("sh"), gi("sw")), padding=(gi("ph"), gi("pw")))
-        elif kind == "linear":
-            y = torch.einsum("nchw,co->nohw", t[gi("i")], P[kv["w"]])
-        elif kind == "deconv":
-            y = F.conv_transpose2d(t[gi("i")], P[kv["w"]], stride=2)
-        elif kind == "pool":
-            a = dict(kernel_size=(gi("kh"), gi("kw")), stride=(gi("sh"), gi("sw")), padding=(gi("ph"), gi("pw")))
-            y = F.max_pool2d(t[gi("i")], **a) if kv["type"] == "max" else F.avg_pool2d(t[gi("i")], count_include_pad=False, **a)
-        elif kind == "concat":
-            ids, ups = [int(v) for v in kv["i"].split(",")], [int(v) for v in kv["up"].split(",")]
-            y = torch.cat([F.interpolate(t[i], scale_factor=u, mode="nearest") if u > 1 else t[i] for i, u in zip(ids, ups)], 1)
-        elif kind == "ew":
-            y = t[gi("i")]
-        elif kind == "ln":
-            z = t[gi("i")].permute(0, 2, 3, 1)
-            y = F.layer_norm(z, z.shape[-1:], P[kv["g"]], P[kv["b"]], float(kv["eps"])).permute(0, 3, 1, 2)
-        elif kind == "attn":
-            z = t[gi("i")]
-            n, c3, h, w = z.shape
-            heads, hd = gi("heads"), gi("hd")
-            T = h * w
-            q, k, v = z.permute(0, 2, 3, 1).reshape(n, T, 3, heads, hd).permute(2, 0, 3, 1, 4)
-            s = (q * float(kv["scale"])) @ k.transpose(-1, -2)
-            lh, lw = gi("lh"), gi("lw")
-            if lh > 0:  # SVTR's Local mixer: -inf outside the window (rec_svtrnet.py builds this mask by slicing a padded grid)
-                yy, xx = np.divmod(np.arange(T), w)
-                ok = (np.abs(yy[:, None] - yy[None]) <= lh // 2) & (np.abs(xx[:, None] - xx[None]) <= lw // 2)
-                s = s.masked_fill(~torch.from_numpy(ok), float("-inf"))
-            y = (torch.softmax(s, -1) @ v).permute(0, 2, 1, 3).reshape(n, h, w, heads * hd).permute(0, 3, 1, 2)
-        else:
-            raise ValueError(kind)
-        t[o] = ep(y, stages)
-    return out.permute(0, 2, 3, 1).numpy(), {k: v.permute(0, 2, 3, 1).numpy() for k, v in t.items() if k}
+    """float64 torch interpretation of a server plan, op by op, written from the plan grammar alone (tools/srv_ref.py)"""
+    import srv_ref
+    return srv_ref.torch_run(plan_text, params, x)
 
 
 @pytest.mark.parametrize("net,shape", [("srv_det", (1, 64, 96)), ("srv_rec", (1, 48, 320))])
