@@ -28,7 +28,9 @@ struct GemmArgs {
   const void* w = nullptr;   // weight image [nkt][Npad][8 granules, XOR-swizzled by row] T (srv_net.hip: weight_image)
   unsigned long long w_bytes = 0;
   void* y = nullptr;         // [N][OH][OW][Cs_out] T (out_f32: float)
-  unsigned long long y_bytes = 0;
+  unsigned long long y_bytes = 0;  // (y_bytes, res_bytes: no kernel reads them; they hold the argument layout the GEMM kernels
+                                   // were measured with - without them the argument loads pack differently and the register
+                                   // allocation of the 256 x 256 tiles changes)
   long M = 0;
   int K = 0, nkt = 0;        // K = KH*KW*Cin (Cin = stored channels), K tiles of 8 granules
   int Npad = 0;              // rows of the weight image: GEMM rows padded to a multiple of 256
@@ -69,7 +71,7 @@ struct GemmArgs {
                              // 1 = (64-channel tile, tap, channel in tile) - the f16 build: a channel tile's nine taps are consecutive K tiles,
                              // so the halo form (srv_conv3_kernel) streams ONE input patch per channel tile; both forms accumulate in this order
 };
-int gemm_num_configs();
+int gemm_num_configs();       // configuration ids run 0 .. gemm_num_configs() - 1; gemm_config_ok refuses an unused one
 int gemm_config_bn(int cfg);  // column-tile width of a configuration (the CTC partials' slot step is bn / 64)
 const char* gemm_config_name(int cfg);
 // can tile configuration `cfg` run this problem? (shape divisibility, LDS attribute) - asked at bind time
@@ -77,7 +79,7 @@ bool gemm_config_ok(const GemmArgs& a, bool half, int cfg);
 bool launch_gemm(const GemmArgs& a, bool half, int cfg, hipStream_t s, std::string& err);
 
 // SVTR's MLP in one launch (f16 build): y = x + fc2(gelu(fc1(x) + b1)) + b2, x / y [M][C] f16, the weight images of the two linears
-// as launch_gemm takes them; C in {192, 256, 512}.  query: instantiation / LDS attribute check only.  Bit-identical to the two
+// as launch_gemm takes them; C in {192, 256}.  query: instantiation / LDS attribute check only.  Bit-identical to the two
 // launches it replaces (srv_mlp.h).
 bool launch_mlp(const void* x, unsigned long long x_bytes, const void* w1, unsigned long long w1_bytes, int w1_npad, const void* w2,
                 unsigned long long w2_bytes, int w2_npad, const float* b1, const float* b2, void* y, long M, int C, hipStream_t s, bool query,

@@ -49,6 +49,23 @@ __device__ __forceinline__ void srv_dma16(unsigned lds, unsigned voff, v4u rsrc,
 }
 template <int N>
 __device__ __forceinline__ void srv_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// the same wait for a wave-uniform count known at run time: a ring whose waits are "at most (issued - mark) outstanding", with
+// `issued` the DMA instructions the wave has issued and `mark` that count when a slot's DMAs went out (the VM counter retires in order)
+__device__ __forceinline__ void srv_wait_vm_le(int n) {  // wave-uniform n; the counter holds at most 63
+  switch (n) {
+#define W1(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
+#define W8(b) W1(b) W1(b + 1) W1(b + 2) W1(b + 3) W1(b + 4) W1(b + 5) W1(b + 6) W1(b + 7)
+    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    W1(1) W1(2) W1(3) W1(4) W1(5) W1(6) W1(7)
+    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
+    W1(9) W1(10) W1(11) W1(12) W1(13) W1(14) W1(15) W1(16) W1(17) W1(18) W1(19) W1(20) W1(21) W1(22) W1(23) W1(24) W1(25) W1(26) W1(27) W1(28)
+    W1(29) W1(30) W1(31) W1(32) W1(33) W1(34) W1(35) W1(36) W1(37) W1(38) W1(39) W1(40) W1(41) W1(42) W1(43) W1(44) W1(45) W1(46) W1(47) W1(48)
+    W1(49) W1(50) W1(51) W1(52) W1(53) W1(54) W1(55) W1(56) W1(57) W1(58) W1(59) W1(60) W1(61) W1(62)
+#undef W8
+#undef W1
+    default: break;
+  }
+}
 
 __device__ __forceinline__ unsigned srv_xcd(unsigned bid, unsigned nblk) {  // blocks that share an XCD get consecutive tiles
   const unsigned q = nblk >> 3, r = nblk & 7, x = bid & 7, i = bid >> 3;
@@ -668,7 +685,6 @@ __global__ void __launch_bounds__(64 * WM * WN) srv_gemm_kernel(const GemmArgs a
   }
 }
 
-#include "srv_pgemm.h"
 #include "srv_mlp.h"
 
 // =================================================================================================== 3x3 convs on a halo patch
@@ -912,70 +928,80 @@ static bool conv3_go(const GemmArgs& a, bool half, hipStream_t s, bool query, st
   return true;
 }
 
-// ---- tile configurations (autotuned per layer at bind time: srv_net.hip)
-struct GemmCfg { const char* name; int bm, bn, nt; unsigned lds_h, lds_f; };
-#define SRV_CFGS(X)          \
-  X(0, 256, 128, 2, 4, 3)    \
-  X(1, 128, 128, 2, 2, 2)    \
-  X(2, 256, 64, 4, 2, 3)     \
-  X(3, 128, 64, 2, 2, 2)     \
-  X(4, 128, 256, 1, 8, 3)    \
-  X(5, 128, 128, 2, 4, 3)    \
-  X(6, 256, 128, 4, 2, 3)    \
-  X(7, 256, 128, 4, 2, 2)    \
-  X(8, 128, 64, 2, 2, 3)     \
-  X(9, 64, 64, 2, 2, 3)
-// the persistent form (srv_pgemm.h; x1 problems only): id, f16 tile and waves, f32-twin tile and waves
-#define SRV_PCFGS(X)                        \
-  X(10, 128, 128, 2, 4, 64, 64, 2, 2)       \
-  X(11, 128, 128, 2, 2, 64, 64, 2, 2)
-// two column blocks per wave on the small tiles (a wave's pixel row = 128 bytes: whole lines in the epilogue above)
-#define SRV_CFGS2(X)         \
-  X(14, 128, 64, 4, 1, 2)    \
-  X(15, 128, 128, 4, 2, 3)   \
-  X(16, 256, 64, 4, 1, 3)    \
-  X(17, 128, 64, 2, 2, 5)    \
-  X(18, 64, 64, 2, 2, 6)     \
-  X(19, 128, 64, 4, 1, 4)
-// the halo form of the 3x3 stride-1 convs (srv_conv3_kernel: 16 x 16 pixel tile, BN columns; f16 build, K order 1 only)
-#define SRV_HCFGS(X) \
-  X(20, 64)
-// big tiles (f16 build only; the f32 twin of such a choice runs 128x128/2x2/s2 - its bits do not depend on the tile)
-#define SRV_BCFGS(X)         \
-  X(12, 256, 256, 2, 4, 2)   \
-  X(13, 256, 256, 4, 2, 2)
-// 192-column tiles (f16 build, register epilogues only): SVTR's qkv widths are multiples of 192 (576, 768, 1536) - a 128-column tile
-// leaves the last column tile of 576 half empty, and these launches' time goes with their tile COUNT (ids follow the table's order)
-#define SRV_BCFGS2(X)        \
-  X(21, 128, 192, 2, 2, 2)   \
-  X(22, 256, 192, 4, 2, 2)
-static const GemmCfg g_cfgs[] = {
-#define X(id, BM, BN, WM, WN, NS) {#BM "x" #BN "/" #WM "x" #WN "/s" #NS, BM, BN, 64 * WM * WN, GemmGeom<_Float16, BM, BN, WM, WN, NS>::LDS, GemmGeom<float, BM, BN, WM, WN, NS>::LDS},
-    SRV_CFGS(X)
-#undef X
-#define X(id, BM, BN, WM, WN, FM, FN, FWM, FWN) {"p" #BM "x" #BN "/" #WM "x" #WN, BM, BN, 64 * WM * WN, PGeom<_Float16, BM, BN, WM, WN, 3, false>::LDS, PGeom<float, FM, FN, FWM, FWN, 3, false>::LDS},
-    SRV_PCFGS(X)
-#undef X
-#define X(id, BM, BN, WM, WN, NS) {#BM "x" #BN "/" #WM "x" #WN "/s" #NS, BM, BN, 64 * WM * WN, GemmGeom<_Float16, BM, BN, WM, WN, NS>::LDS, GemmGeom<float, 128, 128, 2, 2, 2>::LDS},
-    SRV_BCFGS(X)
-#undef X
-#define X(id, BM, BN, WM, WN, NS) {#BM "x" #BN "/" #WM "x" #WN "/s" #NS, BM, BN, 64 * WM * WN, GemmGeom<_Float16, BM, BN, WM, WN, NS>::LDS, GemmGeom<float, BM, BN, WM, WN, NS>::LDS},
-    SRV_CFGS2(X)
-#undef X
-#define X(id, BN) {"halo16x16x" #BN, 256, BN, 512, Conv3Geom<BN>::LDS, 0u},
-    SRV_HCFGS(X)
-#undef X
-#define X(id, BM, BN, WM, WN, NS) {#BM "x" #BN "/" #WM "x" #WN "/s" #NS, BM, BN, 64 * WM * WN, GemmGeom<_Float16, BM, BN, WM, WN, NS>::LDS, GemmGeom<float, 128, 128, 2, 2, 2>::LDS},
-    SRV_BCFGS2(X)
+// ---- tile configurations (autotuned per layer at bind time: srv_net.hip): ONE row per id, in id order - the name table and the
+// dispatch below both expand it.  The ids are what tune files (OCR_SRV_TUNE_FILE), OCR_SRV_CFG, the no-tuning heuristic and recorded
+// profiles name: a row keeps its id, and 10 / 11 (the persistent form, removed: DESIGN.md section 10) stay unused.
+// Row: id, form, f16 geometry, f32-twin geometry (what the parity build runs for a layer the f16 build runs with this id).
+//   GEMM  srv_gemm_kernel (BM, BN, WM, WN, NS) with every epilogue; its twin runs the same tile
+//   REG   srv_gemm_kernel with the register epilogues only (GemmGeom::BIG: 256 x 256, or 192 columns; f16 build) - its twin runs
+//         128x128/2x2/s2: the twin's bits do not depend on the tile
+//   HALO  srv_conv3_kernel (BN) on a 16 x 16 pixel tile (f16 3x3 stride-1 convs, K order 1); no twin
+// 14 - 19: two column blocks per wave on the small tiles (a wave's pixel row = 128 bytes: whole lines in the epilogue).  21 / 22:
+// SVTR's qkv widths are multiples of 192 (576, 768, 1536) - a 128-column tile leaves the last column tile of 576 half empty, and
+// these launches' time goes with their tile COUNT.
+#define SRV_TILES(X)                                    \
+  X(0, GEMM, (256, 128, 2, 4, 3), (256, 128, 2, 4, 3))  \
+  X(1, GEMM, (128, 128, 2, 2, 2), (128, 128, 2, 2, 2))  \
+  X(2, GEMM, (256, 64, 4, 2, 3), (256, 64, 4, 2, 3))    \
+  X(3, GEMM, (128, 64, 2, 2, 2), (128, 64, 2, 2, 2))    \
+  X(4, GEMM, (128, 256, 1, 8, 3), (128, 256, 1, 8, 3))  \
+  X(5, GEMM, (128, 128, 2, 4, 3), (128, 128, 2, 4, 3))  \
+  X(6, GEMM, (256, 128, 4, 2, 3), (256, 128, 4, 2, 3))  \
+  X(7, GEMM, (256, 128, 4, 2, 2), (256, 128, 4, 2, 2))  \
+  X(8, GEMM, (128, 64, 2, 2, 3), (128, 64, 2, 2, 3))    \
+  X(9, GEMM, (64, 64, 2, 2, 3), (64, 64, 2, 2, 3))      \
+  X(12, REG, (256, 256, 2, 4, 2), (128, 128, 2, 2, 2))  \
+  X(13, REG, (256, 256, 4, 2, 2), (128, 128, 2, 2, 2))  \
+  X(14, GEMM, (128, 64, 4, 1, 2), (128, 64, 4, 1, 2))   \
+  X(15, GEMM, (128, 128, 4, 2, 3), (128, 128, 4, 2, 3)) \
+  X(16, GEMM, (256, 64, 4, 1, 3), (256, 64, 4, 1, 3))   \
+  X(17, GEMM, (128, 64, 2, 2, 5), (128, 64, 2, 2, 5))   \
+  X(18, GEMM, (64, 64, 2, 2, 6), (64, 64, 2, 2, 6))     \
+  X(19, GEMM, (128, 64, 4, 1, 4), (128, 64, 4, 1, 4))   \
+  X(20, HALO, (64), ())                                 \
+  X(21, REG, (128, 192, 2, 2, 2), (128, 128, 2, 2, 2))  \
+  X(22, REG, (256, 192, 4, 2, 2), (128, 128, 2, 2, 2))
+#define SRV_GEOM(...) __VA_ARGS__
+// per form: the name-table entry (name, column-tile width) and the dispatch cases (2 id + 1: f16 build, 2 id: f32 twin) of a row
+#define SRV_GEMM_ROW(BM, BN, WM, WN, NS) #BM "x" #BN "/" #WM "x" #WN "/s" #NS, BN
+#define SRV_REG_ROW SRV_GEMM_ROW
+#define SRV_HALO_ROW(BN) "halo16x16x" #BN, BN
+#define SRV_GEMM_CASES(id, h, f) SRV_TILE_CASES(id, h, f, false)
+#define SRV_REG_CASES(id, h, f) SRV_TILE_CASES(id, h, f, true)
+#define SRV_TILE_CASES(id, h, f, big)                                                                                  \
+  static_assert(GemmGeom<_Float16, SRV_GEOM h>::BIG == big, "form REG: the register epilogues only; GEMM: every epilogue"); \
+  case id * 2 + 1: return gemm_go<_Float16, SRV_GEOM h>(a, s, query, err);                                             \
+  case id * 2: return gemm_go<float, SRV_GEOM f>(a, s, query, err);
+#define SRV_HALO_CASES(id, h, f)                                          \
+  case id * 2 + 1: return conv3_go<SRV_GEOM h>(a, true, s, query, err); \
+  case id * 2: err = "the halo form is f16 only"; return false;
+
+struct GemmCfg { int id; const char* name; int bn; };
+static constexpr GemmCfg g_cfgs[] = {
+#define X(id, form, h, f) {id, SRV_##form##_ROW h},
+    SRV_TILES(X)
 #undef X
 };
-int gemm_num_configs() { return (int)(sizeof(g_cfgs) / sizeof(g_cfgs[0])); }
-int gemm_config_bn(int cfg) { return cfg >= 0 && cfg < gemm_num_configs() ? g_cfgs[cfg].bn : 0; }
-const char* gemm_config_name(int cfg) { return cfg >= 0 && cfg < gemm_num_configs() ? g_cfgs[cfg].name : "?"; }
+constexpr int NCFG_ROWS = (int)(sizeof(g_cfgs) / sizeof(g_cfgs[0]));
+constexpr bool ids_ascending() {
+  for (int i = 1; i < NCFG_ROWS; ++i)
+    if (g_cfgs[i].id <= g_cfgs[i - 1].id) return false;
+  return true;
+}
+static_assert(ids_ascending(), "tile configuration ids: unique and in ascending order");
+static const GemmCfg* cfg_row(int cfg) {
+  for (const GemmCfg& c : g_cfgs)
+    if (c.id == cfg) return &c;
+  return nullptr;
+}
+int gemm_num_configs() { return g_cfgs[NCFG_ROWS - 1].id + 1; }
+int gemm_config_bn(int cfg) { const GemmCfg* c = cfg_row(cfg); return c ? c->bn : 0; }
+const char* gemm_config_name(int cfg) { const GemmCfg* c = cfg_row(cfg); return c ? c->name : "?"; }
 
 template <typename T, int BM, int BN, int WM, int WN, int NS>
 static bool gemm_go(const GemmArgs& a, hipStream_t s, bool query, std::string& err) {
   using G = GemmGeom<T, BM, BN, WM, WN, NS>;
+  static_assert(sizeof(T) == 2 || !G::BIG, "an f32 twin runs a tile with every epilogue");
   auto kern = srv_gemm_kernel<T, BM, BN, WM, WN, NS>;
   static LdsAttrMemo memo;
   if (G::BIG && !(sizeof(T) == 2 && !a.deconv && !a.scale && (!a.out_f32 || a.ctc_part))) { err = "a big tile has the register epilogues only"; return false; }
@@ -993,65 +1019,13 @@ static bool gemm_go(const GemmArgs& a, hipStream_t s, bool query, std::string& e
   hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(G::NT), lds, s, a);
   return true;
 }
-template <typename T, int BM, int BN, int WM, int WN, bool OF32>
-static bool pgemm_go(const GemmArgs& a, hipStream_t s, bool query, std::string& err) {
-  using G = PGeom<T, BM, BN, WM, WN, 3, OF32>;
-  auto kern = srv_pgemm_kernel<T, BM, BN, WM, WN, 3, OF32>;
-  static LdsAttrMemo memo;
-  if (!a.x1) { err = "the persistent form takes 1x1 problems"; return false; }
-  if (a.ctc_part || a.cat_n) { err = "the persistent form has neither the CTC epilogue nor a concatenated input"; return false; }
-  if (a.res_up && (OF32 || a.res_bytes >= 0xfffffff0ull)) { err = "residual"; return false; }
-  if (a.y_bytes >= 0xfffffff0ull) { err = "output beyond the 4 GB a buffer descriptor spans"; return false; }
-  if (G::LDS > 64 * 1024 && !raise_dynamic_lds((const void*)kern, (int)G::LDS, memo)) { err = "dynamic LDS attribute refused"; return false; }
-  if (query) return true;
-  const long ntiles = ((a.M + BM - 1) / BM) * ((a.Ncols + BN - 1) / BN);
-  if (ntiles <= 0 || ntiles > 0x7fffffffL) { err = "grid"; return false; }
-  static const int ncu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, dev) == hipSuccess) n = pr.multiProcessorCount; }
-    return n > 0 ? n : 256;
-  }();
-  const int per_cu = (int)(160 * 1024 / G::LDS) > 0 ? (int)(160 * 1024 / G::LDS) : 1;
-  const long g0 = std::min<long>(ntiles, (long)ncu * per_cu);
-  const int tpb = (int)((ntiles + g0 - 1) / g0);
-  const unsigned grid = (unsigned)((ntiles + tpb - 1) / tpb);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT), G::LDS, s, a, tpb);
-  return true;
-}
 static bool gemm_dispatch(const GemmArgs& a, bool half, int cfg, hipStream_t s, bool query, std::string& err) {
   // shape contract of the kernel
   if (a.x_bytes >= 0xfffffff0ull || a.w_bytes >= 0xfffffff0ull) { err = "tensor beyond the 4 GB a buffer descriptor spans"; return false; }
   if (a.Npad % 256 || a.Ncols > a.Npad || a.nkt < 1) { err = "weight image shape"; return false; }
   switch (cfg * 2 + (half ? 1 : 0)) {
-#define X(id, BM, BN, WM, WN, NS)                                                   \
-    case id * 2 + 1: return gemm_go<_Float16, BM, BN, WM, WN, NS>(a, s, query, err); \
-    case id * 2: return gemm_go<float, BM, BN, WM, WN, NS>(a, s, query, err);
-    SRV_CFGS(X)
-#undef X
-#define X(id, BM, BN, WM, WN, FM, FN, FWM, FWN)                                                                          \
-    case id * 2 + 1: return a.out_f32 ? pgemm_go<_Float16, BM, BN, WM, WN, true>(a, s, query, err) : pgemm_go<_Float16, BM, BN, WM, WN, false>(a, s, query, err); \
-    case id * 2: return pgemm_go<float, FM, FN, FWM, FWN, false>(a, s, query, err);
-    SRV_PCFGS(X)
-#undef X
-#define X(id, BM, BN, WM, WN, NS)                                                   \
-    case id * 2 + 1: return gemm_go<_Float16, BM, BN, WM, WN, NS>(a, s, query, err); \
-    case id * 2: return gemm_go<float, 128, 128, 2, 2, 2>(a, s, query, err);
-    SRV_BCFGS(X)
-#undef X
-#define X(id, BM, BN, WM, WN, NS)                                                   \
-    case id * 2 + 1: return gemm_go<_Float16, BM, BN, WM, WN, NS>(a, s, query, err); \
-    case id * 2: return gemm_go<float, BM, BN, WM, WN, NS>(a, s, query, err);
-    SRV_CFGS2(X)
-#undef X
-#define X(id, BN)                                                  \
-    case id * 2 + 1: return conv3_go<BN>(a, true, s, query, err); \
-    case id * 2: err = "the halo form is f16 only"; return false;
-    SRV_HCFGS(X)
-#undef X
-#define X(id, BM, BN, WM, WN, NS)                                                   \
-    case id * 2 + 1: return gemm_go<_Float16, BM, BN, WM, WN, NS>(a, s, query, err); \
-    case id * 2: return gemm_go<float, 128, 128, 2, 2, 2>(a, s, query, err);
-    SRV_BCFGS2(X)
+#define X(id, form, h, f) SRV_##form##_CASES(id, h, f)
+    SRV_TILES(X)
 #undef X
   }
   err = "no such tile configuration";
@@ -1083,7 +1057,7 @@ static bool mlp_go(const MlpArgs& a, unsigned long long x_bytes, unsigned long l
                    std::string& err) {
   if (x_bytes >= 0xfffffff0ull || w1_bytes >= 0xfffffff0ull || w2_bytes >= 0xfffffff0ull) { err = "tensor beyond the 4 GB a buffer descriptor spans"; return false; }
   const unsigned nb = (unsigned)((M + 127) / 128);
-  static LdsAttrMemo m192, m256, m512;
+  static LdsAttrMemo m192, m256;
   switch (C) {
 #define SRV_MLP_CASE(CC, memo)                                                                                              \
     case CC:                                                                                                                \
@@ -1098,7 +1072,6 @@ static bool mlp_go(const MlpArgs& a, unsigned long long x_bytes, unsigned long l
       return true;
     SRV_MLP_CASE(192, m192)
     SRV_MLP_CASE(256, m256)
-    SRV_MLP_CASE(512, m512)
 #undef SRV_MLP_CASE
   }
   err = "fused MLP: channel count not instantiated";

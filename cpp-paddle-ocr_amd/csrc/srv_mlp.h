@@ -10,8 +10,8 @@
 // Arithmetic = the two launches': the hidden values are rounded to f16 once, fc2 accumulates them in ascending k - the fused
 // output equals the unfused f16 output bit for bit (tests/test_gpu_round6.py).
 // Waves: 8, wave = (wn = wave >> 2, wm = wave & 3): tokens 32 wm .. + 31; fc1: hidden 64 wn .. + 63 of the chunk (two 32-row
-// blocks); fc2: outputs (C / 2) wn .. (three / four / eight blocks).  C = 512: an fc2 K tile is 64 KB - two ring slots' worth - so
-// it travels as two half-tiles of 256 output rows, each consumed by the four waves of one wn (one wave per SIMD stays busy).
+// blocks); fc2: outputs (C / 2) wn .. (three / four blocks).  An fc2 K tile (C rows x 128 bytes) fills at most one ring slot:
+// C = 192 and 256 are instantiated (srv_kernels.hip mlp_go) - at C = 512 the accumulators of the 128-token tile spill.
 #pragma once
 
 struct MlpArgs {
@@ -44,19 +44,17 @@ struct MlpGeom {
   static constexpr int BM = 128, HC = 128, NW = 8, NT = 512, NS = 3;
   static constexpr int H = 4 * C, NCH = H / HC;        // hidden chunks
   static constexpr int NKT1 = C / 64;                  // fc1 K tiles per chunk
-  static constexpr int SPLIT = C > 256 ? 2 : 1;        // fc2 K tiles travel as SPLIT row pieces
-  static constexpr int ROWS2 = C / SPLIT;              // output rows per fc2 stage
-  static constexpr int SPC = NKT1 + 2 * SPLIT;         // stages per chunk
+  static constexpr int SPC = NKT1 + 2;                 // stages per chunk: fc1's K tiles, then fc2's two
   static constexpr int TN2 = C / 64;                   // 32-row output blocks per wave
   static constexpr unsigned SLOT = 32768u, HBUF = NS * SLOT, BIAS = HBUF + 32768u, LDS = BIAS + 2048u;  // BIAS: the chunk's 128 fc1 biases, two slots (+ 1 KB: the column sums s of the absorbed LayerNorm)
-  static constexpr int W1I = HC / 8 / NW, XI = BM / 8 / NW, W2I = (ROWS2 / 8 + NW - 1) / NW;  // DMA instructions per wave per stage
-  static_assert(C % 64 == 0 && ROWS2 * 128 <= (int)SLOT && (ROWS2 / 8) % NW == 0, "stage fits a ring slot, every wave issues equally");
+  static constexpr int W1I = HC / 8 / NW, XI = BM / 8 / NW, W2I = (C / 8 + NW - 1) / NW;  // DMA instructions per wave per stage
+  static_assert(C % 64 == 0 && C * 128 <= (int)SLOT && (C / 8) % NW == 0, "stage fits a ring slot, every wave issues equally");
 };
 
 template <int C, bool LN>  // LN: the LayerNorm of the input absorbed (MlpArgs::ln_*) - its own instantiation: the plain form's loops carry no test of it
 __global__ void __launch_bounds__(512) srv_mlp_kernel(const MlpArgs a) {
   using G = MlpGeom<C>;
-  constexpr int BM = G::BM, NW = G::NW, NKT1 = G::NKT1, SPLIT = G::SPLIT, ROWS2 = G::ROWS2, SPC = G::SPC, TN2 = G::TN2, NCH = G::NCH;
+  constexpr int BM = G::BM, NW = G::NW, NKT1 = G::NKT1, SPC = G::SPC, TN2 = G::TN2, NCH = G::NCH;
   constexpr int W1I = G::W1I, XI = G::XI, W2I = G::W2I;
   constexpr unsigned SLOT = G::SLOT, HBUF = G::HBUF, BIAS = G::BIAS;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -122,9 +120,9 @@ __global__ void __launch_bounds__(512) srv_mlp_kernel(const MlpArgs a) {
 #pragma unroll
       for (int j = 0; j < XI; ++j) srv_dma16(slot_base + 16384u + (unsigned)(wave + NW * j) * 1024u, xvo[j], rs_x, xso);
       issued += W1I + XI;
-    } else {  // fc2: W2 piece (K tile 2 i_c + j of the hidden axis, output rows ROWS2 * piece ..)
-      const int q = i_s - NKT1, j = q / SPLIT, piece = q - j * SPLIT;
-      const unsigned wso = (unsigned)(((unsigned long long)(2 * i_c + j) * (unsigned)a.w2_npad + (unsigned)(piece * ROWS2)) * 128ull);
+    } else {  // fc2: W2 tile (K tile 2 i_c + j of the hidden axis, every output row)
+      const int j = i_s - NKT1;
+      const unsigned wso = (unsigned)((unsigned long long)(2 * i_c + j) * (unsigned)a.w2_npad * 128ull);
 #pragma unroll
       for (int i = 0; i < W2I; ++i) srv_dma16(slot_base + (unsigned)(wave + NW * i) * 1024u, lvo + (unsigned)(wave + NW * i) * 1024u, rs_w2, wso);
       issued += W2I;
@@ -272,24 +270,22 @@ __global__ void __launch_bounds__(512) srv_mlp_kernel(const MlpArgs a) {
         }
       } else {
         // ---- fc2 stage: acc2[i] += W2 rows x hidden image rows (32 wm + r), K tile j of the chunk
-        const int q = c_s - NKT1, j = q / SPLIT, piece = q - j * SPLIT;
-        if (SPLIT == 1 || piece == wn) {
-          const unsigned char* sw = slot + (unsigned)((SPLIT == 1 ? wn * (C / 2) : 0) + r) * 128u;
-          const unsigned char* sx = smem + HBUF + (unsigned)j * 16384u + (unsigned)(wm * 32 + r) * 128u;
-          h8v fb[2], fa[2][TN2];
-          auto ld2 = [&](int s, int b) __attribute__((always_inline)) {
-            const unsigned ko = (unsigned)(((2 * s + h) ^ swz) * 16);
-            fb[b] = *(const h8v*)(sx + ko);
+        const int j = c_s - NKT1;
+        const unsigned char* sw = slot + (unsigned)(wn * (C / 2) + r) * 128u;
+        const unsigned char* sx = smem + HBUF + (unsigned)j * 16384u + (unsigned)(wm * 32 + r) * 128u;
+        h8v fb[2], fa[2][TN2];
+        auto ld2 = [&](int s, int b) __attribute__((always_inline)) {
+          const unsigned ko = (unsigned)(((2 * s + h) ^ swz) * 16);
+          fb[b] = *(const h8v*)(sx + ko);
 #pragma unroll
-            for (int i = 0; i < TN2; ++i) fa[b][i] = *(const h8v*)(sw + i * 4096 + ko);
-          };
-          ld2(0, 0);
+          for (int i = 0; i < TN2; ++i) fa[b][i] = *(const h8v*)(sw + i * 4096 + ko);
+        };
+        ld2(0, 0);
 #pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            if (s < 3) ld2(s + 1, (s + 1) & 1);
+        for (int s = 0; s < 4; ++s) {
+          if (s < 3) ld2(s + 1, (s + 1) & 1);
 #pragma unroll
-            for (int i = 0; i < TN2; ++i) acc2[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s & 1][i], fb[s & 1], acc2[i], 0, 0, 0);
-          }
+          for (int i = 0; i < TN2; ++i) acc2[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[s & 1][i], fb[s & 1], acc2[i], 0, 0, 0);
         }
       }
 #ifdef SRV_MLP_CLOCKS

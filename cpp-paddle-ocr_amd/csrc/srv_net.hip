@@ -448,11 +448,11 @@ bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
   // `linear 4C -> C | + the first linear's input`: the hidden tensor then never exists (no arena slot, no launch of its own)
   std::vector<char> mlp_head(ops_.size(), 0), mlp_tail(ops_.size(), 0), ht_head(ops_.size(), 0), ht_tail(ops_.size(), 0), cat_head(ops_.size(), 0), ln_abs(ops_.size(), 0);
   {
-    // OCR_SRV_MLP=0: never; =all: every width; default: C <= 256 (measured, tools/micro/srv_mlp_probe + tools/srv_bench.py: 1.46 ms
-    // against 1.60 for the two launches at C = 192, 1.22 against 1.20 at C = 256 with 1.5 / 1.0 GB less HBM traffic per launch;
-    // at C = 512 the 128 accumulator registers of the 128-token tile spill - 8.2 ms against 1.77 - and the pair stays two launches)
-    static const int mlp_max_c = [] { const char* e = getenv("OCR_SRV_MLP"); return e && e[0] == '0' ? 0 : (e && e[0] == 'a' ? 1 << 30 : 256); }();
-    const bool mlp_on = mlp_max_c > 0;
+    // OCR_SRV_MLP=0: never; default: every width the kernel is instantiated for, C = 192 and 256 (launch_mlp's query below; measured,
+    // tools/micro/srv_mlp_probe + tools/srv_bench.py: 1.46 ms against 1.60 for the two launches at C = 192, 1.22 against 1.20 at
+    // C = 256 with 1.5 / 1.0 GB less HBM traffic per launch; at C = 512 the 128 accumulator registers of the 128-token tile spilled -
+    // 8.2 ms against 1.77 - and such a pair stays two launches)
+    static const bool mlp_on = [] { const char* e = getenv("OCR_SRV_MLP"); return !(e && e[0] == '0'); }();
     std::vector<int> readers(ntensors_ + 1, 0);
     for (const Op& op : ops_) {
       if (op.kind == "output") { readers[op.geti("i")] += 2; continue; }
@@ -465,7 +465,6 @@ bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
       if (f1.kind != "linear" || f2.kind != "linear" || f1.act != srv::SACT_GELU || f1.res_tid >= 0 || !f1.bias || !f2.bias) continue;
       if (f2.geti("i") != f1.geti("o") || readers[f1.geti("o")] != 1 || f2.res_tid != f1.geti("i") || f2.res_up != 1 || f2.act != srv::SACT_NONE) continue;
       const int c = f1.geti("cin");
-      if (c > mlp_max_c) continue;
       if (f1.geti("cout") != 4 * c || f2.geti("cin") != 4 * c || f2.geti("cout") != c || f2.geti("o") == out_tid_) continue;
       std::string e;
       if (!srv::launch_mlp(nullptr, 0, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, c, nullptr, true, e)) continue;

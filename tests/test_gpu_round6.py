@@ -289,24 +289,25 @@ for kind, shape, seed in (("rec", (3, 48, 320), 31), ("det", (1, 96, 160), 32)):
     net.timing(True)
     net.forward(x, keep_all=False)
     names = " ".join(net.timing_report())
-    out.append(hashlib.sha1(np.ascontiguousarray(y).view(np.uint8)).hexdigest() + ":" + str(names.count("[" + sys.argv[2] + "/") + names.count("[" + sys.argv[2] + "]")))
+    out.append(hashlib.sha1(np.ascontiguousarray(y).view(np.uint8)).hexdigest() + ":" + str(names.count("[" + sys.argv[2] + "]")))
     net.close()
 print("CFG", *out)
 """
 
 
 def test_every_tile_configuration_gives_the_same_bits(pkg, built):
-    """The f16 GEMM family's tile configurations (csrc/srv_kernels.hip: SRV_CFGS, the 256 x 256 tiles, the two-column-block small
-    tiles) accumulate every output in the same order and share one epilogue (residual in, output out as whole lines through a
-    wave-private LDS block): forced one at a time (OCR_SRV_CFG, read once per
-    process - child processes, four at a time), the recognizer's logits and the detector's map are bit-identical to the tuned
-    run's, and the timing report shows that the forced configuration really ran."""
+    """The f16 GEMM family's tile configurations (csrc/srv_kernels.hip SRV_TILES: every id of the table) accumulate every output in
+    the same order and share one epilogue (residual in, output out as whole lines through a wave-private LDS block): forced one at
+    a time (OCR_SRV_CFG, read once per process - child processes, four at a time), the recognizer's logits and the detector's map
+    are bit-identical to the tuned run's, and the timing report shows that the forced configuration really ran (its full name)."""
     import subprocess
     import sys
     _srv_ready()
-    cfgs = [("", "", {}), ("0", "256x128/2x4", {}), ("4", "128x256/1x8", {}), ("6", "256x128/4x2", {}), ("9", "64x64/2x2", {}),
-            ("12", "256x256/2x4", {}), ("13", "256x256/4x2", {}), ("14", "128x64/4x1", {}), ("15", "128x128/4x2", {}), ("16", "256x64/4x1", {}),
-            ("3", "128x64/2x2", {}), ("1", "128x128/2x2", {}), ("20", "halo16x16x64", {}), ("21", "128x192/2x2", {}), ("22", "256x192/4x2", {})]
+    cfgs = [("", "", {})] + [(str(i), name, {}) for i, name in (
+        (0, "256x128/2x4/s3"), (1, "128x128/2x2/s2"), (2, "256x64/4x2/s3"), (3, "128x64/2x2/s2"), (4, "128x256/1x8/s3"), (5, "128x128/2x4/s3"),
+        (6, "256x128/4x2/s3"), (7, "256x128/4x2/s2"), (8, "128x64/2x2/s3"), (9, "64x64/2x2/s3"), (12, "256x256/2x4/s2"), (13, "256x256/4x2/s2"),
+        (14, "128x64/4x1/s2"), (15, "128x128/4x2/s3"), (16, "256x64/4x1/s3"), (17, "128x64/2x2/s5"), (18, "64x64/2x2/s6"), (19, "128x64/4x1/s4"),
+        (20, "halo16x16x64"), (21, "128x192/2x2/s2"), (22, "256x192/4x2/s2"))]
     pending, running, res = list(enumerate(cfgs)), [], {}
     while pending or running:
         while pending and len(running) < 4:

@@ -18,7 +18,7 @@ for d in sorted(glob.glob("$O/*/")):
     for f in glob.glob(d + "**/*counter_collection.csv", recursive=True):
         acc = collections.defaultdict(lambda: [0.0, 0])
         for row in csv.DictReader(open(f)):
-            if "srv_gemm" not in row.get("Kernel_Name", "") and "pgemm" not in row.get("Kernel_Name", ""):
+            if "srv_gemm" not in row.get("Kernel_Name", ""):
                 continue
             a = acc[row["Counter_Name"]]; a[0] += float(row["Counter_Value"]); a[1] += 1
         for k, (v, n) in sorted(acc.items()):
