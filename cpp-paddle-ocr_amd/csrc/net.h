@@ -87,10 +87,11 @@ class Net {
   bool run_ragged(const float* x, int H, const int* widths, int N, hipStream_t s, std::string& err);
   // Ragged batch of IMAGES (the detector on mixed sizes): image n is heights[n] x widths[n] (multiples of 32, as
   // ResizeImgType0 leaves them); x = the images' [h][w][3] blocks one after the other; the output (and every tensor)
-  // holds the images one after the other likewise.  Production launch list only (keep_all 0 or 2).
+  // holds the images one after the other likewise: the first pixel of image n in the output is the prefix sum of the
+  // images' h * w.  Production launch list only (keep_all 0 or 2).
   bool run_ragged_images(const float* x, const int* heights, const int* widths, int N, hipStream_t s, std::string& err);
-  // first pixel of image n in the output tensor of the current ragged-images binding is the prefix sum of h*w
-  // line widths of tensor `tid` under the current ragged binding (host copy), e.g. the CTC step counts of the output
+  // Line widths of tensor `tid` under the current ragged binding of LINES (host copy), e.g. the CTC step counts of the
+  // output.  Only for a binding of lines: a binding of images has levels but no width lists.
   const std::vector<int>& ragged_widths(int tid) const;
   // can this many lines / pixels go into one ragged launch? (32-bit pixel indices, attention working set)
   static bool ragged_ok(int H, const int* widths, int N, std::string& why);
@@ -150,8 +151,9 @@ class Net {
   };
   struct Binding {
     int n = 0, h = 0, w = 0;
-    // ragged batch: the lines' widths per level, the packed tables (per level: w[N], cw[N+1], and the prefix sums of
-    // ceil(w / 16), ceil(w / 8), ceil(w / 4), N + 2 entries each) on the host and on the device
+    // ragged batch: the lines' widths per level and the packed tables on the host and on the device - lines: per width
+    // level w[N+1] | cw[N+1]; images: one set w[N+1] | h[N+1] | cw[N+1] | ch[N+1] at input resolution; behind them the
+    // launches' memoised work tables (prefix sums of tiles / patches / bands per sample, N+1 entries each)
     std::vector<int> widths, heights;  // heights: a ragged batch of IMAGES (the detector on mixed sizes)
     std::vector<std::vector<int>> level_w;
     std::vector<int> rag_host;
@@ -179,6 +181,7 @@ class Net {
   static constexpr size_t kMaxRaggedBindings = 32;
   size_t max_bindings_ = 512;  // a mixed-size stream revisits sizes: BASELINE configs[2] has ~400 distinct det shapes (OCR_NET_BINDINGS, read at load)
   void invalidate() { cache_.clear(); cur_ = nullptr; }
+  struct BindCtx;  // net.hip: what the phases of bind share
   bool bind(int N, int H, int W, std::string& err, const int* widths = nullptr, const int* heights = nullptr);
   bool run_bound(const float* x, hipStream_t s, std::string& err);
   static std::vector<int> shape_key(int N, int H, int W, const int* widths, const int* heights);

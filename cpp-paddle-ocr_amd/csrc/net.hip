@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -594,29 +595,126 @@ const std::vector<int>& Net::ragged_widths(int tid) const {
   return cur_->level_w[tensors_[tid].lvl];
 }
 
-bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const int* heights) {
-  stats_.binds++;
-  std::unique_ptr<Binding> B(new Binding());
-  const bool rag = widths != nullptr;
-  const bool img = rag && heights != nullptr;  // ragged batch of images (own height and width) instead of lines
-  B->n = N; B->h = H; B->w = W;
-  B->pool = pool_;
-  std::vector<Launch>& launches_ = B->launches;
+// ------------------------------------------------------------------ binding one input shape
+// Net::bind is a driver over named phases - shapes, ragged tables, fusion decisions, arena, launches - that share one
+// explicit context instead of captured locals.  Every phase is a member of the context; what a later phase reads of an
+// earlier one (e.g. `gate_src[oj] < 0 && dwpw_of[oj] < 0`) is a field below.
+namespace {
+
+// Activation arena: best fit (the first smallest block) over a free list that coalesces on release; the top shrinks when
+// the last block is freed.  Sizes in floats, rounded up to 64.
+class ArenaPlan {
+ public:
+  static size_t round(size_t n) { return (n + 63) & ~(size_t)63; }
+  size_t alloc(size_t n) {
+    n = round(n);
+    int best = -1;
+    for (int i = 0; i < (int)free_.size(); ++i)
+      if (free_[i].sz >= n && (best < 0 || free_[i].sz < free_[best].sz)) best = i;
+    size_t off = top_;
+    if (best >= 0) {
+      off = free_[best].off;
+      if (free_[best].sz == n) free_.erase(free_.begin() + best);
+      else { free_[best].off += n; free_[best].sz -= n; }
+    } else top_ += n;
+    high_ = std::max(high_, off + n);
+    return off;
+  }
+  void release(size_t off, size_t n) {
+    free_.push_back({off, round(n)});
+    std::sort(free_.begin(), free_.end(), [](const Blk& a, const Blk& b) { return a.off < b.off; });
+    for (size_t i = 0; i + 1 < free_.size();) {
+      if (free_[i].off + free_[i].sz == free_[i + 1].off) { free_[i].sz += free_[i + 1].sz; free_.erase(free_.begin() + i + 1); }
+      else ++i;
+    }
+    if (!free_.empty() && free_.back().off + free_.back().sz == top_) { top_ = free_.back().off; free_.pop_back(); }
+  }
+  size_t high() const { return high_; }  // `top` may have shrunk at the end; capacity must cover the high-water mark
+
+ private:
+  struct Blk { size_t off, sz; };
+  std::vector<Blk> free_;
+  size_t top_ = 0, high_ = 0;
+};
+
+int out_size(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }  // C++ truncation on purpose
+bool plain_1x1(const PlanOp& c) {
+  return c.kind == PlanOp::CONV && c.kh == 1 && c.kw == 1 && c.sh == 1 && c.sw == 1 && c.ph == 0 && c.pw == 0 && c.cin != 3;
+}
+// column tiles of a fragment image: whole groups of the launch's tiles-per-wave (build_frag)
+int nt_total(int cols) {
+  const int tiles = (cols + 31) / 32, nt = conv_nt_for(tiles);
+  return (tiles + nt - 1) / nt * nt;
+}
+double EB(const TensorDesc& t) { return t.f16 ? 2.0 : 4.0; }  // bytes per stored element (the launches' algorithmic bytes)
+std::string fmt(const char* f, ...) __attribute__((format(printf, 1, 2)));
+std::string fmt(const char* f, ...) {
+  char nm[160];
+  va_list ap;
+  va_start(ap, f);
+  vsnprintf(nm, sizeof nm, f, ap);
+  va_end(ap);
+  return nm;
+}
+
+}  // namespace
+
+struct Net::BindCtx {
+  Net& net;
+  Binding* const B;
+  std::string& err;
+  const int N, H, W;
+  const int* const widths;
+  const int* const heights;
+  const bool rag, img;  // img: ragged batch of images (own height and width) instead of lines
+  std::vector<TensorDesc>& T;
+  const Plan& plan;
+  const int nops, out_tid, keep_all;
+  const bool half;
+  // ragged batch: width levels.  A level = the lines' widths after some chain of (kernel, stride, pad) along x;
+  // ops that keep the width stay on their input's level.
+  std::vector<std::vector<int>>& LW;
+  std::vector<long> ltot;
+  std::vector<int> lmax, lmin;
+  // images: ONE table set at input resolution; a tensor's level is its power-of-two shift against the input
+  long ipix = 0, irows = 0;  // pixels / rows of the batch at input resolution
+  int ihmax = 0, iwmax = 0, ihmin = 0x7fffffff, iwmin = 0x7fffffff;
+  // the sample tables (ragged_tables) and the launches' memoised work tables behind them
+  size_t lstride = 0, tab_cap = 0;
+  const int* rag_dev = nullptr;
+  std::map<std::string, std::pair<size_t, int>> tabs;
+  bool tab_overflow = false;
+  // fusion decisions, per op (-1 / 0: none)
+  bool fuse = false;
+  std::vector<int> uses;
+  std::vector<int> gate_src, gate_tid;  // conv op -> the tensor it reads instead of the folded ew's output, and the gate
+  std::vector<char> folded;             // ew / concat op: no launch, no tensor, its reads happen in the conv behind it
+  std::vector<int> xdw_of;              // depthwise op -> the 1x1 conv it absorbs
+  std::vector<int> dwpw_of;             // conv op -> the depthwise op it absorbs
+  std::vector<char> fused_dw;           // absorbed op (depthwise, expand conv, first DB-head deconv): no launch, no tensor
+  std::vector<char> dw_rowsum;          // depthwise op leaves the pool's row sums
+  std::vector<int> dbhead_of;           // tail op -> the deconv it absorbs
+  std::vector<int> cat_of;              // conv op -> the concat it absorbs
+  std::vector<int> rse_conv;            // ew op -> the conv it absorbs
+  std::vector<char> rse_first;          // that conv: its launch is the row-sum pass, its tensor never exists
+  size_t gap_need = 0;
   bool moved = false;  // a shared device buffer was reallocated: the other bindings' launches point into the old one
-  fused_head_rows_ = -1;
-  // 1. shapes
-  auto& T = tensors_;
-  auto setdims = [&](int t, int n, int h, int w, int c) {
+
+  BindCtx(Net& n, Binding* b, int N_, int H_, int W_, const int* ws, const int* hs, std::string& e)
+      : net(n), B(b), err(e), N(N_), H(H_), W(W_), widths(ws), heights(hs), rag(ws != nullptr), img(ws && hs), T(n.tensors_),
+        plan(n.plan_), nops((int)n.plan_.ops.size()), out_tid(n.out_tid_), keep_all(n.keep_all_), half(n.half_), LW(b->level_w) {}
+
+  const float* dev_vec(const std::string& key) const { return net.dev_vec(key); }
+  float* at(const TensorDesc& t) const { return net.arena_ + t.offset; }
+  const char* pname() const { return plan.name.c_str(); }
+
+  // ---------------------------------------------------------------- 1. shapes
+  void setdims(int t, int n, int h, int w, int c) {
     T[t].n = n; T[t].h = h; T[t].w = w; T[t].c = c;
     T[t].cs = T[t].plain ? c : c8i_stride(c);
     T[t].lvl = -1; T[t].pix = 0;
-  };
-  // ragged batch: width levels.  A level = the lines' widths after some chain of (kernel, stride, pad) along x;
-  // ops that keep the width stay on their input's level.
-  std::vector<std::vector<int>>& LW = B->level_w;
-  std::vector<long> ltot;
-  std::vector<int> lmax, lmin;
-  auto add_level = [&](std::vector<int> w) -> int {
+  }
+  int add_level(std::vector<int> w) {
     for (size_t l = 0; l < LW.size(); ++l) if (LW[l] == w) return (int)l;
     long tot = 0;
     int mx = 0, mn = 0x7fffffff;
@@ -624,33 +722,96 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
     LW.push_back(std::move(w));
     ltot.push_back(tot); lmax.push_back(mx); lmin.push_back(mn);
     return (int)LW.size() - 1;
-  };
-  auto derive = [&](int lvl, int k, int s, int p) -> int {  // < 0: a line got too narrow
+  }
+  int derive(int lvl, int k, int s, int p) {  // < 0: a line got too narrow
     if (k == 1 && s == 1 && p == 0) return lvl;
     std::vector<int> w(LW[lvl].size());
     for (size_t i = 0; i < w.size(); ++i) {
-      w[i] = (LW[lvl][i] + 2 * p - k) / s + 1;  // C++ truncation, as the uniform shapes below
+      w[i] = out_size(LW[lvl][i], k, s, p);
       if (LW[lvl][i] + 2 * p - k < 0 || w[i] <= 0) return -1;
     }
     return add_level(std::move(w));
-  };
-  auto setrag = [&](int t, int h, int lvl, int c) {
+  }
+  void setrag(int t, int h, int lvl, int c) {
     setdims(t, N, h, lmax[lvl], c);
     T[t].lvl = lvl;
     T[t].pix = (long)h * ltot[lvl];
-  };
-  // images: ONE table set at input resolution; a tensor's level is its power-of-two shift against the input
-  std::vector<int>& IH = B->heights;
-  long ipix = 0, irows = 0;   // pixels / rows of the batch at input resolution
-  int ihmax = 0, iwmax = 0, ihmin = 0x7fffffff, iwmin = 0x7fffffff;
-  auto setimg = [&](int t, int shift, int c) {
+  }
+  void setimg(int t, int shift, int c) {
     setdims(t, N, ihmax >> shift, iwmax >> shift, c);
     T[t].lvl = shift;
     T[t].pix = ipix >> (2 * shift);
-  };
-  if (img) {
+  }
+  // (every op kind but OUTPUT, which the callers skip, and CONCAT has in >= 0: the plan loader's invariant)
+  const TensorDesc& shape_src(const PlanOp& op) const { return T[op.kind == PlanOp::CONCAT ? op.ins.back() : op.in]; }
+
+  bool shapes_uniform() {
+    setdims(0, N, H, W, 3);
+    for (auto& op : plan.ops) {
+      if (op.kind == PlanOp::OUTPUT) continue;
+      const TensorDesc& i = shape_src(op);
+      switch (op.kind) {
+        case PlanOp::CONV: case PlanOp::DW:
+          setdims(op.out, i.n, out_size(i.h, op.kh, op.sh, op.ph), out_size(i.w, op.kw, op.sw, op.pw), op.kind == PlanOp::CONV ? op.cout : op.c);
+          break;
+        case PlanOp::DECONV: setdims(op.out, i.n, i.h * 2, i.w * 2, op.cout); break;
+        case PlanOp::LINEAR: setdims(op.out, i.n, i.h, i.w, op.cout); break;
+        case PlanOp::SEFC: case PlanOp::GAP: setdims(op.out, i.n, 1, 1, op.c); break;
+        case PlanOp::POOL: setdims(op.out, i.n, out_size(i.h, op.kh, op.sh, 0), out_size(i.w, op.kw, op.sw, 0), op.c); break;
+        case PlanOp::EW: case PlanOp::LN: case PlanOp::SOFTMAX: setdims(op.out, i.n, i.h, i.w, i.c); break;
+        case PlanOp::CONCAT: setdims(op.out, i.n, i.h * op.ups.back(), i.w * op.ups.back(), op.c); break;
+        case PlanOp::ATTN: setdims(op.out, i.n, i.h, i.w, op.heads * op.hd); break;
+        default: break;
+      }
+      if (op.out >= 0 && (T[op.out].h <= 0 || T[op.out].w <= 0)) { err = "input too small for the network"; return false; }
+    }
+    return true;
+  }
+
+  bool shapes_lines() {
     B->widths.assign(widths, widths + N);
-    IH.assign(heights, heights + N);
+    setrag(0, H, add_level(B->widths), 3);
+    for (auto& op : plan.ops) {
+      if (op.kind == PlanOp::OUTPUT) continue;
+      const TensorDesc& i = shape_src(op);
+      int lvl = i.lvl, oh = i.h, oc = i.c;
+      bool per_line = false;  // the op's output is one vector per line
+      switch (op.kind) {
+        case PlanOp::CONV: case PlanOp::DW:
+          if (lvl < 0) { err = "ragged batch: spatial op on a per-line vector"; return false; }
+          oh = out_size(i.h, op.kh, op.sh, op.ph);
+          lvl = derive(lvl, op.kw, op.sw, op.pw);
+          oc = op.kind == PlanOp::CONV ? op.cout : op.c;
+          break;
+        case PlanOp::POOL:
+          if (lvl < 0) { err = "ragged batch: spatial op on a per-line vector"; return false; }
+          oh = out_size(i.h, op.kh, op.sh, 0);
+          lvl = derive(lvl, op.kw, op.sw, 0);
+          oc = op.c;
+          break;
+        case PlanOp::LINEAR: oc = op.cout; break;
+        case PlanOp::SEFC: case PlanOp::GAP: per_line = true; oc = op.c; break;
+        case PlanOp::EW: case PlanOp::LN: case PlanOp::SOFTMAX: break;
+        case PlanOp::CONCAT:
+          for (size_t j = 0; j < op.ins.size(); ++j)
+            if (op.ups[j] != 1 || T[op.ins[j]].lvl != lvl || T[op.ins[j]].h != oh) { err = "ragged batch: concat of different resolutions is not on this path"; return false; }
+          oc = op.c;
+          break;
+        case PlanOp::ATTN: oc = op.heads * op.hd; break;
+        default: err = "ragged batch: op kind not on this path (transposed conv)"; return false;
+      }
+      if (per_line) { setdims(op.out, N, 1, 1, oc); continue; }
+      if (lvl < 0 && T[op.in].lvl >= 0) { err = "input too small for the network"; return false; }
+      if (lvl < 0) { setdims(op.out, i.n, i.h, i.w, oc); continue; }  // per-line vector -> per-line vector (sefc chain)
+      if (oh <= 0) { err = "input too small for the network"; return false; }
+      setrag(op.out, oh, lvl, oc);
+    }
+    return true;
+  }
+
+  bool shapes_images() {
+    B->widths.assign(widths, widths + N);
+    B->heights.assign(heights, heights + N);
     for (int i = 0; i < N; ++i) {
       if (widths[i] < 32 || heights[i] < 32 || widths[i] % 32 || heights[i] % 32 || widths[i] > 32767 || heights[i] > 32767) {
         err = "ragged batch of images: sizes must be multiples of 32 (ResizeImgType0 output)";
@@ -663,21 +824,14 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
     }
     if (ipix >= (1L << 31)) { err = "too many pixels for one ragged launch"; return false; }
     setimg(0, 0, 3);
-  } else if (rag) {
-    B->widths.assign(widths, widths + N);
-    setrag(0, H, add_level(B->widths), 3);
-  } else setdims(0, N, H, W, 3);
-  for (auto& op : plan_.ops) {
-    if (img && op.kind != PlanOp::OUTPUT) {
-      const TensorDesc& i = T[op.kind == PlanOp::CONCAT ? op.ins.back() : op.in];
-      // every spatial op of the detector keeps the size or halves it exactly (inputs are multiples of 32)
-      auto step = [&](int kh, int kw, int sh, int sw, int ph, int pw) -> int {
-        if (kh != kw || sh != sw || ph != pw || kh != 2 * ph + 1 || (sh != 1 && sh != 2)) return -1;
-        return sh == 2 ? 1 : 0;
-      };
+    for (auto& op : plan.ops) {
+      if (op.kind == PlanOp::OUTPUT) continue;
+      const TensorDesc& i = shape_src(op);
       switch (op.kind) {
         case PlanOp::CONV: case PlanOp::DW: {
-          const int d = step(op.kh, op.kw, op.sh, op.sw, op.ph, op.pw);
+          // every spatial op of the detector keeps the size or halves it exactly (inputs are multiples of 32)
+          const bool ok = op.kh == op.kw && op.sh == op.sw && op.ph == op.pw && op.kh == 2 * op.ph + 1 && (op.sh == 1 || op.sh == 2);
+          const int d = ok ? op.sh - 1 : -1;
           if (i.lvl < 0 || d < 0 || i.lvl + d > 5) { err = "ragged batch of images: conv geometry not on this path"; return false; }
           setimg(op.out, i.lvl + d, op.kind == PlanOp::CONV ? op.cout : op.c);
         } break;
@@ -698,77 +852,19 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
           break;
         default: err = "ragged batch of images: op kind not on this path"; return false;
       }
-      continue;
     }
-    if (rag && op.kind != PlanOp::OUTPUT) {
-      const TensorDesc& i = T[op.kind == PlanOp::CONCAT ? op.ins.back() : op.in];
-      int lvl = i.lvl, oh = i.h, oc = i.c;
-      bool per_line = false;  // the op's output is one vector per line
-      switch (op.kind) {
-        case PlanOp::CONV: case PlanOp::DW:
-          if (lvl < 0) { err = "ragged batch: spatial op on a per-line vector"; return false; }
-          oh = (i.h + 2 * op.ph - op.kh) / op.sh + 1;
-          lvl = derive(lvl, op.kw, op.sw, op.pw);
-          oc = op.kind == PlanOp::CONV ? op.cout : op.c;
-          break;
-        case PlanOp::POOL:
-          if (lvl < 0) { err = "ragged batch: spatial op on a per-line vector"; return false; }
-          oh = (i.h - op.kh) / op.sh + 1;
-          lvl = derive(lvl, op.kw, op.sw, 0);
-          oc = op.c;
-          break;
-        case PlanOp::LINEAR: oc = op.cout; break;
-        case PlanOp::SEFC: case PlanOp::GAP: per_line = true; oc = op.c; break;
-        case PlanOp::EW: case PlanOp::LN: case PlanOp::SOFTMAX: break;
-        case PlanOp::CONCAT:
-          for (size_t j = 0; j < op.ins.size(); ++j)
-            if (op.ups[j] != 1 || T[op.ins[j]].lvl != lvl || T[op.ins[j]].h != oh) { err = "ragged batch: concat of different resolutions is not on this path"; return false; }
-          oc = op.c;
-          break;
-        case PlanOp::ATTN: oc = op.heads * op.hd; break;
-        default: err = "ragged batch: op kind not on this path (transposed conv)"; return false;
-      }
-      if (per_line) { setdims(op.out, N, 1, 1, oc); continue; }
-      if (lvl < 0 && T[op.in].lvl >= 0) { err = "input too small for the network"; return false; }
-      if (lvl < 0) { setdims(op.out, i.n, i.h, i.w, oc); continue; }  // per-line vector -> per-line vector (sefc chain)
-      if (oh <= 0) { err = "input too small for the network"; return false; }
-      setrag(op.out, oh, lvl, oc);
-      continue;
-    }
-    switch (op.kind) {
-      case PlanOp::CONV: {
-        auto& i = T[op.in];
-        setdims(op.out, i.n, (i.h + 2 * op.ph - op.kh) / op.sh + 1, (i.w + 2 * op.pw - op.kw) / op.sw + 1, op.cout);
-      } break;
-      case PlanOp::DW: {
-        auto& i = T[op.in];
-        setdims(op.out, i.n, (i.h + 2 * op.ph - op.kh) / op.sh + 1, (i.w + 2 * op.pw - op.kw) / op.sw + 1, op.c);
-      } break;
-      case PlanOp::DECONV: { auto& i = T[op.in]; setdims(op.out, i.n, i.h * 2, i.w * 2, op.cout); } break;
-      case PlanOp::LINEAR: { auto& i = T[op.in]; setdims(op.out, i.n, i.h, i.w, op.cout); } break;
-      case PlanOp::SEFC: case PlanOp::GAP: { auto& i = T[op.in]; setdims(op.out, i.n, 1, 1, op.c); } break;
-      case PlanOp::POOL: {
-        auto& i = T[op.in];
-        setdims(op.out, i.n, (i.h - op.kh) / op.sh + 1, (i.w - op.kw) / op.sw + 1, op.c);  // C++ truncation on purpose
-      } break;
-      case PlanOp::EW: case PlanOp::LN: case PlanOp::SOFTMAX: { auto& i = T[op.in]; setdims(op.out, i.n, i.h, i.w, i.c); } break;
-      case PlanOp::CONCAT: {
-        auto& l = T[op.ins.back()];
-        setdims(op.out, l.n, l.h * op.ups.back(), l.w * op.ups.back(), op.c);
-      } break;
-      case PlanOp::ATTN: { auto& i = T[op.in]; setdims(op.out, i.n, i.h, i.w, op.heads * op.hd); } break;
-      case PlanOp::OUTPUT: break;
-    }
-    if (op.out >= 0 && (T[op.out].h <= 0 || T[op.out].w <= 0)) { err = "input too small for the network"; return false; }
+    return true;
   }
-  // ragged batch: the sample tables.  Lines: per width level  w[N+1] | cw[N+1].  Images: one set at input resolution
-  // w[N+1] | h[N+1] | cw[N+1] | ch[N+1] (w / h carry one entry past N: the tile walks step onto "sample N" after their
-  // last unit).  Behind them the launches' own work tables (prefix sums of tiles / patches / bands per sample, N+1
-  // entries each), appended while the launch list is built: the device buffer is sized for all of them up front.
-  const size_t lstride = img ? 4 * ((size_t)N + 1) : 2 * ((size_t)N + 1);
-  const size_t tab_base = rag ? lstride * (img ? 1 : LW.size()) : 0;
-  const size_t tab_cap = rag ? tab_base + 96 * ((size_t)N + 1) : 0;
-  if (rag) {
+
+  // ---------------------------------------------------------------- 2. ragged batch: the sample tables
+  // Lines: per width level  w[N+1] | cw[N+1].  Images: one set at input resolution  w[N+1] | h[N+1] | cw[N+1] | ch[N+1]
+  // (w / h carry one entry past N: the tile walks step onto "sample N" after their last unit).  Behind them the launches'
+  // own work tables (prefix sums of tiles / patches / bands per sample, N+1 entries each), appended while the launch list
+  // is built: the device buffer is sized for all of them up front.
+  bool ragged_tables() {
+    lstride = img ? 4 * ((size_t)N + 1) : 2 * ((size_t)N + 1);
+    const size_t tab_base = lstride * (img ? 1 : LW.size());
+    tab_cap = tab_base + 96 * ((size_t)N + 1);
     B->rag_host.assign(tab_base, 0);
     if (img) {
       int* w = B->rag_host.data();
@@ -787,11 +883,12 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
       w[N] = w[N - 1];
     }
     B->rag_host.reserve(tab_cap);
-    for (size_t i = 0; i < pool_->free_list.size(); ++i)
-      if (pool_->free_list[i].second >= tab_cap) {
-        B->rag_dev = pool_->free_list[i].first;
-        B->rag_cap = pool_->free_list[i].second;
-        pool_->free_list.erase(pool_->free_list.begin() + i);
+    auto& free_list = net.pool_->free_list;
+    for (size_t i = 0; i < free_list.size(); ++i)
+      if (free_list[i].second >= tab_cap) {
+        B->rag_dev = free_list[i].first;
+        B->rag_cap = free_list[i].second;
+        free_list.erase(free_list.begin() + i);
         break;
       }
     if (!B->rag_dev) {
@@ -799,26 +896,25 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
       HIP_OK(g_malloc(&B->rag_dev, cap * sizeof(int)));
       B->rag_cap = cap;
     }
+    rag_dev = B->rag_dev;
+    return true;
   }
-  const int* rag_dev = B->rag_dev;
-  auto rlevel = [&](const TensorDesc& t) {
+  RagLevel rlevel(const TensorDesc& t) const {
     RagLevel r;
     if (rag && t.lvl >= 0) {
       if (img) { r.w = rag_dev; r.h = r.w + (N + 1); r.cw = r.h + (N + 1); r.ch = r.cw + (N + 1); r.shift = t.lvl; }
       else { r.w = rag_dev + (size_t)t.lvl * lstride; r.cw = r.w + (N + 1); }
     }
     return r;
-  };
+  }
   // size of sample i on a tensor's level
-  auto sw_of = [&](const TensorDesc& t, int i) { return img ? widths[i] >> t.lvl : LW[t.lvl][i]; };
-  auto sh_of = [&](const TensorDesc& t, int i) { return img ? heights[i] >> t.lvl : t.h; };
-  auto min_w = [&](const TensorDesc& t) { return img ? iwmin >> t.lvl : lmin[t.lvl]; };
-  auto min_h = [&](const TensorDesc& t) { return img ? ihmin >> t.lvl : t.h; };
-  auto rows_of = [&](const TensorDesc& t) -> long { return img ? irows >> t.lvl : (long)N * t.h; };
+  int sw_of(const TensorDesc& t, int i) const { return img ? widths[i] >> t.lvl : LW[t.lvl][i]; }
+  int sh_of(const TensorDesc& t, int i) const { return img ? heights[i] >> t.lvl : t.h; }
+  int min_w(const TensorDesc& t) const { return img ? iwmin >> t.lvl : lmin[t.lvl]; }
+  int min_h(const TensorDesc& t) const { return img ? ihmin >> t.lvl : t.h; }
+  long rows_of(const TensorDesc& t) const { return img ? irows >> t.lvl : (long)N * t.h; }
   // a launch's work table: prefix sums of count(sample), memoised by key; returns its device address and total
-  std::map<std::string, std::pair<size_t, int>> tabs;
-  bool tab_overflow = false;
-  auto work_table = [&](const std::string& key, const std::function<int(int)>& count, int& total) -> const int* {
+  const int* work_table(const std::string& key, const std::function<int(int)>& count, int& total) {
     auto it = tabs.find(key);
     if (it == tabs.end()) {
       if (B->rag_host.size() + N + 1 > tab_cap) { tab_overflow = true; total = 0; return rag_dev; }
@@ -830,35 +926,38 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
     }
     total = it->second.second;
     return rag_dev + it->second.first;
-  };
-  auto tiles_table = [&](const TensorDesc& t, int th, int& total) {  // th x 16 pixel tiles per sample
+  }
+  const int* tiles_table(const TensorDesc& t, int th, int& total) {  // th x 16 pixel tiles per sample
     return work_table("tiles:" + std::to_string(t.lvl) + ":" + std::to_string(t.h) + ":" + std::to_string(th),  // (lines: tensors of one width level differ in height)
                       [&](int i) { return ((sh_of(t, i) + th - 1) / th) * ((sw_of(t, i) + 15) / 16); }, total);
-  };
-  // 2. arena with liveness reuse
-  const int nops = (int)plan_.ops.size();
+  }
+
+  // ---------------------------------------------------------------- 3. fusion decisions, in this order
+  void count_uses() {
+    uses.assign(plan.ntensors, 0);
+    for (auto& op : plan.ops) {
+      if (op.in >= 0) uses[op.in]++;
+      for (int t : op.ins) uses[t]++;
+      for (auto& st : op.ep) if (st.tid >= 0) uses[st.tid]++;
+    }
+    fuse = keep_all != 1 && rt_options().fuse;  // (OCR_FUSE=0: one launch per plan op, as the parity taps' keep_all = 1)
+    gate_src.assign(nops, -1); gate_tid.assign(nops, -1); xdw_of.assign(nops, -1); dwpw_of.assign(nops, -1);
+    dbhead_of.assign(nops, -1); cat_of.assign(nops, -1); rse_conv.assign(nops, -1);
+    folded.assign(nops, 0); fused_dw.assign(nops, 0); dw_rowsum.assign(nops, 0); rse_first.assign(nops, 0);
+  }
   // SE gate folding: `ew x -> x * gate[n][c]` whose only reader is a 1x1 conv disappears - the conv reads x and
   // the gate and forms the same product (one rounding) on its way into the matrix pipe.  Saves a full read +
   // write pass per SE block (cls: 9, rec: 2, det backbone: 2).  Not in keep-all mode (every plan tensor must
   // exist for the parity taps) and not with OCR_FUSE=0 (A/B; results are identical).
-  std::vector<int> gate_src(nops, -1), gate_tid(nops, -1);
-  std::vector<char> folded(nops, 0);
-  std::vector<int> uses(plan_.ntensors, 0);
-  for (auto& op : plan_.ops) {
-    if (op.in >= 0) uses[op.in]++;
-    for (int t : op.ins) uses[t]++;
-    for (auto& st : op.ep) if (st.tid >= 0) uses[st.tid]++;
-  }
-  const bool fuse = keep_all_ != 1 && rt_options().fuse;  // (OCR_FUSE=0: one launch per plan op, as the parity taps' keep_all = 1)
-  if (fuse) {
+  void plan_gate_fold() {
+    if (!fuse) return;
     for (int oi = 0; oi < nops; ++oi) {
-      auto& op = plan_.ops[oi];
-      if (op.kind != PlanOp::EW || op.ep.size() != 1 || op.ep[0].kind != EP_MULC || op.out == out_tid_ || uses[op.out] != 1) continue;
+      auto& op = plan.ops[oi];
+      if (op.kind != PlanOp::EW || op.ep.size() != 1 || op.ep[0].kind != EP_MULC || op.out == out_tid || uses[op.out] != 1) continue;
       for (int oj = oi + 1; oj < nops; ++oj) {
-        auto& c = plan_.ops[oj];
+        auto& c = plan.ops[oj];
         if (c.in != op.out) continue;
-        const bool one = c.kind == PlanOp::CONV && c.kh == 1 && c.kw == 1 && c.sh == 1 && c.sw == 1 && c.ph == 0 && c.pw == 0 && c.cin != 3;
-        if (one && !T[c.out].plain && T[op.in].pixels() < 0x7fffffffL) {
+        if (plain_1x1(c) && !T[c.out].plain && T[op.in].pixels() < 0x7fffffffL) {
           folded[oi] = 1;
           gate_src[oj] = op.in;
           gate_tid[oj] = op.ep[0].tid;
@@ -869,25 +968,23 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
   }
   // Expand 1x1 conv -> depthwise 5x5 on small maps (kernels_xdw.hip; the classifier's inverted-residual blocks): the conv
   // runs inside the depthwise op's launch, chunk by chunk into LDS; its output tensor never exists.  Uniform batches, f32.
-  std::vector<int> xdw_of(nops, -1);  // depthwise op -> the 1x1 conv it absorbs
-  if (fuse && !rag && !half_ && rt_options().xdw) {
+  void plan_xdw() {
+    if (!fuse || rag || half || !rt_options().xdw) return;
     auto bn_hswish = [](const std::vector<PlanStage>& ep) {
       return ep.size() == 2 && ep[0].kind == EP_BN && ep[1].kind == EP_ACT && ep[1].act == ACT_HSWISH;
     };
     for (int oi = 0; oi + 1 < nops; ++oi) {
-      const PlanOp& c = plan_.ops[oi];
-      const bool one = c.kind == PlanOp::CONV && c.kh == 1 && c.kw == 1 && c.sh == 1 && c.sw == 1 && c.ph == 0 && c.pw == 0 && c.cin != 3;
-      if (!one || gate_src[oi] >= 0 || c.out == out_tid_ || uses[c.out] != 1 || T[c.in].plain || T[c.out].plain || !bn_hswish(c.ep)) continue;
+      const PlanOp& c = plan.ops[oi];
+      if (!plain_1x1(c) || gate_src[oi] >= 0 || c.out == out_tid || uses[c.out] != 1 || T[c.in].plain || T[c.out].plain || !bn_hswish(c.ep)) continue;
       for (int oj = oi + 1; oj < nops; ++oj) {
-        const PlanOp& d = plan_.ops[oj];
+        const PlanOp& d = plan.ops[oj];
         if (d.kind == PlanOp::CONCAT || d.in != c.out) continue;
         if (d.kind == PlanOp::DW && d.kh == d.kw && bn_hswish(d.ep) && !T[d.out].plain && dev_vec("frag:" + c.w)) {
           XdwArgs q{};
           q.N = T[c.in].n; q.Hin = T[c.in].h; q.Hout = T[d.out].h; q.W = T[c.in].w; q.Cs_in = T[c.in].cs; q.Cs_e = T[d.out].cs;
-          const int tiles = (T[c.out].cs + 31) / 32, nt = conv_nt_for(tiles);
-          q.NTtot = (tiles + nt - 1) / nt * nt;
+          q.NTtot = nt_total(T[c.out].cs);
           q.K = d.kh; q.SH = d.sh; q.SW = d.sw; q.PH = d.ph; q.PW = d.pw;
-          if (T[d.out].w == T[c.in].w && T[c.out].cs == T[d.out].cs && launch_xdw(q, nullptr, true)) xdw_of[oj] = oi;
+          if (T[d.out].w == T[c.in].w && T[c.out].cs == T[d.out].cs && launch_xdw(q, nullptr, true)) { xdw_of[oj] = oi; fused_dw[oi] = 1; }  // (the absorbed 1x1 conv: no launch, no tensor)
         }
         break;
       }
@@ -895,51 +992,45 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
   }
   // Depthwise -> pointwise fusion (kernels_dwpw.hip): a depthwise conv whose only reader is an ungated 1x1 conv runs
   // inside that conv's launch; its output tensor never exists.
-  std::vector<int> dwpw_of(nops, -1);  // conv op -> the depthwise op it absorbs
-  if (fuse) {
+  void plan_dwpw() {
+    if (!fuse) return;
+    // both epilogues must be the folded LAB chains the kernel compiles in (fold_lab): bias | hsw6 in the depthwise half
+    // (its scale / shift absorbed by the conv), bias | hsw6 | sfma behind the conv
+    auto is_lab = [](const std::vector<PlanStage>& ep, bool sfma) {
+      return ep.size() == (sfma ? 3u : 2u) && ep[0].kind == EP_BIAS && ep[1].kind == EP_ACT && ep[1].act == ACT_HSW6 &&
+             (!sfma || ep[2].kind == EP_SFMA);
+    };
     for (int oi = 0; oi + 1 < nops; ++oi) {
-      auto& d = plan_.ops[oi];
-      if (d.kind != PlanOp::DW || d.out == out_tid_ || uses[d.out] != 1) continue;
-      // both epilogues must be the folded LAB chains the kernel compiles in (fold_lab): bias | hsw6 in the depthwise half
-      // (its scale / shift absorbed by the conv), bias | hsw6 | sfma behind the conv
-      auto is_lab = [](const std::vector<PlanStage>& ep, bool sfma) {
-        return ep.size() == (sfma ? 3u : 2u) && ep[0].kind == EP_BIAS && ep[1].kind == EP_ACT && ep[1].act == ACT_HSW6 &&
-               (!sfma || ep[2].kind == EP_SFMA);
-      };
-      if (!is_lab(d.ep, false)) continue;
+      auto& d = plan.ops[oi];
+      if (d.kind != PlanOp::DW || d.out == out_tid || uses[d.out] != 1 || !is_lab(d.ep, false)) continue;
       for (int oj = oi + 1; oj < nops; ++oj) {
-        auto& c = plan_.ops[oj];
+        auto& c = plan.ops[oj];
         if (c.in != d.out) continue;
-        const bool one = c.kind == PlanOp::CONV && c.kh == 1 && c.kw == 1 && c.sh == 1 && c.sw == 1 && c.ph == 0 && c.pw == 0 && c.cin != 3;
-        if (one && gate_src[oj] < 0 && !T[c.out].plain && is_lab(c.ep, true) && T[d.in].cs % 8 == 0 && !T[d.in].plain && c.cout % 8 == 0) {
+        if (plain_1x1(c) && gate_src[oj] < 0 && !T[c.out].plain && is_lab(c.ep, true) && T[d.in].cs % 8 == 0 && !T[d.in].plain && c.cout % 8 == 0) {
           // shape on the fused path?  (asks the launcher, which also raises the kernel's LDS limit on this device)
           DwPwArgs q{};
           q.K = d.kh; q.SH = d.sh; q.SW = d.sw;
           q.c.Cs_in = T[d.out].cs;
-          const int tiles = (T[c.out].cs + 31) / 32, nt = conv_nt_for(tiles);
-          q.c.NTtot = (tiles + nt - 1) / nt * nt;
+          q.c.NTtot = nt_total(T[c.out].cs);
           q.dw_ep.sfma = 0; q.pw_ep.sfma = 1;
           q.dw_wq16 = dev_vec("dwq16:" + d.w); q.dw_wq32 = dev_vec("dwq32:" + d.w);  // (the LDS-DMA form's instance, where there is one: its own LDS attribute)
-          q.c.half = half_ ? 1 : 0;  // (the f16 build's instance: its own LDS attribute)
+          q.c.half = half ? 1 : 0;  // (the f16 build's instance: its own LDS attribute)
           if (rag) q.rtiles = rag_dev;  // (the ragged instantiation is its own kernel: own LDS attribute)
-          if (d.kh == d.kw && launch_dwpw(q, nullptr, true)) dwpw_of[oj] = oi;
+          if (d.kh == d.kw && launch_dwpw(q, nullptr, true)) { dwpw_of[oj] = oi; fused_dw[oi] = 1; }
         }
         break;
       }
     }
   }
-  std::vector<char> fused_dw(nops, 0);
-  for (int oj = 0; oj < nops; ++oj) if (dwpw_of[oj] >= 0) fused_dw[dwpw_of[oj]] = 1;
-  for (int oj = 0; oj < nops; ++oj) if (xdw_of[oj] >= 0) fused_dw[xdw_of[oj]] = 1;  // (the absorbed 1x1 conv: no launch, no tensor)
-  // ---- depthwise conv -> global average pool (the SE blocks): the conv leaves the pool's row sums (its first pass, a
+  // Depthwise conv -> global average pool (the SE blocks): the conv leaves the pool's row sums (its first pass, a
   // second full read of the tensor otherwise) while it writes the tensor; only the column pass stays a launch.  Needs
   // enough bands (a thread owns whole rows then) to fill the chip.
-  std::vector<char> dw_rowsum(nops, 0);
-  if (fuse) {
+  void plan_dw_rowsum() {
+    if (!fuse) return;
     for (int oi = 1; oi < nops; ++oi) {
-      const PlanOp& g = plan_.ops[oi];
-      const PlanOp& d = plan_.ops[oi - 1];
-      if (g.kind != PlanOp::GAP || d.kind != PlanOp::DW || d.out != g.in || fused_dw[oi - 1] || d.out == out_tid_) continue;
+      const PlanOp& g = plan.ops[oi];
+      const PlanOp& d = plan.ops[oi - 1];
+      if (g.kind != PlanOp::GAP || d.kind != PlanOp::DW || d.out != g.in || fused_dw[oi - 1] || d.out == out_tid) continue;
       if (xdw_of[oi - 1] >= 0) { dw_rowsum[oi - 1] = 1; continue; }  // (that kernel leaves the row sums whatever the size and stride)
       const TensorDesc& o = T[d.out];
       const int rows_per_band = (rag ? min_h(o) : o.h) >= 2 ? 2 : 1;
@@ -949,37 +1040,33 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
       if (threads >= min_threads && d.sh == 1 && d.sw == 1) dw_rowsum[oi - 1] = 1;
     }
   }
-  // ---- DB head: deconv (C -> C, bias + BN + relu) -> deconv (C -> 1, bias + sigmoid) as one kernel; the C-channel map
+  // DB head: deconv (C -> C, bias + BN + relu) -> deconv (C -> 1, bias + sigmoid) as one kernel; the C-channel map
   // between them (1.4 GB at configs[1]) is never written.
-  std::vector<int> dbhead_of(nops, -1);  // tail op -> the deconv it absorbs
-  if (fuse) {
+  void plan_db_head() {
+    if (!fuse) return;
     for (int oi = 0; oi + 1 < nops; ++oi) {
-      const PlanOp& d = plan_.ops[oi];
-      const PlanOp& t = plan_.ops[oi + 1];
+      const PlanOp& d = plan.ops[oi];
+      const PlanOp& t = plan.ops[oi + 1];
       if (d.kind != PlanOp::DECONV || d.cout == 1 || t.kind != PlanOp::DECONV || t.cout != 1 || t.in != d.out) continue;
-      if (uses[d.out] != 1 || d.out == out_tid_ || d.cin != 24 || d.cout != 24 || T[d.in].cs != 24) continue;
+      if (uses[d.out] != 1 || d.out == out_tid || d.cin != 24 || d.cout != 24 || T[d.in].cs != 24) continue;
       if (d.ep.size() != 3 || d.ep[0].kind != EP_BIAS || d.ep[1].kind != EP_BN || d.ep[2].kind != EP_ACT || d.ep[2].act != ACT_RELU) continue;
       dbhead_of[oi + 1] = oi;
       fused_dw[oi] = 1;  // (same bookkeeping as a fused depthwise conv: no launch, no tensor)
     }
   }
-  // ---- the DB neck's concat (four 24-channel maps, upsampled x1 / x2 / x4 / x8) -> conv 3x3 96 -> 24: the conv's LDS-tile
-  // fill reads the four sources itself (kernels_net.hip, ConvArgs::cat_*); the 96-channel tensor (1.4 GB at configs[1]) is never
-  // written.  Only where the conv runs on a kernel that has the folded fill: the 4x4x1 form (f32) or the f16-staged form
-  // (precision "fp16", uniform batches).
-  std::vector<int> cat_of(nops, -1);  // conv op -> the concat it absorbs
-  // The recognizer's neck has the same shape without upsampling: concat (two 480-channel sequences) -> conv 1x3 960 -> 60; the
-  // LDS-staged conv (f32) reads chunk c of its input from source c * BK / 480 (conv_lds_kernel, load_a).
-  if (fuse && !half_) {
+  // The recognizer's neck: concat (two 480-channel sequences, no upsampling) -> conv 1x3 960 -> 60; the LDS-staged conv
+  // (f32) reads chunk c of its input from source c * BK / 480 (conv_lds_kernel, load_a).
+  void plan_concat_same_res() {
+    if (!fuse || half) return;
     for (int oi = 0; oi + 1 < nops; ++oi) {
-      const PlanOp& k = plan_.ops[oi];
-      if (k.kind != PlanOp::CONCAT || k.out == out_tid_ || uses[k.out] != 1 || k.ins.size() < 2 || k.ins.size() > 4) continue;
+      const PlanOp& k = plan.ops[oi];
+      if (k.kind != PlanOp::CONCAT || k.out == out_tid || uses[k.out] != 1 || k.ins.size() < 2 || k.ins.size() > 4) continue;
       bool same = true;
       for (size_t j = 0; j < k.ins.size(); ++j)
         same = same && k.ups[j] == 1 && T[k.ins[j]].cs == T[k.ins[0]].cs && !T[k.ins[j]].plain && T[k.ins[j]].lvl == T[k.out].lvl;
       if (!same || T[k.ins[0]].cs % 32 || T[k.ins[0]].cs * (int)k.ins.size() != T[k.out].cs) continue;
       for (int oj = oi + 1; oj < nops; ++oj) {
-        const PlanOp& c = plan_.ops[oj];
+        const PlanOp& c = plan.ops[oj];
         if (c.in != k.out) continue;
         const bool lds_conv = c.kind == PlanOp::CONV && c.kh * c.kw > 1 && c.sh == 1 && c.sw == 1 && !(c.kh == 3 && c.kw == 3 && c.cin == 96);
         if (lds_conv && !T[c.out].plain && gate_src[oj] < 0 && dwpw_of[oj] < 0) {
@@ -990,22 +1077,27 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
       }
     }
   }
-  if (fuse && (!rag || img)) {
+  // The DB neck's concat (four 24-channel maps, upsampled x1 / x2 / x4 / x8) -> conv 3x3 96 -> 24: the conv's LDS-tile
+  // fill reads the four sources itself (kernels_net.hip, ConvArgs::cat_*); the 96-channel tensor (1.4 GB at configs[1]) is never
+  // written.  Only where the conv runs on a kernel that has the folded fill: the 4x4x1 form (f32) or the f16-staged form
+  // (precision "fp16", uniform batches).
+  void plan_concat_neck() {
+    if (!fuse || (rag && !img)) return;
     for (int oi = 0; oi + 1 < nops; ++oi) {
-      const PlanOp& k = plan_.ops[oi];
-      if (k.kind != PlanOp::CONCAT || folded[oi] || k.out == out_tid_ || uses[k.out] != 1 || k.ins.size() != 4 || T[k.out].cs != 96) continue;
+      const PlanOp& k = plan.ops[oi];
+      if (k.kind != PlanOp::CONCAT || folded[oi] || k.out == out_tid || uses[k.out] != 1 || k.ins.size() != 4 || T[k.out].cs != 96) continue;
       if (T[k.out].numel() >= (1ul << 31)) continue;  // (the folded fill indexes its sources with 32 bits)
       bool same = true;
       for (int t : k.ins) same = same && T[t].cs * (int)k.ins.size() == 96 && T[t].f16 == T[k.out].f16 && !T[t].plain;
       if (!same) continue;
       for (int oj = oi + 1; oj < nops; ++oj) {
-        const PlanOp& c = plan_.ops[oj];
+        const PlanOp& c = plan.ops[oj];
         if (c.in != k.out) continue;
         const bool conv33 = c.kind == PlanOp::CONV && c.kh == 3 && c.kw == 3 && c.sh == 1 && c.sw == 1 && c.ph == 1 && c.pw == 1 && c.cin == 96 && c.cout == 24;
         bool ep_ok = true;
         for (auto& st : c.ep) ep_ok = ep_ok && st.kind != EP_ADDUP && !(img && st.kind == EP_MULC);
-        bool kernel_ok = half_ ? (rt_options().mfma_x16 && dev_vec("frag16x:" + c.w))
-                               : (rt_options().conv_c24 && dev_vec("c24:" + c.w) != nullptr);
+        bool kernel_ok = half ? (rt_options().mfma_x16 && dev_vec("frag16x:" + c.w))
+                              : (rt_options().conv_c24 && dev_vec("c24:" + c.w) != nullptr);
         if (conv33 && ep_ok && kernel_ok) {
           // the folded fill exists in ONE kernel per precision: ask its launcher now, on the device that will run it (shape
           // checks and the dynamic-LDS attribute) - a refusal at launch time would leave the conv without an input tensor.
@@ -1013,12 +1105,12 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
           ConvArgs q{};
           q.KH = q.KW = 3; q.PH = q.PW = 1; q.H = q.OH = T[c.out].h; q.W = q.OW = T[c.out].w; q.N = T[c.out].n;
           q.Cs_in = 96; q.Cs_out = T[c.out].cs; q.Cout = c.cout; q.out_mode = OUT_C8I; q.NTtot = 1;
-          q.cat_n = 4; q.cat_cs = 24; q.half = half_ ? 1 : 0;
+          q.cat_n = 4; q.cat_cs = 24; q.half = half ? 1 : 0;
           if (rag) { q.rin.w = q.rout.w = rag_dev; q.rin.h = q.rout.h = rag_dev; q.rtiles = rag_dev; q.rtiles_total = 1; }
           Epilogue qe{};
           qe.n = (int)std::min<size_t>(c.ep.size(), OCR_MAX_EP);
           for (int k = 0; k < qe.n; ++k) qe.st[k].kind = c.ep[k].kind;
-          if (half_) { q.wfrag_x16 = dev_vec("frag16x:" + c.w); kernel_ok = launch_conv3x3_tile(q, qe, 1, nullptr, true); }
+          if (half) { q.wfrag_x16 = dev_vec("frag16x:" + c.w); kernel_ok = launch_conv3x3_tile(q, qe, 1, nullptr, true); }
           else kernel_ok = launch_conv3x3_c24(q, qe, dev_vec("c24:" + c.w), nullptr, true);
         }
         if (conv33 && ep_ok && kernel_ok && !T[c.out].plain && gate_src[oj] < 0 && dwpw_of[oj] < 0) {
@@ -1029,583 +1121,617 @@ bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const i
       }
     }
   }
-  // ---- RSE blocks of the detector's neck: conv 1x1 (Cin <= 24, no epilogue) -> gap -> sefc -> ew (x * g + x [+ upsampled]).
+  // RSE blocks of the detector's neck: conv 1x1 (Cin <= 24, no epilogue) -> gap -> sefc -> ew (x * g + x [+ upsampled]).
   // Materialised, the conv's 96-channel output is written once and read twice (pool, ew) before the result is written
   // again: three passes over 1.4 GB at 240 x 240 x 64 images for a K = 12 matrix product.  Instead the conv runs twice:
   // first as conv_rowsum_kernel, which leaves only the pool's row sums, then - with the gate known - as the ordinary
   // conv kernel with the ew's stages in its epilogue (EP_GATERES + the FPN's addup), writing the block's output.  Both
   // passes compute the same chain per output, so nothing changes bit for bit.  Uniform batches and ragged batches of images
   // (the conv epilogue's per-image stages decode (n, y, x) from either).
-  std::vector<int> rse_conv(nops, -1);   // ew op -> the conv it absorbs
-  std::vector<char> rse_first(nops, 0);  // that conv: its launch is the row-sum pass, its tensor never exists
-  if (fuse && (!rag || img)) {
+  void plan_rse() {
+    if (!fuse || (rag && !img)) return;
     for (int oi = 0; oi + 3 < nops; ++oi) {
-      const PlanOp& c = plan_.ops[oi];
-      const PlanOp& g = plan_.ops[oi + 1];
-      const PlanOp& f = plan_.ops[oi + 2];
-      const PlanOp& e = plan_.ops[oi + 3];
-      const bool one = c.kind == PlanOp::CONV && c.kh == 1 && c.kw == 1 && c.sh == 1 && c.sw == 1 && c.ph == 0 && c.pw == 0 && c.cin != 3;
-      if (!one || !c.ep.empty() || c.cin > 24 || T[c.out].plain || T[c.in].plain || gate_src[oi] >= 0 || dwpw_of[oi] >= 0) continue;
+      const PlanOp& c = plan.ops[oi];
+      const PlanOp& g = plan.ops[oi + 1];
+      const PlanOp& f = plan.ops[oi + 2];
+      const PlanOp& e = plan.ops[oi + 3];
+      if (!plain_1x1(c) || !c.ep.empty() || c.cin > 24 || T[c.out].plain || T[c.in].plain || gate_src[oi] >= 0 || dwpw_of[oi] >= 0) continue;
       if (g.kind != PlanOp::GAP || g.in != c.out || f.kind != PlanOp::SEFC || f.in != g.out || e.kind != PlanOp::EW || e.in != c.out) continue;
       if (e.ep.size() < 2 || e.ep[0].kind != EP_MULC || e.ep[0].tid != f.out || e.ep[1].kind != EP_ADDT || e.ep[1].tid != c.out) continue;
       bool rest_ok = true;
       for (size_t k = 2; k < e.ep.size(); ++k) rest_ok = rest_ok && (e.ep[k].kind == EP_ADDUP || e.ep[k].kind == EP_ADDT) && e.ep[k].tid != c.out;
-      if (!rest_ok || uses[c.out] != 3 || c.out == out_tid_ || (T[c.in].cs != 16 && T[c.in].cs != 24)) continue;
+      if (!rest_ok || uses[c.out] != 3 || c.out == out_tid || (T[c.in].cs != 16 && T[c.in].cs != 24)) continue;
       rse_conv[oi + 3] = oi;
       rse_first[oi] = 1;
     }
   }
-  std::vector<int> last(plan_.ntensors, -1);
-  for (int oi = 0; oi < nops; ++oi) {
-    auto& op = plan_.ops[oi];
-    if (folded[oi] || fused_dw[oi]) continue;  // its reads happen in the conv it was folded / fused into
-    if (rse_conv[oi] >= 0) {  // the second conv pass: reads the conv's input again, the gate and the upsampled operand; never the conv's (dead) output
-      const PlanOp& c = plan_.ops[rse_conv[oi]];
-      last[c.in] = oi;
-      for (auto& st : op.ep) if (st.tid >= 0 && st.tid != c.out) last[st.tid] = oi;
-      continue;
-    }
-    if (oi > 0 && rse_first[oi - 1]) continue;  // the pool after a row-sum pass reads gap_part_, not the conv's tensor
-    if (gate_src[oi] >= 0) { last[gate_src[oi]] = oi; last[gate_tid[oi]] = oi; }
-    else if (dwpw_of[oi] >= 0) last[plan_.ops[dwpw_of[oi]].in] = oi;
-    else if (xdw_of[oi] >= 0) last[plan_.ops[xdw_of[oi]].in] = oi;
-    else if (dbhead_of[oi] >= 0) last[plan_.ops[dbhead_of[oi]].in] = oi;
-    else if (cat_of[oi] >= 0) { for (int t : plan_.ops[cat_of[oi]].ins) last[t] = oi; }
-    else if (op.in >= 0) last[op.in] = oi;
-    for (int t : op.ins) last[t] = oi;
-    for (auto& st : op.ep) if (st.tid >= 0) last[st.tid] = oi;
-  }
-  last[out_tid_] = nops + 1;
-  struct Blk { size_t off, sz; };
-  std::vector<Blk> freeb;
-  size_t top = 0;
-  size_t gap_need = 0;
-  auto alloc = [&](size_t n) {
-    n = (n + 63) & ~(size_t)63;
-    int best = -1;
-    for (int i = 0; i < (int)freeb.size(); ++i)
-      if (freeb[i].sz >= n && (best < 0 || freeb[i].sz < freeb[best].sz)) best = i;
-    if (best >= 0) {
-      size_t off = freeb[best].off;
-      if (freeb[best].sz == n) freeb.erase(freeb.begin() + best);
-      else { freeb[best].off += n; freeb[best].sz -= n; }
-      return off;
-    }
-    size_t off = top;
-    top += n;
-    return off;
-  };
-  auto release = [&](size_t off, size_t n) {
-    n = (n + 63) & ~(size_t)63;
-    freeb.push_back({off, n});
-    std::sort(freeb.begin(), freeb.end(), [](const Blk& a, const Blk& b) { return a.off < b.off; });
-    for (size_t i = 0; i + 1 < freeb.size();) {
-      if (freeb[i].off + freeb[i].sz == freeb[i + 1].off) { freeb[i].sz += freeb[i + 1].sz; freeb.erase(freeb.begin() + i + 1); }
-      else ++i;
-    }
-    if (!freeb.empty() && freeb.back().off + freeb.back().sz == top) { top = freeb.back().off; freeb.pop_back(); }
-  };
-  for (int oi = 0; oi < nops; ++oi) {
-    auto& op = plan_.ops[oi];
-    if (folded[oi] || fused_dw[oi]) { T[op.out].offset = 0; continue; }  // never materialised
-    if (rse_first[oi]) T[op.out].offset = 0;  // (the row-sum pass writes gap_part_ only)
-    else if (op.out >= 0) T[op.out].offset = alloc(T[op.out].numel());
-    if (op.kind == PlanOp::GAP) gap_need = std::max(gap_need, (size_t)(rag ? rows_of(T[op.in]) : (long)T[op.in].n * T[op.in].h) * T[op.in].cs);
-    // free tensors whose last reader is this op (never the op's own output)
-    for (int t = 1; t < plan_.ntensors; ++t)
-      if (keep_all_ == 0 && last[t] == oi && t != op.out && T[t].numel()) release(T[t].offset, T[t].numel());
-  }
-  // `top` may have shrunk at the end; capacity must cover the high-water mark
-  size_t high = 0;
-  std::vector<char> dead(plan_.ntensors, 0);
-  for (int oi = 0; oi < nops; ++oi) if (folded[oi] || fused_dw[oi] || rse_first[oi]) dead[plan_.ops[oi].out] = 1;
-  B->exists.assign(plan_.ntensors, 0);
-  for (int t = 1; t < plan_.ntensors; ++t) B->exists[t] = !dead[t];
-  for (int t = 1; t < plan_.ntensors; ++t) if (!dead[t]) high = std::max(high, T[t].offset + ((T[t].numel() + 63) & ~(size_t)63));
-  if (high > arena_cap_) {
-    if (arena_) (void)g_free(arena_);
+
+  // ---------------------------------------------------------------- 4. arena with liveness reuse
+  // grows one of the network's shared device buffers (`what`: the allocation as the error text names it)
+  bool grow(float*& buf, size_t& cap, size_t need, size_t slack, const char* what) {
+    if (need <= cap) return true;
+    if (buf) (void)g_free(buf);
     moved = true;
-    arena_ = nullptr;
-    arena_cap_ = 0;
-    HIP_OK(g_malloc(&arena_, (high + 64) * sizeof(float)));  // + 256 B: conv1x1 block loads may run past the last row
-    arena_cap_ = high;
+    buf = nullptr;
+    cap = 0;
+    const hipError_t e = g_malloc(&buf, (need + slack) * sizeof(float));
+    if (e != hipSuccess) { err = std::string(what) + ": " + hipGetErrorString(e); return false; }
+    cap = need;
+    return true;
   }
-  if (gap_need > gap_part_cap_) {
-    if (gap_part_) (void)g_free(gap_part_);
-    moved = true;
-    gap_part_ = nullptr;
-    gap_part_cap_ = 0;
-    HIP_OK(g_malloc(&gap_part_, gap_need * sizeof(float)));
-    gap_part_cap_ = gap_need;
+  bool plan_arena() {
+    std::vector<int> last(plan.ntensors, -1);  // per tensor: the last op whose launch reads it
+    for (int oi = 0; oi < nops; ++oi) {
+      auto& op = plan.ops[oi];
+      if (folded[oi] || fused_dw[oi]) continue;  // its reads happen in the conv it was folded / fused into
+      if (rse_conv[oi] >= 0) {  // the second conv pass: reads the conv's input again, the gate and the upsampled operand; never the conv's (dead) output
+        const PlanOp& c = plan.ops[rse_conv[oi]];
+        last[c.in] = oi;
+        for (auto& st : op.ep) if (st.tid >= 0 && st.tid != c.out) last[st.tid] = oi;
+        continue;
+      }
+      if (oi > 0 && rse_first[oi - 1]) continue;  // the pool after a row-sum pass reads gap_part_, not the conv's tensor
+      if (gate_src[oi] >= 0) { last[gate_src[oi]] = oi; last[gate_tid[oi]] = oi; }
+      else if (dwpw_of[oi] >= 0) last[plan.ops[dwpw_of[oi]].in] = oi;
+      else if (xdw_of[oi] >= 0) last[plan.ops[xdw_of[oi]].in] = oi;
+      else if (dbhead_of[oi] >= 0) last[plan.ops[dbhead_of[oi]].in] = oi;
+      else if (cat_of[oi] >= 0) { for (int t : plan.ops[cat_of[oi]].ins) last[t] = oi; }
+      else if (op.in >= 0) last[op.in] = oi;
+      for (int t : op.ins) last[t] = oi;
+      for (auto& st : op.ep) if (st.tid >= 0) last[st.tid] = oi;
+    }
+    last[out_tid] = nops + 1;
+    ArenaPlan arena;
+    B->exists.assign(plan.ntensors, 1);
+    B->exists[0] = 0;
+    for (int oi = 0; oi < nops; ++oi) {
+      auto& op = plan.ops[oi];
+      if (folded[oi] || fused_dw[oi] || rse_first[oi]) B->exists[op.out] = 0;  // never materialised (the row-sum pass writes gap_part_ only)
+      if (folded[oi] || fused_dw[oi]) { T[op.out].offset = 0; continue; }
+      if (rse_first[oi]) T[op.out].offset = 0;
+      else if (op.out >= 0) T[op.out].offset = arena.alloc(T[op.out].numel());
+      if (op.kind == PlanOp::GAP) gap_need = std::max(gap_need, (size_t)(rag ? rows_of(T[op.in]) : (long)T[op.in].n * T[op.in].h) * T[op.in].cs);
+      // free tensors whose last reader is this op (never the op's own output)
+      for (int t = 1; t < plan.ntensors; ++t)
+        if (keep_all == 0 && last[t] == oi && t != op.out && T[t].numel()) arena.release(T[t].offset, T[t].numel());
+    }
+    // + 256 B: conv1x1 block loads may run past the last row
+    return grow(net.arena_, net.arena_cap_, arena.high(), 64, "g_malloc(&arena_, (high + 64) * sizeof(float))") &&
+           grow(net.gap_part_, net.gap_part_cap_, gap_need, 0, "g_malloc(&gap_part_, gap_need * sizeof(float))");
   }
-  // 3. launches
-  auto EB = [](const TensorDesc& t) { return t.f16 ? 2.0 : 4.0; };  // bytes per stored element (the launches' algorithmic bytes)
-  char nm[160];
-  for (int oi = 0; oi < nops; ++oi) {
-    if (plan_.ops[oi].kind == PlanOp::OUTPUT || folded[oi] || fused_dw[oi]) continue;
+
+  // ---------------------------------------------------------------- 5. launches: one function per launch kind
+  // RSE block, first pass: the pool's row sums, nothing else
+  bool emit_conv_rowsum(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[op.in], &o = T[op.out];
+    ConvRowsumArgs a{};
+    a.in = at(in); a.w = dev_vec("rsw:" + op.w); a.part = net.gap_part_;
+    a.rows = rag ? rows_of(in) : (long)in.n * in.h; a.W = in.w; a.Cin = op.cin; a.Cs_in = in.cs; a.Cs_out = o.cs;
+    a.N = in.n; a.H = in.h; a.rag = rlevel(in);
+    a.h16 = in.f16;
+    if (!a.w) { err = "RSE block: no row-sum weight image for " + op.w; return false; }
+    L.name = fmt("%s.%02d.conv1x1_%d_%d_rowsum", pname(), oi, op.cin, op.cout);
+    L.flops = 2.0 * in.pixels() * op.cin * op.cout;
+    L.bytes = EB(in) * in.pixels() * op.cin + 4.0 * a.rows * op.cout;
+    L.fn = [net = &net, a](hipStream_t s) {
+      if (!launch_conv_rowsum(a, s)) net->launch_error_ = "launch_conv_rowsum: shape accepted at bind time was refused at launch";
+    };
+    return true;
+  }
+
+  bool emit_stem(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[gate_src[oi] >= 0 ? gate_src[oi] : op.in], &o = T[op.out];
+    Epilogue ep;
+    if (!net.build_epilogue(op, ep, false, err)) return false;
+    StemArgs a{};
+    a.out = at(o); a.w = dev_vec("stem:" + op.w);
+    a.N = in.n; a.H = in.h; a.W = in.w; a.OH = o.h; a.OW = o.w; a.Cs_out = o.cs;
+    a.KH = op.kh; a.KW = op.kw; a.SH = op.sh; a.SW = op.sw; a.PH = op.ph; a.PW = op.pw;
+    a.M = o.pixels();
+    a.rin = rlevel(in); a.rout = rlevel(o);
+    a.h16 = o.f16;
+    if (in.f16) { err = "stem input must be the plain f32 image"; return false; }
+    if (o.cs != 8 && o.cs != 16) { err = "stem width not on this path"; return false; }
+    L.name = fmt("%s.%02d.stem%dx%d_3_%d", pname(), oi, op.kh, op.kw, op.cout);
+    L.flops = 2.0 * a.M * op.kh * op.kw * 3 * op.cout;
+    L.bytes = 4.0 * in.numel() + EB(o) * a.M * op.cout;
+    const bool ext_in = (op.in == 0);
+    const float* in_ptr = ext_in ? nullptr : at(in);
+    L.fn = [net = &net, a, ep, ext_in, in_ptr](hipStream_t s) mutable {
+      StemArgs b = a;
+      b.in = ext_in ? net->bound_x_ : in_ptr;
+      launch_stem(b, ep, s);
+    };
+    return true;
+  }
+
+  // tail: deconv -> 1 channel, bias (scalar), sigmoid  (+ fused u8 threshold); with the deconv before it as the fused DB head
+  bool emit_det_tail(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[gate_src[oi] >= 0 ? gate_src[oi] : op.in], &o = T[op.out];
+    float bias = 0.f;
+    bool ok = op.ep.size() == 2 && (op.ep[0].kind == EP_SADD || op.ep[0].kind == EP_BIAS) && op.ep[1].kind == EP_ACT && op.ep[1].act == ACT_SIGMOID;
+    if (!ok) { err = "unexpected DB head tail"; return false; }
+    bias = net.host_w_[op.ep[0].n0].data[0];
+    DetTailArgs a{};
+    a.in = at(in); a.prob = at(o); a.bitmap = net.det_bitmap_; a.w = dev_vec("tail:" + op.w);
+    a.N = in.n; a.H = in.h; a.W = in.w; a.C = op.cin; a.Cs = in.cs; a.bias = bias; a.ithresh = net.det_ithresh_;
+    a.M = in.pixels();
+    a.h16 = in.f16;
+    L.name = fmt("%s.%02d.det_tail", pname(), oi);
+    L.flops = 2.0 * a.M * op.cin * 4;
+    L.bytes = EB(in) * a.M * op.cin + 4.0 * a.M * 4 + (net.det_bitmap_ ? 1.0 * a.M * 4 : 0.0);
+    L.fn = [a](hipStream_t s) { launch_det_tail(a, s); };
+    if (img && dbhead_of[oi] < 0) { err = "ragged batch of images: the DB head needs its fused kernel (production launch list, OCR_FUSE on)"; return false; }
+    if (dbhead_of[oi] < 0) return true;
+    const PlanOp& d = plan.ops[dbhead_of[oi]];
+    const TensorDesc& din = T[d.in];
+    Epilogue epd;
+    if (!net.build_epilogue(d, epd, true, err)) return false;
+    DbHeadArgs h{};
+    h.in = at(din); h.prob = at(o); h.bitmap = net.det_bitmap_;
+    h.w1 = dev_vec("dbh1:" + d.w); h.bias1 = epd.st[0].v0; h.bn_s = epd.st[1].v0; h.bn_t = epd.st[1].v1;
+    if (d.cin == 24 && d.cout == 24) h.wfrag = dev_vec("dbhf:" + d.w);
+    h.w2 = a.w; h.M = din.pixels(); h.N = din.n; h.H = din.h; h.W = din.w; h.Cs = din.cs;
+    h.bias2 = a.bias; h.ithresh = a.ithresh;
+    h.h16 = din.f16;
+    if (img) h.rin = rlevel(din);
+    L.name = fmt("%s.%02d.db_head_%d", pname(), dbhead_of[oi], d.cin);
+    L.flops = 2.0 * h.M * (4.0 * d.cin * d.cout + 16.0 * d.cout);
+    L.bytes = EB(din) * h.M * d.cin + 4.0 * h.M * 16 + (net.det_bitmap_ ? 1.0 * h.M * 16 : 0.0);
+    const int C = d.cin;
+    L.fn = [net = &net, h, C](hipStream_t s) {
+      if (!launch_db_head(h, C, s)) net->launch_error_ = "launch_db_head: shape accepted at bind time was refused at launch";
+    };
+    return true;
+  }
+
+  // linear -> softmax with only (arg max, max prob) wanted: the softmax is folded into the linear's
+  // epilogue (no logits tensor) and a per-row combine; canonical groups are 128 columns wide
+  bool dense_fused_head(int oi, const PlanOp& op, ConvArgs& a, long hrows, int tiles, int nt) {
+    const bool fuse_head = op.kind == PlanOp::LINEAR && T[op.out].plain && oi + 1 < nops && plan.ops[oi + 1].kind == PlanOp::SOFTMAX &&
+                           plan.ops[oi + 1].in == op.out && (net.head_amax_ || net.head_pmax_) && !net.head_probs_ && keep_all == 0 &&
+                           (tiles <= 4 || nt == 4);
+    if (!fuse_head) return true;
+    a.out_mode = OUT_HEAD;
+    const int groups = a.NTtot / nt;
+    if (!grow(net.head_part_, net.head_part_cap_, (size_t)hrows * groups * 3, 0, "g_malloc(&head_part_, need * sizeof(float))")) return false;
+    a.head_max = net.head_part_;
+    a.head_sum = net.head_part_ + (size_t)hrows * groups;
+    a.head_idx = (int*)(net.head_part_ + (size_t)hrows * groups * 2);
+    net.fused_head_rows_ = hrows;
+    net.fused_head_groups_ = groups;
+    return true;
+  }
+
+  // dense conv / linear / transposed conv on the matrix cores (with a folded concat or gate, or as the 1x1 half of a fused
+  // depthwise block)
+  bool emit_dense(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[gate_src[oi] >= 0 ? gate_src[oi] : op.in], &o = T[op.out];
+    Epilogue ep;
+    if (!net.build_epilogue(op, ep, true, err)) return false;
+    ConvArgs a{};
+    // precision "fp16": a conv on an f16 tensor runs in f16; one on a per-image f32 vector (the classifier's pool -> fc)
+    // keeps the f32 kernel and fragments
+    const bool hconv = half && in.f16;
+    a.in = at(in); a.out = at(o); a.wfrag = dev_vec((hconv ? "frag16:" : "frag:") + op.w);
+    a.half = hconv ? 1 : 0;
+    if (hconv && op.kind == PlanOp::CONV) a.wfrag_x16 = dev_vec("frag16x:" + op.w);  // (null: no such image - other than 1x1 and the 3x3 96-channel convs, or an odd number of octets)
+    if (!o.plain && o.f16 != in.f16) { err = "precision fp16: a dense conv between tensors of different storage"; return false; }
+    a.N = in.n; a.H = in.h; a.W = in.w; a.Cs_in = in.cs; a.C8 = in.cs / 8;
+    a.KH = op.kh; a.KW = op.kw; a.PH = op.ph; a.PW = op.pw;
+    a.need_nyx = 0;
+    if (in.plain) { err = "conv input must be C8I"; return false; }
+    if (rag) {
+      // pointwise, or a stride-1 "same" conv (the recognizer's 1x3 neck convs, the detector's 3x3 neck / head convs):
+      // rows in = rows out, one level
+      if (in.lvl < 0 || o.lvl != in.lvl || o.h != in.h || op.kind == PlanOp::DECONV) { err = "ragged batch: dense conv must keep its input's shape"; return false; }
+      for (auto& st : op.ep) if (st.kind == EP_ADDUP && !img) { err = "ragged batch of lines: an upsampled operand after a dense conv is not on this path"; return false; }
+      a.rin = rlevel(in); a.rout = rlevel(o);
+      if (img && op.kh == 3 && op.kw == 3) a.rtiles = tiles_table(o, 8, a.rtiles_total);  // (the 8x16 LDS-tile kernel)
+    }
+    if (op.kind == PlanOp::DECONV) {
+      a.OH = in.h; a.OW = in.w; a.Cs_out = o.cs; a.Cout = op.cout; a.CoutPadded = o.cs;
+      a.ColsStore = 4 * o.cs; a.out_mode = OUT_DECONV; a.KH = a.KW = 1; a.PH = a.PW = 0;
+    } else {
+      a.OH = o.h; a.OW = o.w; a.Cs_out = o.cs; a.Cout = op.cout; a.CoutPadded = o.cs;
+      a.ColsStore = o.plain ? op.cout : o.cs; a.out_mode = o.plain ? OUT_PLAIN : OUT_C8I;
+    }
+    const int tiles = (a.ColsStore + 31) / 32;
+    const int nt = conv_nt_for(tiles);
+    a.NTtot = nt_total(a.ColsStore);
+    if (!dense_fused_head(oi, op, a, in.pixels(), tiles, nt)) return false;
+    a.zeros = dev_vec("zeros");
+    double cat_bytes = 0;
+    if (cat_of[oi] >= 0) {  // the folded concat: the tile fill reads its sources
+      const PlanOp& k = plan.ops[cat_of[oi]];
+      a.in = nullptr;
+      a.cat_n = (int)k.ins.size();
+      a.cat_cs = T[k.ins[0]].cs;
+      for (int j = 0; j < a.cat_n; ++j) {
+        a.cat_src[j] = at(T[k.ins[j]]);
+        a.cat_up[j] = k.ups[j];
+        if (k.ups[j] < 1 || (k.ups[j] & (k.ups[j] - 1))) { err = "folded concat: upsampling factor is not a power of two"; return false; }
+        cat_bytes += EB(T[k.ins[j]]) * T[k.ins[j]].numel();
+      }
+    }
+    if (gate_src[oi] >= 0) { a.gate = at(T[gate_tid[oi]]); a.gate_hw = in.h * in.w; }
+    a.M = (long)in.n * a.OH * a.OW;
+    if (op.kind == PlanOp::LINEAR) a.M = (long)in.n * in.h * in.w;
+    if (rag) a.M = in.pixels();
+    const int taps = a.KH * a.KW;
+    const char* kind = op.kind == PlanOp::DECONV ? "deconv" : (op.kind == PlanOp::LINEAR ? "linear" : "conv");
+    L.name = fmt("%s.%02d.%s%dx%d_%d_%d", pname(), oi, kind, a.KH, a.KW, op.cin, op.cout);
+    const double cols = op.kind == PlanOp::DECONV ? 4.0 * op.cout : op.cout;
+    L.flops = 2.0 * a.M * taps * op.cin * cols;
+    if (a.gate) L.name += "_gated";
+    if (a.cat_n) L.name += "_cat" + std::to_string(a.cat_n);
+    L.bytes = (a.cat_n ? cat_bytes : EB(in) * a.M * op.cin) + (a.out_mode == OUT_HEAD ? 12.0 * a.M * (a.NTtot / nt) : EB(o) * a.M * cols) +
+              (hconv ? 2.0 : 4.0) * taps * op.cin * cols;
+    if (dwpw_of[oi] >= 0) return emit_dwpw(oi, op, a, ep, cols, L);
+    dense_closure(op, a, ep, in, hconv, nt, L);
+    return true;
+  }
+
+  // which matrix-core kernel runs a dense conv, and its fallbacks
+  void dense_closure(const PlanOp& op, const ConvArgs& a, const Epilogue& ep, const TensorDesc& in, bool hconv, int nt, Launch& L) {
+    const int taps = a.KH * a.KW;
+    // measured (round 1): LDS staging wins for multi-tap convs (3x3 96->24: 58 vs 51 TFLOP/s), the direct kernel for 1x1
+    // (480->480: 88 vs 71; thin K: 54 vs 39).  precision "fp16": the LDS-staged and the 4x4x1 kernels are f32 only - every
+    // dense conv goes through the direct kernel
+    const bool use_lds = !hconv && !a.gate && a.out_mode == OUT_C8I && taps > 1 && in.cs >= 64;
+    if (use_lds) {
+      const float* c24 = dev_vec("c24:" + op.w);
+      L.fn = [net = &net, a, ep, nt, c24](hipStream_t s) {
+        if (launch_conv3x3_c24(a, ep, c24, s)) return;
+        bool cat_same_res = a.cat_n > 0;  // (a same-resolution concat folds into the LDS-staged conv's chunk loads)
+        for (int j = 0; j < a.cat_n; ++j) cat_same_res = cat_same_res && a.cat_up[j] == 1;
+        if (a.cat_n && !cat_same_res) { net->launch_error_ = "folded concat: the 3x3 conv's 4x4x1 kernel refused the launch"; return; }
+        if (a.cat_n || !launch_conv3x3_tile(a, ep, nt, s)) launch_conv_lds(a, ep, nt, s);
+      };
+      return;
+    }
+    // Small GEMMs (a request's few text lines, the small-width rec launches): fewer column tiles per wave, as long
+    // as that keeps dividing the fragment image's tile count, until the launch has ~2 workgroups per CU - a wave's
+    // K walk is a chain of NT * K / 2 dependent-in-order MFMAs and with one wave per SIMD its length IS the
+    // kernel's time (rec op 30 on 32 lines: 720 -> 240 MFMAs per wave).  Results do not depend on NT.
+    int ntl = nt;
+    if (a.out_mode != OUT_HEAD && rt_options().conv_small_nt) {  // OCR_CONV_SMALL_NT=0: keep the table's NT (A/B)
+      auto wgs = [&](int t) { return ((a.M + 127) / 128) * (long)(a.NTtot / t); };
+      while (ntl > 1 && wgs(ntl) < 512) {
+        int t = ntl - 1;
+        while (t > 1 && a.NTtot % t) --t;
+        ntl = t;
+      }
+    }
+    // Big 1x1 convs: two pixel tiles per wave (kernels_net.hip, conv_mfma_mt_kernel) - a weight fragment feeds two
+    // MFMAs, half the workgroups stage parameters; worth it from K = 192 on while the launch still has ~4
+    // workgroups per CU (rec ops 25/30/32/34, det ops 30/38).  Results do not depend on the tiling.
+    const bool mt2 = rt_options().conv_mt2 && (nt == 3 || nt == 4) && taps == 1 && a.out_mode == OUT_C8I &&
+                     (rt_options().conv_mt2_force || (ntl == nt && in.cs >= 192 && ((a.M + 255) / 256) * (long)(a.NTtot / nt) >= 1024));
+    if (mt2) ntl = nt;  // (the two-tile kernel is instantiated for the table's NT)
+    const bool half_tile = hconv && taps == 9 && (!rag || img);  // precision "fp16": the LDS-resident 3x3 tile kernel has an f16 form (uniform batches, ragged batches of images)
+    L.fn = [net = &net, a, ep, ntl, nt, mt2, half_tile](hipStream_t s) {
+      if (half_tile && launch_conv3x3_tile(a, ep, nt, s)) return;
+      if (a.cat_n) { net->launch_error_ = "folded concat: the 3x3 conv's f16 tile kernel refused the launch"; return; }
+      if (mt2 && launch_conv_mfma_mt2(a, ep, ntl, s)) return;
+      if (!launch_conv_mfma(a, ep, ntl, s)) net->launch_error_ = "launch_conv_mfma: this conv shape / output mode is not instantiated";
+    };
+  }
+
+  // the fused depthwise -> pointwise block: the dense conv `a` (already named and counted in L) with the depthwise op in front
+  bool emit_dwpw(int oi, const PlanOp& op, const ConvArgs& a, const Epilogue& ep, double cols, Launch& L) {
+    const PlanOp& d = plan.ops[dwpw_of[oi]];
+    const TensorDesc &din = T[d.in], &o = T[op.out];
+    Epilogue epd;
+    if (!net.build_epilogue(d, epd, false, err)) return false;
+    DwPwArgs f{};
+    f.c = a;
+    f.c.in = nullptr;
+    f.dw_in = at(din); f.dw_w = dev_vec("dw:" + d.w);
+    f.dw_wq16 = dev_vec("dwq16:" + d.w); f.dw_wq32 = dev_vec("dwq32:" + d.w);
+    if (!lab_from_epilogue(epd, f.dw_ep) || !lab_from_epilogue(ep, f.pw_ep)) { err = "dwpw: epilogue is not the LAB chain"; return false; }
+    f.H = din.h; f.W = din.w; f.K = d.kh; f.SH = d.sh; f.SW = d.sw; f.PH = d.ph; f.PW = d.pw;
+    if (rag) {
+      f.rin = rlevel(din); f.rout = rlevel(o);
+      f.c.rin = f.c.rout = RagLevel();
+      const int th = dwpw_tile_rows(f);
+      if (th <= 0) { err = "dwpw: no instance for this shape"; return false; }
+      f.rtiles = tiles_table(o, th, f.rtiles_total);
+    }
+    L.name = fmt("%s.%02d.dwpw%dx%d_%d_%d_s%d%d", pname(), dwpw_of[oi], d.kh, d.kw, op.cin, op.cout, d.sh, d.sw);
+    L.flops += 2.0 * a.M * d.kh * d.kw * d.c;
+    if (din.f16 != (half != 0)) { err = "precision fp16: a fused depthwise block on an f32 tensor is not on this path"; return false; }
+    L.bytes = EB(din) * din.pixels() * d.c + EB(o) * a.M * cols + (half ? 2.0 : 4.0) * op.cin * cols + 4.0 * d.kh * d.kw * d.c;
+    L.fn = [net = &net, f](hipStream_t s) {
+      if (!launch_dwpw(f, s)) net->launch_error_ = "launch_dwpw: shape accepted at bind time was refused at launch";
+    };
+    return true;
+  }
+
+  // the expand 1x1 conv in front of a depthwise op runs inside its launch (kernels_xdw.hip)
+  bool emit_xdw(int oi, const PlanOp& op, Launch& L) {
+    const PlanOp& c = plan.ops[xdw_of[oi]];
+    const TensorDesc &xin = T[c.in], &o = T[op.out];
+    Epilogue ce, de;
+    if (!net.build_epilogue(c, ce, true, err) || !net.build_epilogue(op, de, false, err)) return false;
+    XdwArgs a{};
+    a.x = at(xin); a.wfrag = dev_vec("frag:" + c.w);
+    a.e_sc = ce.st[0].v0; a.e_sh = ce.st[0].v1;
+    a.dw_w = dev_vec("dw:" + op.w); a.d_sc = de.st[0].v0; a.d_sh = de.st[0].v1;
+    a.out = at(o); a.part = dw_rowsum[oi] ? net.gap_part_ : nullptr;
+    a.N = xin.n; a.Hin = xin.h; a.Hout = o.h; a.W = xin.w; a.Cs_in = xin.cs; a.Cs_e = o.cs;
+    a.NTtot = nt_total(T[c.out].cs);
+    a.K = op.kh; a.SH = op.sh; a.SW = op.sw; a.PH = op.ph; a.PW = op.pw;
+    if (!a.wfrag || !a.e_sc || !a.e_sh || !a.dw_w || !a.d_sc || !a.d_sh) { err = "expand -> depthwise block: a parameter image is missing for " + c.w; return false; }
+    L.name = fmt("%s.%02d.xdw%dx%d_%d_%d_s%d%d%s", pname(), oi, op.kh, op.kw, c.cin, op.c, op.sh, op.sw, dw_rowsum[oi] ? "_rowsum" : "");
+    L.flops = 2.0 * xin.pixels() * c.cin * c.cout + 2.0 * o.pixels() * op.kh * op.kw * op.c;
+    L.bytes = EB(xin) * xin.pixels() * c.cin + EB(o) * o.pixels() * op.c;
+    L.fn = [net = &net, a](hipStream_t s) {
+      if (!launch_xdw(a, s)) net->launch_error_ = "launch_xdw: shape accepted at bind time was refused at launch";
+    };
+    return true;
+  }
+
+  bool emit_dw(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[op.in], &o = T[op.out];
+    Epilogue ep;
+    if (!net.build_epilogue(op, ep, false, err)) return false;
+    for (auto& st : op.ep) if (st.kind == EP_ADDUP) { err = "addup after a depthwise conv is not on this path"; return false; }
+    DwArgs a{};
+    a.in = at(in); a.out = at(o); a.w = dev_vec("dw:" + op.w);
+    a.N = in.n; a.H = in.h; a.W = in.w; a.OH = o.h; a.OW = o.w; a.Cs = o.cs; a.K = op.kh;
+    a.SH = op.sh; a.SW = op.sw; a.PH = op.ph; a.PW = op.pw; a.M = o.pixels();
+    if (dw_rowsum[oi]) a.rowsum = net.gap_part_;
+    a.h16 = o.f16;
+    if (in.f16 != o.f16) { err = "precision fp16: depthwise conv between tensors of different storage"; return false; }
+    if (rag) {
+      a.rin = rlevel(in); a.rout = rlevel(o);
+      a.OW = min_w(o);            // the launcher picks its patch from the narrowest / lowest sample
+      if (img) a.OH = min_h(o);
+      const int to = dw_patch_to(a.OW, a.SW, img ? a.OH : o.h, a.K), pr = dw_patch_r(img ? a.OH : o.h, a.K);
+      const bool rs = dw_rowsum[oi] != 0;
+      a.rwork = work_table("dw:" + std::to_string(o.lvl) + ":" + std::to_string(o.h) + ":" + std::to_string(to) + ":" + std::to_string(pr) + (rs ? ":rs" : ""),
+                           [&, to, pr, rs](int i) {
+                             const int bands = (sh_of(o, i) + pr - 1) / pr;
+                             return rs ? bands : bands * ((sw_of(o, i) + to - 1) / to);
+                           }, a.rwork_total);
+    }
+    L.name = fmt("%s.%02d.dw%dx%d_%d_s%d%d%s", pname(), oi, op.kh, op.kw, op.c, op.sh, op.sw, dw_rowsum[oi] ? "_rowsum" : "");
+    L.flops = 2.0 * a.M * op.kh * op.kw * op.c;
+    L.bytes = EB(in) * in.pixels() * op.c + EB(o) * a.M * op.c;
+    // the low maps' 5x5 layers: region staged through LDS (kernels_dwlds.hip); asked now, on the device that will run it
+    const bool lds_dw = rt_options().dw_lds && launch_dw_lds(a, ep, nullptr, true);
+    L.fn = [net = &net, a, ep, lds_dw](hipStream_t s) {
+      if (lds_dw) {
+        if (!launch_dw_lds(a, ep, s)) net->launch_error_ = "launch_dw_lds: shape accepted at bind time was refused at launch";
+        return;
+      }
+      launch_dw(a, ep, s);
+    };
+    return true;
+  }
+
+  bool emit_ew(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[op.in], &o = T[op.out];
+    Epilogue ep;
+    if (!net.build_epilogue(op, ep, false, err)) return false;
+    const float* ip = at(in);
+    float* optr = at(o);
+    const long M = o.pixels();
+    const int H2 = o.h, W2 = o.w, Cs = o.cs;
+    if (rag && !img) for (auto& st : op.ep) if (st.kind == EP_ADDUP) { err = "ragged batch: upsampled operand is not on this path"; return false; }
+    const RagLevel rl = rlevel(o);
+    const int nl = o.n;
+    L.name = fmt("%s.%02d.ew_%d", pname(), oi, op.c);
+    L.bytes = EB(o) * M * op.c * (2.0 + (double)op.ep.size() - 1.0);
+    const bool h16 = o.f16;
+    if (in.f16 != o.f16) { err = "precision fp16: elementwise op between tensors of different storage"; return false; }
+    L.fn = [ip, optr, M, H2, W2, Cs, ep, nl, rl, h16](hipStream_t s) { launch_ew(ip, optr, M, H2, W2, Cs, ep, s, nl, rl, h16); };
+    return true;
+  }
+
+  bool emit_gap(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc& in = T[op.in];
+    const float* ip = at(in);
+    float* optr = at(T[op.out]);
+    float* part = net.gap_part_;
+    const int n = in.n, h = in.h, w = in.w, cs = in.cs;
+    const RagLevel rl = rlevel(in);
+    const long grows = rag ? rows_of(in) : 0;
+    L.name = fmt("%s.%02d.gap_%d", pname(), oi, op.c);
+    L.bytes = EB(in) * in.pixels() * op.c;
+    const bool h16 = in.f16;
+    if (oi > 0 && (dw_rowsum[oi - 1] || rse_first[oi - 1])) {  // the row sums are already in `part` (written by the depthwise conv / the conv's row-sum pass before this op)
+      L.bytes = 4.0 * (double)n * h * op.c;
+      L.fn = [part, optr, n, h, w, cs, rl](hipStream_t s) { launch_gap_cols(part, optr, n, h, w, cs, s, rl); };
+    } else
+    L.fn = [ip, part, optr, n, h, w, cs, rl, grows, h16](hipStream_t s) { launch_gap(ip, part, optr, n, h, w, cs, s, rl, grows, h16); };
+    return true;
+  }
+
+  bool emit_sefc(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[op.in], &o = T[op.out];
+    SeArgs a{};
+    a.in = at(in); a.out = at(o);
+    a.w1 = dev_vec("raw:" + op.w1); a.b1 = dev_vec("raw:" + op.b1);
+    a.w2 = dev_vec("raw:" + op.w2); a.b2 = dev_vec("raw:" + op.b2);
+    a.C = op.c; a.Cs = o.cs; a.R = op.cr; a.slope = op.slope; a.offset = op.offset;
+    const int n = in.n;
+    L.name = fmt("%s.%02d.sefc_%d", pname(), oi, op.c);
+    L.flops = 4.0 * n * op.c * op.cr;
+    L.fn = [a, n](hipStream_t s) { launch_sefc(a, n, s); };
+    return true;
+  }
+
+  bool emit_concat(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc& o = T[op.out];
+    ConcatArgs a{};
+    a.out = at(o); a.H = o.h; a.W = o.w; a.Cs = o.cs; a.M = o.pixels();
+    if (img) { a.rout = rlevel(o); a.N = N; }
+    else if (rag) { a.H = 1; a.W = (int)a.M; }  // lines: same-resolution sources (checked in shapes_lines), one row axis
+    a.nsrc = (int)op.ins.size();
+    if (a.nsrc > 4) { err = "concat arity not on this path"; return false; }
+    int off = 0;
+    for (int j = 0; j < a.nsrc; ++j) {
+      const TensorDesc& sj = T[op.ins[j]];
+      if (sj.c % 8) { err = "concat source channels must be a multiple of 8"; return false; }
+      if (sj.f16 != o.f16) { err = "precision fp16: concat of tensors of different storage"; return false; }
+      a.src[j] = at(sj); a.coff[j] = off; a.scs[j] = sj.cs; a.up[j] = op.ups[j];
+      off += sj.cs;
+    }
+    L.name = fmt("%s.%02d.concat_%d", pname(), oi, op.c);
+    a.h16 = o.f16;
+    L.bytes = 2.0 * EB(o) * a.M * op.c;
+    L.fn = [a](hipStream_t s) { launch_concat(a, s); };
+    return true;
+  }
+
+  bool emit_pool(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[op.in], &o = T[op.out];
+    PoolArgs a{};
+    a.in = at(in); a.out = at(o); a.N = in.n; a.H = in.h; a.W = in.w; a.OH = o.h; a.OW = o.w;
+    a.Cs = o.cs; a.KH = op.kh; a.KW = op.kw; a.SH = op.sh; a.SW = op.sw; a.is_max = op.pool_max;
+    a.M = o.pixels();
+    a.rin = rlevel(in); a.rout = rlevel(o);
+    a.h16 = o.f16;
+    if (in.f16 != o.f16) { err = "precision fp16: pool between tensors of different storage"; return false; }
+    L.name = fmt("%s.%02d.pool_%d", pname(), oi, op.c);
+    L.bytes = EB(in) * in.pixels() * op.c + EB(o) * a.M * op.c;
+    L.fn = [a](hipStream_t s) { launch_pool(a, s); };
+    return true;
+  }
+
+  bool emit_ln(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[op.in], &o = T[op.out];
+    const float* ip = at(in);
+    float* optr = at(o);
+    const long rows = in.pixels();
+    const int C = op.c, Cs = in.cs;
+    const float eps = op.eps;
+    const float* g = dev_vec("raw:" + op.g);
+    const float* b = dev_vec("raw:" + op.b);
+    L.name = fmt("%s.%02d.ln_%d", pname(), oi, op.c);
+    L.bytes = 2.0 * EB(in) * rows * C;
+    const bool h16 = in.f16;
+    if (in.f16 != o.f16) { err = "precision fp16: layer norm between tensors of different storage"; return false; }
+    L.fn = [ip, optr, rows, C, Cs, eps, g, b, h16](hipStream_t s) { launch_ln(ip, optr, rows, C, Cs, eps, g, b, s, h16); };
+    return true;
+  }
+
+  bool emit_attn(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc &in = T[op.in], &o = T[op.out];
+    if (in.h != 1) { err = "attention expects a sequence (H == 1): rec input height must reduce to 1"; return false; }
+    const float* ip = at(in);
+    float* optr = at(o);
+    const int n = in.n, t = in.w, heads = op.heads, hd = op.hd, csi = in.cs, cso = o.cs;
+    const float sc = op.scale;
+    const RagLevel rl = rlevel(in);
+    if (rag && !attn_ragged_fits(t)) { err = "ragged batch: line too wide for the attention kernel"; return false; }
+    double tt = (double)n * t * t;  // sum over lines of T^2
+    if (rag) { tt = 0; for (int v : LW[in.lvl]) tt += (double)v * v; }
+    L.name = fmt("%s.%02d.attn_%dx%d", pname(), oi, op.heads, op.hd);
+    L.flops = 3.0 * 2.0 * heads * tt * hd + 2.0 * heads * tt * hd;
+    L.bytes = EB(in) * in.pixels() * (3.0 + 1.0) * heads * hd;
+    const bool h16 = in.f16;
+    if (in.f16 != o.f16) { err = "precision fp16: attention between tensors of different storage"; return false; }
+    L.fn = [ip, optr, n, t, heads, hd, csi, cso, sc, rl, h16](hipStream_t s) { launch_attn(ip, optr, n, t, heads, hd, csi, cso, sc, s, rl, h16); };
+    return true;
+  }
+
+  bool emit_softmax(int oi, const PlanOp& op, Launch& L) {
+    const TensorDesc& in = T[op.in];
+    const float* ip = at(in);
+    float* optr = at(T[op.out]);
+    const long rows = in.pixels();
+    const int C = op.c;
+    L.name = fmt("%s.%02d.softmax_%d", pname(), oi, op.c);
+    L.bytes = 4.0 * rows * C * 3;
+    // `optr` (the plan's softmax tensor) is only filled when no external sink is set or probs are requested
+    if (net.fused_head_rows_ == rows && oi > 0 && plan.ops[oi - 1].kind == PlanOp::LINEAR && plan.ops[oi - 1].out == op.in) {
+      // second half of the fused head (the linear before this op ran in OUT_HEAD mode)
+      const float* hm = net.head_part_;
+      const float* hs = net.head_part_ + (size_t)rows * net.fused_head_groups_;
+      const int* hi = (const int*)(net.head_part_ + (size_t)rows * net.fused_head_groups_ * 2);
+      const int G = net.fused_head_groups_;
+      L.bytes = 12.0 * rows * G;
+      L.fn = [net = &net, hm, hs, hi, rows, G](hipStream_t s) { launch_head_combine(hm, hs, hi, rows, G, net->head_amax_, net->head_pmax_, s); };
+    } else {
+      L.fn = [net = &net, ip, optr, rows, C](hipStream_t s) {
+        float* probs = (net->head_amax_ || net->head_pmax_) ? net->head_probs_ : optr;
+        launch_softmax_argmax(ip, probs, net->head_amax_, net->head_pmax_, rows, C, s);
+      };
+    }
+    return true;
+  }
+
+  // the launch of plan op `oi` (the caller skips output, folded and fused-away ops)
+  bool emit(int oi, Launch& L) {
     PlanOp second_pass;  // RSE block: the ew's launch is its conv again, with the ew's stages behind the conv's own
     if (rse_conv[oi] >= 0) {
-      const PlanOp& e = plan_.ops[oi];
-      second_pass = plan_.ops[rse_conv[oi]];
+      const PlanOp& e = plan.ops[oi];
+      second_pass = plan.ops[rse_conv[oi]];
       second_pass.out = e.out;
       PlanStage gr = e.ep[0];
       gr.kind = EP_GATERES;
       second_pass.ep.push_back(gr);
       for (size_t k = 2; k < e.ep.size(); ++k) second_pass.ep.push_back(e.ep[k]);
     }
-    const PlanOp& op = rse_conv[oi] >= 0 ? second_pass : plan_.ops[oi];
-    const TensorDesc& o = T[op.out];
-    float* optr = arena_ + o.offset;
-    Launch L;
-    if (rse_first[oi]) {  // first pass: the pool's row sums, nothing else
-      const TensorDesc& in = T[op.in];
-      ConvRowsumArgs a{};
-      a.in = arena_ + in.offset; a.w = dev_vec("rsw:" + op.w); a.part = gap_part_;
-      a.rows = rag ? rows_of(in) : (long)in.n * in.h; a.W = in.w; a.Cin = op.cin; a.Cs_in = in.cs; a.Cs_out = o.cs;
-      a.N = in.n; a.H = in.h; a.rag = rlevel(in);
-      a.h16 = in.f16;
-      if (!a.w) { err = "RSE block: no row-sum weight image for " + op.w; return false; }
-      snprintf(nm, sizeof nm, "%s.%02d.conv1x1_%d_%d_rowsum", plan_.name.c_str(), oi, op.cin, op.cout);
-      L.name = nm;
-      L.flops = 2.0 * in.pixels() * op.cin * op.cout;
-      L.bytes = EB(in) * in.pixels() * op.cin + 4.0 * a.rows * op.cout;
-      L.fn = [this, a](hipStream_t s) {
-        if (!launch_conv_rowsum(a, s)) this->launch_error_ = "launch_conv_rowsum: shape accepted at bind time was refused at launch";
-      };
+    const PlanOp& op = rse_conv[oi] >= 0 ? second_pass : plan.ops[oi];
+    if (rse_first[oi]) return emit_conv_rowsum(oi, op, L);
+    switch (op.kind) {
+      case PlanOp::CONV: case PlanOp::LINEAR: case PlanOp::DECONV:
+        if (op.kind == PlanOp::CONV && op.cin == 3) return emit_stem(oi, op, L);
+        if (op.kind == PlanOp::DECONV && op.cout == 1) return emit_det_tail(oi, op, L);
+        return emit_dense(oi, op, L);
+      case PlanOp::DW: return xdw_of[oi] >= 0 ? emit_xdw(oi, op, L) : emit_dw(oi, op, L);
+      case PlanOp::EW: return emit_ew(oi, op, L);
+      case PlanOp::GAP: return emit_gap(oi, op, L);
+      case PlanOp::SEFC: return emit_sefc(oi, op, L);
+      case PlanOp::CONCAT: return emit_concat(oi, op, L);
+      case PlanOp::POOL: return emit_pool(oi, op, L);
+      case PlanOp::LN: return emit_ln(oi, op, L);
+      case PlanOp::ATTN: return emit_attn(oi, op, L);
+      case PlanOp::SOFTMAX: return emit_softmax(oi, op, L);
+      default: return true;
     }
-    else switch (op.kind) {
-      case PlanOp::CONV: case PlanOp::LINEAR: case PlanOp::DECONV: {
-        const TensorDesc& in = T[gate_src[oi] >= 0 ? gate_src[oi] : op.in];
-        Epilogue ep;
-        if (op.kind == PlanOp::CONV && op.cin == 3) {
-          if (!build_epilogue(op, ep, false, err)) return false;
-          StemArgs a{};
-          a.out = optr; a.w = dev_vec("stem:" + op.w);
-          a.N = in.n; a.H = in.h; a.W = in.w; a.OH = o.h; a.OW = o.w; a.Cs_out = o.cs;
-          a.KH = op.kh; a.KW = op.kw; a.SH = op.sh; a.SW = op.sw; a.PH = op.ph; a.PW = op.pw;
-          a.M = o.pixels();
-          a.rin = rlevel(in); a.rout = rlevel(o);
-          a.h16 = o.f16;
-          if (in.f16) { err = "stem input must be the plain f32 image"; return false; }
-          if (o.cs != 8 && o.cs != 16) { err = "stem width not on this path"; return false; }
-          snprintf(nm, sizeof nm, "%s.%02d.stem%dx%d_3_%d", plan_.name.c_str(), oi, op.kh, op.kw, op.cout);
-          L.name = nm;
-          L.flops = 2.0 * a.M * op.kh * op.kw * 3 * op.cout;
-          L.bytes = 4.0 * in.numel() + EB(o) * a.M * op.cout;
-          const bool ext_in = (op.in == 0);
-          const float* in_ptr = ext_in ? nullptr : arena_ + in.offset;
-          L.fn = [this, a, ep, ext_in, in_ptr](hipStream_t s) mutable {
-            StemArgs b = a;
-            b.in = ext_in ? this->bound_x_ : in_ptr;
-            launch_stem(b, ep, s);
-          };
-        } else if (op.kind == PlanOp::DECONV && op.cout == 1) {
-          // tail: deconv -> 1 channel, bias (scalar), sigmoid  (+ fused u8 threshold)
-          float bias = 0.f;
-          bool ok = op.ep.size() == 2 && (op.ep[0].kind == EP_SADD || op.ep[0].kind == EP_BIAS) && op.ep[1].kind == EP_ACT && op.ep[1].act == ACT_SIGMOID;
-          if (!ok) { err = "unexpected DB head tail"; return false; }
-          bias = host_w_[op.ep[0].n0].data[0];
-          DetTailArgs a{};
-          a.in = arena_ + in.offset; a.prob = optr; a.bitmap = det_bitmap_; a.w = dev_vec("tail:" + op.w);
-          a.N = in.n; a.H = in.h; a.W = in.w; a.C = op.cin; a.Cs = in.cs; a.bias = bias; a.ithresh = det_ithresh_;
-          a.M = in.pixels();
-          a.h16 = in.f16;
-          snprintf(nm, sizeof nm, "%s.%02d.det_tail", plan_.name.c_str(), oi);
-          L.name = nm;
-          L.flops = 2.0 * a.M * op.cin * 4;
-          L.bytes = EB(in) * a.M * op.cin + 4.0 * a.M * 4 + (det_bitmap_ ? 1.0 * a.M * 4 : 0.0);
-          L.fn = [a](hipStream_t s) { launch_det_tail(a, s); };
-          if (img && dbhead_of[oi] < 0) { err = "ragged batch of images: the DB head needs its fused kernel (production launch list, OCR_FUSE on)"; return false; }
-          if (dbhead_of[oi] >= 0) {
-            const PlanOp& d = plan_.ops[dbhead_of[oi]];
-            const TensorDesc& din = T[d.in];
-            Epilogue epd;
-            if (!build_epilogue(d, epd, true, err)) return false;
-            DbHeadArgs h{};
-            h.in = arena_ + din.offset; h.prob = optr; h.bitmap = det_bitmap_;
-            h.w1 = dev_vec("dbh1:" + d.w); h.bias1 = epd.st[0].v0; h.bn_s = epd.st[1].v0; h.bn_t = epd.st[1].v1;
-            if (d.cin == 24 && d.cout == 24) h.wfrag = dev_vec("dbhf:" + d.w);
-            h.w2 = a.w; h.M = din.pixels(); h.N = din.n; h.H = din.h; h.W = din.w; h.Cs = din.cs;
-            h.bias2 = a.bias; h.ithresh = a.ithresh;
-            h.h16 = din.f16;
-            if (img) h.rin = rlevel(din);
-            snprintf(nm, sizeof nm, "%s.%02d.db_head_%d", plan_.name.c_str(), dbhead_of[oi], d.cin);
-            L.name = nm;
-            L.flops = 2.0 * h.M * (4.0 * d.cin * d.cout + 16.0 * d.cout);
-            L.bytes = EB(din) * h.M * d.cin + 4.0 * h.M * 16 + (det_bitmap_ ? 1.0 * h.M * 16 : 0.0);
-            const int C = d.cin;
-            L.fn = [this, h, C](hipStream_t s) {
-              if (!launch_db_head(h, C, s)) this->launch_error_ = "launch_db_head: shape accepted at bind time was refused at launch";
-            };
-          }
-        } else {
-          if (!build_epilogue(op, ep, true, err)) return false;
-          ConvArgs a{};
-          // precision "fp16": a conv on an f16 tensor runs in f16; one on a per-image f32 vector (the classifier's pool -> fc)
-          // keeps the f32 kernel and fragments
-          const bool hconv = half_ && in.f16;
-          a.in = arena_ + in.offset; a.out = optr; a.wfrag = dev_vec((hconv ? "frag16:" : "frag:") + op.w);
-          a.half = hconv ? 1 : 0;
-          if (hconv && op.kind == PlanOp::CONV) a.wfrag_x16 = dev_vec("frag16x:" + op.w);  // (null: no such image - other than 1x1 and the 3x3 96-channel convs, or an odd number of octets)
-          if (!o.plain && o.f16 != in.f16) { err = "precision fp16: a dense conv between tensors of different storage"; return false; }
-          a.N = in.n; a.H = in.h; a.W = in.w; a.Cs_in = in.cs; a.C8 = in.cs / 8;
-          a.KH = op.kh; a.KW = op.kw; a.PH = op.ph; a.PW = op.pw;
-          a.need_nyx = 0;
-          if (in.plain) { err = "conv input must be C8I"; return false; }
-          if (rag) {
-            // pointwise, or a stride-1 "same" conv (the recognizer's 1x3 neck convs, the detector's 3x3 neck / head convs):
-            // rows in = rows out, one level
-            if (in.lvl < 0 || o.lvl != in.lvl || o.h != in.h || op.kind == PlanOp::DECONV) { err = "ragged batch: dense conv must keep its input's shape"; return false; }
-            for (auto& st : op.ep) if (st.kind == EP_ADDUP && !img) { err = "ragged batch of lines: an upsampled operand after a dense conv is not on this path"; return false; }
-            a.rin = rlevel(in); a.rout = rlevel(o);
-            if (img && op.kh == 3 && op.kw == 3) a.rtiles = tiles_table(o, 8, a.rtiles_total);  // (the 8x16 LDS-tile kernel)
-          }
-          if (op.kind == PlanOp::DECONV) {
-            a.OH = in.h; a.OW = in.w; a.Cs_out = o.cs; a.Cout = op.cout; a.CoutPadded = o.cs;
-            a.ColsStore = 4 * o.cs; a.out_mode = OUT_DECONV; a.KH = a.KW = 1; a.PH = a.PW = 0;
-          } else {
-            a.OH = o.h; a.OW = o.w; a.Cs_out = o.cs; a.Cout = op.cout; a.CoutPadded = o.cs;
-            a.ColsStore = o.plain ? op.cout : o.cs; a.out_mode = o.plain ? OUT_PLAIN : OUT_C8I;
-          }
-          const int tiles = (a.ColsStore + 31) / 32;
-          const int nt = conv_nt_for(tiles);
-          a.NTtot = (tiles + nt - 1) / nt * nt;
-          // linear -> softmax with only (arg max, max prob) wanted: the softmax is folded into the linear's
-          // epilogue (no logits tensor) and a per-row combine; canonical groups are 128 columns wide
-          const bool fuse_head = op.kind == PlanOp::LINEAR && o.plain && oi + 1 < nops && plan_.ops[oi + 1].kind == PlanOp::SOFTMAX &&
-                                 plan_.ops[oi + 1].in == op.out && (head_amax_ || head_pmax_) && !head_probs_ && keep_all_ == 0 &&
-                                 (tiles <= 4 || nt == 4);
-          if (fuse_head) {
-            a.out_mode = OUT_HEAD;
-            const long hrows = in.pixels();
-            const int groups = a.NTtot / nt;
-            const size_t need = (size_t)hrows * groups * 3;
-            if (need > head_part_cap_) {
-              if (head_part_) (void)g_free(head_part_);
-              moved = true;
-              head_part_ = nullptr;
-              head_part_cap_ = 0;
-              HIP_OK(g_malloc(&head_part_, need * sizeof(float)));
-              head_part_cap_ = need;
-            }
-            a.head_max = head_part_;
-            a.head_sum = head_part_ + (size_t)hrows * groups;
-            a.head_idx = (int*)(head_part_ + (size_t)hrows * groups * 2);
-            fused_head_rows_ = hrows;
-            fused_head_groups_ = groups;
-          }
-          a.zeros = dev_vec("zeros");
-          double cat_bytes = 0;
-          if (cat_of[oi] >= 0) {  // the folded concat: the tile fill reads its sources
-            const PlanOp& k = plan_.ops[cat_of[oi]];
-            a.in = nullptr;
-            a.cat_n = (int)k.ins.size();
-            a.cat_cs = T[k.ins[0]].cs;
-            for (int j = 0; j < a.cat_n; ++j) {
-              a.cat_src[j] = arena_ + T[k.ins[j]].offset;
-              a.cat_up[j] = k.ups[j];
-              if (k.ups[j] < 1 || (k.ups[j] & (k.ups[j] - 1))) { err = "folded concat: upsampling factor is not a power of two"; return false; }
-              cat_bytes += EB(T[k.ins[j]]) * T[k.ins[j]].numel();
-            }
-          }
-          if (gate_src[oi] >= 0) { a.gate = arena_ + T[gate_tid[oi]].offset; a.gate_hw = in.h * in.w; }
-          a.M = (long)in.n * a.OH * a.OW;
-          if (op.kind == PlanOp::LINEAR) a.M = (long)in.n * in.h * in.w;
-          if (rag) a.M = in.pixels();
-          const int taps = a.KH * a.KW;
-          const char* kind = op.kind == PlanOp::DECONV ? "deconv" : (op.kind == PlanOp::LINEAR ? "linear" : "conv");
-          snprintf(nm, sizeof nm, "%s.%02d.%s%dx%d_%d_%d", plan_.name.c_str(), oi, kind, a.KH, a.KW, op.cin, op.cout);
-          L.name = nm;
-          const double cols = op.kind == PlanOp::DECONV ? 4.0 * op.cout : op.cout;
-          L.flops = 2.0 * a.M * taps * op.cin * cols;
-          if (a.gate) L.name += "_gated";
-          if (a.cat_n) L.name += "_cat" + std::to_string(a.cat_n);
-          L.bytes = (a.cat_n ? cat_bytes : EB(in) * a.M * op.cin) + (a.out_mode == OUT_HEAD ? 12.0 * a.M * (a.NTtot / nt) : EB(o) * a.M * cols) +
-                    (hconv ? 2.0 : 4.0) * taps * op.cin * cols;
-          // measured (round 1): LDS staging wins for multi-tap convs (3x3 96->24: 58 vs 51 TFLOP/s), the direct kernel for 1x1
-          // (480->480: 88 vs 71; thin K: 54 vs 39).  precision "fp16": the LDS-staged and the 4x4x1 kernels are f32 only - every
-          // dense conv goes through the direct kernel
-          const bool use_lds = !hconv && !a.gate && a.out_mode == OUT_C8I && taps > 1 && in.cs >= 64;
-          if (dwpw_of[oi] >= 0) {
-            const PlanOp& d = plan_.ops[dwpw_of[oi]];
-            const TensorDesc& din = T[d.in];
-            Epilogue epd;
-            if (!build_epilogue(d, epd, false, err)) return false;
-            DwPwArgs f{};
-            f.c = a;
-            f.c.in = nullptr;
-            f.dw_in = arena_ + din.offset; f.dw_w = dev_vec("dw:" + d.w);
-            f.dw_wq16 = dev_vec("dwq16:" + d.w); f.dw_wq32 = dev_vec("dwq32:" + d.w);
-            if (!lab_from_epilogue(epd, f.dw_ep) || !lab_from_epilogue(ep, f.pw_ep)) { err = "dwpw: epilogue is not the LAB chain"; return false; }
-            f.H = din.h; f.W = din.w; f.K = d.kh; f.SH = d.sh; f.SW = d.sw; f.PH = d.ph; f.PW = d.pw;
-            if (rag) {
-              f.rin = rlevel(din); f.rout = rlevel(o);
-              f.c.rin = f.c.rout = RagLevel();
-              const int th = dwpw_tile_rows(f);
-              if (th <= 0) { err = "dwpw: no instance for this shape"; return false; }
-              f.rtiles = tiles_table(o, th, f.rtiles_total);
-            }
-            snprintf(nm, sizeof nm, "%s.%02d.dwpw%dx%d_%d_%d_s%d%d", plan_.name.c_str(), dwpw_of[oi], d.kh, d.kw, op.cin, op.cout, d.sh, d.sw);
-            L.name = nm;
-            L.flops += 2.0 * a.M * d.kh * d.kw * d.c;
-            if (din.f16 != (half_ != 0)) { err = "precision fp16: a fused depthwise block on an f32 tensor is not on this path"; return false; }
-            L.bytes = EB(din) * din.pixels() * d.c + EB(o) * a.M * cols + (half_ ? 2.0 : 4.0) * op.cin * cols + 4.0 * d.kh * d.kw * d.c;
-            L.fn = [this, f](hipStream_t s) {
-              if (!launch_dwpw(f, s)) this->launch_error_ = "launch_dwpw: shape accepted at bind time was refused at launch";
-            };
-          } else if (use_lds) {
-            const float* c24 = dev_vec("c24:" + op.w);
-            L.fn = [this, a, ep, nt, c24](hipStream_t s) {
-              if (launch_conv3x3_c24(a, ep, c24, s)) return;
-              bool cat_same_res = a.cat_n > 0;  // (a same-resolution concat folds into the LDS-staged conv's chunk loads)
-              for (int j = 0; j < a.cat_n; ++j) cat_same_res = cat_same_res && a.cat_up[j] == 1;
-              if (a.cat_n && !cat_same_res) { this->launch_error_ = "folded concat: the 3x3 conv's 4x4x1 kernel refused the launch"; return; }
-              if (a.cat_n || !launch_conv3x3_tile(a, ep, nt, s)) launch_conv_lds(a, ep, nt, s);
-            };
-          }
-          else {
-            // Small GEMMs (a request's few text lines, the small-width rec launches): fewer column tiles per wave, as long
-            // as that keeps dividing the fragment image's tile count, until the launch has ~2 workgroups per CU - a wave's
-            // K walk is a chain of NT * K / 2 dependent-in-order MFMAs and with one wave per SIMD its length IS the
-            // kernel's time (rec op 30 on 32 lines: 720 -> 240 MFMAs per wave).  Results do not depend on NT.
-            int ntl = nt;
-            if (a.out_mode != OUT_HEAD && rt_options().conv_small_nt) {  // OCR_CONV_SMALL_NT=0: keep the table's NT (A/B)
-              auto wgs = [&](int t) { return ((a.M + 127) / 128) * (long)(a.NTtot / t); };
-              while (ntl > 1 && wgs(ntl) < 512) {
-                int t = ntl - 1;
-                while (t > 1 && a.NTtot % t) --t;
-                ntl = t;
-              }
-            }
-            // Big 1x1 convs: two pixel tiles per wave (kernels_net.hip, conv_mfma_mt_kernel) - a weight fragment feeds two
-            // MFMAs, half the workgroups stage parameters; worth it from K = 192 on while the launch still has ~4
-            // workgroups per CU (rec ops 25/30/32/34, det ops 30/38).  Results do not depend on the tiling.
-            const bool mt2 = rt_options().conv_mt2 && (nt == 3 || nt == 4) && taps == 1 && a.out_mode == OUT_C8I &&
-                             (rt_options().conv_mt2_force || (ntl == nt && in.cs >= 192 && ((a.M + 255) / 256) * (long)(a.NTtot / nt) >= 1024));
-            if (mt2) ntl = nt;  // (the two-tile kernel is instantiated for the table's NT)
-            const bool half_tile = hconv && taps == 9 && (!rag || img);  // precision "fp16": the LDS-resident 3x3 tile kernel has an f16 form (uniform batches, ragged batches of images)
-            L.fn = [this, a, ep, ntl, nt, mt2, half_tile](hipStream_t s) {
-              if (half_tile && launch_conv3x3_tile(a, ep, nt, s)) return;
-              if (a.cat_n) { this->launch_error_ = "folded concat: the 3x3 conv's f16 tile kernel refused the launch"; return; }
-              if (mt2 && launch_conv_mfma_mt2(a, ep, ntl, s)) return;
-              if (!launch_conv_mfma(a, ep, ntl, s)) this->launch_error_ = "launch_conv_mfma: this conv shape / output mode is not instantiated";
-            };
-          }
-        }
-      } break;
-      case PlanOp::DW: {
-        if (xdw_of[oi] >= 0) {  // the expand 1x1 conv in front of it runs inside this launch (kernels_xdw.hip)
-          const PlanOp& c = plan_.ops[xdw_of[oi]];
-          const TensorDesc& xin = T[c.in];
-          Epilogue ce, de;
-          if (!build_epilogue(c, ce, true, err) || !build_epilogue(op, de, false, err)) return false;
-          XdwArgs a{};
-          a.x = arena_ + xin.offset; a.wfrag = dev_vec("frag:" + c.w);
-          a.e_sc = ce.st[0].v0; a.e_sh = ce.st[0].v1;
-          a.dw_w = dev_vec("dw:" + op.w); a.d_sc = de.st[0].v0; a.d_sh = de.st[0].v1;
-          a.out = optr; a.part = dw_rowsum[oi] ? gap_part_ : nullptr;
-          a.N = xin.n; a.Hin = xin.h; a.Hout = o.h; a.W = xin.w; a.Cs_in = xin.cs; a.Cs_e = o.cs;
-          const int tiles = (T[c.out].cs + 31) / 32, nt = conv_nt_for(tiles);
-          a.NTtot = (tiles + nt - 1) / nt * nt;
-          a.K = op.kh; a.SH = op.sh; a.SW = op.sw; a.PH = op.ph; a.PW = op.pw;
-          if (!a.wfrag || !a.e_sc || !a.e_sh || !a.dw_w || !a.d_sc || !a.d_sh) { err = "expand -> depthwise block: a parameter image is missing for " + c.w; return false; }
-          snprintf(nm, sizeof nm, "%s.%02d.xdw%dx%d_%d_%d_s%d%d%s", plan_.name.c_str(), oi, op.kh, op.kw, c.cin, op.c, op.sh, op.sw, dw_rowsum[oi] ? "_rowsum" : "");
-          L.name = nm;
-          L.flops = 2.0 * xin.pixels() * c.cin * c.cout + 2.0 * o.pixels() * op.kh * op.kw * op.c;
-          L.bytes = EB(xin) * xin.pixels() * c.cin + EB(o) * o.pixels() * op.c;
-          L.fn = [this, a](hipStream_t s) {
-            if (!launch_xdw(a, s)) this->launch_error_ = "launch_xdw: shape accepted at bind time was refused at launch";
-          };
-          break;
-        }
-        const TensorDesc& in = T[op.in];
-        Epilogue ep;
-        if (!build_epilogue(op, ep, false, err)) return false;
-        for (auto& st : op.ep) if (st.kind == EP_ADDUP) { err = "addup after a depthwise conv is not on this path"; return false; }
-        DwArgs a{};
-        a.in = arena_ + in.offset; a.out = optr; a.w = dev_vec("dw:" + op.w);
-        a.N = in.n; a.H = in.h; a.W = in.w; a.OH = o.h; a.OW = o.w; a.Cs = o.cs; a.K = op.kh;
-        a.SH = op.sh; a.SW = op.sw; a.PH = op.ph; a.PW = op.pw; a.M = o.pixels();
-        if (dw_rowsum[oi]) a.rowsum = gap_part_;
-        a.h16 = o.f16;
-        if (in.f16 != o.f16) { err = "precision fp16: depthwise conv between tensors of different storage"; return false; }
-        if (rag) {
-          a.rin = rlevel(in); a.rout = rlevel(o);
-          a.OW = min_w(o);            // the launcher picks its patch from the narrowest / lowest sample
-          if (img) a.OH = min_h(o);
-          const int to = dw_patch_to(a.OW, a.SW, img ? a.OH : o.h, a.K), pr = dw_patch_r(img ? a.OH : o.h, a.K);
-          const bool rs = dw_rowsum[oi] != 0;
-          const TensorDesc ot = o;
-          a.rwork = work_table("dw:" + std::to_string(o.lvl) + ":" + std::to_string(o.h) + ":" + std::to_string(to) + ":" + std::to_string(pr) + (rs ? ":rs" : ""),
-                               [&, to, pr, rs](int i) {
-                                 const int bands = (sh_of(ot, i) + pr - 1) / pr;
-                                 return rs ? bands : bands * ((sw_of(ot, i) + to - 1) / to);
-                               }, a.rwork_total);
-        }
-        snprintf(nm, sizeof nm, "%s.%02d.dw%dx%d_%d_s%d%d%s", plan_.name.c_str(), oi, op.kh, op.kw, op.c, op.sh, op.sw, dw_rowsum[oi] ? "_rowsum" : "");
-        L.name = nm;
-        L.flops = 2.0 * a.M * op.kh * op.kw * op.c;
-        L.bytes = EB(in) * in.pixels() * op.c + EB(o) * a.M * op.c;
-        // the low maps' 5x5 layers: region staged through LDS (kernels_dwlds.hip); asked now, on the device that will run it
-        const bool lds_dw = rt_options().dw_lds && launch_dw_lds(a, ep, nullptr, true);
-        L.fn = [this, a, ep, lds_dw](hipStream_t s) {
-          if (lds_dw) {
-            if (!launch_dw_lds(a, ep, s)) this->launch_error_ = "launch_dw_lds: shape accepted at bind time was refused at launch";
-            return;
-          }
-          launch_dw(a, ep, s);
-        };
-      } break;
-      case PlanOp::EW: {
-        const TensorDesc& in = T[op.in];
-        Epilogue ep;
-        if (!build_epilogue(op, ep, false, err)) return false;
-        const float* ip = arena_ + in.offset;
-        const long M = o.pixels();
-        const int H2 = o.h, W2 = o.w, Cs = o.cs;
-        if (rag && !img) for (auto& st : op.ep) if (st.kind == EP_ADDUP) { err = "ragged batch: upsampled operand is not on this path"; return false; }
-        const RagLevel rl = rlevel(o);
-        const int nl = o.n;
-        snprintf(nm, sizeof nm, "%s.%02d.ew_%d", plan_.name.c_str(), oi, op.c);
-        L.name = nm;
-        L.bytes = EB(o) * M * op.c * (2.0 + (double)op.ep.size() - 1.0);
-        const bool h16 = o.f16;
-        if (in.f16 != o.f16) { err = "precision fp16: elementwise op between tensors of different storage"; return false; }
-        L.fn = [ip, optr, M, H2, W2, Cs, ep, nl, rl, h16](hipStream_t s) { launch_ew(ip, optr, M, H2, W2, Cs, ep, s, nl, rl, h16); };
-      } break;
-      case PlanOp::GAP: {
-        const TensorDesc& in = T[op.in];
-        const float* ip = arena_ + in.offset;
-        float* part = gap_part_;
-        const int n = in.n, h = in.h, w = in.w, cs = in.cs;
-        const RagLevel rl = rlevel(in);
-        const long grows = rag ? rows_of(in) : 0;
-        snprintf(nm, sizeof nm, "%s.%02d.gap_%d", plan_.name.c_str(), oi, op.c);
-        L.name = nm;
-        L.bytes = EB(in) * in.pixels() * op.c;
-        const bool h16 = in.f16;
-        if (oi > 0 && (dw_rowsum[oi - 1] || rse_first[oi - 1])) {  // the row sums are already in `part` (written by the depthwise conv / the conv's row-sum pass before this op)
-          L.bytes = 4.0 * (double)n * h * op.c;
-          L.fn = [part, optr, n, h, w, cs, rl](hipStream_t s) { launch_gap_cols(part, optr, n, h, w, cs, s, rl); };
-        } else
-        L.fn = [ip, part, optr, n, h, w, cs, rl, grows, h16](hipStream_t s) { launch_gap(ip, part, optr, n, h, w, cs, s, rl, grows, h16); };
-      } break;
-      case PlanOp::SEFC: {
-        const TensorDesc& in = T[op.in];
-        SeArgs a{};
-        a.in = arena_ + in.offset; a.out = optr;
-        a.w1 = dev_vec("raw:" + op.w1); a.b1 = dev_vec("raw:" + op.b1);
-        a.w2 = dev_vec("raw:" + op.w2); a.b2 = dev_vec("raw:" + op.b2);
-        a.C = op.c; a.Cs = o.cs; a.R = op.cr; a.slope = op.slope; a.offset = op.offset;
-        const int n = in.n;
-        snprintf(nm, sizeof nm, "%s.%02d.sefc_%d", plan_.name.c_str(), oi, op.c);
-        L.name = nm;
-        L.flops = 4.0 * n * op.c * op.cr;
-        L.fn = [a, n](hipStream_t s) { launch_sefc(a, n, s); };
-      } break;
-      case PlanOp::CONCAT: {
-        ConcatArgs a{};
-        a.out = optr; a.H = o.h; a.W = o.w; a.Cs = o.cs; a.M = o.pixels();
-        if (img) { a.rout = rlevel(o); a.N = N; }
-        else if (rag) { a.H = 1; a.W = (int)a.M; }  // lines: same-resolution sources (checked above), one row axis
-        a.nsrc = (int)op.ins.size();
-        if (a.nsrc > 4) { err = "concat arity not on this path"; return false; }
-        int off = 0;
-        for (int j = 0; j < a.nsrc; ++j) {
-          const TensorDesc& sj = T[op.ins[j]];
-          if (sj.c % 8) { err = "concat source channels must be a multiple of 8"; return false; }
-          if (sj.f16 != o.f16) { err = "precision fp16: concat of tensors of different storage"; return false; }
-          a.src[j] = arena_ + sj.offset; a.coff[j] = off; a.scs[j] = sj.cs; a.up[j] = op.ups[j];
-          off += sj.cs;
-        }
-        snprintf(nm, sizeof nm, "%s.%02d.concat_%d", plan_.name.c_str(), oi, op.c);
-        L.name = nm;
-        a.h16 = o.f16;
-        L.bytes = 2.0 * EB(o) * a.M * op.c;
-        L.fn = [a](hipStream_t s) { launch_concat(a, s); };
-      } break;
-      case PlanOp::POOL: {
-        const TensorDesc& in = T[op.in];
-        PoolArgs a{};
-        a.in = arena_ + in.offset; a.out = optr; a.N = in.n; a.H = in.h; a.W = in.w; a.OH = o.h; a.OW = o.w;
-        a.Cs = o.cs; a.KH = op.kh; a.KW = op.kw; a.SH = op.sh; a.SW = op.sw; a.is_max = op.pool_max;
-        a.M = o.pixels();
-        a.rin = rlevel(in); a.rout = rlevel(o);
-        a.h16 = o.f16;
-        if (in.f16 != o.f16) { err = "precision fp16: pool between tensors of different storage"; return false; }
-        snprintf(nm, sizeof nm, "%s.%02d.pool_%d", plan_.name.c_str(), oi, op.c);
-        L.name = nm;
-        L.bytes = EB(in) * in.pixels() * op.c + EB(o) * a.M * op.c;
-        L.fn = [a](hipStream_t s) { launch_pool(a, s); };
-      } break;
-      case PlanOp::LN: {
-        const TensorDesc& in = T[op.in];
-        const float* ip = arena_ + in.offset;
-        const long rows = in.pixels();
-        const int C = op.c, Cs = in.cs;
-        const float eps = op.eps;
-        const float* g = dev_vec("raw:" + op.g);
-        const float* b = dev_vec("raw:" + op.b);
-        snprintf(nm, sizeof nm, "%s.%02d.ln_%d", plan_.name.c_str(), oi, op.c);
-        L.name = nm;
-        L.bytes = 2.0 * EB(in) * rows * C;
-        const bool h16 = in.f16;
-        if (in.f16 != o.f16) { err = "precision fp16: layer norm between tensors of different storage"; return false; }
-        L.fn = [ip, optr, rows, C, Cs, eps, g, b, h16](hipStream_t s) { launch_ln(ip, optr, rows, C, Cs, eps, g, b, s, h16); };
-      } break;
-      case PlanOp::ATTN: {
-        const TensorDesc& in = T[op.in];
-        if (in.h != 1) { err = "attention expects a sequence (H == 1): rec input height must reduce to 1"; return false; }
-        const float* ip = arena_ + in.offset;
-        const int n = in.n, t = in.w, heads = op.heads, hd = op.hd, csi = in.cs, cso = o.cs;
-        const float sc = op.scale;
-        const RagLevel rl = rlevel(in);
-        if (rag && !attn_ragged_fits(t)) { err = "ragged batch: line too wide for the attention kernel"; return false; }
-        double tt = (double)n * t * t;  // sum over lines of T^2
-        if (rag) { tt = 0; for (int v : LW[in.lvl]) tt += (double)v * v; }
-        snprintf(nm, sizeof nm, "%s.%02d.attn_%dx%d", plan_.name.c_str(), oi, op.heads, op.hd);
-        L.name = nm;
-        L.flops = 3.0 * 2.0 * heads * tt * hd + 2.0 * heads * tt * hd;
-        L.bytes = EB(in) * in.pixels() * (3.0 + 1.0) * heads * hd;
-        const bool h16 = in.f16;
-        if (in.f16 != o.f16) { err = "precision fp16: attention between tensors of different storage"; return false; }
-        L.fn = [ip, optr, n, t, heads, hd, csi, cso, sc, rl, h16](hipStream_t s) { launch_attn(ip, optr, n, t, heads, hd, csi, cso, sc, s, rl, h16); };
-      } break;
-      case PlanOp::SOFTMAX: {
-        const TensorDesc& in = T[op.in];
-        const float* ip = arena_ + in.offset;
-        const long rows = in.pixels();
-        const int C = op.c;
-        snprintf(nm, sizeof nm, "%s.%02d.softmax_%d", plan_.name.c_str(), oi, op.c);
-        L.name = nm;
-        L.bytes = 4.0 * rows * C * 3;
-        // `optr` (the plan's softmax tensor) is only filled when no external sink is set or probs are requested
-        if (fused_head_rows_ == rows && oi > 0 && plan_.ops[oi - 1].kind == PlanOp::LINEAR && plan_.ops[oi - 1].out == op.in) {
-          // second half of the fused head (the linear before this op ran in OUT_HEAD mode)
-          const float* hm = head_part_;
-          const float* hs = head_part_ + (size_t)rows * fused_head_groups_;
-          const int* hi = (const int*)(head_part_ + (size_t)rows * fused_head_groups_ * 2);
-          const int G = fused_head_groups_;
-          L.bytes = 12.0 * rows * G;
-          L.fn = [this, hm, hs, hi, rows, G](hipStream_t s) { launch_head_combine(hm, hs, hi, rows, G, this->head_amax_, this->head_pmax_, s); };
-        } else {
-          L.fn = [this, ip, optr, rows, C](hipStream_t s) {
-            float* probs = (this->head_amax_ || this->head_pmax_) ? this->head_probs_ : optr;
-            launch_softmax_argmax(ip, probs, this->head_amax_, this->head_pmax_, rows, C, s);
-          };
-        }
-      } break;
-      default: break;
-    }
-    // instance tag: the same op at another bound shape is another roofline row
-    if (img) snprintf(nm, sizeof nm, "@%dx~%ldx~%ld", N, irows / N, ipix / irows);  // ragged images: mean height, mean width
-    else if (rag) snprintf(nm, sizeof nm, "@%dx%dx~%ld", N, H, ltot[0] / N);  // ragged: the lines' mean width
-    else snprintf(nm, sizeof nm, "@%dx%dx%d", N, H, W);
-    L.name += nm;
-    launches_.push_back(std::move(L));
   }
-  if (tab_overflow) { err = "ragged batch: work-table space exhausted"; return false; }
-  if (moved) cache_.clear();
+  // instance tag: the same op at another bound shape is another roofline row
+  std::string instance_tag() const {
+    if (img) return fmt("@%dx~%ldx~%ld", N, irows / N, ipix / irows);  // ragged images: mean height, mean width
+    if (rag) return fmt("@%dx%dx~%ld", N, H, ltot[0] / N);             // ragged: the lines' mean width
+    return fmt("@%dx%dx%d", N, H, W);
+  }
+};
+
+bool Net::bind(int N, int H, int W, std::string& err, const int* widths, const int* heights) {
+  stats_.binds++;
+  std::unique_ptr<Binding> B(new Binding());
+  B->n = N; B->h = H; B->w = W;
+  B->pool = pool_;
+  fused_head_rows_ = -1;
+  BindCtx c(*this, B.get(), N, H, W, widths, heights, err);
+  if (!(c.img ? c.shapes_images() : c.rag ? c.shapes_lines() : c.shapes_uniform())) return false;
+  if (c.rag && !c.ragged_tables()) return false;
+  c.count_uses();
+  c.plan_gate_fold();
+  c.plan_xdw();
+  c.plan_dwpw();
+  c.plan_dw_rowsum();
+  c.plan_db_head();
+  c.plan_concat_same_res();
+  c.plan_concat_neck();
+  c.plan_rse();
+  if (!c.plan_arena()) return false;
+  const std::string tag = c.instance_tag();
+  for (int oi = 0; oi < c.nops; ++oi) {
+    if (plan_.ops[oi].kind == PlanOp::OUTPUT || c.folded[oi] || c.fused_dw[oi]) continue;
+    Launch L;
+    if (!c.emit(oi, L)) return false;
+    L.name += tag;
+    B->launches.push_back(std::move(L));
+  }
+  if (c.tab_overflow) { err = "ragged batch: work-table space exhausted"; return false; }
+  if (c.moved) cache_.clear();
   while (cache_.size() >= max_bindings_) {  // least recently used out
     auto old = cache_.begin();
     for (auto it = cache_.begin(); it != cache_.end(); ++it)

@@ -160,6 +160,27 @@ def test_ab_switches_do_not_change_results(built, idx):
     assert rc == 0 and "AB OK" in so, so[-2000:] + se[-2000:]
 
 
+_LAUNCH_LISTS = {}
+
+
+@pytest.mark.parametrize("group", ["cases", "gap_min1_mt2_force", "fuse0"])
+def test_binder_decisions_equal_the_recorded_launch_lists(built, group):
+    """What Net::bind decides is invisible to the bit-exact tests above (a launch moved to another launcher gives the same
+    numbers): tools/net_launch_list.py lists, per case, every launch of one forward (name, count, flops, bytes) and which plan
+    tensors exist.  tests/golden/net_launch_lists.json is its output at the commit before bind was split into phases; the same
+    tool now must give exactly that - uniform fp32 / fp16 batches at keep_all 0, 1, 2, both ragged forms, one Pipe run, and
+    the det / rec cases again under two switch sets (one child process each, started together with the main cases)."""
+    import json
+    import net_launch_list
+    if not _LAUNCH_LISTS:
+        _LAUNCH_LISTS.update(net_launch_list.collect_all())
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "net_launch_lists.json")))
+    want, got = (want["cases"], _LAUNCH_LISTS["cases"]) if group == "cases" else (want["switches"][group], _LAUNCH_LISTS["switches"][group])
+    assert sorted(got) == sorted(want)
+    for key in sorted(want):
+        assert got[key] == want[key], key
+
+
 @pytest.mark.parametrize("kind,shape", [("det", (2, 96, 160)), ("det", (1, 192, 384)), ("det", (3, 64, 64)), ("rec", (3, 48, 320)),
                                         ("rec", (2, 28, 192)), ("rec", (1, 48, 1000)), ("rec", (5, 48, 136)), ("cls", (3, 48, 192))])
 def test_fused_launch_list_every_materialised_tensor_bit_identical(pkg, built, kind, shape):
