@@ -52,7 +52,7 @@ EXPORTS = [
     "ocr_det_last_shape", "ocr_det_prob_map", "ocr_det_bitmap", "ocr_det_resized", "ocr_det_post",
     "ocr_cls_cfg_default", "ocr_cls_create", "ocr_cls_destroy", "ocr_cls_run", "ocr_cls_probs",
     "ocr_rec_cfg_default", "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_run", "ocr_rec_label",
-    "ocr_rec_num_classes", "ocr_rec_steps",
+    "ocr_rec_num_classes", "ocr_rec_steps", "ocr_rec_run_chars", "ocr_rec_logits_row", "ocr_selftest_topk",
     "ocr_net_create", "ocr_net_create_precision", "ocr_net_destroy", "ocr_net_forward", "ocr_net_forward_ragged", "ocr_net_forward_ragged_images", "ocr_net_num_tensors", "ocr_net_tensor_exists", "ocr_net_fetch",
     "ocr_net_timing", "ocr_net_timing_report", "ocr_probe", "ocr_selftest_refuse_launch", "ocr_selftest_lds_memo",
     "ocr_selftest_unclip", "ocr_selftest_unclip_box",
@@ -216,6 +216,23 @@ def selftest_unclip_box(boxes, unclip_ratio):
     return out, st
 
 
+def selftest_topk(rows, p0, k, ncols=None):
+    """the top-k kernel alone (ocr_selftest_topk): rows [n, pitch] f32 of which the first ncols columns are a logits row, p0 [n]
+    the rank-0 probability -> (ids [n, k] int32, probs [n, k] f32); ranks a row does not have: id -1, prob 0"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    assert rows.ndim == 2
+    n, pitch = rows.shape
+    C_ = pitch if ncols is None else int(ncols)
+    p0 = np.ascontiguousarray(p0, dtype=np.float32).reshape(n)
+    ids = np.zeros((n, k), np.int32)
+    probs = np.zeros((n, k), np.float32)
+    L = lib()
+    L.ocr_selftest_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_void_p]
+    check(L.ocr_selftest_topk(rows.ctypes.data, n, C_, pitch, p0.ctypes.data, int(k), ids.ctypes.data, probs.ctypes.data))
+    return ids, probs
+
+
 def probe(a, b):
     a = np.ascontiguousarray(a, dtype=np.float32)
     b = np.ascontiguousarray(b, dtype=np.float32)
@@ -348,6 +365,9 @@ def _stage_protos(L):
     L.ocr_rec_label.restype = C.c_char_p
     L.ocr_rec_num_classes.argtypes = [vp]
     L.ocr_rec_steps.argtypes = [vp, C.c_int, vp, vp, C.c_int, ip]
+    L.ocr_rec_run_chars.argtypes = [vp, C.POINTER(ocr_img), C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp,
+                                    C.POINTER(C.c_double)]
+    L.ocr_rec_logits_row.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
     L._stage_protos_done = True
 
 
@@ -477,6 +497,40 @@ class Rec:
                                     scores.ctypes.data, self.times))
         return [ids[i, :lens[i]].copy() for i in range(n)], scores
 
+    def run_chars(self, crops, max_len=512, topk=0):
+        """ocr_rec_run_chars: run() plus, per line, dict(steps, nsteps, probs [len], geom (T, tensor_w, resize_w) and, with
+        topk > 0, alt_ids / alt_probs [len, topk]) -> (ids list, scores, chars list)"""
+        n = len(crops)
+        ids = np.zeros((n, max_len), np.int32)
+        lens = np.zeros(n, np.int32)
+        scores = np.zeros(n, np.float32)
+        steps = np.zeros((n, max_len), np.int32)
+        nsteps = np.zeros((n, max_len), np.int32)
+        probs = np.zeros((n, max_len), np.float32)
+        geom = np.zeros((n, 3), np.int32)
+        kk = max(int(topk), 1)
+        alt_ids = np.zeros((n, max_len, kk), np.int32)
+        alt_probs = np.zeros((n, max_len, kk), np.float32)
+        if n:
+            check(lib().ocr_rec_run_chars(self.h, _imgs(crops), n, ids.ctypes.data, max_len, lens.ctypes.data, scores.ctypes.data,
+                                          steps.ctypes.data, nsteps.ctypes.data, probs.ctypes.data, geom.ctypes.data, int(topk),
+                                          alt_ids.ctypes.data, alt_probs.ctypes.data, self.times))
+        chars = []
+        for i in range(n):
+            m = lens[i]
+            c = dict(steps=steps[i, :m].copy(), nsteps=nsteps[i, :m].copy(), probs=probs[i, :m].copy(), geom=tuple(int(v) for v in geom[i]))
+            if topk > 0:
+                c["alt_ids"] = alt_ids[i, :m].copy()
+                c["alt_probs"] = alt_probs[i, :m].copy()
+            chars.append(c)
+        return [ids[i, :lens[i]].copy() for i in range(n)], scores, chars
+
+    def logits_row(self, index, step):
+        """tap: the logits row the top-k kernel read for step `step` of line `index` of the last run_chars(topk > 0)"""
+        out = np.zeros(self.num_classes(), np.float32)
+        check(lib().ocr_rec_logits_row(self.h, int(index), int(step), out.ctypes.data, out.size))
+        return out
+
     def steps(self, index, cap=4096):
         amax = np.zeros(cap, np.int32)
         pmax = np.zeros(cap, np.float32)
@@ -512,7 +566,11 @@ class ocr_word(C.Structure):
     _fields_ = [("box", C.c_int32 * 8), ("ids_off", C.c_int32), ("ids_len", C.c_int32), ("confidence", C.c_float)]
 
 
-EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_pipe_run", "ocr_pipe_run_device",
+class ocr_char(C.Structure):
+    _fields_ = [("step", C.c_int32), ("nsteps", C.c_int32), ("prob", C.c_float), ("quad", C.c_int32 * 8)]
+
+
+EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_pipe_run", "ocr_pipe_run_chars", "ocr_pipe_run_device",
             "ocr_pipe_stage", "ocr_pipe_slot_probs", "ocr_pipe_run_staged", "ocr_pipe_run_device_on", "ocr_pipe_run_staged_on", "ocr_pipe_stage_jpeg", "ocr_jpeg_decode",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
@@ -527,6 +585,7 @@ def _pipe_protos(L):
     L.ocr_pipe_create.argtypes = [C.POINTER(ocr_pipe_cfg), C.POINTER(vp)]
     L.ocr_pipe_destroy.argtypes = [vp]
     L.ocr_pipe_run.argtypes = [vp, C.POINTER(ocr_img), C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(C.c_double)]
+    L.ocr_pipe_run_chars.argtypes = [vp, C.POINTER(ocr_img), C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.POINTER(C.c_double)]
     L.ocr_pipe_run_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int,
                                       C.POINTER(C.c_double)]
     L.ocr_pipe_stage.argtypes = [vp, C.c_int, C.POINTER(ocr_img), C.c_int]
@@ -680,6 +739,25 @@ class Pipe:
         check(lib().ocr_pipe_run(self.h, _imgs(imgs), n, words, self._cap_words, off.ctypes.data, nw.ctypes.data,
                                  ids.ctypes.data, self._cap_ids, self.times))
         return self._collect(n, words, ids, off, nw)
+
+    def run_chars(self, imgs):
+        """ocr_pipe_run_chars: run() with, per word, chars = [dict(step, nsteps, prob, quad [4, 2])] parallel to its ids"""
+        n = len(imgs)
+        words, ids = self._bufs(n)
+        chars = np.zeros((self._cap_ids, 11), np.int32)  # ocr_char: 11 dwords (step, nsteps, prob as f32 bits, quad[8])
+        assert C.sizeof(ocr_char) == 44
+        off = np.zeros(n, np.int32)
+        nw = np.zeros(n, np.int32)
+        check(lib().ocr_pipe_run_chars(self.h, _imgs(imgs), n, words, self._cap_words, off.ctypes.data, nw.ctypes.data,
+                                       ids.ctypes.data, self._cap_ids, chars.ctypes.data, self.times))
+        out = self._collect(n, words, ids, off, nw)
+        for i in range(n):
+            for k, w in enumerate(out[i]):
+                cw = words[off[i] + k]
+                rows = chars[cw.ids_off:cw.ids_off + cw.ids_len]
+                w["chars"] = [dict(step=int(r[0]), nsteps=int(r[1]), prob=float(r[2:3].view(np.float32)[0]),
+                                   quad=r[3:].reshape(4, 2).copy()) for r in rows]
+        return out
 
     def stage(self, slot, imgs, probs=None):
         """ocr_pipe_stage: host images (any sizes) -> pinned memory -> device, asynchronously.  probs: per image a

@@ -1,6 +1,7 @@
 // C-ABI: detector / classifier / recognizer handles (include/ocr_hip.h).
 #include <cstring>
 #include <memory>
+#include <vector>
 
 #include "capi_common.h"
 #include "stages.h"
@@ -203,6 +204,43 @@ int ocr_rec_run(ocr_rec* h, const ocr_img* imgs, int n, int32_t* ids, int max_le
   std::string err;
   const int rc = h->s.run(imgs, n, ids, max_len, lens, scores, times, err);
   return rc ? fail(rc, err) : OCR_OK;
+}
+int ocr_rec_run_chars(ocr_rec* h, const ocr_img* imgs, int n, int32_t* ids, int max_len, int* lens, float* scores, int32_t* steps,
+                      int32_t* nsteps, float* probs, int32_t* geom, int topk, int32_t* alt_ids, float* alt_probs, double times[3]) {
+  if (!h) return fail(OCR_ERR_ARG, "null handle");
+  RecStage::CharOut co;
+  co.steps = steps; co.nsteps = nsteps; co.probs = probs; co.geom = geom;
+  co.topk = topk; co.alt_ids = alt_ids; co.alt_probs = alt_probs;
+  std::string err;
+  const int rc = h->s.run_chars(imgs, n, ids, max_len, lens, scores, co, times, err);
+  return rc ? fail(rc, err) : OCR_OK;
+}
+int ocr_rec_logits_row(ocr_rec* h, int index, int step, float* out, size_t cap_floats) {
+  if (!h) return fail(OCR_ERR_ARG, "null handle");
+  std::string err;
+  const int rc = h->s.logits_row(index, step, out, cap_floats, err);
+  return rc ? fail(rc, err) : OCR_OK;
+}
+// self-test: the top-k kernel alone - every caller row is "line i, one step, one kept character" of a uniform table
+int ocr_selftest_topk(const float* rows, int n, int C, int pitch, const float* p0, int k, int32_t* out_ids, float* out_probs) {
+  if (!rows || !p0 || !out_ids || !out_probs || n < 1 || C < 1 || pitch < C || k < 1 || k > 8) return fail(OCR_ERR_ARG, "bad argument");
+  std::string err;
+  DevBuf<float> drows, dp0, dprobs;
+  DevBuf<int> dlens, dsteps, dids;
+  const size_t nfl = (size_t)(n - 1) * pitch + C;
+  if (!drows.ensure(nfl, err) || !dp0.ensure(n, err) || !dprobs.ensure((size_t)n * k, err) || !dlens.ensure(n, err) ||
+      !dsteps.ensure(n, err) || !dids.ensure((size_t)n * k, err))
+    return fail(OCR_ERR_DEVICE, err);
+  const std::vector<int> ones(n, 1), zeros(n, 0);
+  CAPI_HIP(g_memcpy(drows.p, rows, nfl * sizeof(float), hipMemcpyHostToDevice));
+  CAPI_HIP(g_memcpy(dp0.p, p0, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  CAPI_HIP(g_memcpy(dlens.p, ones.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  CAPI_HIP(g_memcpy(dsteps.p, zeros.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  launch_ctc_topk(drows.p, pitch, C, k, nullptr, n, 1, 1, dlens.p, dsteps.p, dp0.p, dids.p, dprobs.p, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(g_memcpy(out_ids, dids.p, (size_t)n * k * sizeof(int), hipMemcpyDeviceToHost));
+  CAPI_HIP(g_memcpy(out_probs, dprobs.p, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost));
+  return OCR_OK;
 }
 const char* ocr_rec_label(ocr_rec* h, int id) {
   if (!h || id < 0 || id >= (int)h->s.labels().size()) return nullptr;

@@ -5,6 +5,7 @@
 // Arithmetic: plain IEEE double, evaluation order of cv::getPerspectiveTransform (LU with partial
 // pivoting) and of cv::invert's 3x3 closed form; this file is compiled with -ffp-contract=off.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <utility>
@@ -110,6 +111,45 @@ inline bool plan_rotate_crop(int rows, int cols, const int32_t* b, CropPlan& p) 
   fwd[8] = 1.;
   cropmath::inverse3(fwd, p.minv);
   return true;
+}
+
+// Where kept character (step, nsteps) of a text line sits in the SOURCE image (ocr_pipe_run_chars), in plain IEEE double:
+// with s = tensor_w / T the character spans tensor columns [step * s, (step + nsteps) * s), clipped to [0, resize_w] and
+// scaled by crop_w / resize_w into the x of the crop_w x crop_h line image the recognizer read; the quad takes the full crop
+// height; corners top-left, top-right, bottom-right, bottom-left in reading orientation.  `turned`: the classifier rotated
+// the crop by 180 degrees before it was read - mirror x and y in the crop.  Then back into the image: plan == null
+// (OCR_CROP_BOUNDING_RECT) adds the crop rectangle's origin (ox, oy); plan != null (OCR_CROP_ROTATE) undoes the 90-degree
+// turn (image row R, column c of the turned crop is warp pixel (dw - 1 - R, c): continuous (x, y) -> (dw - y, x)) and maps
+// through the crop's inverse homography.  Rounded half up, clamped to [0, cols - 1] x [0, rows - 1].
+inline void char_quad(int step, int nsteps, int T, int tensor_w, int resize_w, int crop_w, int crop_h, bool turned, const CropPlan* plan,
+                      int ox, int oy, int rows, int cols, int32_t quad[8]) {
+  const double s = (double)tensor_w / (double)T;
+  double xa = (double)step * s, xb = (double)(step + nsteps) * s;
+  xa = std::min(std::max(xa, 0.), (double)resize_w);
+  xb = std::min(std::max(xb, 0.), (double)resize_w);
+  const double sx = (double)crop_w / (double)resize_w;
+  xa = xa * sx;
+  xb = xb * sx;
+  const double px[4] = {xa, xb, xb, xa}, py[4] = {0., 0., (double)crop_h, (double)crop_h};
+  for (int k = 0; k < 4; ++k) {
+    double x = px[k], y = py[k];
+    if (turned) { x = (double)crop_w - x; y = (double)crop_h - y; }
+    double X, Y;
+    if (!plan) {
+      X = (double)ox + x;
+      Y = (double)oy + y;
+    } else {
+      const double u = plan->rot ? (double)plan->dw - y : x, v = plan->rot ? x : y;
+      const double* m = plan->minv;
+      const double w = m[6] * u + m[7] * v + m[8];
+      const double iw = w != 0. ? 1. / w : 0.;
+      X = (double)plan->left + (m[0] * u + m[1] * v + m[2]) * iw;
+      Y = (double)plan->top + (m[3] * u + m[4] * v + m[5]) * iw;
+    }
+    const double rx = std::floor(X + 0.5), ry = std::floor(Y + 0.5);
+    quad[2 * k] = (int32_t)std::min(std::max(rx, 0.), (double)(cols - 1));
+    quad[2 * k + 1] = (int32_t)std::min(std::max(ry, 0.), (double)(rows - 1));
+  }
 }
 
 }  // namespace ocr

@@ -67,5 +67,16 @@ void launch_ctc(const int* amax, const float* pmax, int nlines, int T, int max_l
 // ragged batch: line i has lines[i].steps steps starting at lines[i].step0 of amax / pmax
 void launch_ctc_ragged(const int* amax, const float* pmax, const LineDesc* lines, int nlines, int max_len, int* ids, int* lens,
                        float* scores, hipStream_t s);
+// launch_ctc / launch_ctc_ragged (lines != null: the ragged form, T unused) that also writes, per kept character (arrays
+// parallel to ids), its CTC step, the length of its run of equal arg maxes and pmax[step]
+void launch_ctc_chars(const int* amax, const float* pmax, const LineDesc* lines, int nlines, int T, int max_len, int* ids, int* lens,
+                      float* scores, int* steps, int* nsteps, float* probs, hipStream_t s);
+// The k (1..8) best classes of the logits row behind every kept character, one wave per character: row = (lines ?
+// lines[li].step0 : li * T) + steps[li * max_len + j] of `logits` (rows of C f32, `pitch` floats apart), j < min(lens[li],
+// max_len).  alt_ids / alt_probs: [nlines][max_len][k], rank-major; ranks a row does not have (k > C): id -1, prob 0.
+// Rank by logit descending, equal logits the lower class first, NaN last.  alt_probs rank 0 = probs[li * max_len + j] bit
+// for bit; rank r > 0 = ocr_expf(x_r - x_0) * that value: an estimate, NOT part of the bit-exact contract.
+void launch_ctc_topk(const float* logits, long pitch, int C, int k, const LineDesc* lines, int nlines, int T, int max_len,
+                     const int* lens, const int* steps, const float* probs, int* alt_ids, float* alt_probs, hipStream_t s);
 
 }  // namespace ocr

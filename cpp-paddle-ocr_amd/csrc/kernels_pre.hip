@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "kernels_pre.h"
+#include "ocr_common.h"
 
 namespace ocr {
 
@@ -421,6 +422,145 @@ void launch_ctc_ragged(const int* amax, const float* pmax, const LineDesc* lines
                        float* scores, hipStream_t s) {
   if (nlines <= 0) return;
   hipLaunchKernelGGL(ctc_kernel, dim3((nlines + 63) / 64), dim3(64), 0, s, amax, pmax, nlines, 0, max_len, ids, lens, scores, lines);
+}
+
+// The same collapse that also says where every kept character came from (ocr_rec_run_chars): per kept character j of line
+// li its CTC step, the length of its run of equal arg maxes from that step on, and pmax[step] - the very term of the score
+// sum.  Order, the max_len cut, lens and the score chain are those of ctc_kernel (which stays as it is: the default path).
+__global__ void __launch_bounds__(64) ctc_chars_kernel(const int* __restrict__ amax, const float* __restrict__ pmax, int nlines,
+                                                       int T, int max_len, int* __restrict__ ids, int* __restrict__ lens,
+                                                       float* __restrict__ scores, const LineDesc* __restrict__ lines,
+                                                       int* __restrict__ steps, int* __restrict__ nsteps, float* __restrict__ probs) {
+  const int li = blockIdx.x * 64 + threadIdx.x;
+  if (li >= nlines) return;
+  long first = (long)li * T;
+  if (lines) { first = lines[li].step0; T = lines[li].steps; }
+  const int* am = amax + first;
+  const float* pm = pmax + first;
+  int last = 0, count = 0, cur = -1, run = 0;
+  float s = 0.f;
+  for (int n = 0; n < T; ++n) {
+    const int idx = am[n];
+    if (idx > 0 && !(n > 0 && idx == last)) {
+      if (cur >= 0) nsteps[(long)li * max_len + cur] = run;
+      s += pm[n];
+      cur = -1;
+      if (count < max_len) {
+        cur = count;
+        ids[(long)li * max_len + count] = idx;
+        steps[(long)li * max_len + count] = n;
+        probs[(long)li * max_len + count] = pm[n];
+      }
+      run = 1;
+      count += 1;
+    } else if (idx > 0) {
+      run += 1;  // a repeat of the character kept last
+    }
+    last = idx;
+  }
+  if (cur >= 0) nsteps[(long)li * max_len + cur] = run;
+  lens[li] = count;
+  scores[li] = count > 0 ? s / (float)count : 0.f;
+}
+void launch_ctc_chars(const int* amax, const float* pmax, const LineDesc* lines, int nlines, int T, int max_len, int* ids, int* lens,
+                      float* scores, int* steps, int* nsteps, float* probs, hipStream_t s) {
+  if (nlines <= 0) return;
+  hipLaunchKernelGGL(ctc_chars_kernel, dim3((nlines + 63) / 64), dim3(64), 0, s, amax, pmax, nlines, lines ? 0 : T, max_len, ids, lens,
+                     scores, lines, steps, nsteps, probs);
+}
+
+// =====================================================================================
+// Top-k classes of the logits row behind every kept character (ocr_rec_run_chars, topk > 0): one wave per kept character.
+// Rank = logit descending, equal logits the lower class first - the head's own "first maximum of the logits" (DESIGN.md
+// section 4), so rank 0 is the character's id; NaN ranks below everything (-inf included), NaNs among themselves by index.
+// A candidate is ONE 64-bit key: the logit as an order-preserving u32 (-0 folded into +0, NaN = 0) above ~index, so that
+// "greater key" is the whole rule and key 0 is "no candidate" (index -1).  Each lane keeps the sorted 8 best of its own
+// columns in registers; the wave then merges in k rounds of a butterfly arg max over the lanes' heads (cross-lane shuffles:
+// DPP / ds_bpermute / permlane swaps as the compiler lowers them), the winning lane popping its head.  No LDS, no atomics.
+// The row is read once: 16-byte loads when every row starts 16-byte aligned (VEC, decided per launch), else dword loads.
+// Probabilities: rank 0 is the caller's p0 (pmax[step]) bit for bit; rank r > 0 is ocr_expf(x_r - x_0) * p0 - an estimate
+// on the head's own exp (its argument clamps at -87), NOT part of the bit-exact contract.
+// =====================================================================================
+__device__ __forceinline__ unsigned topk_key(float x) {
+  if (x != x) return 0u;
+  const unsigned u = __float_as_uint(x + 0.0f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float topk_value(unsigned key) {
+  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+__device__ __forceinline__ void topk_insert(unsigned long long (&t)[8], float x, int c) {
+  const unsigned long long v = ((unsigned long long)topk_key(x) << 32) | (unsigned)~c;
+  if (v > t[7]) {
+    t[7] = v;
+#pragma unroll
+    for (int i = 7; i > 0; --i)
+      if (t[i] > t[i - 1]) { const unsigned long long o = t[i]; t[i] = t[i - 1]; t[i - 1] = o; }
+  }
+}
+template <bool VEC>
+__global__ void __launch_bounds__(256) ctc_topk_kernel(const float* __restrict__ logits, long pitch, int C, int k, int T, int max_len,
+                                                       const LineDesc* __restrict__ lines, const int* __restrict__ lens,
+                                                       const int* __restrict__ steps, const float* __restrict__ probs,
+                                                       int* __restrict__ alt_ids, float* __restrict__ alt_probs) {
+  const int lane = threadIdx.x & 63, li = blockIdx.y, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= max_len || j >= lens[li]) return;  // (wave-uniform)
+  const long item = (long)li * max_len + j;
+  const long row = (lines ? (long)lines[li].step0 : (long)li * T) + steps[item];
+  const float* src = logits + row * pitch;
+  unsigned long long t[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) t[i] = 0ull;
+  if (VEC) {
+    for (int c = lane * 4; c < C; c += 256) {
+      if (c + 3 < C) {
+        const float4 v = *(const float4*)(src + c);
+        topk_insert(t, v.x, c); topk_insert(t, v.y, c + 1); topk_insert(t, v.z, c + 2); topk_insert(t, v.w, c + 3);
+      } else {
+        for (int e = c; e < C; ++e) topk_insert(t, src[e], e);
+      }
+    }
+  } else {
+    for (int c = lane; c < C; c += 64) topk_insert(t, src[c], c);
+  }
+  const float p0 = probs[item];
+  float x0 = 0.f;
+  for (int r = 0; r < k; ++r) {
+    unsigned long long best = t[0];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const unsigned hi = __shfl_xor((unsigned)(best >> 32), off), lo = __shfl_xor((unsigned)best, off);
+      const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+      best = o > best ? o : best;
+    }
+    if (best != 0ull && t[0] == best) {  // the owner (keys are unique: they carry the index) pops its head
+#pragma unroll
+      for (int i = 0; i < 7; ++i) t[i] = t[i + 1];
+      t[7] = 0ull;
+    }
+    if (lane == 0) {
+      const float x = topk_value((unsigned)(best >> 32));
+      if (r == 0) x0 = x;
+      float p = 0.f;
+      if (best != 0ull) p = r == 0 ? p0 : (x != x ? x : ocr_expf(x - x0) * p0);  // (a NaN logit has a NaN probability)
+      alt_ids[item * k + r] = best != 0ull ? (int)~(unsigned)best : -1;
+      alt_probs[item * k + r] = p;
+    }
+  }
+}
+void launch_ctc_topk(const float* logits, long pitch, int C, int k, const LineDesc* lines, int nlines, int T, int max_len,
+                     const int* lens, const int* steps, const float* probs, int* alt_ids, float* alt_probs, hipStream_t s) {
+  if (nlines <= 0 || max_len <= 0 || k <= 0) return;
+  const bool vec = pitch % 4 == 0 && ((uintptr_t)logits & 15) == 0;
+  for (int at = 0; at < nlines; at += 65535) {  // grid.y limit
+    const int n = std::min(65535, nlines - at);
+    const dim3 grid((unsigned)((max_len + 3) / 4), (unsigned)n);
+    const float* lg = lines ? logits : logits + (long)at * T * pitch;
+    const LineDesc* ld = lines ? lines + at : nullptr;
+    const size_t o = (size_t)at * max_len;
+    if (vec) hipLaunchKernelGGL(ctc_topk_kernel<true>, grid, dim3(256), 0, s, lg, pitch, C, k, T, max_len, ld, lens + at, steps + o, probs + o, alt_ids + o * k, alt_probs + o * k);
+    else hipLaunchKernelGGL(ctc_topk_kernel<false>, grid, dim3(256), 0, s, lg, pitch, C, k, T, max_len, ld, lens + at, steps + o, probs + o, alt_ids + o * k, alt_probs + o * k);
+  }
 }
 
 }  // namespace ocr

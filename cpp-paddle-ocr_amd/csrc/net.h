@@ -115,6 +115,18 @@ class Net {
     if (!same_kind) invalidate();
   }
 
+  // --- rec head option: keep the final linear's logits (top-k classes per kept character, ocr_rec_run_chars) ---
+  // on: the head stays UNFUSED whatever sinks are set - the linear writes its logits tensor, softmax_argmax_kernel fills
+  // amax / pmax from it, and the tensor is intact after the run (nothing is launched behind the softmax and its arena
+  // bytes are shared with no later tensor).  Drops the bindings like a change of the kind of head outputs; off (the
+  // default) leaves the launch lists as they are.
+  void set_keep_logits(bool on) { if (on != keep_logits_) { keep_logits_ = on; invalidate(); } }
+  bool keep_logits() const { return keep_logits_; }
+  // The logits of the current binding: device pointer, rows of C f32 `pitch` floats apart; a uniform binding holds line n's
+  // T steps at rows n * T .., a ragged one line n's at row0[n] .. (row0: N + 1 prefix sums of the lines' step counts).
+  struct HeadLogits { const float* ptr = nullptr; long pitch = 0; int C = 0; std::vector<long> row0; };
+  bool head_logits(HeadLogits& out, std::string& err) const;
+
   // parity debugging: give every tensor its own arena slot so intermediate taps stay valid.
   // 0 = production (liveness-reused arena, fusions on), 1 = every plan tensor materialised (no fusion),
   // 2 = production launch list (gate folding, depthwise->pointwise fusion) but no arena reuse: every tensor that
@@ -212,6 +224,7 @@ class Net {
   float* head_probs_ = nullptr;
   int* head_amax_ = nullptr;
   float* head_pmax_ = nullptr;
+  bool keep_logits_ = false;
   bool timing_ = false;
   bool half_ = false;
   bool graphs_ = true;          // OCR_GRAPH=0 (read when the network is loaded): plain launches only

@@ -1289,7 +1289,7 @@ struct Net::BindCtx {
   // epilogue (no logits tensor) and a per-row combine; canonical groups are 128 columns wide
   bool dense_fused_head(int oi, const PlanOp& op, ConvArgs& a, long hrows, int tiles, int nt) {
     const bool fuse_head = op.kind == PlanOp::LINEAR && T[op.out].plain && oi + 1 < nops && plan.ops[oi + 1].kind == PlanOp::SOFTMAX &&
-                           plan.ops[oi + 1].in == op.out && (net.head_amax_ || net.head_pmax_) && !net.head_probs_ && keep_all == 0 &&
+                           plan.ops[oi + 1].in == op.out && (net.head_amax_ || net.head_pmax_) && !net.head_probs_ && !net.keep_logits_ && keep_all == 0 &&
                            (tiles <= 4 || nt == 4);
     if (!fuse_head) return true;
     a.out_mode = OUT_HEAD;
@@ -1906,6 +1906,27 @@ void Net::collect_timings() {
     ev_pool_.push_back(p.b);
   }
   ev_pending_.clear();
+}
+
+bool Net::head_logits(HeadLogits& out, std::string& err) const {
+  if (!cur_ || !keep_logits_) { err = "no binding that keeps the head's logits (set_keep_logits)"; return false; }
+  for (size_t oi = 1; oi < plan_.ops.size(); ++oi) {
+    const PlanOp& op = plan_.ops[oi];
+    if (op.kind != PlanOp::SOFTMAX || plan_.ops[oi - 1].kind != PlanOp::LINEAR || plan_.ops[oi - 1].out != op.in) continue;
+    const TensorDesc& t = tensors_[op.in];
+    if (!t.plain || !cur_->exists[op.in]) break;
+    out.ptr = arena_ + t.offset;
+    out.pitch = t.cs;
+    out.C = t.c;
+    out.row0.clear();
+    if (t.lvl >= 0 && !cur_->level_w.empty()) {
+      out.row0.push_back(0);
+      for (int w : cur_->level_w[t.lvl]) out.row0.push_back(out.row0.back() + (long)t.h * w);
+    }
+    return true;
+  }
+  err = "the plan has no linear -> softmax head";
+  return false;
 }
 
 bool Net::fetch_logical(int tid, std::vector<float>& host, int dims[4], hipStream_t s, std::string& err) {

@@ -22,8 +22,10 @@ double now_ms() {
 }
 }  // namespace
 
+using CharLists = std::vector<std::vector<ocr_char>>;  // per image: one ocr_char per class id (ocr_pipe_run_chars)
 static int emit(const std::vector<std::vector<ocr_word>>& W, const std::vector<std::vector<int32_t>>& I, const std::vector<int>& order,
-                ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids);
+                ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids, const CharLists* C = nullptr,
+                ocr_char* chars = nullptr);
 
 // One staged batch: host images copied into pinned memory and sent to the device on the copy stream, laid out size
 // group by size group (images of one size are contiguous: one det pass each).  Two slots = double buffering: batch
@@ -114,6 +116,7 @@ struct PipeWorker {
   int crop_mode = 0;  // OCR_CROP_BOUNDING_RECT | OCR_CROP_ROTATE
   DevBuf<uint8_t> crop_arena;
   DevBuf<WarpDesc> warp_desc;
+  std::vector<CropPlan> line_plan;  // OCR_CROP_ROTATE: the crop geometry of every line of the current run
   std::vector<int32_t> boxes;  // [image in layout order][cap][8]
   std::vector<int> nbox;
   static constexpr int kCap = 1000;  // max_candidates bounds the boxes of one image (postprocess_op.cpp:260)
@@ -149,7 +152,8 @@ struct PipeWorker {
   // ---- run: det per size group, then ONE cls pass and ONE rec pass over the crops of every image of the batch
   // (results are batch-invariant, so pooling lines across sizes changes nothing but the launch count)
   int run_images(uint8_t* base, const std::vector<StageSlot::Img>& imgs, const std::vector<StageSlot::Group>& groups, const float* probs,
-                 std::vector<std::vector<ocr_word>>& out_words, std::vector<std::vector<int32_t>>& out_ids, double times[3], std::string& err) {
+                 std::vector<std::vector<ocr_word>>& out_words, std::vector<std::vector<int32_t>>& out_ids, double times[3], std::string& err,
+                 CharLists* out_chars = nullptr) {
     const int count = (int)imgs.size();
     boxes.resize((size_t)count * kCap * 8);
     nbox.assign(count, 0);
@@ -281,6 +285,7 @@ struct PipeWorker {
     std::vector<LineSrc> lines;
     std::vector<int> seg(1, 0);
     std::vector<int> line_box;  // box index (within its image) of every line
+    line_plan.clear();
     if (crop_mode == OCR_CROP_ROTATE) {
       int rc = rotate_crops(base, imgs, lines, seg, line_box, err);
       if (rc) return rc;
@@ -308,9 +313,11 @@ struct PipeWorker {
     }
     out_words.assign(count, {});
     out_ids.assign(count, {});
+    if (out_chars) out_chars->assign(count, {});
     if (lines.empty()) return OCR_OK;
+    std::vector<int> labels;  // per line: 1 = the classifier turned the crop by 180 degrees
     if (cls) {
-      std::vector<int> labels(lines.size());
+      labels.resize(lines.size());
       std::vector<float> scores(lines.size());
       int rc = cls->run_lines(lines, labels.data(), scores.data(), err);
       if (rc) return rc;
@@ -328,7 +335,17 @@ struct PipeWorker {
     std::vector<int32_t> ids(lines.size() * max_len);
     std::vector<int> lens(lines.size());
     std::vector<float> scores(lines.size());
-    int rc = rec.run_lines(lines, seg, ids.data(), max_len, lens.data(), scores.data(), err);
+    std::vector<int32_t> csteps, cnsteps, geom;
+    std::vector<float> cprobs;
+    int rc;
+    if (out_chars) {
+      csteps.resize(ids.size()); cnsteps.resize(ids.size()); cprobs.resize(ids.size()); geom.resize(lines.size() * 3);
+      RecStage::CharOut co;
+      co.steps = csteps.data(); co.nsteps = cnsteps.data(); co.probs = cprobs.data(); co.geom = geom.data();
+      rc = rec.run_lines_chars(lines, seg, ids.data(), max_len, lens.data(), scores.data(), co, err);
+    } else {
+      rc = rec.run_lines(lines, seg, ids.data(), max_len, lens.data(), scores.data(), err);
+    }
     if (rc) return rc;
     times[2] += now_ms() - t2;
     for (int i = 0; i < count; ++i) {
@@ -340,6 +357,16 @@ struct PipeWorker {
         w.confidence = scores[k];
         out_ids[i].insert(out_ids[i].end(), ids.begin() + (size_t)k * max_len, ids.begin() + (size_t)k * max_len + lens[k]);
         out_words[i].push_back(w);
+        if (out_chars)
+          for (int j = 0; j < lens[k]; ++j) {  // the character's quad from the line's own geometry (crop.h, char_quad)
+            const size_t q = (size_t)k * max_len + j;
+            ocr_char ch;
+            ch.step = csteps[q]; ch.nsteps = cnsteps[q]; ch.prob = cprobs[q];
+            const LineSrc& L = lines[k];
+            char_quad(ch.step, ch.nsteps, geom[3 * k], geom[3 * k + 1], geom[3 * k + 2], L.w, L.h, !labels.empty() && labels[k] == 1,
+                      crop_mode == OCR_CROP_ROTATE ? &line_plan[k] : nullptr, L.x, L.y, imgs[i].rows, imgs[i].cols, ch.quad);
+            (*out_chars)[i].push_back(ch);
+          }
       }
     }
     return OCR_OK;
@@ -368,6 +395,7 @@ struct PipeWorker {
         total += ((size_t)p.dw * p.dh * 3 + 15) & ~(size_t)15;
         max_px = std::max(max_px, p.dw * p.dh);
         line_box.push_back(j);
+        line_plan.push_back(p);
         lines.push_back(LineSrc{nullptr, (size_t)p.ocols * 3, 0, 0, p.ocols, p.orows});
       }
       seg.push_back((int)lines.size());
@@ -523,10 +551,11 @@ struct ocr_pipe {
 
   // ---- run: one chain, or several chains on as many parts of the batch
   int run_images(uint8_t* base, const std::vector<StageSlot::Img>& imgs, const std::vector<StageSlot::Group>& groups, const float* probs,
-                 std::vector<std::vector<ocr_word>>& out_words, std::vector<std::vector<int32_t>>& out_ids, double times[3], std::string& err) {
+                 std::vector<std::vector<ocr_word>>& out_words, std::vector<std::vector<int32_t>>& out_ids, double times[3], std::string& err,
+                 CharLists* out_chars = nullptr) {
     const int count = (int)imgs.size();
     const int nchains = (int)std::min<size_t>(1 + extra.size(), (size_t)count);
-    if (nchains < 2) return w0.run_images(base, imgs, groups, probs, out_words, out_ids, times, err);
+    if (nchains < 2) return w0.run_images(base, imgs, groups, probs, out_words, out_ids, times, err, out_chars);
     // K parts, dealt round-robin to the chains (parts_per_chain > 1: a chain runs several smaller parts one after the
     // other, so that the chains drift out of phase and the tail of the call is a part, not half a batch)
     const int K = (int)std::min<size_t>((size_t)nchains * parts_per_chain, (size_t)count);
@@ -567,6 +596,7 @@ struct ocr_pipe {
     if (g_stream_sync(w0.det.stream()) != hipSuccess) { err = "det stream sync failed"; return OCR_ERR_DEVICE; }
     std::vector<std::vector<std::vector<ocr_word>>> W(K);
     std::vector<std::vector<std::vector<int32_t>>> I(K);
+    std::vector<CharLists> Ch(K);
     std::vector<std::array<double, 3>> t(K, std::array<double, 3>{0, 0, 0});
     std::vector<int> rc(K, OCR_OK);
     std::vector<std::string> errs(K);
@@ -574,7 +604,7 @@ struct ocr_pipe {
       PipeWorker& w = c == 0 ? w0 : *extra[c - 1];
       for (int p = c; p < K; p += nchains) {
         if (pi[p].empty()) continue;
-        rc[p] = w.run_images(base, pi[p], pg[p], probs, W[p], I[p], t[p].data(), errs[p]);
+        rc[p] = w.run_images(base, pi[p], pg[p], probs, W[p], I[p], t[p].data(), errs[p], out_chars ? &Ch[p] : nullptr);
         if (rc[p]) return;
       }
     };
@@ -589,10 +619,12 @@ struct ocr_pipe {
       if (rc[p]) { err = errs[p]; return rc[p]; }
     out_words.assign(count, {});
     out_ids.assign(count, {});
+    if (out_chars) out_chars->assign(count, {});
     for (int p = 0; p < K; ++p)
       for (size_t k = 0; k < gidx[p].size(); ++k) {
         out_words[gidx[p][k]] = std::move(W[p][k]);
         out_ids[gidx[p][k]] = std::move(I[p][k]);
+        if (out_chars) (*out_chars)[gidx[p][k]] = std::move(Ch[p][k]);
       }
     for (int k = 0; k < 3; ++k) {  // the chains ran side by side: per stage, the busiest chain's time
       double m = 0;
@@ -607,7 +639,8 @@ struct ocr_pipe {
   }
 
   // run a staged slot: wait for its upload, clone, run, hand the results back in the caller's order
-  int run_slot(int si, ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids, double times[3], int chain = -1) {
+  int run_slot(int si, ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids, double times[3], int chain = -1,
+               ocr_char* chars = nullptr) {
     StageSlot& S = slots[si];
     if (!S.staged || S.imgs.empty()) return fail(OCR_ERR_ARG, "nothing staged in this slot");
     std::string err;
@@ -621,19 +654,21 @@ struct ocr_pipe {
     double t[3] = {0, 0, 0};
     std::vector<std::vector<ocr_word>> W;
     std::vector<std::vector<int32_t>> I;
-    const int rc = one ? one->run_images(clone.p, S.imgs, S.groups, S.has_probs ? S.probs.p : nullptr, W, I, t, err)
-                       : run_images(clone.p, S.imgs, S.groups, S.has_probs ? S.probs.p : nullptr, W, I, t, err);
+    CharLists C;
+    CharLists* pc = chars ? &C : nullptr;
+    const int rc = one ? one->run_images(clone.p, S.imgs, S.groups, S.has_probs ? S.probs.p : nullptr, W, I, t, err, pc)
+                       : run_images(clone.p, S.imgs, S.groups, S.has_probs ? S.probs.p : nullptr, W, I, t, err, pc);
     if (rc) return fail(rc, err);
     if (times) { times[0] = t[0]; times[1] = t[1]; times[2] = t[2]; }
     const int count = (int)S.imgs.size();
     std::vector<int> order(count);  // order[original index] = layout index
     for (int k = 0; k < count; ++k) order[S.imgs[k].orig] = k;
-    return emit(W, I, order, words, cap_words, word_off, nwords, ids, cap_ids);
+    return emit(W, I, order, words, cap_words, word_off, nwords, ids, cap_ids, pc, chars);
   }
 };
 
 static int emit(const std::vector<std::vector<ocr_word>>& W, const std::vector<std::vector<int32_t>>& I, const std::vector<int>& order,
-                ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids) {
+                ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids, const CharLists* C, ocr_char* chars) {
   int wo = 0, io = 0;
   for (size_t i = 0; i < order.size(); ++i) {
     const auto& w = W[order[i]];
@@ -646,6 +681,7 @@ static int emit(const std::vector<std::vector<ocr_word>>& W, const std::vector<s
       words[wo + k].ids_off += io;
     }
     if (!d.empty()) memcpy(ids + io, d.data(), d.size() * sizeof(int32_t));
+    if (C && chars && !d.empty()) memcpy(chars + io, (*C)[order[i]].data(), d.size() * sizeof(ocr_char));
     wo += (int)w.size();
     io += (int)d.size();
   }
@@ -807,6 +843,14 @@ int ocr_pipe_run(ocr_pipe* h, const ocr_img* imgs, int count, ocr_word* words, i
   const int rc = ocr_pipe_stage(h, 0, imgs, count);
   if (rc) return rc;
   return h->run_slot(0, words, cap_words, word_off, nwords, ids, cap_ids, times);
+}
+
+int ocr_pipe_run_chars(ocr_pipe* h, const ocr_img* imgs, int count, ocr_word* words, int cap_words, int* word_off, int* nwords,
+                       int32_t* ids, int cap_ids, ocr_char* chars, double times[3]) {
+  if (!h || !imgs || count < 1 || !words || !word_off || !nwords || !ids || !chars) return fail(OCR_ERR_ARG, "bad argument");
+  const int rc = ocr_pipe_stage(h, 0, imgs, count);
+  if (rc) return rc;
+  return h->run_slot(0, words, cap_words, word_off, nwords, ids, cap_ids, times, -1, chars);
 }
 
 const char* ocr_pipe_label(ocr_pipe* h, int id) {

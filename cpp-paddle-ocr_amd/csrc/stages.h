@@ -144,6 +144,18 @@ struct RecConfig {
 class RecStage {
  public:
   ~RecStage();
+  // Per-character evidence (ocr_rec_run_chars): arrays parallel to ids (n x max_len) - the CTC step a kept character came
+  // from, the length of its run of equal arg maxes, pmax of that step; geom per line {T, tensor_w, resize_w}; with
+  // topk in 1..8 the topk best classes of that step's logits row (n x max_len x topk).  steps/nsteps/probs/geom may be null.
+  struct CharOut {
+    int32_t* steps = nullptr;
+    int32_t* nsteps = nullptr;
+    float* probs = nullptr;
+    int32_t* geom = nullptr;
+    int topk = 0;
+    int32_t* alt_ids = nullptr;
+    float* alt_probs = nullptr;
+  };
   bool create(const RecConfig& cfg, std::string& err, int& code);
   int run(const ocr_img* imgs, int n, int32_t* ids, int max_len, int* lens, float* scores, double times[3],
           std::string& err);
@@ -151,7 +163,15 @@ class RecStage {
   // seg: offsets of per-image segments (size nimages+1); the reference's aspect-sort / batch-of-16
   // rule is applied inside each segment, launches are shared across segments of equal tensor width.
   int run_lines(const std::vector<LineSrc>& lines, const std::vector<int>& seg, int32_t* ids, int max_len, int* lens,
-                float* scores, std::string& err);
+                float* scores, std::string& err, const CharOut* co = nullptr);
+  int run_chars(const ocr_img* imgs, int n, int32_t* ids, int max_len, int* lens, float* scores, const CharOut& co, double times[3],
+                std::string& err);
+  int run_lines_chars(const std::vector<LineSrc>& lines, const std::vector<int>& seg, int32_t* ids, int max_len, int* lens,
+                      float* scores, const CharOut& co, std::string& err) {
+    return run_lines(lines, seg, ids, max_len, lens, scores, err, &co);
+  }
+  // tap: the logits row behind step `step` of line `index` of the last run_chars(topk > 0) with want_taps (C floats)
+  int logits_row(int index, int step, float* out, size_t cap_floats, std::string& err);
   bool want_taps = true;
   int max_lines_per_launch = 4096;  // bounds the activation arena of one launch: this many 48x320 lines' pixels (~1.2 MB each)
   const std::vector<std::string>& labels() const { return labels_; }
@@ -176,6 +196,13 @@ class RecStage {
   DevBuf<int> amax_, ids_, lens_;
   DevBuf<uint8_t> staging_;
   DevBuf<LineDesc> descs_;
+  // run_chars: per kept character step / run length / probability, the top-k classes, and (want_taps) a copy of the
+  // logits rows of the last topk run, C floats each, line li's at row tap_row0_[li]
+  DevBuf<int> csteps_, cnsteps_, alt_ids_;
+  DevBuf<float> cprobs_, alt_probs_, logit_tap_;
+  std::vector<long> tap_row0_;
+  int tap_C_ = 0;
+  bool srv_ctc_ = false;  // the server head's CTC-partials mode outside top-k calls (create)
 };
 
 struct ClsConfig {

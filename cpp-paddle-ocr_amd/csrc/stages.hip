@@ -444,6 +444,7 @@ bool RecStage::create(const RecConfig& cfg, std::string& err, int& code) {
     if (!srv_->load(embedded_plan("srv_rec"), w, cfg.precision == "fp16", err)) return false;
     {  // the pipeline needs arg max and its probability, never the logits: the CTC head in partial mode (f16 build; OCR_SRV_CTC=0: logits + one pass over them)
       static const bool ctc_on = [] { const char* e = getenv("OCR_SRV_CTC"); return !(e && e[0] == '0'); }();
+      srv_ctc_ = ctc_on;
       srv_->set_ctc_partials(ctc_on);
     }
   } else {
@@ -480,9 +481,45 @@ int RecStage::run(const ocr_img* imgs, int n, int32_t* ids, int max_len, int* le
   return rc;
 }
 
+int RecStage::run_chars(const ocr_img* imgs, int n, int32_t* ids, int max_len, int* lens, float* scores, const CharOut& co,
+                        double times[3], std::string& err) {
+  if (n < 0 || (n > 0 && (!imgs || !ids || !lens || !scores)) || max_len < 1) { err = "bad argument"; return OCR_ERR_ARG; }
+  if (co.topk < 0 || co.topk > 8) { err = "topk must be 0..8"; return OCR_ERR_ARG; }
+  if (co.topk > 0 && n > 0 && (!co.alt_ids || !co.alt_probs)) { err = "topk > 0 needs alt_ids and alt_probs"; return OCR_ERR_ARG; }
+  if (times) times[0] = times[1] = times[2] = 0;
+  if (n == 0) return OCR_OK;
+  ST_HIP(rt_set_device(cfg_.device));
+  timer_.mark(0, stream_);
+  std::vector<LineSrc> lines;
+  if (!upload_lines(imgs, n, staging_, lines, stream_, err)) return OCR_ERR_DEVICE;
+  timer_.mark(1, stream_);
+  const std::vector<int> seg = {0, n};
+  const int rc = run_lines(lines, seg, ids, max_len, lens, scores, err, &co);
+  timer_.mark(2, stream_);
+  timer_.mark(3, stream_);
+  (void)g_stream_sync(stream_);
+  timer_.read(times);
+  return rc;
+}
+
+int RecStage::logits_row(int index, int step, float* out, size_t cap_floats, std::string& err) {
+  if (!out || index < 0 || index >= (int)tap_row0_.size() || tap_row0_[index] < 0) { err = "no logits of such a line: the last run was not run_chars with topk > 0 (and taps)"; return OCR_ERR_ARG; }
+  if (step < 0 || step >= tap_T[index]) { err = "no such step"; return OCR_ERR_ARG; }
+  if ((size_t)tap_C_ > cap_floats) { err = "output buffer too small"; return OCR_ERR_CAPACITY; }
+  ST_HIP(rt_set_device(cfg_.device));
+  ST_HIP(g_memcpy(out, logit_tap_.p + (size_t)(tap_row0_[index] + step) * tap_C_, (size_t)tap_C_ * sizeof(float), hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
 int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int>& seg, int32_t* ids, int max_len,
-                        int* lens, float* scores, std::string& err) {
+                        int* lens, float* scores, std::string& err, const CharOut* co) {
   const int n = (int)lines.size();
+  const int topk = co ? co->topk : 0;
+  // top-k needs the logits in HBM: the mobile head unfused (Net::set_keep_logits), the server head without CTC partials.
+  // Both switches re-bind only when they change; every other call keeps its launch lists.
+  if (srv_) srv_->set_ctc_partials(topk > 0 ? false : srv_ctc_);
+  else net_.set_keep_logits(topk > 0);
+  tap_row0_.assign(n, -1);
   const int imgH = cfg_.img_h, imgW = cfg_.img_w;
   struct Item { int line, resize_w, tensor_w; };
   std::vector<Item> items;
@@ -608,6 +645,40 @@ int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int
   if (!amax_.ensure(step_total, err) || !pmax_.ensure(step_total, err) || !ids_.ensure((size_t)ni * max_len, err) ||
       !lens_.ensure(ni, err) || !scores_.ensure(ni, err) || !descs_.ensure(ni, err) || !x_.ensure(xneed, err))
     return OCR_ERR_DEVICE;
+  const size_t nchar = (size_t)ni * max_len;
+  if (co && (!csteps_.ensure(nchar, err) || !cnsteps_.ensure(nchar, err) || !cprobs_.ensure(nchar, err))) return OCR_ERR_DEVICE;
+  if (topk > 0 && (!alt_ids_.ensure(nchar * topk, err) || !alt_probs_.ensure(nchar * topk, err))) return OCR_ERR_DEVICE;
+  const int C = (int)labels_.size();
+  // (tap) a copy of every logits row of the call, while that stays a test-sized buffer
+  const bool tap_logits = topk > 0 && want_taps && step_total * (size_t)C * sizeof(float) <= ((size_t)1 << 30);
+  if (tap_logits && !logit_tap_.ensure(step_total * (size_t)C, err)) return OCR_ERR_DEVICE;
+  tap_C_ = C;
+  // the collapse of one launch's lines (lines_dev: the ragged table, or null with uniform T) and, behind it, the top-k
+  // classes of its kept characters from the launch's logits (still in place: the next launch overwrites them)
+  auto collapse = [&](const Slot& sl, const LineDesc* lines_dev, int T, const float* logits, long pitch) -> int {
+    const size_t o = (size_t)sl.first * max_len;
+    launch_ctc_chars(amax_.p + sl.step_off, pmax_.p + sl.step_off, lines_dev, sl.count, T, max_len, ids_.p + o, lens_.p + sl.first,
+                     scores_.p + sl.first, csteps_.p + o, cnsteps_.p + o, cprobs_.p + o, stream_);
+    if (topk <= 0) return OCR_OK;
+    launch_ctc_topk(logits, pitch, C, topk, lines_dev, sl.count, T, max_len, lens_.p + sl.first, csteps_.p + o, cprobs_.p + o,
+                    alt_ids_.p + o * topk, alt_probs_.p + o * topk, stream_);
+    if (tap_logits) {
+      const size_t rows = lines_dev ? (size_t)(d[sl.first + sl.count - 1].step0 + d[sl.first + sl.count - 1].steps) : (size_t)sl.count * T;
+      ST_HIP(hipMemcpy2DAsync(logit_tap_.p + sl.step_off * (size_t)C, (size_t)C * sizeof(float), logits, (size_t)pitch * sizeof(float),
+                              (size_t)C * sizeof(float), rows, hipMemcpyDeviceToDevice, stream_));
+    }
+    return OCR_OK;
+  };
+  // the mobile network's logits under the binding that just ran
+  auto mobile_logits = [&](Net::HeadLogits& hl, const Slot& sl, bool ragged) -> int {
+    if (topk <= 0) return OCR_OK;
+    if (!net_.head_logits(hl, err)) return OCR_ERR_DEVICE;
+    if (hl.C != C) { err = "dictionary size does not match the CTC head"; return OCR_ERR_MODEL; }
+    if (ragged)
+      for (int j = 0; j < sl.count; ++j)
+        if ((int)hl.row0.size() != sl.count + 1 || hl.row0[j] != d[sl.first + j].step0) { err = "ragged logits rows do not match the step table"; return OCR_ERR_DEVICE; }
+    return OCR_OK;
+  };
   ST_HIP(hipMemcpyAsync(descs_.p, d.data(), (size_t)ni * sizeof(LineDesc), hipMemcpyHostToDevice, stream_));
   for (Slot& sl : slots) {
     if (!srv_) net_.set_head_outputs(nullptr, amax_.p + sl.step_off, pmax_.p + sl.step_off);
@@ -626,6 +697,10 @@ int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int
       else
         srv::launch_argmax_softmax((const float*)srv_->tensor_ptr(srv_->output_tid()), (long)sl.count * sl.T, ot.c, ot.cs, amax_.p + sl.step_off,
                                    pmax_.p + sl.step_off, srv_->half(), stream_);
+      if (co) {
+        const int rc = collapse(sl, nullptr, sl.T, (const float*)srv_->tensor_ptr(srv_->output_tid()), ot.cs);
+        if (rc) return rc;
+      } else
       launch_ctc(amax_.p + sl.step_off, pmax_.p + sl.step_off, sl.count, sl.T, max_len, ids_.p + (size_t)sl.first * max_len,
                  lens_.p + sl.first, scores_.p + sl.first, stream_);
     } else if (sl.ragged) {
@@ -634,6 +709,12 @@ int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int
       for (int j = 0; j < sl.count; ++j) { widths[j] = items[sl.first + j].tensor_w; pix += (long)imgH * widths[j]; }
       launch_line_pre_ragged(descs_.p + sl.first, sl.count, pix, imgH, lut_.p, x_.p, stream_);
       if (!net_.run_ragged(x_.p, imgH, widths.data(), sl.count, stream_, err)) return OCR_ERR_DEVICE;
+      if (co) {
+        Net::HeadLogits hl;
+        int rc = mobile_logits(hl, sl, true);
+        if (!rc) rc = collapse(sl, descs_.p + sl.first, 0, hl.ptr, hl.pitch);
+        if (rc) return rc;
+      } else
       launch_ctc_ragged(amax_.p + sl.step_off, pmax_.p + sl.step_off, descs_.p + sl.first, sl.count, max_len,
                         ids_.p + (size_t)sl.first * max_len, lens_.p + sl.first, scores_.p + sl.first, stream_);
     } else {
@@ -645,6 +726,12 @@ int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int
       if (ot.c != (int)labels_.size()) { err = "dictionary size does not match the CTC head"; return OCR_ERR_MODEL; }
       sl.T = ot.w;
       if (sl.T > Wt / 4 + 8) { err = "rec step buffer too small"; return OCR_ERR_CAPACITY; }
+      if (co) {
+        Net::HeadLogits hl;
+        int rc = mobile_logits(hl, sl, false);
+        if (!rc) rc = collapse(sl, nullptr, sl.T, hl.ptr, hl.pitch);
+        if (rc) return rc;
+      } else
       launch_ctc(amax_.p + sl.step_off, pmax_.p + sl.step_off, sl.count, sl.T, max_len, ids_.p + (size_t)sl.first * max_len,
                  lens_.p + sl.first, scores_.p + sl.first, stream_);
     }
@@ -660,6 +747,19 @@ int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int
     ST_HIP(hipMemcpyAsync(h_amax.data(), amax_.p, step_total * sizeof(int), hipMemcpyDeviceToHost, stream_));
     ST_HIP(hipMemcpyAsync(h_pmax.data(), pmax_.p, step_total * sizeof(float), hipMemcpyDeviceToHost, stream_));
   }
+  std::vector<int> h_steps, h_nsteps, h_alt_ids;
+  std::vector<float> h_cprobs, h_alt_probs;
+  if (co) {
+    h_steps.resize(nchar); h_nsteps.resize(nchar); h_cprobs.resize(nchar);
+    ST_HIP(hipMemcpyAsync(h_steps.data(), csteps_.p, nchar * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    ST_HIP(hipMemcpyAsync(h_nsteps.data(), cnsteps_.p, nchar * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    ST_HIP(hipMemcpyAsync(h_cprobs.data(), cprobs_.p, nchar * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  }
+  if (topk > 0) {
+    h_alt_ids.resize(nchar * topk); h_alt_probs.resize(nchar * topk);
+    ST_HIP(hipMemcpyAsync(h_alt_ids.data(), alt_ids_.p, nchar * topk * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    ST_HIP(hipMemcpyAsync(h_alt_probs.data(), alt_probs_.p, nchar * topk * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  }
   ST_HIP(g_stream_sync(stream_));
   net_.collect_timings();
   if (srv_) srv_->collect_timings();
@@ -671,6 +771,18 @@ int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int
       scores[li] = h_scores[q];
       memcpy(ids + (size_t)li * max_len, h_ids.data() + (size_t)q * max_len, (size_t)h_lens[q] * sizeof(int));
       const int T = sl.ragged ? d[q].steps : sl.T;
+      if (co) {
+        const size_t from = (size_t)q * max_len, to = (size_t)li * max_len, len = (size_t)h_lens[q];
+        if (co->steps) memcpy(co->steps + to, h_steps.data() + from, len * sizeof(int));
+        if (co->nsteps) memcpy(co->nsteps + to, h_nsteps.data() + from, len * sizeof(int));
+        if (co->probs) memcpy(co->probs + to, h_cprobs.data() + from, len * sizeof(float));
+        if (co->geom) { co->geom[3 * li] = T; co->geom[3 * li + 1] = items[q].tensor_w; co->geom[3 * li + 2] = items[q].resize_w; }
+        if (topk > 0) {
+          memcpy(co->alt_ids + to * topk, h_alt_ids.data() + from * topk, len * topk * sizeof(int));
+          memcpy(co->alt_probs + to * topk, h_alt_probs.data() + from * topk, len * topk * sizeof(float));
+        }
+        if (tap_logits) tap_row0_[li] = (long)(sl.step_off + (sl.ragged ? (size_t)d[q].step0 : (size_t)j * sl.T));
+      }
       tap_T[li] = T;
       if (want_taps) {
         tap_off[li] = (int)tap_amax.size();

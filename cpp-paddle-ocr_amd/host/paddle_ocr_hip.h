@@ -210,6 +210,49 @@ class CRNNRecognizer {
     }
     times.insert(times.end(), t, t + 3);
   }
+  // Per-character evidence of a line (extension; ocr_rec_run_chars): for kept character j its class id, the CTC step it
+  // came from, the length of its run of equal arg maxes, the max-probability of that step, and - topk > 0 - the topk
+  // best classes of that step with their probabilities (rank 0 = the character itself; ranks > 0 are estimates).
+  // geom = {T, tensor_w, resize_w}: the character spans tensor columns [step, step + nsteps) * tensor_w / T.
+  struct LineChars {
+    std::vector<int> ids, steps, nsteps;
+    std::vector<float> probs;
+    std::vector<std::vector<int>> alt_ids;
+    std::vector<std::vector<float>> alt_probs;
+    int geom[3] = {0, 0, 0};
+  };
+  // Run plus `chars` (resized to img_list.size()); texts and scores are Run's
+  void RunChars(const std::vector<ImageView>& img_list, std::vector<std::string>& rec_texts, std::vector<float>& rec_text_scores,
+                std::vector<LineChars>& chars, int topk, std::vector<double>& times) {
+    const int n = (int)img_list.size(), max_len = 512, kk = topk > 0 ? topk : 1;
+    std::vector<ocr_img> v;
+    for (auto& i : img_list) v.push_back(i.c());
+    std::vector<int32_t> ids((size_t)n * max_len), steps(ids.size()), nsteps(ids.size()), geom((size_t)n * 3), alt_ids(ids.size() * kk);
+    std::vector<int> lens(n);
+    std::vector<float> scores(n), probs(ids.size()), alt_probs(ids.size() * kk);
+    double t[3] = {0, 0, 0};
+    check_ocr(ocr_rec_run_chars(h_, v.data(), n, ids.data(), max_len, lens.data(), scores.data(), steps.data(), nsteps.data(), probs.data(),
+                                geom.data(), topk, alt_ids.data(), alt_probs.data(), t), "CRNNRecognizer::RunChars");
+    chars.assign(n, LineChars());
+    for (int i = 0; i < n; ++i) {
+      LineChars& c = chars[i];
+      for (int k = 0; k < 3; ++k) c.geom[k] = geom[(size_t)i * 3 + k];
+      if (lens[i] == 0) continue;
+      std::string s;
+      for (int k = 0; k < lens[i]; ++k) {
+        const size_t q = (size_t)i * max_len + k;
+        s += ocr_rec_label(h_, ids[q]);
+        c.ids.push_back(ids[q]); c.steps.push_back(steps[q]); c.nsteps.push_back(nsteps[q]); c.probs.push_back(probs[q]);
+        if (topk > 0) {
+          c.alt_ids.emplace_back(alt_ids.begin() + q * topk, alt_ids.begin() + (q + 1) * topk);
+          c.alt_probs.emplace_back(alt_probs.begin() + q * topk, alt_probs.begin() + (q + 1) * topk);
+        }
+      }
+      rec_texts[i] = std::move(s);
+      rec_text_scores[i] = scores[i];
+    }
+    times.insert(times.end(), t, t + 3);
+  }
 
  private:
   ocr_rec* h_ = nullptr;
@@ -223,10 +266,15 @@ struct OCRRequest {
   OCRRequest(int id, const ImageView& img) : request_id(id), image_data(img) {}
   OCRRequest(int id, Image&& img) : request_id(id), image_data(std::move(img)) {}  // keeps a JPEG coefficient payload
 };
+struct CharResult {  // extension (OCRWorker::setCharBoxes): one kept character of a word
+  std::vector<std::vector<int>> box;  // 4 points in source-image coordinates, reading orientation
+  float confidence;                   // the max-probability of the CTC step the character came from
+};
 struct WordResult {
   std::string text;
   std::vector<std::vector<int>> box;
   float confidence;
+  std::vector<CharResult> chars;  // filled only when the worker's char_boxes setting is on
 };
 struct OCRResult {
   int request_id = 0;
@@ -235,6 +283,7 @@ struct OCRResult {
   std::string error_message;
   std::vector<WordResult> words;
   double processing_time_ms = 0;
+  bool char_boxes = false;  // the words carry `chars`: the JSON gains a "chars" array per word
 };
 
 namespace detail {
@@ -274,7 +323,21 @@ inline std::string result_json(const OCRResult& r, int worker_id) {
         snprintf(buf, sizeof buf, "%s[%d,%d]", k ? "," : "", w.box[k][0], w.box[k][1]);
         o += buf;
       }
-      snprintf(buf, sizeof buf, "],\"confidence\":%.17g,\"text\":", (double)w.confidence);
+      o += "],";
+      if (r.char_boxes) {  // (alphabetical: box, chars, confidence, text)
+        o += "\"chars\":[";
+        for (size_t c = 0; c < w.chars.size(); ++c) {
+          o += c ? ",{\"box\":[" : "{\"box\":[";
+          for (size_t k = 0; k < w.chars[c].box.size(); ++k) {
+            snprintf(buf, sizeof buf, "%s[%d,%d]", k ? "," : "", w.chars[c].box[k][0], w.chars[c].box[k][1]);
+            o += buf;
+          }
+          snprintf(buf, sizeof buf, "],\"confidence\":%.17g}", (double)w.chars[c].confidence);
+          o += buf;
+        }
+        o += "],";
+      }
+      snprintf(buf, sizeof buf, "\"confidence\":%.17g,\"text\":", (double)w.confidence);
       o += buf;
       json_escape(o, w.text);
       o += "}";
@@ -363,6 +426,11 @@ class OCRWorker {
     { std::lock_guard<std::mutex> lock(queue_mutex_); request_queue_.push(request); }
     cv_.notify_one();
   }
+  // char_boxes (extension, default off; set before start()): every word of a reply carries its characters' boxes in
+  // source-image coordinates and their confidences (ocr_pipe_run_chars) - "chars":[{"box":[[x,y]x4],"confidence":p},..]
+  // in the JSON.  Off, the JSON is byte for byte what it was.  JPEG requests are then decoded on the host.
+  void setCharBoxes(bool on) { char_boxes_ = on; }
+  bool charBoxes() const { return char_boxes_; }
   bool isIdle() const { return is_idle_; }
   int getWorkerId() const { return worker_id_; }
   int getGpuId() const { return gpu_id_; }
@@ -385,8 +453,14 @@ class OCRWorker {
     result.height = request.image_data.rows;
     std::vector<ocr_word> words(1000);
     std::vector<int32_t> ids(1000 * 256);
+    std::vector<ocr_char> chars(char_boxes_ ? ids.size() : 0);
     int off = 0, n = 0;
     int rc;
+    if (char_boxes_) {
+      const_cast<OCRRequest&>(request).image_data.materialise();
+      ocr_img im = request.image_data.view().c();
+      rc = ocr_pipe_run_chars(pipe_, &im, 1, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), chars.data(), nullptr);
+    } else
     if (request.image_data.device_decodable()) {  // JPEG: pixels are produced on the device, straight into the staging slot
       const ocr_jpeg_img jd = request.image_data.jpeg_desc();
       rc = ocr_pipe_stage_jpeg(pipe_, 0, &jd, 1);
@@ -397,12 +471,14 @@ class OCRWorker {
     }
     if (rc != OCR_OK) { result.error_message = ocr_last_error(); return result; }  // the reference's catch (...) path
     result.success = true;
+    result.char_boxes = char_boxes_;
     for (int i = 0; i < n; ++i) {
       WordResult w;
       for (int k = 0; k < words[i].ids_len; ++k) w.text += ocr_pipe_label(pipe_, ids[words[i].ids_off + k]);
       w.confidence = words[i].confidence;
       w.box.assign(4, std::vector<int>(2));
       for (int k = 0; k < 4; ++k) { w.box[k][0] = words[i].box[2 * k]; w.box[k][1] = words[i].box[2 * k + 1]; }
+      if (char_boxes_) fill_chars(w, words[i], chars.data());
       result.words.push_back(std::move(w));
     }
     result.processing_time_ms =
@@ -421,7 +497,7 @@ class OCRWorker {
     std::vector<ocr_jpeg_img> jimgs;
     std::vector<size_t> owner;
     // a batch of JPEGs only is decoded on the device; a mixed batch takes the host path for its JPEGs
-    bool all_jpeg = true;
+    bool all_jpeg = !char_boxes_;
     for (size_t i = 0; i < requests.size(); ++i)
       if (!requests[i]->image_data.empty() && !requests[i]->image_data.device_decodable()) all_jpeg = false;
     for (size_t i = 0; i < requests.size(); ++i) {
@@ -444,7 +520,11 @@ class OCRWorker {
     std::vector<ocr_word>& words = batch_words_;
     std::vector<int32_t>& ids = batch_ids_;
     std::vector<int> off(k), cnt(k);
+    if (char_boxes_ && batch_chars_.size() < ids.size()) batch_chars_.resize(ids.size());
     int rc;
+    if (char_boxes_) {
+      rc = ocr_pipe_run_chars(pipe_, imgs.data(), k, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, batch_chars_.data(), nullptr);
+    } else
     if (all_jpeg) {
       rc = ocr_pipe_stage_jpeg(pipe_, 0, jimgs.data(), k);
       if (rc == OCR_OK) rc = ocr_pipe_run_staged(pipe_, 0, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, nullptr);
@@ -459,12 +539,14 @@ class OCRWorker {
     for (int j = 0; j < k; ++j) {
       OCRResult& r = results[owner[j]];
       r.success = true;
+      r.char_boxes = char_boxes_;
       for (int i = off[j]; i < off[j] + cnt[j]; ++i) {
         WordResult w;
         for (int q = 0; q < words[i].ids_len; ++q) w.text += ocr_pipe_label(pipe_, ids[words[i].ids_off + q]);
         w.confidence = words[i].confidence;
         w.box.assign(4, std::vector<int>(2));
         for (int q = 0; q < 4; ++q) { w.box[q][0] = words[i].box[2 * q]; w.box[q][1] = words[i].box[2 * q + 1]; }
+        if (char_boxes_) fill_chars(w, words[i], batch_chars_.data());
         r.words.push_back(std::move(w));
       }
       r.processing_time_ms = ms;
@@ -472,6 +554,18 @@ class OCRWorker {
     return results;
   }
   int maxBatch() const { return max_batch_; }
+
+  // the characters of one word out of the pipeline's ocr_char array (parallel to the class ids)
+  static void fill_chars(WordResult& w, const ocr_word& word, const ocr_char* chars) {
+    for (int k = 0; k < word.ids_len; ++k) {
+      const ocr_char& c = chars[word.ids_off + k];
+      CharResult cr;
+      cr.confidence = c.prob;
+      cr.box.assign(4, std::vector<int>(2));
+      for (int q = 0; q < 4; ++q) { cr.box[q][0] = c.quad[2 * q]; cr.box[q][1] = c.quad[2 * q + 1]; }
+      w.chars.push_back(std::move(cr));
+    }
+  }
 
  private:
   void workerLoop() {
@@ -517,6 +611,8 @@ class OCRWorker {
   std::string precision_;  // OCR_WORKER_PRECISION (kept alive for the configuration's pointers)
   std::vector<ocr_word> batch_words_;
   std::vector<int32_t> batch_ids_;
+  std::vector<ocr_char> batch_chars_;
+  bool char_boxes_ = false;
   std::atomic<bool> running_, is_idle_;
   std::atomic<int> in_flight_{0};
   std::atomic<long> served_{0};

@@ -18,7 +18,29 @@ static int failures = 0;
     else printf("ok   %s\n", #cond);                           \
   } while (0)
 
+// mode "json": the JSON emitter alone on hand-made words (no device): one line with char_boxes off, one with it on
+static int json_mode() {
+  OCRResult r;
+  r.request_id = 42; r.success = true; r.width = 640; r.height = 480; r.processing_time_ms = 12.5;
+  WordResult a;
+  a.text = "A\"b\\\xe4\xb8\xad"; a.confidence = 0.987654321f;
+  a.box = {{1, 2}, {30, 2}, {30, 14}, {1, 14}};
+  a.chars = {{{{1, 2}, {9, 2}, {9, 14}, {1, 14}}, 0.5f}, {{{9, 2}, {20, 2}, {20, 14}, {9, 14}}, 0.999f}, {{{20, 2}, {30, 2}, {30, 14}, {20, 14}}, 1.0f}};
+  WordResult b;
+  b.text = ""; b.confidence = 0.f;
+  b.box = {{100, 200}, {300, 200}, {300, 240}, {100, 240}};
+  r.words = {a, b};
+  printf("JSONOFF %s\n", detail::result_json(r, 3).c_str());
+  r.char_boxes = true;
+  printf("JSONON %s\n", detail::result_json(r, 3).c_str());
+  OCRResult e;
+  e.request_id = 7; e.error_message = "Empty image data provided"; e.char_boxes = true;
+  printf("JSONERR %s\n", detail::result_json(e, 3).c_str());
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "json") return json_mode();
   if (argc < 4) { fprintf(stderr, "usage: test_worker <model_root> <raw_bgr_file> <rows>x<cols>\n"); return 2; }
   const std::string model_root = argv[1];
   int rows = 0, cols = 0;

@@ -145,6 +145,26 @@ void ocr_rec_destroy(ocr_rec* h);
  * reference leaves untouched (NaN score: no kept step) get lens[i] = 0, scores[i] = 0. */
 int ocr_rec_run(ocr_rec* h, const ocr_img* imgs, int n, int32_t* ids, int max_len, int* lens, float* scores,
                 double times[3]);
+/* ocr_rec_run plus, per kept character (arrays parallel to ids, n x max_len): its CTC step, the length of its run of
+ * equal arg maxes, and the max-probability of that step; per line geom[3] = {T, tensor_w, resize_w}; and, when topk > 0,
+ * the topk best classes of that step's logits row (n x max_len x topk, rank-major per character). Any of steps/nsteps/
+ * probs/geom may be NULL; topk == 0 ignores alt_*.  topk is 0..8 (else OCR_ERR_ARG).
+ * ids / lens / scores are ocr_rec_run's, bit for bit, for every topk; probs[j] is the exact term of the score sum.
+ * Ranking: by logit, descending; equal logits rank the lower class first (the head's own "first maximum"), so rank 0 is
+ * the character's id; NaN ranks last.  A character's column span on the line's tensor is [step * tensor_w / T,
+ * (step + nsteps) * tensor_w / T), of which [0, resize_w) holds the resized crop.
+ * alt_probs: rank 0 is probs[j], the same bits.  Rank r > 0 is ocr_expf(x_r - x_0) * probs[j], an ESTIMATE of the softmax
+ * probability that is NOT part of the bit-exact contract (the head's exp clamps its argument at -87; the relative error
+ * is the head's own plus a few ulps).  Ranks a row does not have: id -1, prob 0.
+ * topk > 0 keeps the recognizer's logits in device memory (the mobile head runs unfused, the server head without its CTC
+ * partials): the call costs more than ocr_rec_run, and switching between topk > 0 and topk == 0 re-binds the network. */
+int ocr_rec_run_chars(ocr_rec* h, const ocr_img* imgs, int n, int32_t* ids, int max_len, int* lens, float* scores,
+                      int32_t* steps, int32_t* nsteps, float* probs, int32_t* geom,
+                      int topk, int32_t* alt_ids, float* alt_probs, double times[3]);
+/* tap: the logits row the top-k kernel read for step `step` of line `index` of the last ocr_rec_run_chars(topk > 0) */
+int ocr_rec_logits_row(ocr_rec* h, int index, int step, float* out, size_t cap_floats);
+/* self-test: the top-k kernel alone on caller rows (n rows of C f32 at `pitch` floats), p0[n] the rank-0 probability */
+int ocr_selftest_topk(const float* rows, int n, int C, int pitch, const float* p0, int k, int32_t* out_ids, float* out_probs);
 /* UTF-8 label of a class id (valid until the handle is destroyed); NULL when out of range. */
 const char* ocr_rec_label(ocr_rec* h, int id);
 int ocr_rec_num_classes(ocr_rec* h);
@@ -177,6 +197,13 @@ typedef struct ocr_word {
   int32_t ids_off, ids_len;
   float confidence;
 } ocr_word;
+/* One kept character of a word (ocr_pipe_run_chars): its CTC step and run length, the max-probability of that step, and
+ * its quad in SOURCE-IMAGE coordinates (4 points x,y: top-left, top-right, bottom-right, bottom-left in reading orientation). */
+typedef struct ocr_char {
+  int32_t step, nsteps;
+  float prob;
+  int32_t quad[8];
+} ocr_char;
 typedef struct ocr_pipe ocr_pipe;
 int ocr_pipe_create(const ocr_pipe_cfg* cfg, ocr_pipe** out);
 void ocr_pipe_destroy(ocr_pipe* h);
@@ -217,6 +244,14 @@ int ocr_pipe_run_device_on(ocr_pipe* h, int chain, const void* dev_bgr, int rows
                            ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids, double times[3]);
 int ocr_pipe_run_staged_on(ocr_pipe* h, int chain, int slot, ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids,
                            int cap_ids, double times[3]);
+/* ocr_pipe_run plus one ocr_char per class id (chars parallel to ids, cap_ids entries); words / ids are ocr_pipe_run's bit
+ * for bit.  The quad is host arithmetic in double on the line's own geometry: with s = tensor_w / T the character spans
+ * tensor columns [step * s, (step + nsteps) * s), clipped to [0, resize_w] and scaled by crop_w / resize_w into crop x; it
+ * takes the full crop height; a crop the classifier turned by 180 degrees is mirrored in x and y first; then back into
+ * the image - OCR_CROP_BOUNDING_RECT: plus the crop rectangle's origin; OCR_CROP_ROTATE: the 90-degree turn undone, then
+ * the crop's own inverse homography (csrc/crop.h).  Corners are rounded half up and clamped to [0, cols-1] x [0, rows-1]. */
+int ocr_pipe_run_chars(ocr_pipe* h, const ocr_img* imgs, int count, ocr_word* words, int cap_words, int* word_off,
+                       int* nwords, int32_t* ids, int cap_ids, ocr_char* chars /* parallel to ids */, double times[3]);
 /* JPEG inputs with the pixel half of the decoder on the device: the caller runs the
  * bit-serial entropy decoding (host/jpeg_decode.h, Decoder::decode_coefficients) and hands over quantised DCT
  * coefficients; dequantisation, IDCT, chroma upsampling and colour conversion run on the copy stream straight into
