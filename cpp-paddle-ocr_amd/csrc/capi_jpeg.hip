@@ -1,5 +1,6 @@
 // Host side of the device JPEG back-end + its C-ABI test entry point.
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <thread>
 
@@ -13,7 +14,11 @@ JpegScratch::~JpegScratch() {
   if (copied) (void)hipEventDestroy(copied);
 }
 
+// orientation took the place of alignment padding: callers built against the header without it keep their layout
+static_assert(sizeof(ocr_jpeg_img) == 24 + 3 * sizeof(ocr_jpeg_comp) && offsetof(ocr_jpeg_img, comp) == 24, "ocr_jpeg_img layout");
+
 bool jpeg_img_valid(const ocr_jpeg_img& im) {
+  if (im.orientation < 0 || im.orientation > 8) return false;
   if (im.rows <= 0 || im.cols <= 0 || (long)im.rows * im.cols > (64L << 20) || (im.ncomp != 1 && im.ncomp != 3)) return false;
   const bool s444 = im.hmax == 1 && im.vmax == 1, s422 = im.hmax == 2 && im.vmax == 1, s420 = im.hmax == 2 && im.vmax == 2;
   if (!(s444 || s422 || s420) || (im.ncomp == 1 && !s444)) return false;
@@ -27,15 +32,18 @@ bool jpeg_img_valid(const ocr_jpeg_img& im) {
   return true;
 }
 
-int jpeg_decode_async(const ocr_jpeg_img* imgs, int count, uint8_t* const* dst, JpegScratch& sc, hipStream_t s, std::string& err) {
+int jpeg_decode_async(const ocr_jpeg_img* imgs, int count, uint8_t* const* dst, JpegScratch& sc, hipStream_t s, std::string& err,
+                      JpegLaunch* launched) {
   std::vector<JpegPlaneDesc> pd;
   std::vector<JpegImageDesc> id((size_t)count);
   std::vector<size_t> coef_off, plane_off;
   size_t ncoef = 0, nplane = 0;
-  long nblocks = 0, max_px = 0;
+  long nblocks = 0;
+  JpegLaunch L;
   for (int i = 0; i < count; ++i) {
     const ocr_jpeg_img& im = imgs[i];
     if (!jpeg_img_valid(im)) { err = "bad JPEG coefficient descriptor"; return OCR_ERR_ARG; }
+    L.count[jpeg_output_kind(im.orientation)]++;
     for (int c = 0; c < im.ncomp; ++c) {
       const ocr_jpeg_comp& k = im.comp[c];
       JpegPlaneDesc d{};
@@ -48,7 +56,6 @@ int jpeg_decode_async(const ocr_jpeg_img* imgs, int count, uint8_t* const* dst, 
       nplane += ((size_t)k.bw * 8 * k.bh * 8 + 255) & ~(size_t)255;
       nblocks += (long)k.bw * k.bh;
     }
-    max_px = std::max(max_px, (long)im.rows * im.cols);
   }
   if (!sc.coef.ensure(ncoef + 64, err) || !sc.planes.ensure(nplane + 256, err) || !sc.pd.ensure(pd.size(), err) || !sc.id.ensure(count, err))
     return OCR_ERR_DEVICE;
@@ -74,12 +81,19 @@ int jpeg_decode_async(const ocr_jpeg_img* imgs, int count, uint8_t* const* dst, 
     run(0);
     for (auto& t : th) t.join();
   }
+  // image descriptors ordered by the kernel that writes them (the destination is in the descriptor: any order will do)
+  for (int k = 1; k < kJpegKinds; ++k) L.first[k] = L.first[k - 1] + L.count[k - 1];
+  int next[kJpegKinds];
+  std::copy(L.first, L.first + kJpegKinds, next);
   size_t p = 0;
   for (int i = 0; i < count; ++i) {
     const ocr_jpeg_img& im = imgs[i];
-    JpegImageDesc& d = id[i];
+    const int kind = jpeg_output_kind(im.orientation);
+    JpegImageDesc& d = id[next[kind]++];
     d = JpegImageDesc{};
     d.rows = im.rows; d.cols = im.cols; d.ncomp = im.ncomp; d.hmax = im.hmax; d.vmax = im.vmax; d.bgr = dst[i];
+    d.orient = im.orientation ? im.orientation : 1;
+    L.blocks[kind] = std::max(L.blocks[kind], jpeg_output_blocks(d));
     for (int c = 0; c < im.ncomp; ++c, ++p) {
       pd[p].coef = sc.coef.p + coef_off[p];
       pd[p].plane = sc.planes.p + plane_off[p];
@@ -96,8 +110,11 @@ int jpeg_decode_async(const ocr_jpeg_img* imgs, int count, uint8_t* const* dst, 
     err = "JPEG coefficient upload failed";
     return OCR_ERR_DEVICE;
   }
-  launch_jpeg_idct(sc.pd.p, (int)pd.size(), nblocks, s);
-  launch_jpeg_output(sc.id.p, count, max_px, s);
+  L.ndesc = (int)pd.size();
+  L.idct_blocks = nblocks;
+  launch_jpeg_idct(sc.pd.p, L.ndesc, L.idct_blocks, s);
+  launch_jpeg_output(sc.id.p, L, s);
+  if (launched) *launched = L;
   if (hipGetLastError() != hipSuccess) { err = "JPEG kernels failed to launch"; return OCR_ERR_DEVICE; }
   return OCR_OK;
 }
@@ -121,5 +138,37 @@ extern "C" int ocr_jpeg_decode(const ocr_jpeg_img* img, int device_id, uint8_t* 
   rc = jpeg_decode_async(img, 1, &dst, sc, nullptr, err);
   if (rc) return fail(rc, err);
   CAPI_HIP(g_memcpy(bgr, out.p, bytes, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
+extern "C" int ocr_jpeg_time(const ocr_jpeg_img* img, int device_id, int iters, double ms[2]) {
+  if (!img || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  if (!jpeg_img_valid(*img)) return fail(OCR_ERR_ARG, "bad JPEG coefficient descriptor");
+  JpegScratch sc;
+  DevBuf<uint8_t> out;
+  std::string err;
+  if (!out.ensure((size_t)img->rows * img->cols * 3, err)) return fail(OCR_ERR_DEVICE, err);
+  uint8_t* dst = out.p;
+  JpegLaunch L;
+  rc = jpeg_decode_async(img, 1, &dst, sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
+  if (rc) return fail(rc, err);
+  struct Events {
+    hipEvent_t e[3] = {};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  } ev;
+  for (auto& e : ev.e) CAPI_HIP(hipEventCreate(&e));
+  CAPI_HIP(hipEventRecord(ev.e[0], nullptr));
+  for (int i = 0; i < iters; ++i) launch_jpeg_idct(sc.pd.p, L.ndesc, L.idct_blocks, nullptr);
+  CAPI_HIP(hipEventRecord(ev.e[1], nullptr));
+  for (int i = 0; i < iters; ++i) launch_jpeg_output(sc.id.p, L, nullptr);
+  CAPI_HIP(hipEventRecord(ev.e[2], nullptr));
+  CAPI_HIP(hipEventSynchronize(ev.e[2]));
+  for (int k = 0; k < 2; ++k) {
+    float t = 0;
+    CAPI_HIP(hipEventElapsedTime(&t, ev.e[k], ev.e[k + 1]));
+    ms[k] = (double)t / iters;
+  }
   return OCR_OK;
 }

@@ -7,6 +7,8 @@
 //   * dequantisation + the "islow" integer IDCT (jidctint.c: 13-bit constants, two passes, PASS1_BITS = 2)
 //   * "fancy" (triangle) chroma upsampling h2v1 / h2v2 with replicated edges (jdsample.c), evaluated per output pixel
 //   * YCbCr -> RGB with the 16-bit fixed-point constants of jdcolor.c, written as packed BGR
+//   * the EXIF orientation (cv::imdecode turns the decoded image; the table in host/jpeg_decode.h): the finished pixel
+//     of stored position (y, x) goes to its place in the oriented image, upsampling stays in the stored frame
 // Integer arithmetic throughout: results equal host/jpeg_decode.h (itself pinned to libjpeg-turbo through PIL) bit for
 // bit - tests/test_ipc_service.py::test_device_jpeg_decode_equals_host.
 #include <hip/hip_runtime.h>
@@ -110,20 +112,8 @@ __device__ __forceinline__ int chroma_at(const uint8_t* plane, int stride, int d
   return (c * 3 + cp + 8) >> 4;
 }
 
-}  // namespace
-
-// one thread per output pixel of one image
-__global__ void __launch_bounds__(256) jpeg_output_kernel(const JpegImageDesc* __restrict__ imgs, int nimg) {
-  const int ii = blockIdx.y;
-  const JpegImageDesc im = imgs[ii];
-  const long t = (long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= (long)im.rows * im.cols) return;
-  const int y = (int)(t / im.cols), x = (int)(t - (long)y * im.cols);
-  const int Y = im.plane[0][(size_t)y * im.stride[0] + x];
-  uint8_t* o = im.bgr + ((size_t)y * im.cols + x) * 3;
-  if (im.ncomp == 1) { o[0] = o[1] = o[2] = (uint8_t)Y; return; }
-  const int cb = chroma_at(im.plane[1], im.stride[1], im.dw[1], im.dh[1], im.hmax, im.vmax, x, y);
-  const int cr = chroma_at(im.plane[2], im.stride[2], im.dw[2], im.dh[2], im.hmax, im.vmax, x, y);
+// jdcolor.c ycc_rgb_convert of one pixel, written as B, G, R to o[0..2]
+__device__ __forceinline__ void ycc_to_bgr(int Y, int cb, int cr, uint8_t* o) {
   const long long xb = cb - 128, xr = cr - 128;
   const int crr = (int)((91881LL * xr + 32768) >> 16);
   const int cbb = (int)((116130LL * xb + 32768) >> 16);
@@ -133,13 +123,79 @@ __global__ void __launch_bounds__(256) jpeg_output_kernel(const JpegImageDesc* _
   o[0] = jclamp8(Y + cbb);
 }
 
+}  // namespace
+
+// Upsampling + colour conversion + orientation, one thread per stored pixel of one image, written to its place in the
+// oriented image (the table in host/jpeg_decode.h).  kFlip false: as stored (orientation 1).  kFlip true: orientations
+// 2..4, which keep rows as rows - plane reads and pixel stores both still run along rows.
+template <bool kFlip>
+__global__ void __launch_bounds__(256) jpeg_output_kernel(const JpegImageDesc* __restrict__ imgs, int nimg) {
+  const int ii = blockIdx.y;
+  const JpegImageDesc im = imgs[ii];
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long)im.rows * im.cols) return;
+  const int y = (int)(t / im.cols), x = (int)(t - (long)y * im.cols);
+  const int Y = im.plane[0][(size_t)y * im.stride[0] + x];
+  uint8_t* o = im.bgr + ((size_t)y * im.cols + x) * 3;
+  if (kFlip) {
+    const int oy = im.orient == 2 ? y : im.rows - 1 - y, ox = im.orient == 4 ? x : im.cols - 1 - x;
+    o = im.bgr + ((size_t)oy * im.cols + ox) * 3;
+  }
+  if (im.ncomp == 1) { o[0] = o[1] = o[2] = (uint8_t)Y; return; }
+  const int cb = chroma_at(im.plane[1], im.stride[1], im.dw[1], im.dh[1], im.hmax, im.vmax, x, y);
+  const int cr = chroma_at(im.plane[2], im.stride[2], im.dw[2], im.dh[2], im.hmax, im.vmax, x, y);
+  ycc_to_bgr(Y, cb, cr, o);
+}
+
+// The transposing orientations 5..8: stored rows become output columns, and a per-pixel store would stride by a whole
+// output row.  A workgroup converts a kJpegTile square of stored pixels reading the planes by rows, keeps the pixels in
+// LDS (one dword each, rows padded by one dword: the column reads of the second half then fall on different banks), and
+// writes every output row segment of the square as contiguous bytes.
+__global__ void __launch_bounds__(256) jpeg_output_tiled_kernel(const JpegImageDesc* __restrict__ imgs, int nimg) {
+  __shared__ uint32_t tile[kJpegTile][kJpegTile + 1];
+  const int ii = blockIdx.y;
+  const JpegImageDesc im = imgs[ii];
+  const int R = im.rows, C = im.cols;
+  const int tiles_x = (C + kJpegTile - 1) / kJpegTile, tiles_y = (R + kJpegTile - 1) / kJpegTile;
+  if ((long)blockIdx.x >= (long)tiles_x * tiles_y) return;  // (the whole workgroup: no barrier is left waiting)
+  const int y0 = (int)(blockIdx.x / tiles_x) * kJpegTile, x0 = (int)(blockIdx.x % tiles_x) * kJpegTile;
+  const int h = min(kJpegTile, R - y0), w = min(kJpegTile, C - x0);  // the part of the square inside the image
+  const int lane = threadIdx.x & (kJpegTile - 1), first = threadIdx.x / kJpegTile, step = 256 / kJpegTile;
+  if (lane < w)
+    for (int r = first; r < h; r += step) {
+      const int y = y0 + r, x = x0 + lane;
+      const int Y = im.plane[0][(size_t)y * im.stride[0] + x];
+      uint8_t px[4] = {(uint8_t)Y, (uint8_t)Y, (uint8_t)Y, 0};
+      if (im.ncomp != 1)
+        ycc_to_bgr(Y, chroma_at(im.plane[1], im.stride[1], im.dw[1], im.dh[1], im.hmax, im.vmax, x, y),
+                   chroma_at(im.plane[2], im.stride[2], im.dw[2], im.dh[2], im.hmax, im.vmax, x, y), px);
+      tile[r][lane] = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);
+    }
+  __syncthreads();
+  // stored column x0 + c is output row x0 + c (5, 6) or C-1 - (x0 + c) (7, 8); along it the stored rows y0 .. y0+h-1 are
+  // the output columns y0 .. y0+h-1 (5, 8) or, in reverse, R-y0-h .. R-1-y0 (6, 7)
+  const bool flip_rows = im.orient == 6 || im.orient == 7, flip_cols = im.orient == 7 || im.orient == 8;
+  if (lane < h) {
+    const int r = flip_rows ? h - 1 - lane : lane;
+    const int ox = (flip_rows ? R - y0 - h : y0) + lane;
+    for (int c = first; c < w; c += step) {
+      const int oy = flip_cols ? C - 1 - (x0 + c) : x0 + c;
+      const uint32_t px = tile[r][c];
+      uint8_t* o = im.bgr + ((size_t)oy * R + ox) * 3;
+      o[0] = (uint8_t)px; o[1] = (uint8_t)(px >> 8); o[2] = (uint8_t)(px >> 16);
+    }
+  }
+}
+
 void launch_jpeg_idct(const JpegPlaneDesc* descs, int ndesc, long total_blocks, hipStream_t s) {
   if (total_blocks <= 0) return;
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((total_blocks + 31) / 32)), dim3(256), 0, s, descs, ndesc);
 }
-void launch_jpeg_output(const JpegImageDesc* imgs, int nimg, long max_pixels, hipStream_t s) {
-  if (nimg <= 0 || max_pixels <= 0) return;
-  hipLaunchKernelGGL(jpeg_output_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)nimg), dim3(256), 0, s, imgs, nimg);
+void launch_jpeg_output(const JpegImageDesc* imgs, const JpegLaunch& L, hipStream_t s) {
+  void (*const kernel[kJpegKinds])(const JpegImageDesc*, int) = {jpeg_output_kernel<false>, jpeg_output_kernel<true>, jpeg_output_tiled_kernel};
+  for (int k = 0; k < kJpegKinds; ++k)
+    if (L.count[k] > 0 && L.blocks[k] > 0)
+      hipLaunchKernelGGL(kernel[k], dim3((unsigned)L.blocks[k], (unsigned)L.count[k]), dim3(256), 0, s, imgs + L.first[k], L.count[k]);
 }
 
 }  // namespace ocr

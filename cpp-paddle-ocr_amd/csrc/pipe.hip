@@ -518,7 +518,11 @@ struct ocr_pipe {
   // ---- stage JPEG coefficients: the pixel half of the decoder runs on the copy stream, into the slot
   int stage_jpeg(int si, const ocr_jpeg_img* imgs, int count, std::string& err) {
     StageSlot& S = slots[si];
-    int rc = layout(S, count, [&](int i, int& r, int& c) { r = imgs[i].rows; c = imgs[i].cols; }, err);
+    // (checked before the sizes are used: a refused batch leaves the slot as it was)
+    for (int i = 0; i < count; ++i)
+      if (!jpeg_img_valid(imgs[i])) { err = "bad JPEG coefficient descriptor"; return OCR_ERR_ARG; }
+    // the oriented size: a 40 x 72 image and a 72 x 40 one that EXIF turns by 90 degrees share a size group and a det pass
+    int rc = layout(S, count, [&](int i, int& r, int& c) { r = jpeg_out_rows(imgs[i]); c = jpeg_out_cols(imgs[i]); }, err);
     if (rc) return rc;
     std::vector<ocr_jpeg_img> ordered(count);
     std::vector<uint8_t*> dst(count);

@@ -8,6 +8,25 @@
 //   * "fancy" (triangle) chroma upsampling, h2v1 and h2v2 (jdsample.c), image edges replicated;
 //   * YCbCr -> RGB with the 16-bit fixed-point tables of jdcolor.c.
 // tests/test_ipc_service.py checks the output bit for bit against PIL (libjpeg-turbo) on encoded test images.
+//
+// EXIF orientation.  cv::imdecode / cv::imread (OpenCV >= 3.1, no IMREAD_IGNORE_ORIENTATION - what the reference calls)
+// turn the decoded image as the Orientation tag of the file says; libjpeg itself ignores the marker.  So does this
+// decoder: the first APP1 segment whose payload starts with "Exif\0\0" is read as Exif 2.x / TIFF (byte order II or
+// MM, magic 42, IFD0), and the entry with tag 0x0112, type SHORT, count 1 gives the orientation.  Values 1..8 are kept;
+// an absent tag, another type or count, any other value, an offset or entry count that leaves the segment, a truncated
+// segment or an APP1 that is not Exif (XMP) all read as 1 and the decode succeeds.  Later Exif segments, IFD1 and the
+// Exif sub-IFD are not read.  The transform applies to the fully decoded pixel (upsampling and edge replication stay in
+// the stored frame).  Stored image S with R rows and C columns, output D:
+//   tag | D size | D(y, x) =
+//    1  | R x C  | S(y, x)
+//    2  | R x C  | S(y, C-1-x)
+//    3  | R x C  | S(R-1-y, C-1-x)
+//    4  | R x C  | S(R-1-y, x)
+//    5  | C x R  | S(x, y)
+//    6  | C x R  | S(R-1-x, y)        (90 degrees clockwise)
+//    7  | C x R  | S(R-1-x, C-1-y)
+//    8  | C x R  | S(x, C-1-y)        (90 degrees counter-clockwise)
+// tests/test_jpeg_orientation.py pins host and device to Pillow's ImageOps.exif_transpose, bit for bit.
 // Arithmetic coding, lossless, 12-bit, CMYK and other samplings are refused (decode fails).
 #pragma once
 #include <cstdint>
@@ -51,7 +70,11 @@ struct Component {
 // The pixel half of decoding (dequantisation, IDCT, upsampling, colour) can then run on the host (Decoder::pixels)
 // or on the device (ocr_pipe_stage_jpeg / ocr_jpeg_decode of include/ocr_hip.h) with identical results.
 struct Coefs {
-  int rows = 0, cols = 0, ncomp = 0, hmax = 1, vmax = 1;
+  int rows = 0, cols = 0, ncomp = 0, hmax = 1, vmax = 1;  // rows / cols: the stored size
+  int orientation = 1;                                     // EXIF tag 0x0112, 1..8 (table above)
+  bool transposed() const { return orientation >= 5; }
+  int out_rows() const { return transposed() ? cols : rows; }
+  int out_cols() const { return transposed() ? rows : cols; }
   struct Comp {
     std::vector<int16_t> coef;  // bw*bh blocks x 64, blocks row-major, natural order inside
     uint16_t quant[64] = {};    // natural order
@@ -59,19 +82,69 @@ struct Coefs {
   } comp[3];
 };
 
+// The Orientation of an APP1 payload (the bytes after the segment's length field), 1 when it has none to give.  Every
+// read is checked against n: these are bytes from the network.
+inline int exif_orientation(const uint8_t* p, size_t n) {
+  if (n < 14 || memcmp(p, "Exif\0\0", 6) != 0) return 1;
+  const uint8_t* t = p + 6;  // the TIFF header: offsets count from here
+  const size_t tn = n - 6;
+  bool le;
+  if (t[0] == 'I' && t[1] == 'I') le = true;
+  else if (t[0] == 'M' && t[1] == 'M') le = false;
+  else return 1;
+  auto u16 = [&](size_t o) { return le ? (uint32_t)t[o] | ((uint32_t)t[o + 1] << 8) : ((uint32_t)t[o] << 8) | (uint32_t)t[o + 1]; };
+  auto u32 = [&](size_t o) { return le ? u16(o) | (u16(o + 2) << 16) : (u16(o) << 16) | u16(o + 2); };
+  if (u16(2) != 42) return 1;
+  const size_t ifd = u32(4);
+  if (ifd > tn || tn - ifd < 2) return 1;
+  const size_t count = u16(ifd);
+  if ((tn - ifd - 2) / 12 < count) return 1;  // the entries leave the segment
+  for (size_t i = 0; i < count; ++i) {
+    const size_t e = ifd + 2 + 12 * i;
+    if (u16(e) != 0x0112) continue;
+    if (u16(e + 2) != 3 || u32(e + 4) != 1) return 1;
+    const uint32_t v = u16(e + 8);
+    return v >= 1 && v <= 8 ? (int)v : 1;
+  }
+  return 1;
+}
+
+// D = the oriented image of the stored R x C image S (3 bytes per pixel), by the table above
+inline void orient_pixels(int orientation, const uint8_t* S, int R, int C, uint8_t* D) {
+  const bool tr = orientation >= 5;
+  const int orows = tr ? C : R, ocols = tr ? R : C;
+  for (int y = 0; y < orows; ++y)
+    for (int x = 0; x < ocols; ++x) {
+      int sy, sx;
+      switch (orientation) {
+        case 2: sy = y; sx = C - 1 - x; break;
+        case 3: sy = R - 1 - y; sx = C - 1 - x; break;
+        case 4: sy = R - 1 - y; sx = x; break;
+        case 5: sy = x; sx = y; break;
+        case 6: sy = R - 1 - x; sx = y; break;
+        case 7: sy = R - 1 - x; sx = C - 1 - y; break;
+        case 8: sy = x; sx = C - 1 - y; break;
+        default: sy = y; sx = x; break;
+      }
+      memcpy(D + ((size_t)y * ocols + x) * 3, S + ((size_t)sy * C + sx) * 3, 3);
+    }
+}
+
 class Decoder {
  public:
-  // decodes to packed BGR; false on anything unsupported or malformed
+  // decodes to packed BGR, turned as the EXIF orientation says (rows / cols: the oriented size); false on anything
+  // unsupported or malformed
   bool decode(const uint8_t* data, size_t size, std::vector<uint8_t>& bgr, int& rows, int& cols) {
     if (!parse(data, size)) return false;
     reconstruct();
-    return output(bgr, rows, cols);
+    return output(bgr, rows, cols) && orient(orientation_, bgr, rows, cols);
   }
   // the bit-serial half only
   bool decode_coefficients(const uint8_t* data, size_t size, Coefs& out) {
     if (!parse(data, size)) return false;
     const uint8_t* zz = zigzag();
     out.rows = H_; out.cols = W_; out.ncomp = nc_; out.hmax = hmax_; out.vmax = vmax_;
+    out.orientation = orientation_;
     for (int i = 0; i < nc_; ++i) {
       Component& c = comp_[i];
       Coefs::Comp& o = out.comp[i];
@@ -96,12 +169,23 @@ class Decoder {
       for (int k = 0; k < 64; ++k) d.qt_[i][k] = s.quant[zz[k]];
     }
     d.reconstruct();
-    return d.output(bgr, rows, cols);
+    return d.output(bgr, rows, cols) && orient(in.orientation, bgr, rows, cols);
   }
 
  private:
+  // the stored image -> the oriented one, in place (rows / cols become the oriented size)
+  static bool orient(int orientation, std::vector<uint8_t>& bgr, int& rows, int& cols) {
+    if (orientation <= 1 || orientation > 8) return true;
+    std::vector<uint8_t> turned(bgr.size());
+    orient_pixels(orientation, bgr.data(), rows, cols, turned.data());
+    bgr.swap(turned);
+    if (orientation >= 5) { const int r = rows; rows = cols; cols = r; }
+    return true;
+  }
   bool parse(const uint8_t* data, size_t size) {
     d_ = data; n_ = size; pos_ = 0;
+    orientation_ = 1;
+    bool have_exif = false;
     if (n_ < 4 || d_[0] != 0xFF || d_[1] != 0xD8) return false;
     pos_ = 2;
     bool have_frame = false, have_scan = false;
@@ -120,6 +204,13 @@ class Decoder {
         continue;
       }
       if (m >= 0xD0 && m <= 0xD7) continue;  // stray RSTn
+      if (m == 0xE1 && !have_exif) {  // APP1: the first Exif one gives the orientation; XMP and the like are passed over
+        size_t len;
+        if (seg(len) && len >= 8 && memcmp(d_ + pos_ + 2, "Exif\0\0", 6) == 0) {
+          have_exif = true;
+          orientation_ = exif_orientation(d_ + pos_ + 2, len - 2);
+        }
+      }
       if (!skip_segment()) return false;
     }
     return true;
@@ -408,7 +499,7 @@ class Decoder {
         long tmp2 = z1 + z3 * (-F1847);
         long tmp3 = z1 + z2 * F0765;
         z2 = s[0]; z3 = s[4];
-        long tmp0 = (z2 + z3) << CB, tmp1 = (z2 - z3) << CB;
+        long tmp0 = (z2 + z3) * (1L << CB), tmp1 = (z2 - z3) * (1L << CB);  // (a multiplication: << of a negative value is undefined before C++20)
         const long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
         tmp0 = s[7]; tmp1 = s[5]; tmp2 = s[3]; tmp3 = s[1];
         z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
@@ -583,6 +674,7 @@ class Decoder {
   Component comp_[3];
   int W_ = 0, H_ = 0, nc_ = 0, hmax_ = 1, vmax_ = 1, mcux_ = 0, mcuy_ = 0, restart_ = 0;
   bool progressive_ = false;
+  int orientation_ = 1;
   int ns_ = 0, scan_[3] = {0, 0, 0}, ss_ = 0, se_ = 63, ah_ = 0, al_ = 0, eobrun_ = 0;
   uint32_t acc_ = 0;
   int bits_ = 0;

@@ -267,7 +267,7 @@ inline bool decode_jpeg(const std::vector<uint8_t>& d, Image& im, bool device_pi
     auto c = std::make_shared<jpeg::Coefs>();
     if (!dec.decode_coefficients(d.data(), d.size(), *c)) { im = Image(); return false; }
     im.pixels.clear();
-    im.rows = c->rows; im.cols = c->cols;
+    im.rows = c->out_rows(); im.cols = c->out_cols();  // the oriented size: what the device decode writes
     im.jpeg = std::move(c);
     return true;
   }

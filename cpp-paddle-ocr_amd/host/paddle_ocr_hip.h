@@ -47,7 +47,8 @@ struct Image {
   std::vector<uint8_t> pixels;
   int rows = 0, cols = 0;
   // a JPEG that has only been entropy-decoded: the worker finishes it on the device (ocr_pipe_stage_jpeg); `pixels`
-  // stays empty unless someone asks for them (materialise())
+  // stays empty unless someone asks for them (materialise()).  rows / cols are the size after the EXIF orientation, the
+  // frame of the reply's width, height and boxes (cv::imdecode turns the image); jpeg->rows / cols stay the stored size
   std::shared_ptr<jpeg::Coefs> jpeg;
   Image() = default;
   explicit Image(const ImageView& v) : rows(v.rows), cols(v.cols) {
@@ -68,6 +69,7 @@ struct Image {
     ocr_jpeg_img d;
     memset(&d, 0, sizeof d);
     d.rows = jpeg->rows; d.cols = jpeg->cols; d.ncomp = jpeg->ncomp; d.hmax = jpeg->hmax; d.vmax = jpeg->vmax;
+    d.orientation = jpeg->orientation;
     for (int i = 0; i < jpeg->ncomp; ++i) {
       const auto& c = jpeg->comp[i];
       d.comp[i].coef = c.coef.data();

@@ -263,13 +263,24 @@ typedef struct ocr_jpeg_comp {
   int dw, dh;          /* component size in samples: ceil(cols*h/hmax), ceil(rows*v/vmax) */
 } ocr_jpeg_comp;
 typedef struct ocr_jpeg_img {
-  int rows, cols, ncomp; /* ncomp 1 (grey) or 3 (YCbCr) */
+  int rows, cols, ncomp; /* STORED size (the SOF's); ncomp 1 (grey) or 3 (YCbCr) */
   int hmax, vmax;        /* luma sampling factors, chroma 1x1: 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0) */
+  /* EXIF Orientation (tag 0x0112 in IFD0 of the file's first Exif APP1 segment), applied to the decoded pixels as
+   * cv::imdecode does: 0 or 1 = as stored, 2..8 = the table in host/jpeg_decode.h; anything else is refused
+   * (OCR_ERR_ARG).  rows / cols stay the stored size: for 5..8 the image that ocr_jpeg_decode writes and the slot
+   * image of ocr_pipe_stage_jpeg are cols x rows.  Producers zero-initialise the struct.  The field sits in what
+   * was alignment padding in front of comp[] (the pointer in ocr_jpeg_comp aligns it to 8): size and every other
+   * offset are unchanged, and a caller built against the older header that zeroed the struct keeps its behaviour. */
+  int orientation;
   ocr_jpeg_comp comp[3];
 } ocr_jpeg_img;
 int ocr_pipe_stage_jpeg(ocr_pipe* h, int slot, const ocr_jpeg_img* imgs, int count);
 /* the same device decode of one image with the pixels copied back to the host (tests, tools) */
 int ocr_jpeg_decode(const ocr_jpeg_img* img, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time): the two kernels of that decode, each launched `iters` times between HIP events
+ * after one untimed decode; ms[0] = mean of the IDCT launch, ms[1] = mean of the pixel stage (upsampling, colour,
+ * orientation). */
+int ocr_jpeg_time(const ocr_jpeg_img* img, int device_id, int iters, double ms[2]);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
 /* network input size the detector uses for a rows x cols image (ResizeImgType0) */
 int ocr_pipe_det_shape(ocr_pipe* h, int rows, int cols, int* net_rows, int* net_cols);
