@@ -13,6 +13,7 @@ struct JpegScratch {
   DevBuf<uint8_t> planes;
   DevBuf<JpegPlaneDesc> pd;
   DevBuf<JpegImageDesc> id;
+  DevBuf<JpegGenDesc> gd;
   int16_t* pinned = nullptr;   // coefficient staging (hipHostMalloc)
   size_t pinned_cap = 0;       // in int16
   hipEvent_t copied = nullptr; // the pinned buffer may be refilled once this has passed
@@ -22,10 +23,16 @@ struct JpegScratch {
 // colour conversion + EXIF orientation on `s`; image i is written as packed BGR to dst[i] (device), jpeg_out_rows x
 // jpeg_out_cols.  launched: the kernels' launch parameters, for a caller that repeats them (ocr_jpeg_time).
 // Returns an OCR_* code.
-int jpeg_decode_async(const ocr_jpeg_img* imgs, int count, uint8_t* const* dst, JpegScratch& sc, hipStream_t s, std::string& err,
+int jpeg_decode_async(const ocr_jpeg_frame* imgs, int count, uint8_t* const* dst, JpegScratch& sc, hipStream_t s, std::string& err,
                       JpegLaunch* launched = nullptr);
 bool jpeg_img_valid(const ocr_jpeg_img& im);
-inline int jpeg_out_rows(const ocr_jpeg_img& im) { return im.orientation >= 5 ? im.cols : im.rows; }
-inline int jpeg_out_cols(const ocr_jpeg_img& im) { return im.orientation >= 5 ? im.rows : im.cols; }
+// why a frame is refused, nullptr when it is sound
+const char* jpeg_frame_fault(const ocr_jpeg_frame& f);
+// the frame that says what a (valid) ocr_jpeg_img says: luma at hmax x vmax, chroma 1x1, grey or YCbCr
+ocr_jpeg_frame jpeg_frame_of(const ocr_jpeg_img& im);
+// the kernel an image runs in (kernels_jpeg.h): the kinds of before for what ocr_jpeg_img can hold, else a general kind
+int jpeg_frame_kind(const ocr_jpeg_frame& f);
+inline int jpeg_out_rows(const ocr_jpeg_frame& im) { return im.orientation >= 5 ? im.cols : im.rows; }
+inline int jpeg_out_cols(const ocr_jpeg_frame& im) { return im.orientation >= 5 ? im.rows : im.cols; }
 
 }  // namespace ocr

@@ -7,6 +7,9 @@
 //   * dequantisation + the "islow" integer IDCT (jidctint.c: 13-bit constants, two passes, PASS1_BITS = 2)
 //   * "fancy" (triangle) chroma upsampling h2v1 / h2v2 with replicated edges (jdsample.c), evaluated per output pixel
 //   * YCbCr -> RGB with the 16-bit fixed-point constants of jdcolor.c, written as packed BGR
+//   * for the files those kernels cannot express (other integral samplings, subsampled luma, RGB, CMYK, YCCK, a fourth
+//     plane) the general kinds at the end of this file: per component copy / fancy h2v1 / h2v2 / h1v2 / box replication as
+//     jdsample.c chooses, YCCK -> CMYK as jdcolor.c, CMYK -> BGR as OpenCV's icvCvt_CMYK2BGR_8u_C4C3R
 //   * the EXIF orientation (cv::imdecode turns the decoded image; the table in host/jpeg_decode.h): the finished pixel
 //     of stored position (y, x) goes to its place in the oriented image, upsampling stays in the stored frame
 // Integer arithmetic throughout: results equal host/jpeg_decode.h (itself pinned to libjpeg-turbo through PIL) bit for
@@ -187,15 +190,105 @@ __global__ void __launch_bounds__(256) jpeg_output_tiled_kernel(const JpegImageD
   }
 }
 
+// ---------------------------------------------------------------- the general kinds
+// Every integral sampling on every component, grey / YCbCr / RGB / CMYK / YCCK (JpegGenDesc).  The images that the
+// kernels above can express never come here, so those kernels stay what they were.
+namespace {
+
+// one sample of a component at position (x, y) of the full-resolution image, by the method jdsample.c chooses
+__device__ __forceinline__ int sample_at(const JpegGenDesc& im, int c, int x, int y) {
+  const uint8_t* plane = im.plane[c];
+  const int stride = im.stride[c];
+  switch (im.method[c]) {
+    case kJpegCopy: return plane[(size_t)y * stride + x];
+    case kJpegFancyH2V1: return chroma_at(plane, stride, im.dw[c], im.dh[c], 2, 1, x, y);
+    case kJpegFancyH2V2: return chroma_at(plane, stride, im.dw[c], im.dh[c], 2, 2, x, y);
+    case kJpegFancyH1V2: {  // h1v2_fancy_upsample: rows 2r, 2r+1 from row r and the row above / below (edges replicated)
+      const int r = y >> 1, dh = im.dh[c];
+      const int rn = (y & 1) ? (r + 1 < dh ? r + 1 : dh - 1) : (r > 0 ? r - 1 : 0);
+      return (plane[(size_t)r * stride + x] * 3 + plane[(size_t)rn * stride + x] + ((y & 1) ? 2 : 1)) >> 2;
+    }
+    default: return plane[(size_t)(y / im.vexp[c]) * stride + x / im.hexp[c]];  // int_upsample: box replication
+  }
+}
+
+// OpenCV's CMYK -> BGR on libjpeg's samples (icvCvt_CMYK2BGR_8u_C4C3R)
+__device__ __forceinline__ uint8_t cmyk_channel(int c, int k) { return (uint8_t)(k - (((255 - c) * k) >> 8)); }
+
+// the finished pixel of stored position (x, y) as B, G, R in o[0..2]
+__device__ __forceinline__ void general_pixel(const JpegGenDesc& im, int x, int y, uint8_t* o) {
+  const int s0 = sample_at(im, 0, x, y);
+  if (im.color == kJpegGrey) { o[0] = o[1] = o[2] = (uint8_t)s0; return; }
+  const int s1 = sample_at(im, 1, x, y), s2 = sample_at(im, 2, x, y);
+  if (im.color == kJpegRGB) { o[2] = (uint8_t)s0; o[1] = (uint8_t)s1; o[0] = (uint8_t)s2; return; }
+  if (im.color == kJpegYCbCr) { ycc_to_bgr(s0, s1, s2, o); return; }
+  const int k = sample_at(im, 3, x, y);
+  int c = s0, m = s1, yy = s2;
+  if (im.color == kJpegYCCK) {  // jdcolor.c ycck_cmyk_convert: C, M, Y = 255 - R, G, B; K as is
+    uint8_t t[3];
+    ycc_to_bgr(s0, s1, s2, t);
+    c = 255 - t[2]; m = 255 - t[1]; yy = 255 - t[0];
+  }
+  o[2] = cmyk_channel(c, k); o[1] = cmyk_channel(m, k); o[0] = cmyk_channel(yy, k);
+}
+
+}  // namespace
+
+// Orientations 1..4: one thread per stored pixel, as jpeg_output_kernel (plane reads and pixel stores run along rows).
+__global__ void __launch_bounds__(256) jpeg_general_kernel(const JpegGenDesc* __restrict__ imgs, int nimg) {
+  const int ii = blockIdx.y;
+  const JpegGenDesc im = imgs[ii];
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long)im.rows * im.cols) return;
+  const int y = (int)(t / im.cols), x = (int)(t - (long)y * im.cols);
+  const int oy = im.orient == 3 || im.orient == 4 ? im.rows - 1 - y : y, ox = im.orient == 2 || im.orient == 3 ? im.cols - 1 - x : x;
+  general_pixel(im, x, y, im.bgr + ((size_t)oy * im.cols + ox) * 3);
+}
+
+// Orientations 5..8: the LDS tile transpose of jpeg_output_tiled_kernel around general_pixel.
+__global__ void __launch_bounds__(256) jpeg_general_tiled_kernel(const JpegGenDesc* __restrict__ imgs, int nimg) {
+  __shared__ uint32_t tile[kJpegTile][kJpegTile + 1];
+  const int ii = blockIdx.y;
+  const JpegGenDesc im = imgs[ii];
+  const int R = im.rows, C = im.cols;
+  const int tiles_x = (C + kJpegTile - 1) / kJpegTile, tiles_y = (R + kJpegTile - 1) / kJpegTile;
+  if ((long)blockIdx.x >= (long)tiles_x * tiles_y) return;  // (the whole workgroup: no barrier is left waiting)
+  const int y0 = (int)(blockIdx.x / tiles_x) * kJpegTile, x0 = (int)(blockIdx.x % tiles_x) * kJpegTile;
+  const int h = min(kJpegTile, R - y0), w = min(kJpegTile, C - x0);
+  const int lane = threadIdx.x & (kJpegTile - 1), first = threadIdx.x / kJpegTile, step = 256 / kJpegTile;
+  if (lane < w)
+    for (int r = first; r < h; r += step) {
+      uint8_t px[4] = {0, 0, 0, 0};
+      general_pixel(im, x0 + lane, y0 + r, px);
+      tile[r][lane] = (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);
+    }
+  __syncthreads();
+  const bool flip_rows = im.orient == 6 || im.orient == 7, flip_cols = im.orient == 7 || im.orient == 8;
+  if (lane < h) {
+    const int r = flip_rows ? h - 1 - lane : lane;
+    const int ox = (flip_rows ? R - y0 - h : y0) + lane;
+    for (int c = first; c < w; c += step) {
+      const int oy = flip_cols ? C - 1 - (x0 + c) : x0 + c;
+      const uint32_t px = tile[r][c];
+      uint8_t* o = im.bgr + ((size_t)oy * R + ox) * 3;
+      o[0] = (uint8_t)px; o[1] = (uint8_t)(px >> 8); o[2] = (uint8_t)(px >> 16);
+    }
+  }
+}
+
 void launch_jpeg_idct(const JpegPlaneDesc* descs, int ndesc, long total_blocks, hipStream_t s) {
   if (total_blocks <= 0) return;
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((total_blocks + 31) / 32)), dim3(256), 0, s, descs, ndesc);
 }
-void launch_jpeg_output(const JpegImageDesc* imgs, const JpegLaunch& L, hipStream_t s) {
-  void (*const kernel[kJpegKinds])(const JpegImageDesc*, int) = {jpeg_output_kernel<false>, jpeg_output_kernel<true>, jpeg_output_tiled_kernel};
-  for (int k = 0; k < kJpegKinds; ++k)
+void launch_jpeg_output(const JpegImageDesc* imgs, const JpegGenDesc* gens, const JpegLaunch& L, hipStream_t s) {
+  void (*const kernel[kJpegGenKind])(const JpegImageDesc*, int) = {jpeg_output_kernel<false>, jpeg_output_kernel<true>, jpeg_output_tiled_kernel};
+  for (int k = 0; k < kJpegGenKind; ++k)
     if (L.count[k] > 0 && L.blocks[k] > 0)
       hipLaunchKernelGGL(kernel[k], dim3((unsigned)L.blocks[k], (unsigned)L.count[k]), dim3(256), 0, s, imgs + L.first[k], L.count[k]);
+  void (*const general[kJpegKinds - kJpegGenKind])(const JpegGenDesc*, int) = {jpeg_general_kernel, jpeg_general_tiled_kernel};
+  for (int k = kJpegGenKind; k < kJpegKinds; ++k)
+    if (L.count[k] > 0 && L.blocks[k] > 0)
+      hipLaunchKernelGGL(general[k - kJpegGenKind], dim3((unsigned)L.blocks[k], (unsigned)L.count[k]), dim3(256), 0, s, gens + L.first[k], L.count[k]);
 }
 
 }  // namespace ocr

@@ -516,15 +516,15 @@ struct ocr_pipe {
   }
 
   // ---- stage JPEG coefficients: the pixel half of the decoder runs on the copy stream, into the slot
-  int stage_jpeg(int si, const ocr_jpeg_img* imgs, int count, std::string& err) {
+  int stage_jpeg(int si, const ocr_jpeg_frame* imgs, int count, std::string& err) {
     StageSlot& S = slots[si];
     // (checked before the sizes are used: a refused batch leaves the slot as it was)
     for (int i = 0; i < count; ++i)
-      if (!jpeg_img_valid(imgs[i])) { err = "bad JPEG coefficient descriptor"; return OCR_ERR_ARG; }
+      if (const char* fault = jpeg_frame_fault(imgs[i])) { err = fault; return OCR_ERR_ARG; }
     // the oriented size: a 40 x 72 image and a 72 x 40 one that EXIF turns by 90 degrees share a size group and a det pass
     int rc = layout(S, count, [&](int i, int& r, int& c) { r = jpeg_out_rows(imgs[i]); c = jpeg_out_cols(imgs[i]); }, err);
     if (rc) return rc;
-    std::vector<ocr_jpeg_img> ordered(count);
+    std::vector<ocr_jpeg_frame> ordered(count);
     std::vector<uint8_t*> dst(count);
     for (int k = 0; k < count; ++k) { ordered[k] = imgs[S.imgs[k].orig]; dst[k] = S.dev.p + S.imgs[k].off; }
     rc = jpeg_decode_async(ordered.data(), count, dst.data(), jpeg, copy_stream, err);
@@ -813,9 +813,38 @@ int ocr_pipe_stage_jpeg(ocr_pipe* h, int slot, const ocr_jpeg_img* imgs, int cou
   for (int i = 0; i < count; ++i)
     if (!jpeg_img_valid(imgs[i])) return fail(OCR_ERR_ARG, "bad JPEG coefficient descriptor");
   CAPI_HIP(rt_set_device(h->device));
+  std::vector<ocr_jpeg_frame> frames((size_t)count);
+  for (int i = 0; i < count; ++i) frames[i] = jpeg_frame_of(imgs[i]);
   std::string err;
-  const int rc = h->stage_jpeg(slot, imgs, count, err);
+  const int rc = h->stage_jpeg(slot, frames.data(), count, err);
   return rc ? fail(rc, err) : OCR_OK;
+}
+
+int ocr_pipe_stage_jpeg_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* frames, int count) {
+  if (!h || !frames || count < 1 || slot < 0 || slot > 1) return fail(OCR_ERR_ARG, "bad argument");
+  for (int i = 0; i < count; ++i)
+    if (const char* fault = jpeg_frame_fault(frames[i])) return fail(OCR_ERR_ARG, fault);
+  CAPI_HIP(rt_set_device(h->device));
+  std::string err;
+  const int rc = h->stage_jpeg(slot, frames, count, err);
+  return rc ? fail(rc, err) : OCR_OK;
+}
+
+int ocr_pipe_slot_image(ocr_pipe* h, int slot, int index, uint8_t* bgr, size_t cap, int* rows, int* cols) {
+  if (!h || !bgr || !rows || !cols || slot < 0 || slot > 1) return fail(OCR_ERR_ARG, "bad argument");
+  StageSlot& S = h->slots[slot];
+  if (!S.staged) return fail(OCR_ERR_ARG, "nothing is staged in the slot");
+  for (const StageSlot::Img& im : S.imgs) {
+    if (im.orig != index) continue;
+    const size_t bytes = (size_t)im.rows * im.cols * 3;
+    if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
+    CAPI_HIP(rt_set_device(h->device));
+    CAPI_HIP(hipEventSynchronize(S.ready));
+    CAPI_HIP(g_memcpy(bgr, S.dev.p + im.off, bytes, hipMemcpyDeviceToHost));
+    *rows = im.rows; *cols = im.cols;
+    return OCR_OK;
+  }
+  return fail(OCR_ERR_ARG, "no staged image with that index");
 }
 
 int ocr_pipe_slot_probs(ocr_pipe* h, int slot, const float* const* probs, int count) {

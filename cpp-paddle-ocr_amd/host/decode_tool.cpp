@@ -1,9 +1,12 @@
-// decode_tool [--device] <image file> <out.ppm> [<image file> <out.ppm> ...]: runs the IPC service's image decoders
-// (test aid; several pairs share one process, the first failure ends it).  --device: a JPEG's
-// pixel half (IDCT, upsampling, colour conversion, EXIF orientation) runs on the GPU through ocr_jpeg_decode instead of
-// on the host.
+// decode_tool [--device | --frame] <image file> <out.ppm> [<image file> <out.ppm> ...]: runs the IPC service's image
+// decoders (test aid; several pairs share one process, the first failure ends it).  --device: a JPEG's
+// pixel half (IDCT, upsampling, colour conversion, EXIF orientation) runs on the GPU instead of on the host - through
+// ocr_jpeg_decode when ocr_jpeg_img can hold the file, else through ocr_jpeg_decode_frame.  --frame: the same, always
+// through ocr_jpeg_decode_frame.
+// decode_tool --stage <model dir> <jpeg file> <out.ppm> [...]: all files as ONE batch through ocr_pipe_stage_jpeg_frames
+// into a pipeline's staging slot, each staged image read back (ocr_pipe_slot_image) and written.
 // decode_tool --time <iters> <jpeg file>: device time of that pixel half's two kernels (HIP events around `iters`
-// launches each, ocr_jpeg_time), one JSON line.
+// launches each, ocr_jpeg_time / ocr_jpeg_time_frame), one JSON line.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,37 +17,85 @@ static int time_device(int iters, const char* in) {
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_jpeg(bytes, im, true) || !im.device_decodable()) { fprintf(stderr, "decode failed\n"); return 1; }
-  const ocr_jpeg_img d = im.jpeg_desc();
+  const ocr_jpeg_frame d = im.jpeg_frame();
   double ms[2];
-  if (ocr_jpeg_time(&d, 0, iters, ms) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+  int rc;
+  if (im.needs_frame()) rc = ocr_jpeg_time_frame(&d, 0, iters, ms);
+  else { const ocr_jpeg_img o = im.jpeg_desc(); rc = ocr_jpeg_time(&o, 0, iters, ms); }
+  if (rc != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
   printf("{\"stored\": [%d, %d], \"orientation\": %d, \"iters\": %d, \"idct_ms\": %.5f, \"pixel_stage_ms\": %.5f}\n",
          d.rows, d.cols, d.orientation, iters, ms[0], ms[1]);
   return 0;
 }
 
-static int decode_one(bool device, const char* in, const char* outp) {
+static void write_ppm(FILE* f, const uint8_t* bgr, int rows, int cols) {
+  fprintf(f, "P6\n%d %d\n255\n", cols, rows);
+  for (size_t p = 0; p < (size_t)rows * cols; ++p) { const uint8_t rgb[3] = {bgr[3 * p + 2], bgr[3 * p + 1], bgr[3 * p]}; fwrite(rgb, 1, 3, f); }
+}
+
+static int stage_batch(const std::string& model_dir, int n, char** pairs) {
+  std::vector<PaddleOCR::Image> ims((size_t)n);
+  std::vector<ocr_jpeg_frame> frames;
+  for (int i = 0; i < n; ++i) {
+    std::vector<uint8_t> bytes;
+    if (!PaddleOCR::ipc::read_file(pairs[2 * i], bytes) || !PaddleOCR::ipc::decode_jpeg(bytes, ims[i], true) || !ims[i].device_decodable()) {
+      fprintf(stderr, "decode failed: %s\n", pairs[2 * i]);
+      return 1;
+    }
+    frames.push_back(ims[i].jpeg_frame());
+  }
+  const std::string det = model_dir + "/det", cls = model_dir + "/cls", rec = model_dir + "/rec", dict = rec + "/ppocr_keys_v1.txt";
+  ocr_pipe_cfg c;
+  ocr_pipe_cfg_default(&c);
+  c.det.model_dir = det.c_str(); c.cls.model_dir = cls.c_str(); c.rec.model_dir = rec.c_str(); c.rec.label_path = dict.c_str();
+  ocr_pipe* pipe = nullptr;
+  if (ocr_pipe_create(&c, &pipe) != OCR_OK) { fprintf(stderr, "pipeline: %s\n", ocr_last_error()); return 1; }
+  int rc = 0;
+  if (ocr_pipe_stage_jpeg_frames(pipe, 0, frames.data(), n) != OCR_OK) { fprintf(stderr, "staging failed: %s\n", ocr_last_error()); rc = 1; }
+  for (int i = 0; i < n && !rc; ++i) {
+    std::vector<uint8_t> px((size_t)ims[i].rows * ims[i].cols * 3);
+    int rows = 0, cols = 0;
+    if (ocr_pipe_slot_image(pipe, 0, i, px.data(), px.size(), &rows, &cols) != OCR_OK || rows != ims[i].rows || cols != ims[i].cols) {
+      fprintf(stderr, "read-back failed: %s: %s\n", pairs[2 * i], ocr_last_error());
+      rc = 1;
+      break;
+    }
+    FILE* f = fopen(pairs[2 * i + 1], "wb");
+    if (!f) { rc = 1; break; }
+    write_ppm(f, px.data(), rows, cols);
+    fclose(f);
+  }
+  ocr_pipe_destroy(pipe);
+  return rc;
+}
+
+static int decode_one(bool device, bool frame, const char* in, const char* outp) {
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
   if (im.device_decodable()) {
-    const ocr_jpeg_img d = im.jpeg_desc();
+    const ocr_jpeg_frame d = im.jpeg_frame();
     im.pixels.resize((size_t)d.rows * d.cols * 3);
-    if (ocr_jpeg_decode(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+    int rc;
+    if (frame || im.needs_frame()) rc = ocr_jpeg_decode_frame(&d, 0, im.pixels.data(), im.pixels.size());
+    else { const ocr_jpeg_img o = im.jpeg_desc(); rc = ocr_jpeg_decode(&o, 0, im.pixels.data(), im.pixels.size()); }
+    if (rc != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
   }
   FILE* f = fopen(outp, "wb");
   if (!f) return 1;
-  fprintf(f, "P6\n%d %d\n255\n", im.cols, im.rows);
-  for (size_t p = 0; p < (size_t)im.rows * im.cols; ++p) { const uint8_t rgb[3] = {im.pixels[3 * p + 2], im.pixels[3 * p + 1], im.pixels[3 * p]}; fwrite(rgb, 1, 3, f); }
+  write_ppm(f, im.pixels.data(), im.rows, im.cols);
   fclose(f);
   return 0;
 }
 
 int main(int argc, char** argv) {
   if (argc == 4 && !strcmp(argv[1], "--time")) return time_device(atoi(argv[2]), argv[3]);
-  const bool device = argc > 1 && !strcmp(argv[1], "--device");
+  if (argc >= 5 && !strcmp(argv[1], "--stage") && (argc - 3) % 2 == 0) return stage_batch(argv[2], (argc - 3) / 2, argv + 3);
+  const bool frame = argc > 1 && !strcmp(argv[1], "--frame");
+  const bool device = frame || (argc > 1 && !strcmp(argv[1], "--device"));
   const int first = device ? 2 : 1;
-  if (argc - first < 2 || (argc - first) % 2) { fprintf(stderr, "usage: decode_tool [--device] <in> <out.ppm> [<in> <out.ppm> ...]\n"); return 2; }
+  if (argc - first < 2 || (argc - first) % 2) { fprintf(stderr, "usage: decode_tool [--device | --frame] <in> <out.ppm> [<in> <out.ppm> ...]\n"); return 2; }
   for (int i = first; i < argc; i += 2)
-    if (int rc = decode_one(device, argv[i], argv[i + 1])) return rc;
+    if (int rc = decode_one(device, frame, argv[i], argv[i + 1])) return rc;
   return 0;
 }

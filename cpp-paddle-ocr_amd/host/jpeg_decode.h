@@ -3,11 +3,22 @@
 // headers, so this is a restatement of what libjpeg(-turbo) computes with default settings, stage by stage:
 //   * Huffman-coded sequential (SOF0 / SOF1) and progressive (SOF2: spectral selection and successive
 //     approximation, jdphuff.c) DCT, 8-bit, restart intervals, interleaved and per-component scans,
-//     1 or 3 components, sampling 4:4:4, 4:2:2 (h2v1) and 4:2:0 (h2v2);
+//     1, 3 or 4 components, sampling factors 1..4 on any component (luma included) as long as every expansion
+//     hmax / h, vmax / v is integral and an interleaved scan has at most 10 blocks per MCU - libjpeg's own limits;
 //   * dequantisation + the "islow" integer IDCT (jidctint.c: 13-bit constants, two passes, PASS1_BITS = 2);
-//   * "fancy" (triangle) chroma upsampling, h2v1 and h2v2 (jdsample.c), image edges replicated;
-//   * YCbCr -> RGB with the 16-bit fixed-point tables of jdcolor.c.
-// tests/test_ipc_service.py checks the output bit for bit against PIL (libjpeg-turbo) on encoded test images.
+//   * upsampling chosen per component from its expansion (hexp, vexp) as jdsample.c chooses it (upsample_method below):
+//     (1,1) copy; (2,1) and (2,2) "fancy" (triangle) h2v1 / h2v2 when the component is more than 2 samples wide, else box
+//     replication; (1,2) fancy h1v2, (3 * near + far + bias) >> 2 along columns with bias 1 for the upper output row and 2
+//     for the lower; every other integral expansion box replication (int_upsample); image edges replicated;
+//   * the colour space by the rule of jdapimin.c default_decompress_parms.  3 components: a JFIF APP0 -> YCbCr; else an
+//     Adobe APP14 with transform 0 -> RGB (stored as is), any other transform -> YCbCr; neither marker: component ids
+//     'R','G','B' -> RGB, else YCbCr.  4 components: an Adobe marker with a transform other than 0 -> YCCK (libjpeg
+//     assumes YCCK for 1 as for 2), else CMYK;
+//   * YCbCr -> RGB with the 16-bit fixed-point tables of jdcolor.c; YCCK -> CMYK as ycck_cmyk_convert (C, M, Y = 255 - the
+//     R, G, B of those tables, K as is); CMYK -> BGR as OpenCV does for 4-component files (grfmt_jpeg.cpp decodes to
+//     JCS_CMYK, then icvCvt_CMYK2BGR_8u_C4C3R of imgcodecs/src/utils.cpp on libjpeg's raw samples c, m, y, k:
+//     R = k - ((255 - c) * k >> 8), G with m, B with y).
+// tests/test_ipc_service.py and tests/test_jpeg_formats.py check the output bit for bit against PIL (libjpeg-turbo).
 //
 // EXIF orientation.  cv::imdecode / cv::imread (OpenCV >= 3.1, no IMREAD_IGNORE_ORIENTATION - what the reference calls)
 // turn the decoded image as the Orientation tag of the file says; libjpeg itself ignores the marker.  So does this
@@ -27,7 +38,9 @@
 //    7  | C x R  | S(R-1-x, C-1-y)
 //    8  | C x R  | S(x, C-1-y)        (90 degrees counter-clockwise)
 // tests/test_jpeg_orientation.py pins host and device to Pillow's ImageOps.exif_transpose, bit for bit.
-// Arithmetic coding, lossless, 12-bit, CMYK and other samplings are refused (decode fails).
+// Arithmetic coding, lossless, 12-bit, 2 or more than 4 components, sampling factors outside 1..4, fractional expansions
+// (3x1 luma over 2x1 chroma) and interleaved scans of more than 10 blocks per MCU are refused (decode fails), as libjpeg
+// refuses them.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -69,9 +82,29 @@ struct Component {
 // Entropy-decoded image: quantised DCT coefficients per component, what the scans of the file say and nothing more.
 // The pixel half of decoding (dequantisation, IDCT, upsampling, colour) can then run on the host (Decoder::pixels)
 // or on the device (ocr_pipe_stage_jpeg / ocr_jpeg_decode of include/ocr_hip.h) with identical results.
+enum Color { kGrey = 0, kYCbCr = 1, kRGB = 2, kCMYK = 3, kYCCK = 4 };  // the values of ocr_jpeg_color (include/ocr_hip.h)
+
+// jdsample.c's choice for a component with expansion (hexp, vexp) = (hmax / h, vmax / v) and dw samples per row
+enum Upsample { kCopy = 0, kFancyH2V1 = 1, kFancyH2V2 = 2, kFancyH1V2 = 3, kBox = 4 };
+inline int upsample_method(int hexp, int vexp, int dw) {
+  if (hexp == 1 && vexp == 1) return kCopy;
+  if (hexp == 2 && vexp == 1) return dw > 2 ? kFancyH2V1 : kBox;
+  if (hexp == 1 && vexp == 2) return kFancyH1V2;
+  if (hexp == 2 && vexp == 2) return dw > 2 ? kFancyH2V2 : kBox;
+  return kBox;
+}
+
 struct Coefs {
   int rows = 0, cols = 0, ncomp = 0, hmax = 1, vmax = 1;  // rows / cols: the stored size
   int orientation = 1;                                     // EXIF tag 0x0112, 1..8 (table above)
+  int color = kYCbCr;
+  // what ocr_jpeg_img can hold: grey, or YCbCr with luma at the maximum factors 1x1 / 2x1 / 2x2 and both chroma 1x1
+  bool classic() const {
+    if (ncomp == 1) return true;
+    if (ncomp != 3 || color != kYCbCr || comp[0].h != hmax || comp[0].v != vmax) return false;
+    if (comp[1].h != 1 || comp[1].v != 1 || comp[2].h != 1 || comp[2].v != 1) return false;
+    return (hmax == 1 || hmax == 2) && (vmax == 1 || (vmax == 2 && hmax == 2));
+  }
   bool transposed() const { return orientation >= 5; }
   int out_rows() const { return transposed() ? cols : rows; }
   int out_cols() const { return transposed() ? rows : cols; }
@@ -79,7 +112,8 @@ struct Coefs {
     std::vector<int16_t> coef;  // bw*bh blocks x 64, blocks row-major, natural order inside
     uint16_t quant[64] = {};    // natural order
     int bw = 0, bh = 0, dw = 0, dh = 0;
-  } comp[3];
+    int h = 1, v = 1;           // sampling factors
+  } comp[4];
 };
 
 // The Orientation of an APP1 payload (the bytes after the segment's length field), 1 when it has none to give.  Every
@@ -145,12 +179,13 @@ class Decoder {
     const uint8_t* zz = zigzag();
     out.rows = H_; out.cols = W_; out.ncomp = nc_; out.hmax = hmax_; out.vmax = vmax_;
     out.orientation = orientation_;
+    out.color = color_;
     for (int i = 0; i < nc_; ++i) {
       Component& c = comp_[i];
       Coefs::Comp& o = out.comp[i];
       o.coef.swap(c.coef);
       for (int k = 0; k < 64; ++k) o.quant[zz[k]] = (uint16_t)qt_[c.tq][k];
-      o.bw = c.bw; o.bh = c.bh; o.dw = c.dw; o.dh = c.dh;
+      o.bw = c.bw; o.bh = c.bh; o.dw = c.dw; o.dh = c.dh; o.h = c.h; o.v = c.v;
     }
     return true;
   }
@@ -158,11 +193,12 @@ class Decoder {
   static bool pixels(const Coefs& in, std::vector<uint8_t>& bgr, int& rows, int& cols) {
     Decoder d;
     const uint8_t* zz = zigzag();
-    d.H_ = in.rows; d.W_ = in.cols; d.nc_ = in.ncomp; d.hmax_ = in.hmax; d.vmax_ = in.vmax;
+    if (in.ncomp < 1 || in.ncomp > 4) return false;
+    d.H_ = in.rows; d.W_ = in.cols; d.nc_ = in.ncomp; d.hmax_ = in.hmax; d.vmax_ = in.vmax; d.color_ = in.color;
     for (int i = 0; i < in.ncomp; ++i) {
       Component& c = d.comp_[i];
       const Coefs::Comp& s = in.comp[i];
-      c.h = i == 0 ? in.hmax : 1; c.v = i == 0 ? in.vmax : 1; c.tq = i;
+      c.h = s.h; c.v = s.v; c.tq = i;
       c.bw = s.bw; c.bh = s.bh; c.dw = s.dw; c.dh = s.dh;
       c.coef = s.coef;
       c.plane.assign((size_t)c.bw * 8 * c.bh * 8, 0);
@@ -185,7 +221,8 @@ class Decoder {
   bool parse(const uint8_t* data, size_t size) {
     d_ = data; n_ = size; pos_ = 0;
     orientation_ = 1;
-    bool have_exif = false;
+    bool have_exif = false, jfif = false, adobe = false;
+    int adobe_transform = 0;
     if (n_ < 4 || d_[0] != 0xFF || d_[1] != 0xD8) return false;
     pos_ = 2;
     bool have_frame = false, have_scan = false;
@@ -204,6 +241,11 @@ class Decoder {
         continue;
       }
       if (m >= 0xD0 && m <= 0xD7) continue;  // stray RSTn
+      if ((m == 0xE0 || m == 0xEE) && !have_scan) {  // jdmarker.c examine_app0 / examine_app14; libjpeg settles the colour space at the first SOS
+        size_t len;
+        if (seg(len) && m == 0xE0 && len >= 2 + 14 && memcmp(d_ + pos_ + 2, "JFIF\0", 5) == 0) jfif = true;
+        if (seg(len) && m == 0xEE && len >= 2 + 12 && memcmp(d_ + pos_ + 2, "Adobe", 5) == 0) { adobe = true; adobe_transform = d_[pos_ + 2 + 11]; }
+      }
       if (m == 0xE1 && !have_exif) {  // APP1: the first Exif one gives the orientation; XMP and the like are passed over
         size_t len;
         if (seg(len) && len >= 8 && memcmp(d_ + pos_ + 2, "Exif\0\0", 6) == 0) {
@@ -212,6 +254,15 @@ class Decoder {
         }
       }
       if (!skip_segment()) return false;
+    }
+    // jdapimin.c default_decompress_parms
+    if (nc_ == 1) color_ = kGrey;
+    else if (nc_ == 3) {
+      if (jfif) color_ = kYCbCr;
+      else if (adobe) color_ = adobe_transform == 0 ? kRGB : kYCbCr;
+      else color_ = comp_[0].id == 'R' && comp_[1].id == 'G' && comp_[2].id == 'B' ? kRGB : kYCbCr;
+    } else {
+      color_ = adobe && adobe_transform != 0 ? kYCCK : kCMYK;
     }
     return true;
   }
@@ -280,7 +331,7 @@ class Decoder {
     H_ = (q[1] << 8) | q[2];
     W_ = (q[3] << 8) | q[4];
     nc_ = q[5];
-    if (H_ <= 0 || W_ <= 0 || (nc_ != 1 && nc_ != 3) || len < (size_t)(8 + 3 * nc_)) return false;
+    if (H_ <= 0 || W_ <= 0 || (nc_ != 1 && nc_ != 3 && nc_ != 4) || len < (size_t)(8 + 3 * nc_)) return false;
     if ((long)H_ * W_ > (64L << 20)) return false;  // 64 Mpixel cap: a service must not be made to allocate gigabytes by a header
     hmax_ = vmax_ = 1;
     for (int i = 0; i < nc_; ++i) {
@@ -288,16 +339,14 @@ class Decoder {
       comp_[i].h = q[7 + 3 * i] >> 4;
       comp_[i].v = q[7 + 3 * i] & 15;
       comp_[i].tq = q[8 + 3 * i];
-      if (comp_[i].h < 1 || comp_[i].h > 2 || comp_[i].v < 1 || comp_[i].v > 2 || comp_[i].tq > 3) return false;
+      if (comp_[i].h < 1 || comp_[i].h > 4 || comp_[i].v < 1 || comp_[i].v > 4 || comp_[i].tq > 3) return false;
       hmax_ = comp_[i].h > hmax_ ? comp_[i].h : hmax_;
       vmax_ = comp_[i].v > vmax_ ? comp_[i].v : vmax_;
     }
     if (nc_ == 1) { comp_[0].h = comp_[0].v = 1; hmax_ = vmax_ = 1; }  // a single component is never subsampled
-    if (nc_ == 3) {
-      // accepted: luma at the maximum factors, both chroma 1x1 -> 4:4:4, 4:2:2 (2x1), 4:2:0 (2x2)
-      if (comp_[0].h != hmax_ || comp_[0].v != vmax_ || comp_[1].h != 1 || comp_[1].v != 1 || comp_[2].h != 1 || comp_[2].v != 1) return false;
-      if (hmax_ == 1 && vmax_ == 2) return false;  // h1v2 is not handled
-    }
+    // only integral expansions: libjpeg has no upsampler for the others (JERR_FRACT_SAMPLE_NOTIMPL)
+    for (int i = 0; i < nc_; ++i)
+      if (hmax_ % comp_[i].h != 0 || vmax_ % comp_[i].v != 0) return false;
     mcux_ = (W_ + 8 * hmax_ - 1) / (8 * hmax_);
     mcuy_ = (H_ + 8 * vmax_ - 1) / (8 * vmax_);
     for (int i = 0; i < nc_; ++i) {
@@ -326,6 +375,11 @@ class Decoder {
       comp_[ci].td = q[2 + 2 * i] >> 4;
       comp_[ci].ta = q[2 + 2 * i] & 15;
       if (comp_[ci].td > 3 || comp_[ci].ta > 3) return false;
+    }
+    if (ns_ > 1) {  // jdinput.c per_scan_setup: an interleaved MCU holds at most D_MAX_BLOCKS_IN_MCU = 10 blocks
+      int blocks = 0;
+      for (int i = 0; i < ns_; ++i) blocks += comp_[scan_[i]].h * comp_[scan_[i]].v;
+      if (blocks > 10) return false;
     }
     ss_ = q[1 + 2 * ns_]; se_ = q[2 + 2 * ns_]; ah_ = q[3 + 2 * ns_] >> 4; al_ = q[3 + 2 * ns_] & 15;
     if (!progressive_) {
@@ -576,19 +630,41 @@ class Decoder {
     }
   }
 
-  // ---------------------------------------------------------------- jdsample.c fancy upsampling
-  // full-resolution chroma plane (W_ x H_) from a component plane
+  // ---------------------------------------------------------------- jdsample.c upsampling
+  // full-resolution plane (W_ x H_) from a component plane, by the method jdsample.c chooses for the component
   void upsample(const Component& c, std::vector<uint8_t>& full) const {
     const int stride = c.bw * 8;
     full.assign((size_t)W_ * H_, 0);
-    if (c.h == hmax_ && c.v == vmax_) {
+    const int hexp = hmax_ / c.h, vexp = vmax_ / c.v;
+    const int method = upsample_method(hexp, vexp, c.dw);
+    if (method == kCopy) {
       for (int y = 0; y < H_; ++y) memcpy(&full[(size_t)y * W_], &c.plane[(size_t)y * stride], (size_t)W_);
       return;
     }
     const int dw = c.dw, dh = c.dh;
+    if (method == kBox) {  // int_upsample: every sample hexp times along the row, every row vexp times
+      for (int y = 0; y < H_; ++y) {
+        const uint8_t* in = &c.plane[(size_t)(y / vexp) * stride];
+        uint8_t* out = &full[(size_t)y * W_];
+        for (int x = 0; x < W_; ++x) out[x] = in[x / hexp];
+      }
+      return;
+    }
+    if (method == kFancyH1V2) {  // h1v2_fancy_upsample: output rows 2r, 2r+1 from row r and the row above / below
+      for (int y = 0; y < H_; ++y) {
+        const int r = y >> 1;
+        const int rn = (y & 1) ? (r + 1 < dh ? r + 1 : dh - 1) : (r > 0 ? r - 1 : 0);
+        const int bias = (y & 1) ? 2 : 1;
+        const uint8_t* in0 = &c.plane[(size_t)r * stride];
+        const uint8_t* in1 = &c.plane[(size_t)rn * stride];
+        uint8_t* out = &full[(size_t)y * W_];
+        for (int x = 0; x < W_; ++x) out[x] = (uint8_t)((in0[x] * 3 + in1[x] + bias) >> 2);
+      }
+      return;
+    }
     std::vector<int> colsum((size_t)dw);
     std::vector<uint8_t> row((size_t)2 * dw + 2);
-    if (vmax_ == 1) {  // h2v1
+    if (method == kFancyH2V1) {
       for (int y = 0; y < H_; ++y) {
         const uint8_t* in = &c.plane[(size_t)y * stride];
         if (dw == 1) { row[0] = row[1] = in[0]; }
@@ -643,9 +719,22 @@ class Decoder {
         }
       return true;
     }
-    std::vector<uint8_t> cb, cr;
-    upsample(comp_[1], cb);
-    upsample(comp_[2], cr);
+    // every component at full resolution: its own plane when it is stored so, else an upsampled copy
+    std::vector<uint8_t> up[4];
+    const uint8_t* full[4];
+    size_t fstride[4];
+    for (int i = 0; i < nc_; ++i) {
+      if (comp_[i].h == hmax_ && comp_[i].v == vmax_) { full[i] = comp_[i].plane.data(); fstride[i] = (size_t)comp_[i].bw * 8; }
+      else { upsample(comp_[i], up[i]); full[i] = up[i].data(); fstride[i] = (size_t)W_; }
+    }
+    if (color_ == kRGB) {
+      for (int y = 0; y < H_; ++y)
+        for (int x = 0; x < W_; ++x) {
+          uint8_t* o = &bgr[((size_t)y * W_ + x) * 3];
+          for (int k = 0; k < 3; ++k) o[2 - k] = full[k][y * fstride[k] + x];
+        }
+      return true;
+    }
     int crr[256], cbb[256];
     long crg[256], cbg[256];
     for (int i = 0; i < 256; ++i) {
@@ -657,12 +746,22 @@ class Decoder {
     }
     for (int y = 0; y < H_; ++y)
       for (int x = 0; x < W_; ++x) {
-        const int Y = comp_[0].plane[(size_t)y * ystride + x];
-        const int b = cb[(size_t)y * W_ + x], r = cr[(size_t)y * W_ + x];
+        int s[4] = {0, 0, 0, 0};
+        for (int k = 0; k < nc_; ++k) s[k] = full[k][y * fstride[k] + x];
         uint8_t* o = &bgr[((size_t)y * W_ + x) * 3];
-        o[2] = clamp8(Y + crr[r]);
-        o[1] = clamp8(Y + (int)((cbg[b] + crg[r]) >> 16));
-        o[0] = clamp8(Y + cbb[b]);
+        if (color_ != kCMYK) {  // YCbCr, and the first three components of YCCK
+          const int Y = s[0], b = s[1], r = s[2];
+          o[2] = clamp8(Y + crr[r]);
+          o[1] = clamp8(Y + (int)((cbg[b] + crg[r]) >> 16));
+          o[0] = clamp8(Y + cbb[b]);
+          if (color_ == kYCbCr) continue;
+          s[0] = 255 - o[2]; s[1] = 255 - o[1]; s[2] = 255 - o[0];  // ycck_cmyk_convert
+        }
+        // OpenCV's CMYK -> BGR on libjpeg's samples
+        const int k = s[3];
+        o[2] = (uint8_t)(k - (((255 - s[0]) * k) >> 8));
+        o[1] = (uint8_t)(k - (((255 - s[1]) * k) >> 8));
+        o[0] = (uint8_t)(k - (((255 - s[2]) * k) >> 8));
       }
     return true;
   }
@@ -671,11 +770,11 @@ class Decoder {
   size_t n_ = 0, pos_ = 0;
   int qt_[4][64] = {};
   Huff dc_[4], ac_[4];
-  Component comp_[3];
+  Component comp_[4];
   int W_ = 0, H_ = 0, nc_ = 0, hmax_ = 1, vmax_ = 1, mcux_ = 0, mcuy_ = 0, restart_ = 0;
   bool progressive_ = false;
-  int orientation_ = 1;
-  int ns_ = 0, scan_[3] = {0, 0, 0}, ss_ = 0, se_ = 63, ah_ = 0, al_ = 0, eobrun_ = 0;
+  int orientation_ = 1, color_ = kYCbCr;
+  int ns_ = 0, scan_[4] = {0, 0, 0, 0}, ss_ = 0, se_ = 63, ah_ = 0, al_ = 0, eobrun_ = 0;
   uint32_t acc_ = 0;
   int bits_ = 0;
   bool hit_marker_ = false;

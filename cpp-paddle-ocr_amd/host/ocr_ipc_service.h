@@ -15,7 +15,8 @@
 // JSON (jsoncpp's default writer indents); cv::imread/imdecode are replaced by the decoders below - PNG through
 // the system's libpng16 (its simplified API, loaded with dlopen: the image ships the .so but no headers), PPM
 // and BMP natively, JPEG with the decoder of jpeg_decode.h (a restatement of libjpeg's default pipeline,
-// sequential and progressive, checked bit for bit against libjpeg-turbo through PIL).
+// sequential and progressive, grey / YCbCr / RGB / CMYK / YCCK at every integral sampling, checked bit for bit against
+// libjpeg-turbo through PIL).
 // There is no CPU worker pool: cpu_workers is accepted and ignored, gpu_workers = 0 leaves `recognize`
 // answering with an error (status / shutdown still work - that is what the CPU-only tests drive).
 #pragma once

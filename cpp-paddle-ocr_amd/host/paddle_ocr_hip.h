@@ -65,7 +65,22 @@ struct Image {
     if (!jpeg::Decoder::pixels(*jpeg, pixels, rows, cols)) throw std::runtime_error("JPEG reconstruction failed");
     jpeg.reset();
   }
-  ocr_jpeg_img jpeg_desc() const {
+  // ocr_jpeg_img holds grey and YCbCr 4:4:4 / 4:2:2 / 4:2:0; every other file (another sampling, RGB, CMYK, YCCK) needs
+  // the general descriptor, jpeg_frame(), which can say what the first says too
+  bool needs_frame() const { return jpeg && !jpeg->classic(); }
+  ocr_jpeg_frame jpeg_frame() const {
+    ocr_jpeg_frame d;
+    memset(&d, 0, sizeof d);
+    d.rows = jpeg->rows; d.cols = jpeg->cols; d.ncomp = jpeg->ncomp; d.orientation = jpeg->orientation; d.color = jpeg->color;
+    for (int i = 0; i < jpeg->ncomp; ++i) {
+      const auto& c = jpeg->comp[i];
+      d.comp[i].coef = c.coef.data();
+      memcpy(d.comp[i].quant, c.quant, sizeof c.quant);
+      d.comp[i].bw = c.bw; d.comp[i].bh = c.bh; d.comp[i].dw = c.dw; d.comp[i].dh = c.dh; d.comp[i].h = c.h; d.comp[i].v = c.v;
+    }
+    return d;
+  }
+  ocr_jpeg_img jpeg_desc() const {  // only when !needs_frame()
     ocr_jpeg_img d;
     memset(&d, 0, sizeof d);
     d.rows = jpeg->rows; d.cols = jpeg->cols; d.ncomp = jpeg->ncomp; d.hmax = jpeg->hmax; d.vmax = jpeg->vmax;
@@ -464,8 +479,13 @@ class OCRWorker {
       rc = ocr_pipe_run_chars(pipe_, &im, 1, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), chars.data(), nullptr);
     } else
     if (request.image_data.device_decodable()) {  // JPEG: pixels are produced on the device, straight into the staging slot
-      const ocr_jpeg_img jd = request.image_data.jpeg_desc();
-      rc = ocr_pipe_stage_jpeg(pipe_, 0, &jd, 1);
+      if (request.image_data.needs_frame()) {
+        const ocr_jpeg_frame jf = request.image_data.jpeg_frame();
+        rc = ocr_pipe_stage_jpeg_frames(pipe_, 0, &jf, 1);
+      } else {
+        const ocr_jpeg_img jd = request.image_data.jpeg_desc();
+        rc = ocr_pipe_stage_jpeg(pipe_, 0, &jd, 1);
+      }
       if (rc == OCR_OK) rc = ocr_pipe_run_staged(pipe_, 0, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), nullptr);
     } else {
       ocr_img im = request.image_data.view().c();
@@ -497,17 +517,22 @@ class OCRWorker {
     std::vector<OCRResult> results(requests.size());
     std::vector<ocr_img> imgs;
     std::vector<ocr_jpeg_img> jimgs;
+    std::vector<ocr_jpeg_frame> jframes;
     std::vector<size_t> owner;
-    // a batch of JPEGs only is decoded on the device; a mixed batch takes the host path for its JPEGs
-    bool all_jpeg = !char_boxes_;
-    for (size_t i = 0; i < requests.size(); ++i)
+    // a batch of JPEGs only is decoded on the device; a mixed batch takes the host path for its JPEGs.  One file that
+    // only the general descriptor can hold (CMYK, 4:4:0, ...) puts the whole batch on that descriptor, not on the host.
+    bool all_jpeg = !char_boxes_, frames = false;
+    for (size_t i = 0; i < requests.size(); ++i) {
       if (!requests[i]->image_data.empty() && !requests[i]->image_data.device_decodable()) all_jpeg = false;
+      if (requests[i]->image_data.needs_frame()) frames = true;
+    }
     for (size_t i = 0; i < requests.size(); ++i) {
       results[i].request_id = requests[i]->request_id;
       if (requests[i]->image_data.empty()) { results[i].error_message = "Empty image data provided"; continue; }
       results[i].width = requests[i]->image_data.cols;
       results[i].height = requests[i]->image_data.rows;
-      if (all_jpeg) jimgs.push_back(requests[i]->image_data.jpeg_desc());
+      if (all_jpeg && frames) jframes.push_back(requests[i]->image_data.jpeg_frame());
+      else if (all_jpeg) jimgs.push_back(requests[i]->image_data.jpeg_desc());
       else {
         const_cast<OCRRequest*>(requests[i])->image_data.materialise();
         imgs.push_back(requests[i]->image_data.view().c());
@@ -528,7 +553,7 @@ class OCRWorker {
       rc = ocr_pipe_run_chars(pipe_, imgs.data(), k, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, batch_chars_.data(), nullptr);
     } else
     if (all_jpeg) {
-      rc = ocr_pipe_stage_jpeg(pipe_, 0, jimgs.data(), k);
+      rc = frames ? ocr_pipe_stage_jpeg_frames(pipe_, 0, jframes.data(), k) : ocr_pipe_stage_jpeg(pipe_, 0, jimgs.data(), k);
       if (rc == OCR_OK) rc = ocr_pipe_run_staged(pipe_, 0, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, nullptr);
     } else {
       rc = ocr_pipe_run(pipe_, imgs.data(), k, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, nullptr);

@@ -281,6 +281,40 @@ int ocr_jpeg_decode(const ocr_jpeg_img* img, int device_id, uint8_t* bgr, size_t
  * after one untimed decode; ms[0] = mean of the IDCT launch, ms[1] = mean of the pixel stage (upsampling, colour,
  * orientation). */
 int ocr_jpeg_time(const ocr_jpeg_img* img, int device_id, int iters, double ms[2]);
+/* The general descriptor: what ocr_jpeg_img (frozen: three components, chroma 1x1) cannot hold.  1, 3 or 4 components,
+ * each with its own sampling factors h, v in 1..4 (luma included) where every hmax / h and vmax / v is integral, and the
+ * colour space of the file by libjpeg's rule (host/jpeg_decode.h).  Upsampling per component as libjpeg-turbo's jdsample.c
+ * chooses it (copy, fancy h2v1 / h2v2 / h1v2, box replication), YCCK -> CMYK as jdcolor.c, CMYK -> BGR as OpenCV.  An
+ * image that ocr_jpeg_img can hold runs the same kernels through either descriptor, with the same result.  The three
+ * entry points are the counterparts of the three above; a descriptor that breaks a rule stated here is refused
+ * (OCR_ERR_ARG, ocr_last_error says which). */
+typedef enum ocr_jpeg_color {
+  OCR_JPEG_GREY = 0,  /* ncomp 1 */
+  OCR_JPEG_YCBCR = 1, /* ncomp 3 */
+  OCR_JPEG_RGB = 2,   /* ncomp 3: stored as R, G, B (Adobe transform 0, or component ids 'R','G','B') */
+  OCR_JPEG_CMYK = 3,  /* ncomp 4: libjpeg's raw samples */
+  OCR_JPEG_YCCK = 4   /* ncomp 4: Adobe transform 2 */
+} ocr_jpeg_color;
+typedef struct ocr_jpeg_fcomp {
+  const int16_t* coef; /* as ocr_jpeg_comp */
+  uint16_t quant[64];
+  int bw, bh;          /* blocks per row / column; bw * 8 >= dw, bh * 8 >= dh */
+  int dw, dh;          /* component size in samples: ceil(cols*h/hmax), ceil(rows*v/vmax) */
+  int h, v;            /* sampling factors 1..4; 1, 1 for a single component */
+} ocr_jpeg_fcomp;
+typedef struct ocr_jpeg_frame {
+  int rows, cols, ncomp; /* STORED size; ncomp 1, 3 or 4 */
+  int orientation;       /* as ocr_jpeg_img.orientation */
+  int color;             /* ocr_jpeg_color, consistent with ncomp */
+  int reserved;          /* 0 */
+  ocr_jpeg_fcomp comp[4];
+} ocr_jpeg_frame;
+int ocr_pipe_stage_jpeg_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* frames, int count);
+/* the staged image that was imgs[index] / frames[index] of the slot's last stage call, copied back to the host as
+ * packed BGR (tests, tools: what a stage call put into the slot, whichever kernels wrote it); rows / cols: its size */
+int ocr_pipe_slot_image(ocr_pipe* h, int slot, int index, uint8_t* bgr, size_t cap_bytes, int* rows, int* cols);
+int ocr_jpeg_decode_frame(const ocr_jpeg_frame* frame, int device_id, uint8_t* bgr, size_t cap_bytes);
+int ocr_jpeg_time_frame(const ocr_jpeg_frame* frame, int device_id, int iters, double ms[2]);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
 /* network input size the detector uses for a rows x cols image (ResizeImgType0) */
 int ocr_pipe_det_shape(ocr_pipe* h, int rows, int cols, int* net_rows, int* net_cols);
