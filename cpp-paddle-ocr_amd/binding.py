@@ -573,6 +573,7 @@ class ocr_char(C.Structure):
 EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_pipe_run", "ocr_pipe_run_chars", "ocr_pipe_run_device",
             "ocr_pipe_stage", "ocr_pipe_slot_probs", "ocr_pipe_run_staged", "ocr_pipe_run_device_on", "ocr_pipe_run_staged_on", "ocr_pipe_stage_jpeg", "ocr_jpeg_decode", "ocr_jpeg_time",
             "ocr_pipe_stage_jpeg_frames", "ocr_jpeg_decode_frame", "ocr_jpeg_time_frame", "ocr_pipe_slot_image",
+            "ocr_png_decode", "ocr_png_time", "ocr_png_time_batch", "ocr_pipe_stage_coded",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
@@ -613,6 +614,45 @@ def _pipe_protos(L):
 
 
 CROP_BOUNDING_RECT, CROP_ROTATE = 0, 1
+
+
+class ocr_png_segment(C.Structure):
+    _fields_ = [("pass_", C.c_int32), ("first_row", C.c_int32), ("rows", C.c_int32)]
+
+
+class ocr_png_frame(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("bit_depth", C.c_int), ("color_type", C.c_int), ("interlace", C.c_int),
+                ("reserved", C.c_int), ("palette", C.c_uint8 * 768), ("data", C.c_void_p), ("data_len", C.c_size_t),
+                ("segments", C.POINTER(ocr_png_segment)), ("nsegments", C.c_int)]
+
+
+class PngFrame:
+    """an ocr_png_frame over Python-owned memory.  stream: the inflated scanline stream (bytes); segments: [(pass, first
+    row, rows)]; palette: (n, 3) RGB or None.  Fields of .c may be changed before a call (the tests' tampering)."""
+
+    def __init__(self, width, height, bit_depth, color_type, interlace, stream, segments, palette=None):
+        self._data = np.frombuffer(bytes(stream), np.uint8).copy()
+        self._segs = (ocr_png_segment * max(1, len(segments)))(*[ocr_png_segment(*s) for s in segments])
+        c = ocr_png_frame()
+        c.width, c.height, c.bit_depth, c.color_type, c.interlace = width, height, bit_depth, color_type, interlace
+        if palette is not None:
+            flat = np.asarray(palette, np.uint8).reshape(-1)
+            C.memmove(c.palette, flat.ctypes.data, len(flat))
+        c.data, c.data_len = self._data.ctypes.data, len(self._data)
+        c.segments, c.nsegments = self._segs, len(segments)
+        self.c = c
+
+    def decode(self, device_id=0):
+        """ocr_png_decode: the (height, width, 3) BGR image; OcrError where the call refuses"""
+        L = lib()
+        L.ocr_png_decode.argtypes = [C.POINTER(ocr_png_frame), C.c_int, C.c_void_p, C.c_size_t]
+        out = np.zeros((max(1, self.c.height), max(1, self.c.width), 3), np.uint8)
+        rc = L.ocr_png_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
+            err.code = rc
+            raise err
+        return out
 
 
 def rotate_crop_shape(rows, cols, box):

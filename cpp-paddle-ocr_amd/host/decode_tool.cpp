@@ -3,20 +3,39 @@
 // pixel half (IDCT, upsampling, colour conversion, EXIF orientation) runs on the GPU instead of on the host - through
 // ocr_jpeg_decode when ocr_jpeg_img can hold the file, else through ocr_jpeg_decode_frame.  --frame: the same, always
 // through ocr_jpeg_decode_frame.
+// A PNG's pixel half (unfiltering, conversion, Adam7 placement) runs on the GPU with --device / --frame too, through
+// ocr_png_decode (whatever OCR_DEVICE_PNG says; a file beyond the device stage's bounds stays on the host); without them
+// on the host (png_decode.h).
 // decode_tool --stage <model dir> <jpeg file> <out.ppm> [...]: all files as ONE batch through ocr_pipe_stage_jpeg_frames
-// into a pipeline's staging slot, each staged image read back (ocr_pipe_slot_image) and written.
+// into a pipeline's staging slot, each staged image read back (ocr_pipe_slot_image) and written.  With a PNG among the
+// files the batch goes through ocr_pipe_stage_coded.
 // decode_tool --time <iters> <jpeg file>: device time of that pixel half's two kernels (HIP events around `iters`
 // launches each, ocr_jpeg_time / ocr_jpeg_time_frame), one JSON line.
+// decode_tool --time <iters> <png file> [<batch>]: the same for a PNG (ocr_png_time: upload of the inflated stream, pixel
+// stage); with <batch> > 1 that many copies of the file as one batch (ocr_png_time_batch), times per batch.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 #include "ocr_ipc_service.h"
 
-static int time_device(int iters, const char* in) {
+static int time_device(int iters, const char* in, int batch) {
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
-  if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_jpeg(bytes, im, true) || !im.device_decodable()) { fprintf(stderr, "decode failed\n"); return 1; }
+  if (PaddleOCR::ipc::read_file(in, bytes) && bytes.size() > 8 && bytes[0] == 0x89 && bytes[1] == 'P') {
+    auto f = std::make_shared<PaddleOCR::png::Frame>();
+    if (!PaddleOCR::png::parse(bytes.data(), bytes.size(), *f)) { fprintf(stderr, "decode failed\n"); return 1; }
+    im.rows = f->height; im.cols = f->width;
+    im.png = f;
+    const ocr_png_frame d = im.png_frame();
+    std::vector<const ocr_png_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
+    double ms[2];
+    if ((batch > 1 ? ocr_png_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_png_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    printf("{\"size\": [%d, %d], \"color_type\": %d, \"bit_depth\": %d, \"interlace\": %d, \"segments\": %d, \"batch\": %d, \"iters\": %d, "
+           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f}\n", d.height, d.width, d.color_type, d.bit_depth, d.interlace, d.nsegments, (int)all.size(), iters, ms[0], ms[1]);
+    return 0;
+  }
+  if (bytes.empty() || !PaddleOCR::ipc::decode_jpeg(bytes, im, true) || !im.device_decodable()) { fprintf(stderr, "decode failed\n"); return 1; }
   const ocr_jpeg_frame d = im.jpeg_frame();
   double ms[2];
   int rc;
@@ -35,14 +54,19 @@ static void write_ppm(FILE* f, const uint8_t* bgr, int rows, int cols) {
 
 static int stage_batch(const std::string& model_dir, int n, char** pairs) {
   std::vector<PaddleOCR::Image> ims((size_t)n);
-  std::vector<ocr_jpeg_frame> frames;
+  std::vector<ocr_jpeg_frame> frames((size_t)n);
+  std::vector<ocr_png_frame> pframes((size_t)n);
+  std::vector<const ocr_jpeg_frame*> jp((size_t)n, nullptr);
+  std::vector<const ocr_png_frame*> pp((size_t)n, nullptr);
+  bool coded = false;
   for (int i = 0; i < n; ++i) {
     std::vector<uint8_t> bytes;
-    if (!PaddleOCR::ipc::read_file(pairs[2 * i], bytes) || !PaddleOCR::ipc::decode_jpeg(bytes, ims[i], true) || !ims[i].device_decodable()) {
+    if (!PaddleOCR::ipc::read_file(pairs[2 * i], bytes) || !PaddleOCR::ipc::decode_image(bytes, ims[i], true, true) || !ims[i].device_decodable()) {
       fprintf(stderr, "decode failed: %s\n", pairs[2 * i]);
       return 1;
     }
-    frames.push_back(ims[i].jpeg_frame());
+    if (ims[i].png) { pframes[i] = ims[i].png_frame(); pp[i] = &pframes[i]; coded = true; }
+    else { frames[i] = ims[i].jpeg_frame(); jp[i] = &frames[i]; }
   }
   const std::string det = model_dir + "/det", cls = model_dir + "/cls", rec = model_dir + "/rec", dict = rec + "/ppocr_keys_v1.txt";
   ocr_pipe_cfg c;
@@ -51,7 +75,7 @@ static int stage_batch(const std::string& model_dir, int n, char** pairs) {
   ocr_pipe* pipe = nullptr;
   if (ocr_pipe_create(&c, &pipe) != OCR_OK) { fprintf(stderr, "pipeline: %s\n", ocr_last_error()); return 1; }
   int rc = 0;
-  if (ocr_pipe_stage_jpeg_frames(pipe, 0, frames.data(), n) != OCR_OK) { fprintf(stderr, "staging failed: %s\n", ocr_last_error()); rc = 1; }
+  if ((coded ? ocr_pipe_stage_coded(pipe, 0, jp.data(), pp.data(), n) : ocr_pipe_stage_jpeg_frames(pipe, 0, frames.data(), n)) != OCR_OK) { fprintf(stderr, "staging failed: %s\n", ocr_last_error()); rc = 1; }
   for (int i = 0; i < n && !rc; ++i) {
     std::vector<uint8_t> px((size_t)ims[i].rows * ims[i].cols * 3);
     int rows = 0, cols = 0;
@@ -72,7 +96,12 @@ static int stage_batch(const std::string& model_dir, int n, char** pairs) {
 static int decode_one(bool device, bool frame, const char* in, const char* outp) {
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
-  if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
+  if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
+  if (im.device_decodable() && im.png) {
+    const ocr_png_frame d = im.png_frame();
+    im.pixels.resize((size_t)d.height * d.width * 3);
+    if (ocr_png_decode(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+  } else
   if (im.device_decodable()) {
     const ocr_jpeg_frame d = im.jpeg_frame();
     im.pixels.resize((size_t)d.rows * d.cols * 3);
@@ -89,7 +118,7 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
 }
 
 int main(int argc, char** argv) {
-  if (argc == 4 && !strcmp(argv[1], "--time")) return time_device(atoi(argv[2]), argv[3]);
+  if ((argc == 4 || argc == 5) && !strcmp(argv[1], "--time")) return time_device(atoi(argv[2]), argv[3], argc == 5 ? atoi(argv[4]) : 1);
   if (argc >= 5 && !strcmp(argv[1], "--stage") && (argc - 3) % 2 == 0) return stage_batch(argv[2], (argc - 3) / 2, argv + 3);
   const bool frame = argc > 1 && !strcmp(argv[1], "--frame");
   const bool device = frame || (argc > 1 && !strcmp(argv[1], "--device"));

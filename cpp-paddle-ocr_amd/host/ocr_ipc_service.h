@@ -12,8 +12,9 @@
 // answered with the reference's "Data too large for buffer" error (ocr_ipc_service.cpp:222-238).
 //
 // Differences, by necessity: the transport (socket path instead of \\.\pipe\ocr_service); replies are compact
-// JSON (jsoncpp's default writer indents); cv::imread/imdecode are replaced by the decoders below - PNG through
-// the system's libpng16 (its simplified API, loaded with dlopen: the image ships the .so but no headers), PPM
+// JSON (jsoncpp's default writer indents); cv::imread/imdecode are replaced by the decoders below - PNG with the decoder
+// of png_decode.h (own container parser, zlib's inflate through dlopen, cv::imdecode's conversions; the system's libpng16
+// simplified API, also through dlopen, only where libz.so.1 is missing), PPM
 // and BMP natively, JPEG with the decoder of jpeg_decode.h (a restatement of libjpeg's default pipeline,
 // sequential and progressive, grey / YCbCr / RGB / CMYK / YCCK at every integral sampling, checked bit for bit against
 // libjpeg-turbo through PIL).
@@ -40,6 +41,7 @@
 
 #include "jpeg_decode.h"
 #include "paddle_ocr_hip.h"
+#include "png_decode.h"
 
 namespace PaddleOCR {
 namespace ipc {
@@ -232,7 +234,7 @@ struct PngImage {
   uint32_t version, width, height, format, flags, colormap_entries, warning_or_error;
   char message[64];
 };
-inline bool decode_png(const std::vector<uint8_t>& d, Image& im) {
+inline bool decode_png_libpng(const std::vector<uint8_t>& d, Image& im) {
   static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
   if (d.size() < 8 || memcmp(d.data(), sig, 8)) return false;
   static void* lib = dlopen("libpng16.so.16", RTLD_NOW | RTLD_GLOBAL);
@@ -258,6 +260,30 @@ inline bool decode_png(const std::vector<uint8_t>& d, Image& im) {
   if (!finish(&pi, nullptr, im.pixels.data(), 0, nullptr)) { pfree(&pi); im = Image(); return false; }
   return true;
 }
+// PNG as cv::imdecode(IMREAD_COLOR) returns it (png_decode.h: alpha dropped, high bytes of 16-bit samples, no gamma).
+// device_pixels: the caller has a GPU worker that can finish the image.  Whether it is asked to is OCR_DEVICE_PNG, read
+// once: =1 stops after the inflate and leaves unfiltering and conversion to the worker (frames within the device
+// stage's bounds, png::Frame::device_ok; others are finished here), =0 or unset finishes every PNG on this host thread -
+// PNG_DEVICE_DEFAULT below, and DESIGN section 1 (f) for why.  force_device: as =1 whatever the environment says
+// (decode_tool --device / --stage).  Without libz.so.1 the libpng path above is what is left - with its differences for
+// translucent, 16-bit and gamma-tagged files.
+constexpr bool PNG_DEVICE_DEFAULT = false;
+inline bool png_device_enabled() {
+  static const char* env = getenv("OCR_DEVICE_PNG");
+  return env && env[0] ? env[0] != '0' : PNG_DEVICE_DEFAULT;
+}
+inline bool decode_png(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false) {
+  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+  if (d.size() < 8 || memcmp(d.data(), sig, 8)) return false;
+  if (!png::available()) return decode_png_libpng(d, im);
+  auto f = std::make_shared<png::Frame>();
+  if (!png::parse(d.data(), d.size(), *f)) { im = Image(); return false; }
+  im.pixels.clear();
+  im.rows = f->height; im.cols = f->width;
+  if (device_pixels && f->device_ok && (force_device || png_device_enabled())) { im.png = std::move(f); return true; }
+  if (!png::pixels(*f, im.pixels)) { im = Image(); return false; }
+  return true;
+}
 // device_pixels: stop after the entropy decoding and leave the pixel half to the GPU worker (OCR_DEVICE_JPEG=0 or
 // device_pixels = false: everything on this host thread)
 inline bool decode_jpeg(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false) {
@@ -275,8 +301,8 @@ inline bool decode_jpeg(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!dec.decode(d.data(), d.size(), im.pixels, im.rows, im.cols)) { im = Image(); return false; }
   return true;
 }
-inline bool decode_image(const std::vector<uint8_t>& bytes, Image& im, bool device_pixels = false) {
-  return decode_png(bytes, im) || decode_jpeg(bytes, im, device_pixels) || decode_ppm(bytes, im) || decode_bmp(bytes, im);
+inline bool decode_image(const std::vector<uint8_t>& bytes, Image& im, bool device_pixels = false, bool force_device_png = false) {
+  return decode_png(bytes, im, device_pixels, force_device_png) || decode_jpeg(bytes, im, device_pixels) || decode_ppm(bytes, im) || decode_bmp(bytes, im);
 }
 inline bool read_file(const std::string& path, std::vector<uint8_t>& out) {
   std::ifstream f(path, std::ios::binary);

@@ -29,6 +29,7 @@
 
 #include "../../include/ocr_hip.h"
 #include "jpeg_decode.h"
+#include "png_decode.h"
 
 namespace PaddleOCR {
 
@@ -50,6 +51,8 @@ struct Image {
   // stays empty unless someone asks for them (materialise()).  rows / cols are the size after the EXIF orientation, the
   // frame of the reply's width, height and boxes (cv::imdecode turns the image); jpeg->rows / cols stay the stored size
   std::shared_ptr<jpeg::Coefs> jpeg;
+  // a PNG that has only been parsed and inflated: the worker unfilters and converts it on the device (ocr_pipe_stage_coded)
+  std::shared_ptr<png::Frame> png;
   Image() = default;
   explicit Image(const ImageView& v) : rows(v.rows), cols(v.cols) {
     if (!v.empty()) {
@@ -58,12 +61,28 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg; }
-  bool device_decodable() const { return pixels.empty() && jpeg; }
-  void materialise() {  // the pixel half of the JPEG on the host
+  bool empty() const { return pixels.empty() && !jpeg && !png; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png); }
+  void materialise() {  // the pixel half of the JPEG / PNG on the host
     if (!device_decodable()) return;
+    if (png) {
+      if (!png::pixels(*png, pixels)) throw std::runtime_error("PNG reconstruction failed");
+      png.reset();
+      return;
+    }
     if (!jpeg::Decoder::pixels(*jpeg, pixels, rows, cols)) throw std::runtime_error("JPEG reconstruction failed");
     jpeg.reset();
+  }
+  void materialize() { materialise(); }
+  ocr_png_frame png_frame() const {  // only when png
+    static_assert(sizeof(png::Segment) == sizeof(ocr_png_segment), "png::Segment is ocr_png_segment");
+    ocr_png_frame d;
+    memset(&d, 0, sizeof d);
+    d.width = png->width; d.height = png->height; d.bit_depth = png->bit_depth; d.color_type = png->color_type; d.interlace = png->interlace;
+    memcpy(d.palette, png->palette, sizeof d.palette);
+    d.data = png->data.data(); d.data_len = png->data.size();
+    d.segments = reinterpret_cast<const ocr_png_segment*>(png->segments.data()); d.nsegments = (int)png->segments.size();
+    return d;
   }
   // ocr_jpeg_img holds grey and YCbCr 4:4:4 / 4:2:2 / 4:2:0; every other file (another sampling, RGB, CMYK, YCCK) needs
   // the general descriptor, jpeg_frame(), which can say what the first says too
@@ -478,7 +497,12 @@ class OCRWorker {
       ocr_img im = request.image_data.view().c();
       rc = ocr_pipe_run_chars(pipe_, &im, 1, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), chars.data(), nullptr);
     } else
-    if (request.image_data.device_decodable()) {  // JPEG: pixels are produced on the device, straight into the staging slot
+    if (request.image_data.device_decodable()) {  // JPEG, PNG: pixels are produced on the device, straight into the staging slot
+      if (request.image_data.png) {
+        const ocr_png_frame pf = request.image_data.png_frame();
+        const ocr_png_frame* pp = &pf;
+        rc = ocr_pipe_stage_coded(pipe_, 0, nullptr, &pp, 1);
+      } else
       if (request.image_data.needs_frame()) {
         const ocr_jpeg_frame jf = request.image_data.jpeg_frame();
         rc = ocr_pipe_stage_jpeg_frames(pipe_, 0, &jf, 1);
@@ -519,19 +543,29 @@ class OCRWorker {
     std::vector<ocr_jpeg_img> jimgs;
     std::vector<ocr_jpeg_frame> jframes;
     std::vector<size_t> owner;
-    // a batch of JPEGs only is decoded on the device; a mixed batch takes the host path for its JPEGs.  One file that
-    // only the general descriptor can hold (CMYK, 4:4:0, ...) puts the whole batch on that descriptor, not on the host.
-    bool all_jpeg = !char_boxes_, frames = false;
+    // a batch of JPEGs only is decoded on the device; a batch with other host pixels in it takes the host path for its
+    // JPEGs and PNGs.  One file that only the general descriptor can hold (CMYK, 4:4:0, ...) puts the whole batch on that
+    // descriptor, not on the host; one PNG puts it on ocr_pipe_stage_coded, which takes both.
+    bool all_jpeg = !char_boxes_, frames = false, coded = false;
     for (size_t i = 0; i < requests.size(); ++i) {
       if (!requests[i]->image_data.empty() && !requests[i]->image_data.device_decodable()) all_jpeg = false;
       if (requests[i]->image_data.needs_frame()) frames = true;
+      if (requests[i]->image_data.png) coded = true;
     }
+    std::vector<ocr_png_frame> pframes;
+    std::vector<char> is_png;
     for (size_t i = 0; i < requests.size(); ++i) {
       results[i].request_id = requests[i]->request_id;
       if (requests[i]->image_data.empty()) { results[i].error_message = "Empty image data provided"; continue; }
       results[i].width = requests[i]->image_data.cols;
       results[i].height = requests[i]->image_data.rows;
-      if (all_jpeg && frames) jframes.push_back(requests[i]->image_data.jpeg_frame());
+      if (all_jpeg && coded) {
+        const bool p = (bool)requests[i]->image_data.png;
+        is_png.push_back(p);
+        if (p) pframes.push_back(requests[i]->image_data.png_frame());
+        else jframes.push_back(requests[i]->image_data.jpeg_frame());
+      }
+      else if (all_jpeg && frames) jframes.push_back(requests[i]->image_data.jpeg_frame());
       else if (all_jpeg) jimgs.push_back(requests[i]->image_data.jpeg_desc());
       else {
         const_cast<OCRRequest*>(requests[i])->image_data.materialise();
@@ -553,6 +587,15 @@ class OCRWorker {
       rc = ocr_pipe_run_chars(pipe_, imgs.data(), k, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, batch_chars_.data(), nullptr);
     } else
     if (all_jpeg) {
+      if (coded) {
+        std::vector<const ocr_jpeg_frame*> jp((size_t)k, nullptr);
+        std::vector<const ocr_png_frame*> pp((size_t)k, nullptr);
+        for (int j = 0, nj = 0, np = 0; j < k; ++j) {
+          if (is_png[j]) pp[j] = &pframes[np++];
+          else jp[j] = &jframes[nj++];
+        }
+        rc = ocr_pipe_stage_coded(pipe_, 0, jp.data(), pp.data(), k);
+      } else
       rc = frames ? ocr_pipe_stage_jpeg_frames(pipe_, 0, jframes.data(), k) : ocr_pipe_stage_jpeg(pipe_, 0, jimgs.data(), k);
       if (rc == OCR_OK) rc = ocr_pipe_run_staged(pipe_, 0, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, nullptr);
     } else {

@@ -315,6 +315,40 @@ int ocr_pipe_stage_jpeg_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* fram
 int ocr_pipe_slot_image(ocr_pipe* h, int slot, int index, uint8_t* bgr, size_t cap_bytes, int* rows, int* cols);
 int ocr_jpeg_decode_frame(const ocr_jpeg_frame* frame, int device_id, uint8_t* bgr, size_t cap_bytes);
 int ocr_jpeg_time_frame(const ocr_jpeg_frame* frame, int device_id, int iters, double ms[2]);
+/* PNG inputs with the pixel half of the decoder on the device, the counterpart of the JPEG descriptors: the caller
+ * parses the container and inflates the IDAT stream (host/png_decode.h, png::parse); unfiltering, conversion and Adam7
+ * placement run on the copy stream straight into the slot.  The pixels are cv::imdecode(IMREAD_COLOR)'s: a 16-bit
+ * sample keeps its high byte, alpha is dropped (nothing is composited), depths 1 / 2 / 4 are expanded by bit
+ * replication, palette indices go through `palette`, grey fills three channels, no gamma.  Every field is checked on the
+ * host before anything is launched (OCR_ERR_ARG, ocr_last_error says which rule). */
+typedef struct ocr_png_segment {
+  int32_t pass;      /* 0 when not interlaced, else the Adam7 pass 0..6 */
+  int32_t first_row; /* row of that pass */
+  int32_t rows;      /* >= 1 */
+} ocr_png_segment;
+typedef struct ocr_png_frame {
+  int width, height;     /* IHDR; width * height <= 64 Mpixel */
+  int bit_depth;         /* 1, 2, 4, 8, 16 as the colour type allows */
+  int color_type;        /* 0, 2, 3, 4, 6 */
+  int interlace;         /* 0, or 1 = Adam7 */
+  int reserved;          /* 0 */
+  uint8_t palette[768];  /* R, G, B x 256; zero beyond PLTE */
+  const uint8_t* data;   /* host: the inflated stream - per non-empty pass, per row, a filter byte (0..4) and the filtered bytes */
+  size_t data_len;       /* exactly what IHDR implies: sum over passes of rows * (1 + rowbytes) */
+  /* Maximal runs of rows that never look at a row outside the run, in stream order: a run starts at the first row of a
+   * (non-empty) pass or at a row whose filter is None (0) or Sub (1); together they cover every row once. */
+  const ocr_png_segment* segments;
+  int nsegments;         /* at most 65536, and no pass with more than 16384 rows: beyond that the decode belongs on the host */
+} ocr_png_frame;
+int ocr_png_decode(const ocr_png_frame* frame, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time): after one untimed decode, `iters` repetitions between HIP events of ms[0] = the
+ * upload of the inflated stream from pinned memory, ms[1] = the pixel-stage kernel (means per repetition).
+ * ocr_png_time_batch: the same for `count` frames as ONE batch (one upload, one launch per bpp kind), per batch. */
+int ocr_png_time(const ocr_png_frame* frame, int device_id, int iters, double ms[2]);
+int ocr_png_time_batch(const ocr_png_frame* const* frames, int count, int device_id, int iters, double ms[2]);
+/* ocr_pipe_stage_jpeg_frames for a batch that mixes JPEG and PNG requests: image i is jpegs[i] or pngs[i], exactly one of
+ * the two non-null (either array may be NULL when no image of the batch uses it). */
+int ocr_pipe_stage_coded(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
 /* network input size the detector uses for a rows x cols image (ResizeImgType0) */
 int ocr_pipe_det_shape(ocr_pipe* h, int rows, int cols, int* net_rows, int* net_cols);

@@ -89,7 +89,7 @@ def run(max_batch, clients, per_client, img_path, fmt, workers=1, extra_env=None
 def jpeg_mode(clients, per):
     """960x960 JPEG requests (a configs[1] card, quality 90, 4:2:0) against a service with two GPU workers on the one
     device: OCR_DEVICE_JPEG=1 (entropy decoding on the client's service thread, dequantisation / IDCT / upsampling /
-    colour on the GPU, straight into the staging slot) against =0 (the whole decode on the host), with the service
+    colour on the GPU, straight into the staging slot) against =0 (the default: the whole decode on the host), with the service
     process's busy host cores beside it.  One JSON line per mode."""
     from PIL import Image
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -130,6 +130,27 @@ def jpeg_mode(clients, per):
     print(json.dumps({"mode": "pipeline_host_input_same_image", "images_per_s": round(64 * steps / dt, 1), "words_per_image": len(w[0]),
                       "what": "ocr_pipe_stage + ocr_pipe_run_staged, 64 copies of the decoded image per batch, double-buffered"}), flush=True)
     pipe.close()
+
+
+def png_mode(clients, per):
+    """960x960 PNG requests (the configs[1] card of jpeg_mode as RGB and as RGBA, written by Pillow: adaptive filters) against
+    a service with two GPU workers: OCR_DEVICE_PNG=1 (opt-in: container + inflate on the client's service thread, unfiltering and
+    conversion on the GPU, straight into the staging slot) against =0 (the whole decode on the host), with the service
+    process's busy host cores beside it.  OCR_LOAD_HOST_DIR names another build's host directory (its ocr_service): how
+    the libpng path of the commit before this decoder was measured on the same files."""
+    from PIL import Image
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from synth_data import cfg2_sample
+    global HOST
+    HOST = os.environ.get("OCR_LOAD_HOST_DIR", HOST)
+    img = cfg2_sample(0, 960, 960, 32)[0]
+    op = {"OCR_WORKER_DET_LIMIT": "960", "OCR_WORKER_REC_H": "48", "OCR_WORKER_REC_W": "320", "OCR_WORKER_CLS": "1"}
+    for name, arr in (("rgb", img[:, :, ::-1]), ("rgba", np.dstack([img[:, :, ::-1], np.full(img.shape[:2], 255, np.uint8)]))):
+        path = f"/tmp/ocr_load_{os.getpid()}_{name}.png"
+        Image.fromarray(np.ascontiguousarray(arr)).save(path)
+        fmt = "png %s 960x960 (%d KB)" % (name, os.path.getsize(path) // 1024)
+        for dev in ("1", "0"):
+            run(16, clients, per, path, fmt, workers=2, extra_env=dict(op, OCR_DEVICE_PNG=dev), tag="device_png" if dev == "1" else "host_png")
 
 
 def sweep_mode(per):
@@ -177,6 +198,13 @@ if __name__ == "__main__":
         import synth_weights
         synth_weights.ensure(ROOT)
         jpeg_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "png":
+        if "OCR_LOAD_HOST_DIR" not in os.environ:
+            subprocess.check_call(["make", "-s", "-C", HOST])
+        import synth_weights
+        synth_weights.ensure(ROOT)
+        png_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
         sys.exit(0)
     clients = int(sys.argv[1]) if len(sys.argv) > 1 else 32
     per = int(sys.argv[2]) if len(sys.argv) > 2 else 8
