@@ -574,6 +574,7 @@ EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_
             "ocr_pipe_stage", "ocr_pipe_slot_probs", "ocr_pipe_run_staged", "ocr_pipe_run_device_on", "ocr_pipe_run_staged_on", "ocr_pipe_stage_jpeg", "ocr_jpeg_decode", "ocr_jpeg_time",
             "ocr_pipe_stage_jpeg_frames", "ocr_jpeg_decode_frame", "ocr_jpeg_time_frame", "ocr_pipe_slot_image",
             "ocr_png_decode", "ocr_png_time", "ocr_png_time_batch", "ocr_pipe_stage_coded",
+            "ocr_raw_decode", "ocr_raw_time", "ocr_raw_time_batch", "ocr_pipe_stage_frames",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
@@ -648,6 +649,42 @@ class PngFrame:
         L.ocr_png_decode.argtypes = [C.POINTER(ocr_png_frame), C.c_int, C.c_void_p, C.c_size_t]
         out = np.zeros((max(1, self.c.height), max(1, self.c.width), 3), np.uint8)
         rc = L.ocr_png_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
+            err.code = rc
+            raise err
+        return out
+
+
+class ocr_raw_frame(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("kind", C.c_int), ("bottom_up", C.c_int), ("row_stride", C.c_size_t),
+                ("palette", C.c_uint8 * 1024), ("data", C.c_void_p), ("data_len", C.c_size_t)]
+
+
+RAW_KINDS = ["INDEX1", "INDEX4", "INDEX8", "BGR555", "BGR565", "BGR24", "BGRX32", "RGB24", "GREY8", "GREY16BE", "RGB48BE", "BIT1_INV"]
+
+
+class RawFrame:
+    """an ocr_raw_frame over Python-owned memory.  kind: index into RAW_KINDS; rows: the stored rows (bytes or uint8 array,
+    row_stride apart); palette: (n, 4) B,G,R,x or None.  Fields of .c may be changed before a call (the tests' tampering)."""
+
+    def __init__(self, width, height, kind, bottom_up, row_stride, rows, palette=None):
+        self._data = np.frombuffer(bytes(rows), np.uint8).copy() if not isinstance(rows, np.ndarray) else np.ascontiguousarray(rows, np.uint8).reshape(-1).copy()
+        c = ocr_raw_frame()
+        c.width, c.height, c.kind, c.bottom_up, c.row_stride = width, height, kind, bottom_up, row_stride
+        if palette is not None:
+            flat = np.ascontiguousarray(palette, np.uint8).reshape(-1)
+            C.memmove(c.palette, flat.ctypes.data, min(1024, len(flat)))
+        c.data, c.data_len = self._data.ctypes.data, len(self._data)
+        self.c = c
+
+    def decode(self, device_id=0):
+        """ocr_raw_decode: the (height, width, 3) BGR image; OcrError where the call refuses"""
+        L = lib()
+        L.ocr_raw_decode.argtypes = [C.POINTER(ocr_raw_frame), C.c_int, C.c_void_p, C.c_size_t]
+        h, w = self.c.height, self.c.width
+        out = np.zeros((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), np.uint8)
+        rc = L.ocr_raw_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
         if rc != 0:
             err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
             err.code = rc

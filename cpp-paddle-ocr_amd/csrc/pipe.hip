@@ -13,6 +13,7 @@
 #include "crop.h"
 #include "jpeg_stage.h"
 #include "png_stage.h"
+#include "raw_stage.h"
 #include "stages.h"
 
 using namespace ocr;
@@ -431,6 +432,7 @@ struct ocr_pipe {
   hipStream_t copy_stream = nullptr;
   JpegScratch jpeg;
   PngScratch png;
+  RawScratch raw;
   DevBuf<uint8_t> work;  // the requests' clones (OCRRequest copies the Mat, ocr_worker.h:28-29): cls rotates in place on them
   // Two batches in flight (round 5, ocr_pipe_run_device_on / ocr_pipe_run_staged_on): a call that names a chain runs its WHOLE
   // batch on that chain's worker, with a clone buffer of the chain's own; calls on different chains may run concurrently from
@@ -536,27 +538,34 @@ struct ocr_pipe {
     return OCR_OK;
   }
 
-  // ---- stage a batch that mixes JPEG coefficients and inflated PNG streams: both pixel stages run on the copy stream, into
-  // the slot.  Image i is jpegs[i] or pngs[i] (validated by the caller: exactly one of them, and a sound descriptor)
-  int stage_coded(int si, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, int count, std::string& err) {
+  // ---- stage a batch that mixes JPEG coefficients, inflated PNG streams and stored BMP / PNM rows: the three pixel stages run on
+  // the copy stream, into the slot.  Image i is jpegs[i], pngs[i] or raws[i] (validated by the caller: exactly one of them, and a
+  // sound descriptor)
+  int stage_coded(int si, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, const ocr_raw_frame* const* raws, int count,
+                  std::string& err) {
     StageSlot& S = slots[si];
     auto jp = [&](int i) { return jpegs ? jpegs[i] : nullptr; };
+    auto pn = [&](int i) { return pngs ? pngs[i] : nullptr; };
     int rc = layout(S, count, [&](int i, int& r, int& c) {
       if (const ocr_jpeg_frame* j = jp(i)) { r = jpeg_out_rows(*j); c = jpeg_out_cols(*j); }
-      else { r = pngs[i]->height; c = pngs[i]->width; }
+      else if (const ocr_png_frame* p = pn(i)) { r = p->height; c = p->width; }
+      else { r = raws[i]->height; c = raws[i]->width; }
     }, err);
     if (rc) return rc;
     std::vector<ocr_jpeg_frame> jf;
     std::vector<const ocr_png_frame*> pf;
-    std::vector<uint8_t*> jdst, pdst;
+    std::vector<const ocr_raw_frame*> rf;
+    std::vector<uint8_t*> jdst, pdst, rdst;
     for (int k = 0; k < count; ++k) {
       const int i = S.imgs[k].orig;
       uint8_t* d = S.dev.p + S.imgs[k].off;
       if (const ocr_jpeg_frame* j = jp(i)) { jf.push_back(*j); jdst.push_back(d); }
-      else { pf.push_back(pngs[i]); pdst.push_back(d); }
+      else if (const ocr_png_frame* p = pn(i)) { pf.push_back(p); pdst.push_back(d); }
+      else { rf.push_back(raws[i]); rdst.push_back(d); }
     }
     if (!jf.empty()) rc = jpeg_decode_async(jf.data(), (int)jf.size(), jdst.data(), jpeg, copy_stream, err);
     if (!rc && !pf.empty()) rc = png_decode_async(pf.data(), (int)pf.size(), pdst.data(), png, copy_stream, err);
+    if (!rc && !rf.empty()) rc = raw_decode_async(rf.data(), (int)rf.size(), rdst.data(), raw, copy_stream, err);
     if (rc) return rc;
     if (hipEventRecord(S.ready, copy_stream) != hipSuccess) { err = "hipEventRecord failed"; return OCR_ERR_DEVICE; }
     S.staged = true;
@@ -859,18 +868,26 @@ int ocr_pipe_stage_jpeg_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* fram
   return rc ? fail(rc, err) : OCR_OK;
 }
 
-int ocr_pipe_stage_coded(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, int count) {
-  if (!h || (!jpegs && !pngs) || count < 1 || slot < 0 || slot > 1) return fail(OCR_ERR_ARG, "bad argument");
+int ocr_pipe_stage_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs,
+                          const ocr_raw_frame* const* raws, int count) {
+  if (!h || (!jpegs && !pngs && !raws) || count < 1 || slot < 0 || slot > 1) return fail(OCR_ERR_ARG, "bad argument");
   for (int i = 0; i < count; ++i) {
     const ocr_jpeg_frame* j = jpegs ? jpegs[i] : nullptr;
     const ocr_png_frame* p = pngs ? pngs[i] : nullptr;
-    if ((j != nullptr) == (p != nullptr)) return fail(OCR_ERR_ARG, "every image is a JPEG frame or a PNG frame, not both and not neither");
-    if (const char* fault = j ? jpeg_frame_fault(*j) : png_frame_fault(*p)) return fail(OCR_ERR_ARG, fault);
+    const ocr_raw_frame* r = raws ? raws[i] : nullptr;
+    if ((j != nullptr) + (p != nullptr) + (r != nullptr) != 1)
+      return fail(OCR_ERR_ARG, raws ? "every image is a JPEG frame, a PNG frame or a raw frame: exactly one of the three"
+                                    : "every image is a JPEG frame or a PNG frame, not both and not neither");
+    if (const char* fault = j ? jpeg_frame_fault(*j) : p ? png_frame_fault(*p) : raw_frame_fault(*r)) return fail(OCR_ERR_ARG, fault);
   }
   CAPI_HIP(rt_set_device(h->device));
   std::string err;
-  const int rc = h->stage_coded(slot, jpegs, pngs, count, err);
+  const int rc = h->stage_coded(slot, jpegs, pngs, raws, count, err);
   return rc ? fail(rc, err) : OCR_OK;
+}
+
+int ocr_pipe_stage_coded(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, int count) {
+  return ocr_pipe_stage_frames(h, slot, jpegs, pngs, nullptr, count);
 }
 
 int ocr_pipe_slot_image(ocr_pipe* h, int slot, int index, uint8_t* bgr, size_t cap, int* rows, int* cols) {

@@ -3,7 +3,8 @@
 // over a Unix-domain stream socket; a message (the pipe's PIPE_TYPE_MESSAGE unit) is framed as a 4-byte
 // little-endian length followed by that many bytes of JSON, in both directions.
 //
-//   {"command":"recognize","image_path":"..."}            image file: PNG, JPEG, binary PPM (P6), BMP
+//   {"command":"recognize","image_path":"..."}            image file: PNG, JPEG, PNM (P1 .. P6, maxval up to 65535), BMP (1 / 4 /
+//                                                         8-bit paletted, RLE8 / RLE4, 16-bit 5-5-5 / 5-6-5, 24, 32 bits)
 //   {"command":"recognize","image_data":"<base64>"}       the same file contents, base64
 //   {"command":"status"}    -> {"success":true,"status":"{\"running\":..,\"total_requests\":..,...}"}
 //   {"command":"shutdown"}  -> {"success":true,"message":"Shutdown command received, stopping service..."}
@@ -14,8 +15,8 @@
 // Differences, by necessity: the transport (socket path instead of \\.\pipe\ocr_service); replies are compact
 // JSON (jsoncpp's default writer indents); cv::imread/imdecode are replaced by the decoders below - PNG with the decoder
 // of png_decode.h (own container parser, zlib's inflate through dlopen, cv::imdecode's conversions; the system's libpng16
-// simplified API, also through dlopen, only where libz.so.1 is missing), PPM
-// and BMP natively, JPEG with the decoder of jpeg_decode.h (a restatement of libjpeg's default pipeline,
+// simplified API, also through dlopen, only where libz.so.1 is missing), PNM
+// and BMP with the decoder of raw_decode.h (every form cv::imdecode reads), JPEG with the decoder of jpeg_decode.h (a restatement of libjpeg's default pipeline,
 // sequential and progressive, grey / YCbCr / RGB / CMYK / YCCK at every integral sampling, checked bit for bit against
 // libjpeg-turbo through PIL).
 // There is no CPU worker pool: cpu_workers is accepted and ignored, gpu_workers = 0 leaves `recognize`
@@ -42,6 +43,7 @@
 #include "jpeg_decode.h"
 #include "paddle_ocr_hip.h"
 #include "png_decode.h"
+#include "raw_decode.h"
 
 namespace PaddleOCR {
 namespace ipc {
@@ -184,49 +186,31 @@ inline bool base64_decode(const std::string& in, std::vector<uint8_t>& out) {
 // Every decoder refuses headers that would make the service allocate gigabytes from a sub-megabyte request
 // (the same 64 Mpixel cap as jpeg_decode.h).
 constexpr long kMaxDecodedPixels = 64L << 20;
-inline bool decode_ppm(const std::vector<uint8_t>& d, Image& im) {
-  if (d.size() < 11 || d[0] != 'P' || d[1] != '6') return false;
-  size_t i = 2;
-  long v[3];
-  for (int k = 0; k < 3; ++k) {
-    for (;;) {  // whitespace and comments
-      while (i < d.size() && (d[i] == ' ' || d[i] == '\n' || d[i] == '\r' || d[i] == '\t')) ++i;
-      if (i < d.size() && d[i] == '#') { while (i < d.size() && d[i] != '\n') ++i; continue; }
-      break;
-    }
-    if (i >= d.size() || d[i] < '0' || d[i] > '9') return false;
-    long x = 0;
-    while (i < d.size() && d[i] >= '0' && d[i] <= '9') { x = x * 10 + (d[i] - '0'); if (x > 1000000) return false; ++i; }
-    v[k] = x;
-  }
-  ++i;  // the single whitespace after maxval
-  const long w = v[0], h = v[1];
-  if (w <= 0 || h <= 0 || w * h > kMaxDecodedPixels || v[2] != 255 || d.size() < i + (size_t)w * h * 3) return false;
-  im.rows = (int)h; im.cols = (int)w;
-  im.pixels.resize((size_t)w * h * 3);
-  for (size_t p = 0; p < (size_t)w * h; ++p) {  // RGB -> BGR
-    im.pixels[3 * p] = d[i + 3 * p + 2]; im.pixels[3 * p + 1] = d[i + 3 * p + 1]; im.pixels[3 * p + 2] = d[i + 3 * p];
-  }
+// BMP (1 / 4 / 8-bit paletted, RLE8 / RLE4, 16-bit 5-5-5 / 5-6-5, 24, 32; OS/2 and V3 .. V5 headers) and PNM (P1 .. P6,
+// maxval up to 65535) as cv::imdecode(IMREAD_COLOR) returns them: raw_decode.h.  device_pixels: the caller has a GPU worker
+// that can finish the image.  Whether it is asked to is OCR_DEVICE_RAW, read once: =1 stops after the container (and the
+// run-length / ASCII expansion) and leaves the per-pixel conversion to the worker, =0 or unset finishes every file on this
+// host thread - RAW_DEVICE_DEFAULT below, and DESIGN section 1 (f) for why.  force_device: as =1 whatever the environment
+// says (decode_tool --device / --stage).
+constexpr bool RAW_DEVICE_DEFAULT = false;
+inline bool raw_device_enabled() {
+  static const char* env = getenv("OCR_DEVICE_RAW");
+  return env && env[0] ? env[0] != '0' : RAW_DEVICE_DEFAULT;
+}
+inline bool decode_raw(const std::vector<uint8_t>& d, Image& im, bool device_pixels, bool force_device) {
+  auto f = std::make_shared<raw::Frame>();
+  if (!raw::parse(d.data(), d.size(), *f)) return false;
+  im.pixels.clear();
+  im.rows = f->height; im.cols = f->width;
+  if (device_pixels && (force_device || raw_device_enabled())) { im.raw = std::move(f); return true; }
+  if (!raw::pixels(*f, im.pixels)) { im = Image(); return false; }
   return true;
 }
-inline bool decode_bmp(const std::vector<uint8_t>& d, Image& im) {
-  if (d.size() < 54 || d[0] != 'B' || d[1] != 'M') return false;
-  auto u32 = [&](size_t o) { return (uint32_t)d[o] | ((uint32_t)d[o + 1] << 8) | ((uint32_t)d[o + 2] << 16) | ((uint32_t)d[o + 3] << 24); };
-  const uint32_t off = u32(10), hdr = u32(14);
-  const int32_t w = (int32_t)u32(18), hs = (int32_t)u32(22);
-  const unsigned bpp = d[28] | (d[29] << 8), comp = u32(30);
-  if (hdr < 40 || w <= 0 || hs == 0 || (bpp != 24 && bpp != 32) || (comp != 0 && !(bpp == 32 && comp == 3))) return false;
-  const int h = hs < 0 ? -hs : hs;
-  if (hs == INT32_MIN || (long)w * h > kMaxDecodedPixels) return false;
-  const size_t stride = ((size_t)w * (bpp / 8) + 3) & ~(size_t)3;
-  if (d.size() < off + stride * h) return false;
-  im.rows = h; im.cols = w;
-  im.pixels.resize((size_t)w * h * 3);
-  for (int y = 0; y < h; ++y) {
-    const uint8_t* src = d.data() + off + stride * (hs < 0 ? y : h - 1 - y);  // bottom-up unless the height is negative
-    for (int x = 0; x < w; ++x) memcpy(&im.pixels[((size_t)y * w + x) * 3], src + (size_t)x * (bpp / 8), 3);  // BMP is BGR(A)
-  }
-  return true;
+inline bool decode_ppm(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false) {
+  return d.size() >= 2 && d[0] == 'P' && decode_raw(d, im, device_pixels, force_device);
+}
+inline bool decode_bmp(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false) {
+  return d.size() >= 2 && d[0] == 'B' && d[1] == 'M' && decode_raw(d, im, device_pixels, force_device);
 }
 // libpng16 simplified API (png.h: png_image, PNG_IMAGE_VERSION 1, PNG_FORMAT_BGR = 0x12), resolved at run time
 struct PngImage {
@@ -301,8 +285,10 @@ inline bool decode_jpeg(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!dec.decode(d.data(), d.size(), im.pixels, im.rows, im.cols)) { im = Image(); return false; }
   return true;
 }
-inline bool decode_image(const std::vector<uint8_t>& bytes, Image& im, bool device_pixels = false, bool force_device_png = false) {
-  return decode_png(bytes, im, device_pixels, force_device_png) || decode_jpeg(bytes, im, device_pixels) || decode_ppm(bytes, im) || decode_bmp(bytes, im);
+// force_device: PNG and BMP / PNM take the device route whatever OCR_DEVICE_PNG / OCR_DEVICE_RAW say (decode_tool)
+inline bool decode_image(const std::vector<uint8_t>& bytes, Image& im, bool device_pixels = false, bool force_device = false) {
+  return decode_png(bytes, im, device_pixels, force_device) || decode_jpeg(bytes, im, device_pixels) ||
+         decode_ppm(bytes, im, device_pixels, force_device) || decode_bmp(bytes, im, device_pixels, force_device);
 }
 inline bool read_file(const std::string& path, std::vector<uint8_t>& out) {
   std::ifstream f(path, std::ios::binary);

@@ -30,6 +30,7 @@
 #include "../../include/ocr_hip.h"
 #include "jpeg_decode.h"
 #include "png_decode.h"
+#include "raw_decode.h"
 
 namespace PaddleOCR {
 
@@ -53,6 +54,9 @@ struct Image {
   std::shared_ptr<jpeg::Coefs> jpeg;
   // a PNG that has only been parsed and inflated: the worker unfilters and converts it on the device (ocr_pipe_stage_coded)
   std::shared_ptr<png::Frame> png;
+  // a BMP / PNM whose container has been parsed (and run-length stream or ASCII numbers expanded): the worker converts the
+  // stored rows on the device (ocr_pipe_stage_frames)
+  std::shared_ptr<raw::Frame> raw;
   Image() = default;
   explicit Image(const ImageView& v) : rows(v.rows), cols(v.cols) {
     if (!v.empty()) {
@@ -61,10 +65,15 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg && !png; }
-  bool device_decodable() const { return pixels.empty() && (jpeg || png); }
-  void materialise() {  // the pixel half of the JPEG / PNG on the host
+  bool empty() const { return pixels.empty() && !jpeg && !png && !raw; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw); }
+  void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM on the host
     if (!device_decodable()) return;
+    if (raw) {
+      if (!raw::pixels(*raw, pixels)) throw std::runtime_error("BMP / PNM conversion failed");
+      raw.reset();
+      return;
+    }
     if (png) {
       if (!png::pixels(*png, pixels)) throw std::runtime_error("PNG reconstruction failed");
       png.reset();
@@ -82,6 +91,15 @@ struct Image {
     memcpy(d.palette, png->palette, sizeof d.palette);
     d.data = png->data.data(); d.data_len = png->data.size();
     d.segments = reinterpret_cast<const ocr_png_segment*>(png->segments.data()); d.nsegments = (int)png->segments.size();
+    return d;
+  }
+  ocr_raw_frame raw_frame() const {  // only when raw
+    static_assert((int)raw::kKinds == (int)OCR_RAW_BIT1_INV + 1 && (int)raw::RGB48BE == (int)OCR_RAW_RGB48BE, "raw::Kind is ocr_raw_kind");
+    ocr_raw_frame d;
+    memset(&d, 0, sizeof d);
+    d.width = raw->width; d.height = raw->height; d.kind = raw->kind; d.bottom_up = raw->bottom_up; d.row_stride = raw->row_stride;
+    memcpy(d.palette, raw->palette, sizeof d.palette);
+    d.data = raw->data.data(); d.data_len = raw->data.size();
     return d;
   }
   // ocr_jpeg_img holds grey and YCbCr 4:4:4 / 4:2:2 / 4:2:0; every other file (another sampling, RGB, CMYK, YCCK) needs
@@ -497,7 +515,12 @@ class OCRWorker {
       ocr_img im = request.image_data.view().c();
       rc = ocr_pipe_run_chars(pipe_, &im, 1, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), chars.data(), nullptr);
     } else
-    if (request.image_data.device_decodable()) {  // JPEG, PNG: pixels are produced on the device, straight into the staging slot
+    if (request.image_data.device_decodable()) {  // JPEG, PNG, BMP / PNM: pixels are produced on the device, straight into the staging slot
+      if (request.image_data.raw) {
+        const ocr_raw_frame rf = request.image_data.raw_frame();
+        const ocr_raw_frame* rp = &rf;
+        rc = ocr_pipe_stage_frames(pipe_, 0, nullptr, nullptr, &rp, 1);
+      } else
       if (request.image_data.png) {
         const ocr_png_frame pf = request.image_data.png_frame();
         const ocr_png_frame* pp = &pf;
@@ -545,24 +568,29 @@ class OCRWorker {
     std::vector<size_t> owner;
     // a batch of JPEGs only is decoded on the device; a batch with other host pixels in it takes the host path for its
     // JPEGs and PNGs.  One file that only the general descriptor can hold (CMYK, 4:4:0, ...) puts the whole batch on that
-    // descriptor, not on the host; one PNG puts it on ocr_pipe_stage_coded, which takes both.
-    bool all_jpeg = !char_boxes_, frames = false, coded = false;
+    // descriptor, not on the host; one PNG puts it on ocr_pipe_stage_coded, which takes both; one raw BMP / PNM frame (there
+    // are none unless OCR_DEVICE_RAW=1: the IPC layer finishes those files on the host) on ocr_pipe_stage_frames, which takes
+    // all three.
+    bool all_jpeg = !char_boxes_, frames = false, coded = false, with_raw = false;
     for (size_t i = 0; i < requests.size(); ++i) {
       if (!requests[i]->image_data.empty() && !requests[i]->image_data.device_decodable()) all_jpeg = false;
       if (requests[i]->image_data.needs_frame()) frames = true;
       if (requests[i]->image_data.png) coded = true;
+      if (requests[i]->image_data.raw) coded = with_raw = true;
     }
     std::vector<ocr_png_frame> pframes;
-    std::vector<char> is_png;
+    std::vector<ocr_raw_frame> rframes;
+    std::vector<char> is_png;  // 0 JPEG, 1 PNG, 2 raw
     for (size_t i = 0; i < requests.size(); ++i) {
       results[i].request_id = requests[i]->request_id;
       if (requests[i]->image_data.empty()) { results[i].error_message = "Empty image data provided"; continue; }
       results[i].width = requests[i]->image_data.cols;
       results[i].height = requests[i]->image_data.rows;
       if (all_jpeg && coded) {
-        const bool p = (bool)requests[i]->image_data.png;
-        is_png.push_back(p);
-        if (p) pframes.push_back(requests[i]->image_data.png_frame());
+        const int p = requests[i]->image_data.raw ? 2 : requests[i]->image_data.png ? 1 : 0;
+        is_png.push_back((char)p);
+        if (p == 2) rframes.push_back(requests[i]->image_data.raw_frame());
+        else if (p == 1) pframes.push_back(requests[i]->image_data.png_frame());
         else jframes.push_back(requests[i]->image_data.jpeg_frame());
       }
       else if (all_jpeg && frames) jframes.push_back(requests[i]->image_data.jpeg_frame());
@@ -590,11 +618,13 @@ class OCRWorker {
       if (coded) {
         std::vector<const ocr_jpeg_frame*> jp((size_t)k, nullptr);
         std::vector<const ocr_png_frame*> pp((size_t)k, nullptr);
-        for (int j = 0, nj = 0, np = 0; j < k; ++j) {
-          if (is_png[j]) pp[j] = &pframes[np++];
+        std::vector<const ocr_raw_frame*> rp((size_t)k, nullptr);
+        for (int j = 0, nj = 0, np = 0, nr = 0; j < k; ++j) {
+          if (is_png[j] == 2) rp[j] = &rframes[nr++];
+          else if (is_png[j]) pp[j] = &pframes[np++];
           else jp[j] = &jframes[nj++];
         }
-        rc = ocr_pipe_stage_coded(pipe_, 0, jp.data(), pp.data(), k);
+        rc = with_raw ? ocr_pipe_stage_frames(pipe_, 0, jp.data(), pp.data(), rp.data(), k) : ocr_pipe_stage_coded(pipe_, 0, jp.data(), pp.data(), k);
       } else
       rc = frames ? ocr_pipe_stage_jpeg_frames(pipe_, 0, jframes.data(), k) : ocr_pipe_stage_jpeg(pipe_, 0, jimgs.data(), k);
       if (rc == OCR_OK) rc = ocr_pipe_run_staged(pipe_, 0, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, nullptr);

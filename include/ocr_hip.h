@@ -349,6 +349,36 @@ int ocr_png_time_batch(const ocr_png_frame* const* frames, int count, int device
 /* ocr_pipe_stage_jpeg_frames for a batch that mixes JPEG and PNG requests: image i is jpegs[i] or pngs[i], exactly one of
  * the two non-null (either array may be NULL when no image of the batch uses it). */
 int ocr_pipe_stage_coded(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, int count);
+/* BMP and PNM inputs with the pixel half of the decoder on the device: the caller parses the container and does what is
+ * serial (run-length expansion, ASCII numbers: host/raw_decode.h, raw::parse); bit, nibble and palette expansion, 5-5-5 /
+ * 5-6-5, the high bytes of 16-bit samples, row order and channel order run on the copy stream straight into the slot.
+ * The pixels are cv::imdecode(IMREAD_COLOR)'s.  Every field is checked on the host before anything is launched
+ * (OCR_ERR_ARG, ocr_last_error says which rule). */
+typedef enum ocr_raw_kind {
+  OCR_RAW_INDEX1, OCR_RAW_INDEX4, OCR_RAW_INDEX8,   /* through palette; most significant bit / high nibble first */
+  OCR_RAW_BGR555, OCR_RAW_BGR565,                   /* 16-bit little-endian, expanded by shifting: low bits 0 */
+  OCR_RAW_BGR24,  OCR_RAW_BGRX32, OCR_RAW_RGB24,
+  OCR_RAW_GREY8,  OCR_RAW_GREY16BE, OCR_RAW_RGB48BE, /* 16-bit big-endian: the high byte is kept */
+  OCR_RAW_BIT1_INV                                  /* PBM: 1 = black */
+} ocr_raw_kind;
+typedef struct ocr_raw_frame {
+  int width, height;       /* width * height <= 64 Mpixel */
+  int kind;                /* ocr_raw_kind */
+  int bottom_up;           /* 1: stored row r is image row height - 1 - r */
+  size_t row_stride;       /* bytes between stored rows, >= the row's own bytes, <= 2 GiB */
+  uint8_t palette[1024];   /* B,G,R,x times 256; zero beyond the file's */
+  const uint8_t* data;     /* host */
+  size_t data_len;         /* >= (height-1)*row_stride + row bytes */
+} ocr_raw_frame;
+int ocr_raw_decode(const ocr_raw_frame* frame, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time), as ocr_png_time: ms[0] = the upload of the stored rows from pinned memory,
+ * ms[1] = the pixel-stage kernel; ocr_raw_time_batch: `count` frames as ONE batch (one upload, one launch per kind). */
+int ocr_raw_time(const ocr_raw_frame* frame, int device_id, int iters, double ms[2]);
+int ocr_raw_time_batch(const ocr_raw_frame* const* frames, int count, int device_id, int iters, double ms[2]);
+/* ocr_pipe_stage_coded with raw frames beside the JPEG and PNG ones: image i is jpegs[i], pngs[i] or raws[i], exactly one
+ * of the three non-null (an array may be NULL when no image of the batch uses it). */
+int ocr_pipe_stage_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs,
+                          const ocr_raw_frame* const* raws, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
 /* network input size the detector uses for a rows x cols image (ResizeImgType0) */
 int ocr_pipe_det_shape(ocr_pipe* h, int rows, int cols, int* net_rows, int* net_cols);

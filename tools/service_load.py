@@ -153,6 +153,23 @@ def png_mode(clients, per):
             run(16, clients, per, path, fmt, workers=2, extra_env=dict(op, OCR_DEVICE_PNG=dev), tag="device_png" if dev == "1" else "host_png")
 
 
+def bmp_mode(clients, per):
+    """960x960 8-bit paletted BMP requests (the configs[1] card of jpeg_mode through a 256-colour palette, written by Pillow)
+    against a service with two GPU workers: OCR_DEVICE_RAW=1 (opt-in: container on the client's service thread, palette
+    expansion and row order on the GPU, straight into the staging slot) against unset (the whole decode on the host), with
+    the service process's busy host cores beside it.  One JSON line per mode."""
+    from PIL import Image
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from synth_data import cfg2_sample
+    img = cfg2_sample(0, 960, 960, 32)[0]
+    path = f"/tmp/ocr_load_{os.getpid()}.bmp"
+    Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).quantize(256).save(path, format="BMP")
+    fmt = "bmp 8-bit paletted 960x960 (%d KB)" % (os.path.getsize(path) // 1024)
+    op = {"OCR_WORKER_DET_LIMIT": "960", "OCR_WORKER_REC_H": "48", "OCR_WORKER_REC_W": "320", "OCR_WORKER_CLS": "1"}
+    for dev in ("1", "0"):
+        run(16, clients, per, path, fmt, workers=2, extra_env=dict(op, OCR_DEVICE_RAW=dev), tag="device_raw" if dev == "1" else "host_raw")
+
+
 def sweep_mode(per):
     """Latency against offered load: the device-JPEG service of jpeg_mode with 8 .. 96 closed-loop
     clients, for the shipped batching (whatever is queued, up to 16: OCRWorker's default since round 4) and for other caps
@@ -198,6 +215,12 @@ if __name__ == "__main__":
         import synth_weights
         synth_weights.ensure(ROOT)
         jpeg_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "bmp":
+        subprocess.check_call(["make", "-s", "-C", HOST])
+        import synth_weights
+        synth_weights.ensure(ROOT)
+        bmp_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "png":
         if "OCR_LOAD_HOST_DIR" not in os.environ:
