@@ -2,17 +2,11 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
-#include <thread>
 
 #include "capi_common.h"
 #include "jpeg_stage.h"
 
 namespace ocr {
-
-JpegScratch::~JpegScratch() {
-  if (pinned) (void)g_host_free(pinned);
-  if (copied) (void)hipEventDestroy(copied);
-}
 
 // orientation took the place of alignment padding: callers built against the header without it keep their layout
 static_assert(sizeof(ocr_jpeg_img) == 24 + 3 * sizeof(ocr_jpeg_comp) && offsetof(ocr_jpeg_img, comp) == 24, "ocr_jpeg_img layout");
@@ -127,27 +121,16 @@ int jpeg_decode_async(const ocr_jpeg_frame* imgs, int count, uint8_t* const* dst
   if (!sc.coef.ensure(ncoef + 64, err) || !sc.planes.ensure(nplane + 256, err) || !sc.pd.ensure(pd.size(), err) || !sc.id.ensure(nclassic + 1, err) ||
       !sc.gd.ensure(ngeneral + 1, err))
     return OCR_ERR_DEVICE;
-  if (!sc.copied && hipEventCreateWithFlags(&sc.copied, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return OCR_ERR_DEVICE; }
-  if (sc.pinned && hipEventSynchronize(sc.copied) != hipSuccess) { err = "staging event failed"; return OCR_ERR_DEVICE; }
-  if (ncoef > sc.pinned_cap) {
-    if (sc.pinned) (void)g_host_free(sc.pinned);
-    sc.pinned = nullptr;
-    sc.pinned_cap = 0;
-    if (g_host_malloc((void**)&sc.pinned, ncoef * sizeof(int16_t), hipHostMallocDefault) != hipSuccess) { err = "hipHostMalloc failed"; return OCR_ERR_DEVICE; }
-    sc.pinned_cap = ncoef;
-  }
-  {  // coefficient arrays -> pinned memory, a few host threads
+  const size_t coef_bytes = ncoef * sizeof(int16_t);
+  if (!sc.stage.reserve(coef_bytes, err)) return OCR_ERR_DEVICE;
+  {  // coefficient arrays -> pinned memory
     struct Piece { const int16_t* src; size_t off, n; };
     std::vector<Piece> pieces;
     size_t p = 0;
     for (int i = 0; i < count; ++i)
       for (int c = 0; c < imgs[i].ncomp; ++c, ++p) pieces.push_back({imgs[i].comp[c].coef, coef_off[p], (size_t)imgs[i].comp[c].bw * imgs[i].comp[c].bh * 64});
-    const int nthreads = (int)std::min<size_t>(8, std::max<size_t>(1, (ncoef * 2) >> 22));
-    auto run = [&](int t) { for (size_t k = t; k < pieces.size(); k += nthreads) memcpy(sc.pinned + pieces[k].off, pieces[k].src, pieces[k].n * sizeof(int16_t)); };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nthreads; ++t) th.emplace_back(run, t);
-    run(0);
-    for (auto& t : th) t.join();
+    int16_t* pinned = reinterpret_cast<int16_t*>(sc.stage.p);
+    parallel_copy(pieces.size(), coef_bytes, [&](size_t k) { memcpy(pinned + pieces[k].off, pieces[k].src, pieces[k].n * sizeof(int16_t)); });
   }
   // image descriptors ordered by the kernel that writes them (the destination is in the descriptor: any order will do);
   // the kinds of before index `id`, the general kinds `gd`
@@ -200,8 +183,7 @@ int jpeg_decode_async(const ocr_jpeg_frame* imgs, int count, uint8_t* const* dst
     }
     p += im.ncomp;
   }
-  if (hipMemcpyAsync(sc.coef.p, sc.pinned, ncoef * sizeof(int16_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipEventRecord(sc.copied, s) != hipSuccess ||
+  if (!sc.stage.upload(sc.coef.p, coef_bytes, s, err) ||
       hipMemcpyAsync(sc.pd.p, pd.data(), pd.size() * sizeof(JpegPlaneDesc), hipMemcpyHostToDevice, s) != hipSuccess ||
       (nclassic && hipMemcpyAsync(sc.id.p, id.data(), id.size() * sizeof(JpegImageDesc), hipMemcpyHostToDevice, s) != hipSuccess) ||
       (ngeneral && hipMemcpyAsync(sc.gd.p, gd.data(), gd.size() * sizeof(JpegGenDesc), hipMemcpyHostToDevice, s) != hipSuccess)) {
@@ -230,14 +212,7 @@ int decode_frame(const ocr_jpeg_frame& f, int device_id, uint8_t* bgr, size_t ca
   const size_t bytes = (size_t)f.rows * f.cols * 3;
   if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
   JpegScratch sc;
-  DevBuf<uint8_t> out;
-  std::string err;
-  if (!out.ensure(bytes, err)) return fail(OCR_ERR_DEVICE, err);
-  uint8_t* dst = out.p;
-  rc = jpeg_decode_async(&f, 1, &dst, sc, nullptr, err);
-  if (rc) return fail(rc, err);
-  CAPI_HIP(g_memcpy(bgr, out.p, bytes, hipMemcpyDeviceToHost));
-  return OCR_OK;
+  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return jpeg_decode_async(&f, 1, dst, sc, nullptr, err); });
 }
 
 int time_frame(const ocr_jpeg_frame& f, int device_id, int iters, double ms[2]) {
@@ -252,23 +227,8 @@ int time_frame(const ocr_jpeg_frame& f, int device_id, int iters, double ms[2]) 
   JpegLaunch L;
   rc = jpeg_decode_async(&f, 1, &dst, sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
   if (rc) return fail(rc, err);
-  struct Events {
-    hipEvent_t e[3] = {};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-  } ev;
-  for (auto& e : ev.e) CAPI_HIP(hipEventCreate(&e));
-  CAPI_HIP(hipEventRecord(ev.e[0], nullptr));
-  for (int i = 0; i < iters; ++i) launch_jpeg_idct(sc.pd.p, L.ndesc, L.idct_blocks, nullptr);
-  CAPI_HIP(hipEventRecord(ev.e[1], nullptr));
-  for (int i = 0; i < iters; ++i) launch_jpeg_output(sc.id.p, sc.gd.p, L, nullptr);
-  CAPI_HIP(hipEventRecord(ev.e[2], nullptr));
-  CAPI_HIP(hipEventSynchronize(ev.e[2]));
-  for (int k = 0; k < 2; ++k) {
-    float t = 0;
-    CAPI_HIP(hipEventElapsedTime(&t, ev.e[k], ev.e[k + 1]));
-    ms[k] = (double)t / iters;
-  }
-  return OCR_OK;
+  return time_phases(iters, ms, [&] { launch_jpeg_idct(sc.pd.p, L.ndesc, L.idct_blocks, nullptr); return hipSuccess; },
+                     [&] { launch_jpeg_output(sc.id.p, sc.gd.p, L, nullptr); return hipSuccess; });
 }
 
 }  // namespace

@@ -1,17 +1,11 @@
 // Host side of the device PNG back-end + its C-ABI entry points.
 #include <algorithm>
 #include <cstring>
-#include <thread>
 
 #include "capi_common.h"
 #include "png_stage.h"
 
 namespace ocr {
-
-PngScratch::~PngScratch() {
-  if (pinned) (void)g_host_free(pinned);
-  if (copied) (void)hipEventDestroy(copied);
-}
 
 namespace {
 
@@ -114,23 +108,8 @@ int png_decode_async(const ocr_png_frame* const* imgs, int count, uint8_t* const
   }
   if (!sc.data.ensure(bytes + 256, err) || !sc.recon.ensure(bytes + 256, err) || !sc.id.ensure((size_t)count, err) || !sc.work.ensure(nwork, err))
     return OCR_ERR_DEVICE;
-  if (!sc.copied && hipEventCreateWithFlags(&sc.copied, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return OCR_ERR_DEVICE; }
-  if (sc.pinned && hipEventSynchronize(sc.copied) != hipSuccess) { err = "staging event failed"; return OCR_ERR_DEVICE; }
-  if (bytes > sc.pinned_cap) {
-    if (sc.pinned) (void)g_host_free(sc.pinned);
-    sc.pinned = nullptr;
-    sc.pinned_cap = 0;
-    if (g_host_malloc((void**)&sc.pinned, bytes, hipHostMallocDefault) != hipSuccess) { err = "hipHostMalloc failed"; return OCR_ERR_DEVICE; }
-    sc.pinned_cap = bytes;
-  }
-  {  // inflated streams -> pinned memory, a few host threads
-    const int nthreads = (int)std::min<size_t>(8, std::max<size_t>(1, bytes >> 22));
-    auto run = [&](int t) { for (int i = t; i < count; i += nthreads) memcpy(sc.pinned + off[i], imgs[i]->data, imgs[i]->data_len); };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nthreads; ++t) th.emplace_back(run, t);
-    run(0);
-    for (auto& t : th) t.join();
-  }
+  if (!sc.stage.reserve(bytes, err)) return OCR_ERR_DEVICE;
+  parallel_copy((size_t)count, bytes, [&](size_t i) { memcpy(sc.stage.p + off[i], imgs[i]->data, imgs[i]->data_len); });  // inflated streams -> pinned memory
   // the segments ordered by the kernel that takes them
   for (int k = 1; k < kPngKinds; ++k) L.first[k] = L.first[k - 1] + L.count[k - 1];
   int next[kPngKinds];
@@ -150,8 +129,7 @@ int png_decode_async(const ocr_png_frame* const* imgs, int count, uint8_t* const
     memcpy(d.palette, f.palette, sizeof d.palette);
     for (int j = 0; j < f.nsegments; ++j) work[next[kinds[i]]++] = PngWork{i, f.segments[j].pass, f.segments[j].first_row, f.segments[j].rows};
   }
-  if (hipMemcpyAsync(sc.data.p, sc.pinned, bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipEventRecord(sc.copied, s) != hipSuccess ||
+  if (!sc.stage.upload(sc.data.p, bytes, s, err) ||
       hipMemcpyAsync(sc.id.p, id.data(), id.size() * sizeof(PngImageDesc), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(sc.work.p, work.data(), work.size() * sizeof(PngWork), hipMemcpyHostToDevice, s) != hipSuccess) {
     err = "PNG stream upload failed";
@@ -185,23 +163,8 @@ int time_batch(const ocr_png_frame* const* frames, int count, int device_id, int
   PngLaunch L;
   rc = png_decode_async(frames, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
   if (rc) return fail(rc, err);
-  struct Events {
-    hipEvent_t e[3] = {};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-  } ev;
-  for (auto& e : ev.e) CAPI_HIP(hipEventCreate(&e));
-  CAPI_HIP(hipEventRecord(ev.e[0], nullptr));
-  for (int i = 0; i < iters; ++i) CAPI_HIP(hipMemcpyAsync(sc.data.p, sc.pinned, L.bytes, hipMemcpyHostToDevice, nullptr));
-  CAPI_HIP(hipEventRecord(ev.e[1], nullptr));
-  for (int i = 0; i < iters; ++i) png_relaunch(sc, L, nullptr);
-  CAPI_HIP(hipEventRecord(ev.e[2], nullptr));
-  CAPI_HIP(hipEventSynchronize(ev.e[2]));
-  for (int k = 0; k < 2; ++k) {
-    float t = 0;
-    CAPI_HIP(hipEventElapsedTime(&t, ev.e[k], ev.e[k + 1]));
-    ms[k] = (double)t / iters;
-  }
-  return OCR_OK;
+  return time_phases(iters, ms, [&] { return hipMemcpyAsync(sc.data.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
+                     [&] { png_relaunch(sc, L, nullptr); return hipSuccess; });
 }
 
 }  // namespace
@@ -215,14 +178,7 @@ extern "C" int ocr_png_decode(const ocr_png_frame* frame, int device_id, uint8_t
   const size_t bytes = (size_t)frame->width * frame->height * 3;
   if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
   PngScratch sc;
-  DevBuf<uint8_t> out;
-  std::string err;
-  if (!out.ensure(bytes, err)) return fail(OCR_ERR_DEVICE, err);
-  uint8_t* dst = out.p;
-  rc = png_decode_async(&frame, 1, &dst, sc, nullptr, err);
-  if (rc) return fail(rc, err);
-  CAPI_HIP(g_memcpy(bgr, out.p, bytes, hipMemcpyDeviceToHost));
-  return OCR_OK;
+  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return png_decode_async(&frame, 1, dst, sc, nullptr, err); });
 }
 
 extern "C" int ocr_png_time(const ocr_png_frame* frame, int device_id, int iters, double ms[2]) {

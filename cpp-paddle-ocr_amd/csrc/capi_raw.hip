@@ -1,17 +1,11 @@
 // Host side of the device BMP / PNM back-end + its C-ABI entry points.
 #include <algorithm>
 #include <cstring>
-#include <thread>
 
 #include "capi_common.h"
 #include "raw_stage.h"
 
 namespace ocr {
-
-RawScratch::~RawScratch() {
-  if (pinned) (void)g_host_free(pinned);
-  if (copied) (void)hipEventDestroy(copied);
-}
 
 namespace {
 
@@ -63,23 +57,8 @@ int raw_decode_async(const ocr_raw_frame* const* imgs, int count, uint8_t* const
   }
   L.bytes = bytes;
   if (!sc.data.ensure(bytes + 256, err) || !sc.id.ensure((size_t)count, err)) return OCR_ERR_DEVICE;
-  if (!sc.copied && hipEventCreateWithFlags(&sc.copied, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return OCR_ERR_DEVICE; }
-  if (sc.pinned && hipEventSynchronize(sc.copied) != hipSuccess) { err = "staging event failed"; return OCR_ERR_DEVICE; }
-  if (bytes > sc.pinned_cap) {
-    if (sc.pinned) (void)g_host_free(sc.pinned);
-    sc.pinned = nullptr;
-    sc.pinned_cap = 0;
-    if (g_host_malloc((void**)&sc.pinned, bytes, hipHostMallocDefault) != hipSuccess) { err = "hipHostMalloc failed"; return OCR_ERR_DEVICE; }
-    sc.pinned_cap = bytes;
-  }
-  {  // stored rows -> pinned memory, a few host threads
-    const int nthreads = (int)std::min<size_t>(8, std::max<size_t>(1, bytes >> 22));
-    auto run = [&](int t) { for (int i = t; i < count; i += nthreads) memcpy(sc.pinned + off[i], imgs[i]->data, raw_need(*imgs[i])); };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nthreads; ++t) th.emplace_back(run, t);
-    run(0);
-    for (auto& t : th) t.join();
-  }
+  if (!sc.stage.reserve(bytes, err)) return OCR_ERR_DEVICE;
+  parallel_copy((size_t)count, bytes, [&](size_t i) { memcpy(sc.stage.p + off[i], imgs[i]->data, raw_need(*imgs[i])); });  // stored rows -> pinned memory
   // the descriptors ordered by the kernel that takes them, the units of a kind numbered through its frames
   for (int k = 1; k < kRawKinds; ++k) L.first[k] = L.first[k - 1] + L.count[k - 1];
   int next[kRawKinds];
@@ -98,8 +77,7 @@ int raw_decode_async(const ocr_raw_frame* const* imgs, int count, uint8_t* const
     L.units[f.kind] += (unsigned long long)f.height * d.spans;  // per frame < 2^32: height * ceil(width / 1024) <= 64M + height
     for (int k = 0; k < 256; ++k) d.palette[k] = (uint32_t)f.palette[4 * k] | ((uint32_t)f.palette[4 * k + 1] << 8) | ((uint32_t)f.palette[4 * k + 2] << 16);
   }
-  if (hipMemcpyAsync(sc.data.p, sc.pinned, bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipEventRecord(sc.copied, s) != hipSuccess ||
+  if (!sc.stage.upload(sc.data.p, bytes, s, err) ||
       hipMemcpyAsync(sc.id.p, id.data(), id.size() * sizeof(RawImageDesc), hipMemcpyHostToDevice, s) != hipSuccess) {
     err = "raw rows upload failed";
     return OCR_ERR_DEVICE;
@@ -134,23 +112,8 @@ int time_batch(const ocr_raw_frame* const* frames, int count, int device_id, int
   RawLaunch L;
   rc = raw_decode_async(frames, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
   if (rc) return fail(rc, err);
-  struct Events {
-    hipEvent_t e[3] = {};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-  } ev;
-  for (auto& e : ev.e) CAPI_HIP(hipEventCreate(&e));
-  CAPI_HIP(hipEventRecord(ev.e[0], nullptr));
-  for (int i = 0; i < iters; ++i) CAPI_HIP(hipMemcpyAsync(sc.data.p, sc.pinned, L.bytes, hipMemcpyHostToDevice, nullptr));
-  CAPI_HIP(hipEventRecord(ev.e[1], nullptr));
-  for (int i = 0; i < iters; ++i) raw_relaunch(sc, L, nullptr);
-  CAPI_HIP(hipEventRecord(ev.e[2], nullptr));
-  CAPI_HIP(hipEventSynchronize(ev.e[2]));
-  for (int k = 0; k < 2; ++k) {
-    float t = 0;
-    CAPI_HIP(hipEventElapsedTime(&t, ev.e[k], ev.e[k + 1]));
-    ms[k] = (double)t / iters;
-  }
-  return OCR_OK;
+  return time_phases(iters, ms, [&] { return hipMemcpyAsync(sc.data.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
+                     [&] { raw_relaunch(sc, L, nullptr); return hipSuccess; });
 }
 
 }  // namespace
@@ -164,14 +127,7 @@ extern "C" int ocr_raw_decode(const ocr_raw_frame* frame, int device_id, uint8_t
   int rc = ocr_rt_init(device_id);
   if (rc) return rc;
   RawScratch sc;
-  DevBuf<uint8_t> out;
-  std::string err;
-  if (!out.ensure(bytes, err)) return fail(OCR_ERR_DEVICE, err);
-  uint8_t* dst = out.p;
-  rc = raw_decode_async(&frame, 1, &dst, sc, nullptr, err);
-  if (rc) return fail(rc, err);
-  CAPI_HIP(g_memcpy(bgr, out.p, bytes, hipMemcpyDeviceToHost));
-  return OCR_OK;
+  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return raw_decode_async(&frame, 1, dst, sc, nullptr, err); });
 }
 
 extern "C" int ocr_raw_time(const ocr_raw_frame* frame, int device_id, int iters, double ms[2]) {

@@ -3,8 +3,8 @@
 #include <string>
 #include <vector>
 
+#include "image_stage.h"
 #include "kernels_jpeg.h"
-#include "stages.h"
 
 namespace ocr {
 
@@ -14,10 +14,7 @@ struct JpegScratch {
   DevBuf<JpegPlaneDesc> pd;
   DevBuf<JpegImageDesc> id;
   DevBuf<JpegGenDesc> gd;
-  int16_t* pinned = nullptr;   // coefficient staging (hipHostMalloc)
-  size_t pinned_cap = 0;       // in int16
-  hipEvent_t copied = nullptr; // the pinned buffer may be refilled once this has passed
-  ~JpegScratch();
+  PinnedStage stage;  // of the coefficients
 };
 // Validates the descriptors, stages the coefficients through pinned memory, and enqueues upload + IDCT + upsampling /
 // colour conversion + EXIF orientation on `s`; image i is written as packed BGR to dst[i] (device), jpeg_out_rows x

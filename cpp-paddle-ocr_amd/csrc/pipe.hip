@@ -35,8 +35,7 @@ static int emit(const std::vector<std::vector<ocr_word>>& W, const std::vector<s
 struct StageSlot {
   struct Img { int rows, cols, orig; size_t off, prob_off; };
   struct Group { int rows, cols, first, count; size_t off, prob_off; };
-  uint8_t* pinned = nullptr;
-  size_t pinned_cap = 0;
+  PinnedStage pinned;  // free again once `ready` has passed (layout() waits for it: pinned.copied is never recorded)
   DevBuf<uint8_t> dev;
   DevBuf<float> probs;
   std::vector<Img> imgs;      // layout order
@@ -44,10 +43,7 @@ struct StageSlot {
   size_t bytes = 0, prob_floats = 0;
   bool has_probs = false, staged = false;
   hipEvent_t ready = nullptr;
-  ~StageSlot() {
-    if (pinned) (void)g_host_free(pinned);
-    if (ready) (void)hipEventDestroy(ready);
-  }
+  ~StageSlot() { if (ready) (void)hipEventDestroy(ready); }
 };
 
 // In-place 180-degree rotations of ROIs in request order (the cls stage: cv::rotate on views that alias their image,
@@ -449,7 +445,7 @@ struct ocr_pipe {
     if (!copy_stream && hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) != hipSuccess) { err = "hipStreamCreate failed"; return OCR_ERR_DEVICE; }
     if (!S.ready && hipEventCreateWithFlags(&S.ready, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return OCR_ERR_DEVICE; }
     if (S.staged && hipEventSynchronize(S.ready) != hipSuccess) { err = "staging event failed"; return OCR_ERR_DEVICE; }  // pinned buffer free again
-    // from here to the end of stage() / stage_jpeg() the slot holds a half-written batch: a failure on the way must not
+    // from here to the end of stage() / stage_coded() the slot holds a half-written batch: a failure on the way must not
     // leave it runnable (a later ocr_pipe_run_staged would run the new layout over stale pixels)
     S.staged = false;
     std::vector<int> order(count), rows(count), cols(count);
@@ -489,64 +485,30 @@ struct ocr_pipe {
     int rc = layout(S, count, [&](int i, int& r, int& c) { r = imgs[i].rows; c = imgs[i].cols; }, err);
     if (rc) return rc;
     const size_t off = S.bytes;
-    if (off > S.pinned_cap) {
-      if (S.pinned) (void)g_host_free(S.pinned);
-      S.pinned = nullptr;
-      S.pinned_cap = 0;
-      if (g_host_malloc((void**)&S.pinned, off, hipHostMallocDefault) != hipSuccess) { err = "hipHostMalloc failed"; return OCR_ERR_DEVICE; }
-      S.pinned_cap = off;
-    }
-    // host copies on a few threads (one thread moves ~10 GB/s: 64 images of 960x960 would take 18 ms)
-    {
-      const int nthreads = (int)std::min<size_t>(8, std::max<size_t>(1, off >> 22));
-      auto copy_range = [&](int t) {
-        for (int k = t; k < count; k += nthreads) {
-          const ocr_img& im = imgs[S.imgs[k].orig];
-          const size_t row = (size_t)im.cols * 3, stride = im.row_stride ? im.row_stride : row;
-          uint8_t* dst = S.pinned + S.imgs[k].off;
-          if (stride == row) memcpy(dst, im.data, row * im.rows);
-          else for (int y = 0; y < im.rows; ++y) memcpy(dst + row * y, im.data + stride * y, row);
-        }
-      };
-      std::vector<std::thread> th;
-      for (int t = 1; t < nthreads; ++t) th.emplace_back(copy_range, t);
-      copy_range(0);
-      for (auto& t : th) t.join();
-    }
-    if (hipMemcpyAsync(S.dev.p, S.pinned, off, hipMemcpyHostToDevice, copy_stream) != hipSuccess) { err = "H2D copy failed"; return OCR_ERR_DEVICE; }
+    if (!S.pinned.reserve(off, err)) return OCR_ERR_DEVICE;
+    parallel_copy((size_t)count, off, [&](size_t k) {
+      const ocr_img& im = imgs[S.imgs[k].orig];
+      const size_t row = (size_t)im.cols * 3, stride = im.row_stride ? im.row_stride : row;
+      uint8_t* dst = S.pinned.p + S.imgs[k].off;
+      if (stride == row) memcpy(dst, im.data, row * im.rows);
+      else for (int y = 0; y < im.rows; ++y) memcpy(dst + row * y, im.data + stride * y, row);
+    });
+    if (hipMemcpyAsync(S.dev.p, S.pinned.p, off, hipMemcpyHostToDevice, copy_stream) != hipSuccess) { err = "H2D copy failed"; return OCR_ERR_DEVICE; }
     if (hipEventRecord(S.ready, copy_stream) != hipSuccess) { err = "hipEventRecord failed"; return OCR_ERR_DEVICE; }
     S.staged = true;
     return OCR_OK;
   }
 
-  // ---- stage JPEG coefficients: the pixel half of the decoder runs on the copy stream, into the slot
-  int stage_jpeg(int si, const ocr_jpeg_frame* imgs, int count, std::string& err) {
-    StageSlot& S = slots[si];
-    // (checked before the sizes are used: a refused batch leaves the slot as it was)
-    for (int i = 0; i < count; ++i)
-      if (const char* fault = jpeg_frame_fault(imgs[i])) { err = fault; return OCR_ERR_ARG; }
-    // the oriented size: a 40 x 72 image and a 72 x 40 one that EXIF turns by 90 degrees share a size group and a det pass
-    int rc = layout(S, count, [&](int i, int& r, int& c) { r = jpeg_out_rows(imgs[i]); c = jpeg_out_cols(imgs[i]); }, err);
-    if (rc) return rc;
-    std::vector<ocr_jpeg_frame> ordered(count);
-    std::vector<uint8_t*> dst(count);
-    for (int k = 0; k < count; ++k) { ordered[k] = imgs[S.imgs[k].orig]; dst[k] = S.dev.p + S.imgs[k].off; }
-    rc = jpeg_decode_async(ordered.data(), count, dst.data(), jpeg, copy_stream, err);
-    if (rc) return rc;
-    if (hipEventRecord(S.ready, copy_stream) != hipSuccess) { err = "hipEventRecord failed"; return OCR_ERR_DEVICE; }
-    S.staged = true;
-    return OCR_OK;
-  }
-
-  // ---- stage a batch that mixes JPEG coefficients, inflated PNG streams and stored BMP / PNM rows: the three pixel stages run on
-  // the copy stream, into the slot.  Image i is jpegs[i], pngs[i] or raws[i] (validated by the caller: exactly one of them, and a
-  // sound descriptor)
+  // ---- stage a batch of JPEG coefficients, inflated PNG streams and stored BMP / PNM rows, in any mix: the three pixel stages run
+  // on the copy stream, into the slot.  Image i is jpegs[i], pngs[i] or raws[i] (validated by the caller before the sizes are used
+  // - a refused batch leaves the slot as it was: exactly one of them, and a sound descriptor)
   int stage_coded(int si, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, const ocr_raw_frame* const* raws, int count,
                   std::string& err) {
     StageSlot& S = slots[si];
     auto jp = [&](int i) { return jpegs ? jpegs[i] : nullptr; };
     auto pn = [&](int i) { return pngs ? pngs[i] : nullptr; };
     int rc = layout(S, count, [&](int i, int& r, int& c) {
+      // the oriented size: a 40 x 72 image and a 72 x 40 one that EXIF turns by 90 degrees share a size group and a det pass
       if (const ocr_jpeg_frame* j = jp(i)) { r = jpeg_out_rows(*j); c = jpeg_out_cols(*j); }
       else if (const ocr_png_frame* p = pn(i)) { r = p->height; c = p->width; }
       else { r = raws[i]->height; c = raws[i]->width; }
@@ -836,8 +798,24 @@ int ocr_pipe_run_device_on(ocr_pipe* h, int chain, const void* dev_bgr, int rows
   return pipe_run_device(h, chain, dev_bgr, rows, cols, count, dev_prob, words, cap_words, word_off, nwords, ids, cap_ids, times);
 }
 
+static bool stage_args_ok(const ocr_pipe* h, bool images, int slot, int count) { return h && images && count >= 1 && (slot == 0 || slot == 1); }
+
+// the tail of the four entry points below: every frame has been validated
+static int stage_validated(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs,
+                           const ocr_raw_frame* const* raws, int count) {
+  CAPI_HIP(rt_set_device(h->device));
+  std::string err;
+  const int rc = h->stage_coded(slot, jpegs, pngs, raws, count, err);
+  return rc ? fail(rc, err) : OCR_OK;
+}
+static std::vector<const ocr_jpeg_frame*> pointers_to(const ocr_jpeg_frame* frames, int count) {
+  std::vector<const ocr_jpeg_frame*> p((size_t)count);
+  for (int i = 0; i < count; ++i) p[i] = frames + i;
+  return p;
+}
+
 int ocr_pipe_stage(ocr_pipe* h, int slot, const ocr_img* imgs, int count) {
-  if (!h || !imgs || count < 1 || slot < 0 || slot > 1) return fail(OCR_ERR_ARG, "bad argument");
+  if (!stage_args_ok(h, imgs, slot, count)) return fail(OCR_ERR_ARG, "bad argument");
   for (int i = 0; i < count; ++i)
     if (!imgs[i].data || imgs[i].rows <= 0 || imgs[i].cols <= 0) return fail(OCR_ERR_ARG, "Empty image data provided");
   CAPI_HIP(rt_set_device(h->device));
@@ -847,30 +825,27 @@ int ocr_pipe_stage(ocr_pipe* h, int slot, const ocr_img* imgs, int count) {
 }
 
 int ocr_pipe_stage_jpeg(ocr_pipe* h, int slot, const ocr_jpeg_img* imgs, int count) {
-  if (!h || !imgs || count < 1 || slot < 0 || slot > 1) return fail(OCR_ERR_ARG, "bad argument");
+  if (!stage_args_ok(h, imgs, slot, count)) return fail(OCR_ERR_ARG, "bad argument");
   for (int i = 0; i < count; ++i)
     if (!jpeg_img_valid(imgs[i])) return fail(OCR_ERR_ARG, "bad JPEG coefficient descriptor");
-  CAPI_HIP(rt_set_device(h->device));
   std::vector<ocr_jpeg_frame> frames((size_t)count);
-  for (int i = 0; i < count; ++i) frames[i] = jpeg_frame_of(imgs[i]);
-  std::string err;
-  const int rc = h->stage_jpeg(slot, frames.data(), count, err);
-  return rc ? fail(rc, err) : OCR_OK;
+  for (int i = 0; i < count; ++i) {
+    frames[i] = jpeg_frame_of(imgs[i]);
+    if (const char* fault = jpeg_frame_fault(frames[i])) return fail(OCR_ERR_ARG, fault);
+  }
+  return stage_validated(h, slot, pointers_to(frames.data(), count).data(), nullptr, nullptr, count);
 }
 
 int ocr_pipe_stage_jpeg_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* frames, int count) {
-  if (!h || !frames || count < 1 || slot < 0 || slot > 1) return fail(OCR_ERR_ARG, "bad argument");
+  if (!stage_args_ok(h, frames, slot, count)) return fail(OCR_ERR_ARG, "bad argument");
   for (int i = 0; i < count; ++i)
     if (const char* fault = jpeg_frame_fault(frames[i])) return fail(OCR_ERR_ARG, fault);
-  CAPI_HIP(rt_set_device(h->device));
-  std::string err;
-  const int rc = h->stage_jpeg(slot, frames, count, err);
-  return rc ? fail(rc, err) : OCR_OK;
+  return stage_validated(h, slot, pointers_to(frames, count).data(), nullptr, nullptr, count);
 }
 
 int ocr_pipe_stage_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs,
                           const ocr_raw_frame* const* raws, int count) {
-  if (!h || (!jpegs && !pngs && !raws) || count < 1 || slot < 0 || slot > 1) return fail(OCR_ERR_ARG, "bad argument");
+  if (!stage_args_ok(h, jpegs || pngs || raws, slot, count)) return fail(OCR_ERR_ARG, "bad argument");
   for (int i = 0; i < count; ++i) {
     const ocr_jpeg_frame* j = jpegs ? jpegs[i] : nullptr;
     const ocr_png_frame* p = pngs ? pngs[i] : nullptr;
@@ -880,10 +855,7 @@ int ocr_pipe_stage_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jp
                                     : "every image is a JPEG frame or a PNG frame, not both and not neither");
     if (const char* fault = j ? jpeg_frame_fault(*j) : p ? png_frame_fault(*p) : raw_frame_fault(*r)) return fail(OCR_ERR_ARG, fault);
   }
-  CAPI_HIP(rt_set_device(h->device));
-  std::string err;
-  const int rc = h->stage_coded(slot, jpegs, pngs, raws, count, err);
-  return rc ? fail(rc, err) : OCR_OK;
+  return stage_validated(h, slot, jpegs, pngs, raws, count);
 }
 
 int ocr_pipe_stage_coded(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, int count) {

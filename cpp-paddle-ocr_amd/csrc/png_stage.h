@@ -3,8 +3,8 @@
 #include <string>
 #include <vector>
 
+#include "image_stage.h"
 #include "kernels_png.h"
-#include "stages.h"
 
 namespace ocr {
 
@@ -12,10 +12,7 @@ struct PngScratch {
   DevBuf<uint8_t> data, recon;
   DevBuf<PngImageDesc> id;
   DevBuf<PngWork> work;
-  uint8_t* pinned = nullptr;   // staging of the inflated streams (hipHostMalloc)
-  size_t pinned_cap = 0;
-  hipEvent_t copied = nullptr; // the pinned buffer may be refilled once this has passed
-  ~PngScratch();
+  PinnedStage stage;  // of the inflated streams
 };
 // what a batch launched, for a caller that repeats it (ocr_png_time): work[first[k]] .. + count[k] are the segments of kind k
 struct PngLaunch {

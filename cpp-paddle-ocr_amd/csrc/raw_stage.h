@@ -3,18 +3,15 @@
 #include <string>
 #include <vector>
 
+#include "image_stage.h"
 #include "kernels_raw.h"
-#include "stages.h"
 
 namespace ocr {
 
 struct RawScratch {
   DevBuf<uint8_t> data;
   DevBuf<RawImageDesc> id;
-  uint8_t* pinned = nullptr;   // staging of the stored rows (hipHostMalloc)
-  size_t pinned_cap = 0;
-  hipEvent_t copied = nullptr; // the pinned buffer may be refilled once this has passed
-  ~RawScratch();
+  PinnedStage stage;  // of the stored rows
 };
 // what a batch launched, for a caller that repeats it (ocr_raw_time): id[first[k]] .. + count[k] are the frames of kind k
 struct RawLaunch {

@@ -9,9 +9,12 @@
 // A BMP's or PNM's pixel half (bit / nibble / palette expansion, 5-5-5 / 5-6-5, high bytes, row and channel order) runs
 // on the GPU with --device / --frame as well, through ocr_raw_decode (whatever OCR_DEVICE_RAW says); without them on the
 // host (raw_decode.h).
-// decode_tool --stage <model dir> <jpeg file> <out.ppm> [...]: all files as ONE batch through ocr_pipe_stage_jpeg_frames
-// into a pipeline's staging slot, each staged image read back (ocr_pipe_slot_image) and written.  With a PNG among the
-// files the batch goes through ocr_pipe_stage_coded, with a BMP or PNM among them through ocr_pipe_stage_frames.
+// decode_tool --stage <model dir> <image file> <out.ppm> [...]: all files (JPEG, PNG, BMP, PNM in any mix) as ONE batch
+// through ocr_pipe_stage_frames into a pipeline's staging slot, each staged image read back (ocr_pipe_slot_image) and written.
+// A "--" between pairs starts a further batch: the batches go through the same slot of the same pipeline, one after the other.
+// decode_tool --stage-ways <model dir> <jpeg file> <out.ppm> <jpeg file> <out.ppm> [...]: one batch of JPEGs that ocr_jpeg_img
+// can hold through each of ocr_pipe_stage_jpeg, _jpeg_frames, _coded and _frames; after each, the same batch with an unsound
+// second image must be refused with OCR_ERR_ARG, and the slot is read back after that: <out.ppm>.jpeg, .jpeg_frames, .coded, .frames.
 // decode_tool --time <iters> <jpeg file>: device time of that pixel half's two kernels (HIP events around `iters`
 // launches each, ocr_jpeg_time / ocr_jpeg_time_frame), one JSON line.
 // decode_tool --time <iters> <png file> [<batch>]: the same for a PNG (ocr_png_time: upload of the inflated stream, pixel
@@ -25,6 +28,21 @@
 #include <cstring>
 
 #include "ocr_ipc_service.h"
+
+// ocr_jpeg_img, the first descriptor (grey and YCbCr 4:4:4 / 4:2:2 / 4:2:0: jpeg::Coefs::classic()), kept as ABI: --device and
+// --time go on exercising its entry points for the files it can hold
+static ocr_jpeg_img jpeg_desc(const PaddleOCR::jpeg::Coefs& j) {
+  ocr_jpeg_img d;
+  memset(&d, 0, sizeof d);
+  d.rows = j.rows; d.cols = j.cols; d.ncomp = j.ncomp; d.hmax = j.hmax; d.vmax = j.vmax; d.orientation = j.orientation;
+  for (int i = 0; i < j.ncomp; ++i) {
+    const auto& c = j.comp[i];
+    d.comp[i].coef = c.coef.data();
+    memcpy(d.comp[i].quant, c.quant, sizeof c.quant);
+    d.comp[i].bw = c.bw; d.comp[i].bh = c.bh; d.comp[i].dw = c.dw; d.comp[i].dh = c.dh;
+  }
+  return d;
+}
 
 static int time_device(int iters, const char* in, int batch) {
   std::vector<uint8_t> bytes;
@@ -64,8 +82,8 @@ static int time_device(int iters, const char* in, int batch) {
   const ocr_jpeg_frame d = im.jpeg_frame();
   double ms[2];
   int rc;
-  if (im.needs_frame()) rc = ocr_jpeg_time_frame(&d, 0, iters, ms);
-  else { const ocr_jpeg_img o = im.jpeg_desc(); rc = ocr_jpeg_time(&o, 0, iters, ms); }
+  if (!im.jpeg->classic()) rc = ocr_jpeg_time_frame(&d, 0, iters, ms);
+  else { const ocr_jpeg_img o = jpeg_desc(*im.jpeg); rc = ocr_jpeg_time(&o, 0, iters, ms); }
   if (rc != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
   printf("{\"stored\": [%d, %d], \"orientation\": %d, \"iters\": %d, \"idct_ms\": %.5f, \"pixel_stage_ms\": %.5f}\n",
          d.rows, d.cols, d.orientation, iters, ms[0], ms[1]);
@@ -77,24 +95,68 @@ static void write_ppm(FILE* f, const uint8_t* bgr, int rows, int cols) {
   for (size_t p = 0; p < (size_t)rows * cols; ++p) { const uint8_t rgb[3] = {bgr[3 * p + 2], bgr[3 * p + 1], bgr[3 * p]}; fwrite(rgb, 1, 3, f); }
 }
 
-static int stage_batch(const std::string& model_dir, int n, char** pairs) {
-  std::vector<PaddleOCR::Image> ims((size_t)n);
-  std::vector<ocr_jpeg_frame> frames((size_t)n);
-  std::vector<ocr_png_frame> pframes((size_t)n);
-  std::vector<const ocr_jpeg_frame*> jp((size_t)n, nullptr);
-  std::vector<const ocr_png_frame*> pp((size_t)n, nullptr);
-  std::vector<ocr_raw_frame> rframes((size_t)n);
-  std::vector<const ocr_raw_frame*> rp((size_t)n, nullptr);
-  bool coded = false, with_raw = false;
-  for (int i = 0; i < n; ++i) {
-    std::vector<uint8_t> bytes;
-    if (!PaddleOCR::ipc::read_file(pairs[2 * i], bytes) || !PaddleOCR::ipc::decode_image(bytes, ims[i], true, true) || !ims[i].device_decodable()) {
-      fprintf(stderr, "decode failed: %s\n", pairs[2 * i]);
+// one batch of --stage / --stage-ways: the files as device-decodable images, their descriptors, where the staged pixels go
+struct Batch {
+  std::vector<PaddleOCR::Image> ims;
+  std::vector<std::string> in, out;
+  PaddleOCR::DeviceFrames frames;
+};
+
+// the batch through one of the four staging entry points (way 0..3: ocr_pipe_stage_jpeg, _jpeg_frames, _coded, _frames; the first
+// three take JPEGs only, the first those ocr_jpeg_img can hold).  spoil: the second image's first component loses its blocks
+static int stage_way(ocr_pipe* pipe, int way, const Batch& b, bool spoil) {
+  const int n = (int)b.ims.size();
+  if (way == 0) {
+    std::vector<ocr_jpeg_img> d;
+    for (const auto& im : b.ims) d.push_back(jpeg_desc(*im.jpeg));
+    if (spoil) d[1].comp[0].bw = 0;
+    return ocr_pipe_stage_jpeg(pipe, 0, d.data(), n);
+  }
+  std::vector<ocr_jpeg_frame> d(b.frames.jf.begin(), b.frames.jf.end());
+  if (spoil) d[1].comp[0].bw = 0;
+  if (way == 1) return ocr_pipe_stage_jpeg_frames(pipe, 0, d.data(), n);
+  std::vector<const ocr_jpeg_frame*> p;
+  for (const auto& f : d) p.push_back(&f);
+  return way == 2 ? ocr_pipe_stage_coded(pipe, 0, p.data(), nullptr, n) : ocr_pipe_stage_frames(pipe, 0, p.data(), nullptr, nullptr, n);
+}
+
+static int read_back(ocr_pipe* pipe, const Batch& b, const std::string& suffix) {
+  for (size_t i = 0; i < b.ims.size(); ++i) {
+    std::vector<uint8_t> px((size_t)b.ims[i].rows * b.ims[i].cols * 3);
+    int rows = 0, cols = 0;
+    if (ocr_pipe_slot_image(pipe, 0, (int)i, px.data(), px.size(), &rows, &cols) != OCR_OK || rows != b.ims[i].rows || cols != b.ims[i].cols) {
+      fprintf(stderr, "read-back failed: %s: %s\n", b.in[i].c_str(), ocr_last_error());
       return 1;
     }
-    if (ims[i].raw) { rframes[i] = ims[i].raw_frame(); rp[i] = &rframes[i]; coded = with_raw = true; }
-    else if (ims[i].png) { pframes[i] = ims[i].png_frame(); pp[i] = &pframes[i]; coded = true; }
-    else { frames[i] = ims[i].jpeg_frame(); jp[i] = &frames[i]; }
+    FILE* f = fopen((b.out[i] + suffix).c_str(), "wb");
+    if (!f) return 1;
+    write_ppm(f, px.data(), rows, cols);
+    fclose(f);
+  }
+  return 0;
+}
+
+static int stage_batches(const std::string& model_dir, int nargs, char** args, bool ways) {
+  std::vector<Batch> batches(1);
+  for (int a = 0; a < nargs; ++a) {
+    if (!strcmp(args[a], "--")) { batches.emplace_back(); continue; }
+    if (a + 1 >= nargs) { fprintf(stderr, "an input without an output: %s\n", args[a]); return 2; }
+    Batch& b = batches.back();
+    b.in.push_back(args[a]);
+    b.out.push_back(args[++a]);
+  }
+  for (Batch& b : batches) {
+    if (b.in.empty() || (ways && (batches.size() != 1 || b.in.size() < 2))) { fprintf(stderr, "empty batch (--stage-ways: one batch of two files or more)\n"); return 2; }
+    b.ims.resize(b.in.size());
+    for (size_t i = 0; i < b.in.size(); ++i) {
+      std::vector<uint8_t> bytes;
+      if (!PaddleOCR::ipc::read_file(b.in[i], bytes) || !PaddleOCR::ipc::decode_image(bytes, b.ims[i], true, true) || !b.ims[i].device_decodable() ||
+          (ways && !(b.ims[i].jpeg && b.ims[i].jpeg->classic()))) {
+        fprintf(stderr, "decode failed: %s\n", b.in[i].c_str());
+        return 1;
+      }
+      b.frames.add(b.ims[i]);
+    }
   }
   const std::string det = model_dir + "/det", cls = model_dir + "/cls", rec = model_dir + "/rec", dict = rec + "/ppocr_keys_v1.txt";
   ocr_pipe_cfg c;
@@ -103,19 +165,20 @@ static int stage_batch(const std::string& model_dir, int n, char** pairs) {
   ocr_pipe* pipe = nullptr;
   if (ocr_pipe_create(&c, &pipe) != OCR_OK) { fprintf(stderr, "pipeline: %s\n", ocr_last_error()); return 1; }
   int rc = 0;
-  if ((with_raw ? ocr_pipe_stage_frames(pipe, 0, jp.data(), pp.data(), rp.data(), n) : coded ? ocr_pipe_stage_coded(pipe, 0, jp.data(), pp.data(), n) : ocr_pipe_stage_jpeg_frames(pipe, 0, frames.data(), n)) != OCR_OK) { fprintf(stderr, "staging failed: %s\n", ocr_last_error()); rc = 1; }
-  for (int i = 0; i < n && !rc; ++i) {
-    std::vector<uint8_t> px((size_t)ims[i].rows * ims[i].cols * 3);
-    int rows = 0, cols = 0;
-    if (ocr_pipe_slot_image(pipe, 0, i, px.data(), px.size(), &rows, &cols) != OCR_OK || rows != ims[i].rows || cols != ims[i].cols) {
-      fprintf(stderr, "read-back failed: %s: %s\n", pairs[2 * i], ocr_last_error());
-      rc = 1;
-      break;
+  if (ways) {
+    static const char* const name[4] = {".jpeg", ".jpeg_frames", ".coded", ".frames"};
+    for (int w = 0; w < 4 && !rc; ++w) {
+      if (stage_way(pipe, w, batches[0], false) != OCR_OK) { fprintf(stderr, "staging failed (%s): %s\n", name[w] + 1, ocr_last_error()); rc = 1; break; }
+      const int refused = stage_way(pipe, w, batches[0], true);
+      if (refused != OCR_ERR_ARG) { fprintf(stderr, "the spoilt batch was not refused with OCR_ERR_ARG (%s): %d\n", name[w] + 1, refused); rc = 1; break; }
+      rc = read_back(pipe, batches[0], name[w]);  // after the refused call: the slot still holds the batch staged before it
     }
-    FILE* f = fopen(pairs[2 * i + 1], "wb");
-    if (!f) { rc = 1; break; }
-    write_ppm(f, px.data(), rows, cols);
-    fclose(f);
+  } else {
+    for (const Batch& b : batches) {
+      if (b.frames.stage(pipe, 0) != OCR_OK) { fprintf(stderr, "staging failed: %s\n", ocr_last_error()); rc = 1; }
+      if (!rc) rc = read_back(pipe, b, "");
+      if (rc) break;
+    }
   }
   ocr_pipe_destroy(pipe);
   return rc;
@@ -139,8 +202,8 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
     const ocr_jpeg_frame d = im.jpeg_frame();
     im.pixels.resize((size_t)d.rows * d.cols * 3);
     int rc;
-    if (frame || im.needs_frame()) rc = ocr_jpeg_decode_frame(&d, 0, im.pixels.data(), im.pixels.size());
-    else { const ocr_jpeg_img o = im.jpeg_desc(); rc = ocr_jpeg_decode(&o, 0, im.pixels.data(), im.pixels.size()); }
+    if (frame || !im.jpeg->classic()) rc = ocr_jpeg_decode_frame(&d, 0, im.pixels.data(), im.pixels.size());
+    else { const ocr_jpeg_img o = jpeg_desc(*im.jpeg); rc = ocr_jpeg_decode(&o, 0, im.pixels.data(), im.pixels.size()); }
     if (rc != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
   }
   FILE* f = fopen(outp, "wb");
@@ -152,7 +215,7 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
 
 int main(int argc, char** argv) {
   if ((argc == 4 || argc == 5) && !strcmp(argv[1], "--time")) return time_device(atoi(argv[2]), argv[3], argc == 5 ? atoi(argv[4]) : 1);
-  if (argc >= 5 && !strcmp(argv[1], "--stage") && (argc - 3) % 2 == 0) return stage_batch(argv[2], (argc - 3) / 2, argv + 3);
+  if (argc >= 5 && (!strcmp(argv[1], "--stage") || !strcmp(argv[1], "--stage-ways"))) return stage_batches(argv[2], argc - 3, argv + 3, argv[1][7] != 0);
   const bool frame = argc > 1 && !strcmp(argv[1], "--frame");
   const bool device = frame || (argc > 1 && !strcmp(argv[1], "--device"));
   const int first = device ? 2 : 1;

@@ -81,7 +81,7 @@ struct Component {
 
 // Entropy-decoded image: quantised DCT coefficients per component, what the scans of the file say and nothing more.
 // The pixel half of decoding (dequantisation, IDCT, upsampling, colour) can then run on the host (Decoder::pixels)
-// or on the device (ocr_pipe_stage_jpeg / ocr_jpeg_decode of include/ocr_hip.h) with identical results.
+// or on the device (ocr_pipe_stage_frames / ocr_jpeg_decode_frame of include/ocr_hip.h) with identical results.
 enum Color { kGrey = 0, kYCbCr = 1, kRGB = 2, kCMYK = 3, kYCCK = 4 };  // the values of ocr_jpeg_color (include/ocr_hip.h)
 
 // jdsample.c's choice for a component with expansion (hexp, vexp) = (hmax / h, vmax / v) and dw samples per row

@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <future>
 #include <memory>
 #include <mutex>
@@ -48,11 +49,11 @@ struct ImageView {
 struct Image {
   std::vector<uint8_t> pixels;
   int rows = 0, cols = 0;
-  // a JPEG that has only been entropy-decoded: the worker finishes it on the device (ocr_pipe_stage_jpeg); `pixels`
+  // a JPEG that has only been entropy-decoded: the worker finishes it on the device (ocr_pipe_stage_frames); `pixels`
   // stays empty unless someone asks for them (materialise()).  rows / cols are the size after the EXIF orientation, the
   // frame of the reply's width, height and boxes (cv::imdecode turns the image); jpeg->rows / cols stay the stored size
   std::shared_ptr<jpeg::Coefs> jpeg;
-  // a PNG that has only been parsed and inflated: the worker unfilters and converts it on the device (ocr_pipe_stage_coded)
+  // a PNG that has only been parsed and inflated: the worker unfilters and converts it on the device (ocr_pipe_stage_frames)
   std::shared_ptr<png::Frame> png;
   // a BMP / PNM whose container has been parsed (and run-length stream or ASCII numbers expanded): the worker converts the
   // stored rows on the device (ocr_pipe_stage_frames)
@@ -102,10 +103,7 @@ struct Image {
     d.data = raw->data.data(); d.data_len = raw->data.size();
     return d;
   }
-  // ocr_jpeg_img holds grey and YCbCr 4:4:4 / 4:2:2 / 4:2:0; every other file (another sampling, RGB, CMYK, YCCK) needs
-  // the general descriptor, jpeg_frame(), which can say what the first says too
-  bool needs_frame() const { return jpeg && !jpeg->classic(); }
-  ocr_jpeg_frame jpeg_frame() const {
+  ocr_jpeg_frame jpeg_frame() const {  // only when jpeg: every file the host half reads (any sampling, grey, YCbCr, RGB, CMYK, YCCK)
     ocr_jpeg_frame d;
     memset(&d, 0, sizeof d);
     d.rows = jpeg->rows; d.cols = jpeg->cols; d.ncomp = jpeg->ncomp; d.orientation = jpeg->orientation; d.color = jpeg->color;
@@ -117,19 +115,24 @@ struct Image {
     }
     return d;
   }
-  ocr_jpeg_img jpeg_desc() const {  // only when !needs_frame()
-    ocr_jpeg_img d;
-    memset(&d, 0, sizeof d);
-    d.rows = jpeg->rows; d.cols = jpeg->cols; d.ncomp = jpeg->ncomp; d.hmax = jpeg->hmax; d.vmax = jpeg->vmax;
-    d.orientation = jpeg->orientation;
-    for (int i = 0; i < jpeg->ncomp; ++i) {
-      const auto& c = jpeg->comp[i];
-      d.comp[i].coef = c.coef.data();
-      memcpy(d.comp[i].quant, c.quant, sizeof c.quant);
-      d.comp[i].bw = c.bw; d.comp[i].bh = c.bh; d.comp[i].dw = c.dw; d.comp[i].dh = c.dh;
-    }
-    return d;
+};
+
+// The descriptors of device-decodable images as ocr_pipe_stage_frames takes them: image i is exactly one of jp[i], pp[i], rp[i].
+// The images must outlive the batch (the descriptors point into them).
+struct DeviceFrames {
+  std::deque<ocr_jpeg_frame> jf;  // (deques: a descriptor stays where it is when the next one is added)
+  std::deque<ocr_png_frame> pf;
+  std::deque<ocr_raw_frame> rf;
+  std::vector<const ocr_jpeg_frame*> jp;
+  std::vector<const ocr_png_frame*> pp;
+  std::vector<const ocr_raw_frame*> rp;
+  void add(const Image& im) {  // only when im.device_decodable()
+    jp.push_back(nullptr); pp.push_back(nullptr); rp.push_back(nullptr);
+    if (im.raw) { rf.push_back(im.raw_frame()); rp.back() = &rf.back(); }
+    else if (im.png) { pf.push_back(im.png_frame()); pp.back() = &pf.back(); }
+    else { jf.push_back(im.jpeg_frame()); jp.back() = &jf.back(); }
   }
+  int stage(ocr_pipe* pipe, int slot) const { return ocr_pipe_stage_frames(pipe, slot, jp.data(), pp.data(), rp.data(), (int)jp.size()); }
 };
 
 inline void check_ocr(int rc, const char* what) {
@@ -516,23 +519,9 @@ class OCRWorker {
       rc = ocr_pipe_run_chars(pipe_, &im, 1, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), chars.data(), nullptr);
     } else
     if (request.image_data.device_decodable()) {  // JPEG, PNG, BMP / PNM: pixels are produced on the device, straight into the staging slot
-      if (request.image_data.raw) {
-        const ocr_raw_frame rf = request.image_data.raw_frame();
-        const ocr_raw_frame* rp = &rf;
-        rc = ocr_pipe_stage_frames(pipe_, 0, nullptr, nullptr, &rp, 1);
-      } else
-      if (request.image_data.png) {
-        const ocr_png_frame pf = request.image_data.png_frame();
-        const ocr_png_frame* pp = &pf;
-        rc = ocr_pipe_stage_coded(pipe_, 0, nullptr, &pp, 1);
-      } else
-      if (request.image_data.needs_frame()) {
-        const ocr_jpeg_frame jf = request.image_data.jpeg_frame();
-        rc = ocr_pipe_stage_jpeg_frames(pipe_, 0, &jf, 1);
-      } else {
-        const ocr_jpeg_img jd = request.image_data.jpeg_desc();
-        rc = ocr_pipe_stage_jpeg(pipe_, 0, &jd, 1);
-      }
+      DeviceFrames frames;
+      frames.add(request.image_data);
+      rc = frames.stage(pipe_, 0);
       if (rc == OCR_OK) rc = ocr_pipe_run_staged(pipe_, 0, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), nullptr);
     } else {
       ocr_img im = request.image_data.view().c();
@@ -563,38 +552,20 @@ class OCRWorker {
     const auto t0 = std::chrono::high_resolution_clock::now();
     std::vector<OCRResult> results(requests.size());
     std::vector<ocr_img> imgs;
-    std::vector<ocr_jpeg_img> jimgs;
-    std::vector<ocr_jpeg_frame> jframes;
+    DeviceFrames frames;
     std::vector<size_t> owner;
-    // a batch of JPEGs only is decoded on the device; a batch with other host pixels in it takes the host path for its
-    // JPEGs and PNGs.  One file that only the general descriptor can hold (CMYK, 4:4:0, ...) puts the whole batch on that
-    // descriptor, not on the host; one PNG puts it on ocr_pipe_stage_coded, which takes both; one raw BMP / PNM frame (there
-    // are none unless OCR_DEVICE_RAW=1: the IPC layer finishes those files on the host) on ocr_pipe_stage_frames, which takes
-    // all three.
-    bool all_jpeg = !char_boxes_, frames = false, coded = false, with_raw = false;
-    for (size_t i = 0; i < requests.size(); ++i) {
-      if (!requests[i]->image_data.empty() && !requests[i]->image_data.device_decodable()) all_jpeg = false;
-      if (requests[i]->image_data.needs_frame()) frames = true;
-      if (requests[i]->image_data.png) coded = true;
-      if (requests[i]->image_data.raw) coded = with_raw = true;
-    }
-    std::vector<ocr_png_frame> pframes;
-    std::vector<ocr_raw_frame> rframes;
-    std::vector<char> is_png;  // 0 JPEG, 1 PNG, 2 raw
+    // a batch of JPEGs, PNGs and raw BMP / PNM frames only (of the last there are none unless OCR_DEVICE_RAW=1: the IPC layer
+    // finishes those files on the host) is decoded on the device, in one ocr_pipe_stage_frames call whatever the mix; a batch
+    // with other host pixels in it takes the host path for all its images
+    bool on_device = !char_boxes_;
+    for (size_t i = 0; i < requests.size(); ++i)
+      if (!requests[i]->image_data.empty() && !requests[i]->image_data.device_decodable()) on_device = false;
     for (size_t i = 0; i < requests.size(); ++i) {
       results[i].request_id = requests[i]->request_id;
       if (requests[i]->image_data.empty()) { results[i].error_message = "Empty image data provided"; continue; }
       results[i].width = requests[i]->image_data.cols;
       results[i].height = requests[i]->image_data.rows;
-      if (all_jpeg && coded) {
-        const int p = requests[i]->image_data.raw ? 2 : requests[i]->image_data.png ? 1 : 0;
-        is_png.push_back((char)p);
-        if (p == 2) rframes.push_back(requests[i]->image_data.raw_frame());
-        else if (p == 1) pframes.push_back(requests[i]->image_data.png_frame());
-        else jframes.push_back(requests[i]->image_data.jpeg_frame());
-      }
-      else if (all_jpeg && frames) jframes.push_back(requests[i]->image_data.jpeg_frame());
-      else if (all_jpeg) jimgs.push_back(requests[i]->image_data.jpeg_desc());
+      if (on_device) frames.add(requests[i]->image_data);
       else {
         const_cast<OCRRequest*>(requests[i])->image_data.materialise();
         imgs.push_back(requests[i]->image_data.view().c());
@@ -614,19 +585,8 @@ class OCRWorker {
     if (char_boxes_) {
       rc = ocr_pipe_run_chars(pipe_, imgs.data(), k, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, batch_chars_.data(), nullptr);
     } else
-    if (all_jpeg) {
-      if (coded) {
-        std::vector<const ocr_jpeg_frame*> jp((size_t)k, nullptr);
-        std::vector<const ocr_png_frame*> pp((size_t)k, nullptr);
-        std::vector<const ocr_raw_frame*> rp((size_t)k, nullptr);
-        for (int j = 0, nj = 0, np = 0, nr = 0; j < k; ++j) {
-          if (is_png[j] == 2) rp[j] = &rframes[nr++];
-          else if (is_png[j]) pp[j] = &pframes[np++];
-          else jp[j] = &jframes[nj++];
-        }
-        rc = with_raw ? ocr_pipe_stage_frames(pipe_, 0, jp.data(), pp.data(), rp.data(), k) : ocr_pipe_stage_coded(pipe_, 0, jp.data(), pp.data(), k);
-      } else
-      rc = frames ? ocr_pipe_stage_jpeg_frames(pipe_, 0, jframes.data(), k) : ocr_pipe_stage_jpeg(pipe_, 0, jimgs.data(), k);
+    if (on_device) {
+      rc = frames.stage(pipe_, 0);
       if (rc == OCR_OK) rc = ocr_pipe_run_staged(pipe_, 0, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, nullptr);
     } else {
       rc = ocr_pipe_run(pipe_, imgs.data(), k, words.data(), k * 1000, off.data(), cnt.data(), ids.data(), k * 1000 * 256, nullptr);

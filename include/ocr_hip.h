@@ -274,6 +274,8 @@ typedef struct ocr_jpeg_img {
   int orientation;
   ocr_jpeg_comp comp[3];
 } ocr_jpeg_img;
+/* (kept for callers built against it: every image becomes the ocr_jpeg_frame that says the same and goes through
+ * ocr_pipe_stage_frames' code; new callers use that entry point) */
 int ocr_pipe_stage_jpeg(ocr_pipe* h, int slot, const ocr_jpeg_img* imgs, int count);
 /* the same device decode of one image with the pixels copied back to the host (tests, tools) */
 int ocr_jpeg_decode(const ocr_jpeg_img* img, int device_id, uint8_t* bgr, size_t cap_bytes);
@@ -309,6 +311,7 @@ typedef struct ocr_jpeg_frame {
   int reserved;          /* 0 */
   ocr_jpeg_fcomp comp[4];
 } ocr_jpeg_frame;
+/* ocr_pipe_stage_frames (below) for JPEG frames only, handed over as an array */
 int ocr_pipe_stage_jpeg_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* frames, int count);
 /* the staged image that was imgs[index] / frames[index] of the slot's last stage call, copied back to the host as
  * packed BGR (tests, tools: what a stage call put into the slot, whichever kernels wrote it); rows / cols: its size */
@@ -346,8 +349,8 @@ int ocr_png_decode(const ocr_png_frame* frame, int device_id, uint8_t* bgr, size
  * ocr_png_time_batch: the same for `count` frames as ONE batch (one upload, one launch per bpp kind), per batch. */
 int ocr_png_time(const ocr_png_frame* frame, int device_id, int iters, double ms[2]);
 int ocr_png_time_batch(const ocr_png_frame* const* frames, int count, int device_id, int iters, double ms[2]);
-/* ocr_pipe_stage_jpeg_frames for a batch that mixes JPEG and PNG requests: image i is jpegs[i] or pngs[i], exactly one of
- * the two non-null (either array may be NULL when no image of the batch uses it). */
+/* ocr_pipe_stage_frames (below) without raw frames: image i is jpegs[i] or pngs[i], exactly one of the two non-null (either
+ * array may be NULL when no image of the batch uses it). */
 int ocr_pipe_stage_coded(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, int count);
 /* BMP and PNM inputs with the pixel half of the decoder on the device: the caller parses the container and does what is
  * serial (run-length expansion, ASCII numbers: host/raw_decode.h, raw::parse); bit, nibble and palette expansion, 5-5-5 /
@@ -375,8 +378,11 @@ int ocr_raw_decode(const ocr_raw_frame* frame, int device_id, uint8_t* bgr, size
  * ms[1] = the pixel-stage kernel; ocr_raw_time_batch: `count` frames as ONE batch (one upload, one launch per kind). */
 int ocr_raw_time(const ocr_raw_frame* frame, int device_id, int iters, double ms[2]);
 int ocr_raw_time_batch(const ocr_raw_frame* const* frames, int count, int device_id, int iters, double ms[2]);
-/* ocr_pipe_stage_coded with raw frames beside the JPEG and PNG ones: image i is jpegs[i], pngs[i] or raws[i], exactly one
- * of the three non-null (an array may be NULL when no image of the batch uses it). */
+/* THE staging entry point for coded images - what new callers use: a batch of JPEG, PNG and raw frames in any mix.  Image i
+ * is jpegs[i], pngs[i] or raws[i], exactly one of the three non-null (an array may be NULL when no image of the batch uses it).
+ * ocr_pipe_stage_jpeg (every image an ocr_jpeg_img), ocr_pipe_stage_jpeg_frames (an array of JPEG frames) and
+ * ocr_pipe_stage_coded (no raws) are kept as equivalents: they validate their own argument list and stage through the same
+ * code, with the same bytes in the slot. */
 int ocr_pipe_stage_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs,
                           const ocr_raw_frame* const* raws, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);

@@ -1,5 +1,5 @@
 """JPEG requests beyond grey / YCbCr 4:4:4, 4:2:2, 4:2:0 on the device (csrc/kernels_jpeg.hip, the general kinds, through
-ocr_jpeg_decode_frame / ocr_pipe_stage_jpeg_frames) and through the service.  Same case table and same expectation as the
+ocr_jpeg_decode_frame / ocr_pipe_stage_frames) and through the service.  Same case table and same expectation as the
 host half, tests/test_jpeg_formats.py: Pillow's decode of the same bytes, bit for bit."""
 import base64
 import os
@@ -70,7 +70,7 @@ def test_old_and_new_entry_points_agree(built, tmp_path):
 
 @pytest.mark.gpu
 def test_one_stage_call_with_a_mixed_batch(built, tmp_path):
-    """One ocr_pipe_stage_jpeg_frames call (decode_tool --stage) with 4:2:0, 4:4:0, CMYK, grey and turned files of several
+    """One ocr_pipe_stage_frames call (decode_tool --stage) with 4:2:0, 4:4:0, CMYK, grey and turned files of several
     sizes, two of them of one oriented size and not adjacent: the classic and the general kernels write one slot, the
     descriptors go to their two arrays, the layout reorders the images by size.  Every staged image, read back with
     ocr_pipe_slot_image, equals the per-file device decode and the expectation, byte for byte."""
@@ -153,7 +153,7 @@ def test_service_answers_cmyk_and_440_requests(built, card, tmp_path, service):
 @pytest.mark.gpu
 def test_concurrent_requests_mix_old_and_new_kinds(built, card, tmp_path, service):
     """Eight concurrent JPEG requests that mix 4:2:0 and grey with CMYK, 4:4:0 and a turned 4:1:1 file (one batch on the
-    device: OCRWorker::processBatch -> ocr_pipe_stage_jpeg_frames): every reply equals the reply the same file gets alone,
+    device: OCRWorker::processBatch -> ocr_pipe_stage_frames): every reply equals the reply the same file gets alone,
     and that one equals the reply to the PNG of the expected pixels."""
     files = card_files(card)
     paths = []

@@ -112,7 +112,7 @@ def test_service_answers_in_the_upright_frame(built, card, tmp_path, service):
 
 @pytest.mark.gpu
 def test_concurrent_jpegs_of_several_orientations(built, card, tmp_path, service):
-    """A burst of JPEG-only requests (decoded on the device as one batch: OCRWorker::processBatch -> ocr_pipe_stage_jpeg)
+    """A burst of JPEG-only requests (decoded on the device as one batch: OCRWorker::processBatch -> ocr_pipe_stage_frames)
     that mixes tags 1, 6 and 8; the card as stored and its transpose stored with tag 6 have the same oriented size and
     share a size group.  Every reply equals the reply the same file gets alone."""
     rgb = card[:, :, ::-1].copy()

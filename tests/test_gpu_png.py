@@ -1,4 +1,4 @@
-"""PNG requests, device half (csrc/kernels_png.hip through ocr_png_decode / ocr_pipe_stage_coded) and through the service.
+"""PNG requests, device half (csrc/kernels_png.hip through ocr_png_decode / ocr_pipe_stage_frames) and through the service.
 Same case table and expectation as the host half, tests/test_png_decode.py: the pixels that cv::imdecode's conversion
 rules give for the samples the file was written from, byte for byte."""
 import base64
@@ -144,7 +144,7 @@ def test_descriptor_validation(built, pkg):
 
 @pytest.mark.gpu
 def test_one_stage_call_with_jpeg_and_png_frames(tool, tmp_path):
-    """One ocr_pipe_stage_coded call (decode_tool --stage) with two JPEG frames and three PNG frames of different bpp
+    """One ocr_pipe_stage_frames call (decode_tool --stage) with two JPEG frames and three PNG frames of different bpp
     kinds, two of the images of one size and not adjacent: every staged image, read back with ocr_pipe_slot_image, equals
     the bytes the single-image calls (ocr_jpeg_decode*, ocr_png_decode) give - for the PNGs, the construction"""
     from PIL import Image
@@ -268,7 +268,7 @@ def test_service_answers_png_requests_like_their_pixels(built, card, tmp_path, s
 @pytest.mark.gpu
 def test_concurrent_clients_mix_png_and_jpeg(built, card, tmp_path, service):
     """Eight concurrent requests that mix the four PNG files with two JPEG files (one batch on the device:
-    OCRWorker::processBatch -> ocr_pipe_stage_coded): every reply equals the reply the same file gets alone"""
+    OCRWorker::processBatch -> ocr_pipe_stage_frames): every reply equals the reply the same file gets alone"""
     from PIL import Image
     paths = []
     for name, (data, _) in card_pngs(card).items():

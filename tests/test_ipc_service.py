@@ -243,7 +243,7 @@ def test_ipc_concurrent_requests_are_batched_with_identical_results(pkg, built, 
             p = tmp_path / f"img{i}.png"
             p.write_bytes(_png_bytes(im))
             paths.append(str(p))
-        # JPEG requests too: a batch of JPEGs only is decoded on the device (OCRWorker::processBatch -> ocr_pipe_stage_jpeg),
+        # JPEG requests too: a batch of JPEGs only is decoded on the device (OCRWorker::processBatch -> ocr_pipe_stage_frames),
         # a batch that mixes them with PNGs finishes its JPEGs on the host - the replies must not depend on which
         for i, (im, ss) in enumerate(zip(imgs, (0, 1, 2, 2))):
             p = tmp_path / f"img{i}.jpg"
