@@ -575,8 +575,9 @@ EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_
             "ocr_pipe_stage_jpeg_frames", "ocr_jpeg_decode_frame", "ocr_jpeg_time_frame", "ocr_pipe_slot_image",
             "ocr_png_decode", "ocr_png_time", "ocr_png_time_batch", "ocr_pipe_stage_coded",
             "ocr_raw_decode", "ocr_raw_time", "ocr_raw_time_batch", "ocr_pipe_stage_frames",
+            "ocr_tiff_decode", "ocr_tiff_time", "ocr_tiff_time_batch", "ocr_pipe_stage_batch",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
-            "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
+            "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_dev_copy_time", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
 
 def _pipe_protos(L):
@@ -685,6 +686,50 @@ class RawFrame:
         h, w = self.c.height, self.c.width
         out = np.zeros((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), np.uint8)
         rc = L.ocr_raw_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
+            err.code = rc
+            raise err
+        return out
+
+
+class ocr_tiff_frame(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("photometric", C.c_int), ("bits_per_sample", C.c_int), ("samples_per_pixel", C.c_int),
+                ("planar", C.c_int), ("predictor", C.c_int), ("big_endian", C.c_int), ("premultiply", C.c_int), ("tile_width", C.c_int),
+                ("tile_height", C.c_int), ("palette", C.c_uint8 * 1024), ("data", C.c_void_p), ("data_len", C.c_size_t)]
+
+
+class ocr_coded_frame(C.Structure):
+    _fields_ = [("kind", C.c_int), ("frame", C.c_void_p)]
+
+
+FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF = 0, 1, 2, 3
+
+
+class TiffFrame:
+    """an ocr_tiff_frame over Python-owned memory.  chunks: the expanded chunks at their nominal size (bytes or uint8 array);
+    tile: (width, height) of a chunk, None for one strip; palette: (n, 4) B,G,R,x or None.  Fields of .c may be changed before
+    a call (the tests' tampering; bits -> bits_per_sample, samples -> samples_per_pixel, w / h -> width / height)."""
+
+    def __init__(self, width, height, photometric, bits, samples, chunks, tile=None, planar=1, predictor=1, big_endian=0, premultiply=0, palette=None):
+        self._data = np.frombuffer(bytes(chunks), np.uint8).copy() if not isinstance(chunks, np.ndarray) else np.ascontiguousarray(chunks, np.uint8).reshape(-1).copy()
+        c = ocr_tiff_frame()
+        c.width, c.height, c.photometric, c.bits_per_sample, c.samples_per_pixel = width, height, photometric, bits, samples
+        c.planar, c.predictor, c.big_endian, c.premultiply = planar, predictor, int(big_endian), premultiply
+        c.tile_width, c.tile_height = tile if tile else (width, height)
+        if palette is not None:
+            flat = np.ascontiguousarray(palette, np.uint8).reshape(-1)
+            C.memmove(c.palette, flat.ctypes.data, min(1024, len(flat)))
+        c.data, c.data_len = self._data.ctypes.data, len(self._data)
+        self.c = c
+
+    def decode(self, device_id=0):
+        """ocr_tiff_decode: the (height, width, 3) BGR image; OcrError where the call refuses"""
+        L = lib()
+        L.ocr_tiff_decode.argtypes = [C.POINTER(ocr_tiff_frame), C.c_int, C.c_void_p, C.c_size_t]
+        h, w = self.c.height, self.c.width
+        out = np.zeros((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), np.uint8)
+        rc = L.ocr_tiff_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
         if rc != 0:
             err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
             err.code = rc

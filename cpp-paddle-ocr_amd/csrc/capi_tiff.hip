@@ -1,0 +1,179 @@
+// Host side of the device TIFF back-end + its C-ABI entry points.
+#include <algorithm>
+#include <cstring>
+
+#include "capi_common.h"
+#include "tiff_stage.h"
+
+namespace ocr {
+
+namespace {
+
+// host/tiff_decode.h Geometry: what follows from a (sound) descriptor
+struct TiffGeometry {
+  int across = 0, down = 0, planes = 1, colour = 1, used = 1;
+  size_t row_bytes = 0, chunk_bytes = 0, total = 0;
+};
+
+// host/tiff_decode.h fault(), rule for rule
+const char* tiff_fault(const ocr_tiff_frame& f, TiffGeometry& g) {
+  if (f.width <= 0 || f.height <= 0 || (long)f.width * f.height > (64L << 20)) return "tiff frame: width and height must be positive and at most 64 Mpixel together";
+  if (f.bits_per_sample != 1 && f.bits_per_sample != 2 && f.bits_per_sample != 4 && f.bits_per_sample != 8 && f.bits_per_sample != 16)
+    return "tiff frame: bits per sample must be 1, 2, 4, 8 or 16";
+  if (f.samples_per_pixel < 1 || f.samples_per_pixel > 16) return "tiff frame: samples per pixel must be 1 .. 16";
+  if (f.planar != 1 && f.planar != 2) return "tiff frame: planar must be 1 or 2";
+  if (f.predictor != 1 && f.predictor != 2) return "tiff frame: predictor must be 1 or 2";
+  if ((f.big_endian | 1) != 1 || (f.premultiply | 1) != 1) return "tiff frame: big_endian and premultiply must be 0 or 1";
+  const int ph = f.photometric, bits = f.bits_per_sample, spp = f.samples_per_pixel;
+  if (ph != 0 && ph != 1 && ph != 2 && ph != 3 && ph != 5) return "tiff frame: photometric must be 0, 1, 2, 3 or 5";
+  g.colour = ph == 2 ? 3 : ph == 5 ? 4 : 1;
+  if (spp < g.colour) return "tiff frame: fewer samples per pixel than the photometric needs";
+  if (bits < 8 && (ph == 2 || ph == 5 || spp != 1 || f.predictor != 1 || f.planar != 1)) return "tiff frame: 1, 2 and 4 bits: grey or palette, one sample, no predictor, chunky";
+  if (ph == 3 && (bits > 8 || f.planar != 1)) return "tiff frame: palette: at most 8 bits, chunky";
+  if (ph == 5 && (bits != 8 || f.planar != 1)) return "tiff frame: CMYK: 8 bits, chunky";
+  if (f.planar == 2 && ph != 2 && spp < 2) return "tiff frame: planar 2: RGB, or grey with extra samples";
+  if (f.premultiply && (spp <= g.colour || !(ph == 2 || (ph <= 1 && f.planar == 2)))) return "tiff frame: premultiply: RGB with alpha, or grey with alpha in planes";
+  if (f.tile_width <= 0 || f.tile_height <= 0 || (long)f.tile_width * f.tile_height > (64L << 20))
+    return "tiff frame: tile_width and tile_height must be positive and at most 64 Mpixel together";
+  g.used = g.colour + f.premultiply;
+  g.planes = f.planar == 2 ? spp : 1;
+  g.across = (int)(((long)f.width + f.tile_width - 1) / f.tile_width);
+  g.down = (int)(((long)f.height + f.tile_height - 1) / f.tile_height);
+  g.row_bytes = ((size_t)f.tile_width * (f.planar == 2 ? 1 : spp) * bits + 7) / 8;  // <= 2^26 * 32
+  g.chunk_bytes = g.row_bytes * (size_t)f.tile_height;                              // <= 2^26 * 32 + 2^26
+  g.total = g.chunk_bytes * (size_t)g.across * g.down * g.planes;                   // < 2^32 * 2^26 * 2^4
+  if (g.total > ((size_t)1 << 30)) return "tiff frame: the chunks at their nominal size exceed 1 GiB";
+  if (!f.data || f.data_len < g.total) return "tiff frame: data_len is less than the chunks at their nominal size";
+  return nullptr;
+}
+
+}  // namespace
+
+const char* tiff_frame_fault(const ocr_tiff_frame& f) {
+  TiffGeometry g;
+  return tiff_fault(f, g);
+}
+
+void tiff_relaunch(const TiffScratch& sc, const TiffLaunch& L, hipStream_t s) {
+  for (int k = 0; k < kTiffKinds; ++k)
+    if (L.count[k] > 0) launch_tiff(k, sc.id.p + L.first[k], L.count[k], L.units[k], s);
+}
+
+int tiff_decode_async(const ocr_tiff_frame* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
+                      TiffLaunch* launched) {
+  std::vector<size_t> off((size_t)count);
+  std::vector<TiffGeometry> geo((size_t)count);
+  size_t bytes = 0;
+  TiffLaunch L;
+  auto kind_of = [](const ocr_tiff_frame& f) { return f.bits_per_sample < 8 ? 0 : f.bits_per_sample == 8 ? 1 : 2; };
+  for (int i = 0; i < count; ++i) {
+    if (!imgs[i]) { err = "null tiff frame"; return OCR_ERR_ARG; }
+    if (const char* fault = tiff_fault(*imgs[i], geo[i])) { err = fault; return OCR_ERR_ARG; }
+    off[i] = bytes;
+    bytes += (geo[i].total + 255) & ~(size_t)255;
+    L.count[kind_of(*imgs[i])]++;
+  }
+  L.bytes = bytes;
+  if (!sc.data.ensure(bytes + 256, err) || !sc.id.ensure((size_t)count, err)) return OCR_ERR_DEVICE;
+  if (!sc.stage.reserve(bytes, err)) return OCR_ERR_DEVICE;
+  parallel_copy((size_t)count, bytes, [&](size_t i) { memcpy(sc.stage.p + off[i], imgs[i]->data, geo[i].total); });  // chunks -> pinned memory
+  // the descriptors ordered by the kernel that takes them, the units of a kind numbered through its frames
+  for (int k = 1; k < kTiffKinds; ++k) L.first[k] = L.first[k - 1] + L.count[k - 1];
+  int next[kTiffKinds];
+  std::copy(L.first, L.first + kTiffKinds, next);
+  std::vector<TiffImageDesc> id((size_t)count);
+  for (int i = 0; i < count; ++i) {
+    const ocr_tiff_frame& f = *imgs[i];
+    const TiffGeometry& g = geo[i];
+    const int kind = kind_of(f);
+    TiffImageDesc& d = id[next[kind]++];
+    memset(&d, 0, sizeof d);
+    d.data = sc.data.p + off[i];
+    d.bgr = dst[i];
+    d.first_unit = L.units[kind];
+    d.chunk_bytes = g.chunk_bytes;
+    d.plane_bytes = f.planar == 2 ? g.chunk_bytes * (size_t)g.across * g.down : 0;
+    d.row_bytes = g.row_bytes;
+    d.width = f.width; d.height = f.height; d.tile_width = f.tile_width; d.tile_height = f.tile_height; d.across = g.across; d.down = g.down;
+    d.bits = f.bits_per_sample; d.samples = f.samples_per_pixel; d.used = g.used;
+    d.mode = f.photometric == 3 ? TIFF_PALETTE : f.photometric == 5 ? TIFF_CMYK : f.photometric == 2 ? TIFF_RGB : f.planar == 2 ? TIFF_GREY_PLANES : TIFF_GREY;
+    d.predictor = f.predictor; d.big_endian = f.big_endian; d.invert = f.photometric == 0; d.premultiply = f.premultiply;
+    d.lanes_per_row = tiff_lanes_per_row(std::min(f.tile_width, f.width));
+    d.rows_per_unit = 64 / d.lanes_per_row;
+    d.units_per_chunk = (unsigned)((std::min(f.tile_height, f.height) + d.rows_per_unit - 1) / d.rows_per_unit);
+    L.units[kind] += (unsigned long long)g.across * g.down * d.units_per_chunk;  // <= chunks * rows of a chunk: < 2^27
+    for (int k = 0; k < 256; ++k) d.palette[k] = (uint32_t)f.palette[4 * k] | ((uint32_t)f.palette[4 * k + 1] << 8) | ((uint32_t)f.palette[4 * k + 2] << 16);
+  }
+  if (!sc.stage.upload(sc.data.p, bytes, s, err) ||
+      hipMemcpyAsync(sc.id.p, id.data(), id.size() * sizeof(TiffImageDesc), hipMemcpyHostToDevice, s) != hipSuccess) {
+    err = "tiff chunks upload failed";
+    return OCR_ERR_DEVICE;
+  }
+  tiff_relaunch(sc, L, s);
+  if (launched) *launched = L;
+  if (hipGetLastError() != hipSuccess) { err = "tiff pixel kernels failed to launch"; return OCR_ERR_DEVICE; }
+  return OCR_OK;
+}
+
+}  // namespace ocr
+
+using namespace ocr;
+
+namespace {
+
+int time_batch(const ocr_tiff_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
+  for (int i = 0; i < count; ++i) {
+    if (!frames[i]) return fail(OCR_ERR_ARG, "null argument");
+    if (const char* fault = tiff_frame_fault(*frames[i])) return fail(OCR_ERR_ARG, fault);
+  }
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  std::vector<DevBuf<uint8_t>> out((size_t)count);
+  std::vector<uint8_t*> dst((size_t)count);
+  std::string err;
+  for (int i = 0; i < count; ++i) {
+    if (!out[i].ensure((size_t)frames[i]->width * frames[i]->height * 3, err)) return fail(OCR_ERR_DEVICE, err);
+    dst[i] = out[i].p;
+  }
+  TiffScratch sc;
+  TiffLaunch L;
+  rc = tiff_decode_async(frames, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
+  if (rc) return fail(rc, err);
+  return time_phases(iters, ms, [&] { return hipMemcpyAsync(sc.data.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
+                     [&] { tiff_relaunch(sc, L, nullptr); return hipSuccess; });
+}
+
+}  // namespace
+
+extern "C" int ocr_tiff_decode(const ocr_tiff_frame* frame, int device_id, uint8_t* bgr, size_t cap) {
+  if (!frame || !bgr) return fail(OCR_ERR_ARG, "null argument");
+  // (the descriptor first: a bad one is an argument error wherever the call is made)
+  if (const char* fault = tiff_frame_fault(*frame)) return fail(OCR_ERR_ARG, fault);
+  const size_t bytes = (size_t)frame->width * frame->height * 3;
+  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  TiffScratch sc;
+  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return tiff_decode_async(&frame, 1, dst, sc, nullptr, err); });
+}
+
+extern "C" int ocr_tiff_time(const ocr_tiff_frame* frame, int device_id, int iters, double ms[2]) {
+  if (!frame || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
+  return time_batch(&frame, 1, device_id, iters, ms);
+}
+
+extern "C" int ocr_tiff_time_batch(const ocr_tiff_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
+  if (!frames || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
+  return time_batch(frames, count, device_id, iters, ms);
+}
+
+// measurement aid (decode_tool --time): the device time of one plain copy KERNEL over `bytes` (16 bytes a lane, grid stride:
+// launch_plain_copy), the yardstick the pixel stage's time is set against in the same run
+extern "C" int ocr_dev_copy_time(void* dst, const void* src, size_t bytes, int iters, double* ms) {
+  if (!dst || !src || !ms || iters <= 0 || bytes < 16 || (((uintptr_t)dst | (uintptr_t)src) & 15)) return fail(OCR_ERR_ARG, "null, unaligned or empty argument");
+  launch_plain_copy(dst, src, bytes, nullptr);  // (the first launch is not timed)
+  double t[2];
+  const int rc = time_phases(iters, t, [&] { launch_plain_copy(dst, src, bytes, nullptr); return hipGetLastError(); }, [] { return hipSuccess; });
+  if (rc == OCR_OK) *ms = t[0];
+  return rc;
+}

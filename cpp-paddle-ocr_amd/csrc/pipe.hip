@@ -14,6 +14,7 @@
 #include "jpeg_stage.h"
 #include "png_stage.h"
 #include "raw_stage.h"
+#include "tiff_stage.h"
 #include "stages.h"
 
 using namespace ocr;
@@ -429,6 +430,7 @@ struct ocr_pipe {
   JpegScratch jpeg;
   PngScratch png;
   RawScratch raw;
+  TiffScratch tiff;
   DevBuf<uint8_t> work;  // the requests' clones (OCRRequest copies the Mat, ocr_worker.h:28-29): cls rotates in place on them
   // Two batches in flight (round 5, ocr_pipe_run_device_on / ocr_pipe_run_staged_on): a call that names a chain runs its WHOLE
   // batch on that chain's worker, with a clone buffer of the chain's own; calls on different chains may run concurrently from
@@ -499,35 +501,44 @@ struct ocr_pipe {
     return OCR_OK;
   }
 
-  // ---- stage a batch of JPEG coefficients, inflated PNG streams and stored BMP / PNM rows, in any mix: the three pixel stages run
-  // on the copy stream, into the slot.  Image i is jpegs[i], pngs[i] or raws[i] (validated by the caller before the sizes are used
-  // - a refused batch leaves the slot as it was: exactly one of them, and a sound descriptor)
-  int stage_coded(int si, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, const ocr_raw_frame* const* raws, int count,
-                  std::string& err) {
+  // ---- stage a batch of JPEG coefficients, inflated PNG streams, stored BMP / PNM rows and expanded TIFF chunks, in any mix: the
+  // four pixel stages run on the copy stream, into the slot.  Image i is frames[i], a tagged descriptor (validated by the caller
+  // before the sizes are used - a refused batch leaves the slot as it was: a known kind, and a sound descriptor)
+  int stage_coded(int si, const ocr_coded_frame* frames, int count, std::string& err) {
     StageSlot& S = slots[si];
-    auto jp = [&](int i) { return jpegs ? jpegs[i] : nullptr; };
-    auto pn = [&](int i) { return pngs ? pngs[i] : nullptr; };
+    auto jp = [&](int i) { return (const ocr_jpeg_frame*)frames[i].frame; };
+    auto pn = [&](int i) { return (const ocr_png_frame*)frames[i].frame; };
+    auto rw = [&](int i) { return (const ocr_raw_frame*)frames[i].frame; };
+    auto tf = [&](int i) { return (const ocr_tiff_frame*)frames[i].frame; };
     int rc = layout(S, count, [&](int i, int& r, int& c) {
       // the oriented size: a 40 x 72 image and a 72 x 40 one that EXIF turns by 90 degrees share a size group and a det pass
-      if (const ocr_jpeg_frame* j = jp(i)) { r = jpeg_out_rows(*j); c = jpeg_out_cols(*j); }
-      else if (const ocr_png_frame* p = pn(i)) { r = p->height; c = p->width; }
-      else { r = raws[i]->height; c = raws[i]->width; }
+      switch (frames[i].kind) {
+        case OCR_FRAME_JPEG: r = jpeg_out_rows(*jp(i)); c = jpeg_out_cols(*jp(i)); break;
+        case OCR_FRAME_PNG: r = pn(i)->height; c = pn(i)->width; break;
+        case OCR_FRAME_RAW: r = rw(i)->height; c = rw(i)->width; break;
+        default: r = tf(i)->height; c = tf(i)->width; break;
+      }
     }, err);
     if (rc) return rc;
     std::vector<ocr_jpeg_frame> jf;
     std::vector<const ocr_png_frame*> pf;
     std::vector<const ocr_raw_frame*> rf;
-    std::vector<uint8_t*> jdst, pdst, rdst;
+    std::vector<const ocr_tiff_frame*> tff;
+    std::vector<uint8_t*> jdst, pdst, rdst, tdst;
     for (int k = 0; k < count; ++k) {
       const int i = S.imgs[k].orig;
       uint8_t* d = S.dev.p + S.imgs[k].off;
-      if (const ocr_jpeg_frame* j = jp(i)) { jf.push_back(*j); jdst.push_back(d); }
-      else if (const ocr_png_frame* p = pn(i)) { pf.push_back(p); pdst.push_back(d); }
-      else { rf.push_back(raws[i]); rdst.push_back(d); }
+      switch (frames[i].kind) {
+        case OCR_FRAME_JPEG: jf.push_back(*jp(i)); jdst.push_back(d); break;
+        case OCR_FRAME_PNG: pf.push_back(pn(i)); pdst.push_back(d); break;
+        case OCR_FRAME_RAW: rf.push_back(rw(i)); rdst.push_back(d); break;
+        default: tff.push_back(tf(i)); tdst.push_back(d); break;
+      }
     }
     if (!jf.empty()) rc = jpeg_decode_async(jf.data(), (int)jf.size(), jdst.data(), jpeg, copy_stream, err);
     if (!rc && !pf.empty()) rc = png_decode_async(pf.data(), (int)pf.size(), pdst.data(), png, copy_stream, err);
     if (!rc && !rf.empty()) rc = raw_decode_async(rf.data(), (int)rf.size(), rdst.data(), raw, copy_stream, err);
+    if (!rc && !tff.empty()) rc = tiff_decode_async(tff.data(), (int)tff.size(), tdst.data(), tiff, copy_stream, err);
     if (rc) return rc;
     if (hipEventRecord(S.ready, copy_stream) != hipSuccess) { err = "hipEventRecord failed"; return OCR_ERR_DEVICE; }
     S.staged = true;
@@ -800,18 +811,17 @@ int ocr_pipe_run_device_on(ocr_pipe* h, int chain, const void* dev_bgr, int rows
 
 static bool stage_args_ok(const ocr_pipe* h, bool images, int slot, int count) { return h && images && count >= 1 && (slot == 0 || slot == 1); }
 
-// the tail of the four entry points below: every frame has been validated
-static int stage_validated(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs,
-                           const ocr_raw_frame* const* raws, int count) {
+// the tail of the five entry points below: every frame has been validated
+static int stage_validated(ocr_pipe* h, int slot, const std::vector<ocr_coded_frame>& frames) {
   CAPI_HIP(rt_set_device(h->device));
   std::string err;
-  const int rc = h->stage_coded(slot, jpegs, pngs, raws, count, err);
+  const int rc = h->stage_coded(slot, frames.data(), (int)frames.size(), err);
   return rc ? fail(rc, err) : OCR_OK;
 }
-static std::vector<const ocr_jpeg_frame*> pointers_to(const ocr_jpeg_frame* frames, int count) {
-  std::vector<const ocr_jpeg_frame*> p((size_t)count);
-  for (int i = 0; i < count; ++i) p[i] = frames + i;
-  return p;
+static std::vector<ocr_coded_frame> tagged(const ocr_jpeg_frame* frames, int count) {
+  std::vector<ocr_coded_frame> t((size_t)count);
+  for (int i = 0; i < count; ++i) t[i] = ocr_coded_frame{OCR_FRAME_JPEG, frames + i};
+  return t;
 }
 
 int ocr_pipe_stage(ocr_pipe* h, int slot, const ocr_img* imgs, int count) {
@@ -833,19 +843,20 @@ int ocr_pipe_stage_jpeg(ocr_pipe* h, int slot, const ocr_jpeg_img* imgs, int cou
     frames[i] = jpeg_frame_of(imgs[i]);
     if (const char* fault = jpeg_frame_fault(frames[i])) return fail(OCR_ERR_ARG, fault);
   }
-  return stage_validated(h, slot, pointers_to(frames.data(), count).data(), nullptr, nullptr, count);
+  return stage_validated(h, slot, tagged(frames.data(), count));
 }
 
 int ocr_pipe_stage_jpeg_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* frames, int count) {
   if (!stage_args_ok(h, frames, slot, count)) return fail(OCR_ERR_ARG, "bad argument");
   for (int i = 0; i < count; ++i)
     if (const char* fault = jpeg_frame_fault(frames[i])) return fail(OCR_ERR_ARG, fault);
-  return stage_validated(h, slot, pointers_to(frames, count).data(), nullptr, nullptr, count);
+  return stage_validated(h, slot, tagged(frames, count));
 }
 
 int ocr_pipe_stage_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs,
                           const ocr_raw_frame* const* raws, int count) {
   if (!stage_args_ok(h, jpegs || pngs || raws, slot, count)) return fail(OCR_ERR_ARG, "bad argument");
+  std::vector<ocr_coded_frame> t((size_t)count);
   for (int i = 0; i < count; ++i) {
     const ocr_jpeg_frame* j = jpegs ? jpegs[i] : nullptr;
     const ocr_png_frame* p = pngs ? pngs[i] : nullptr;
@@ -854,8 +865,27 @@ int ocr_pipe_stage_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jp
       return fail(OCR_ERR_ARG, raws ? "every image is a JPEG frame, a PNG frame or a raw frame: exactly one of the three"
                                     : "every image is a JPEG frame or a PNG frame, not both and not neither");
     if (const char* fault = j ? jpeg_frame_fault(*j) : p ? png_frame_fault(*p) : raw_frame_fault(*r)) return fail(OCR_ERR_ARG, fault);
+    t[i] = j ? ocr_coded_frame{OCR_FRAME_JPEG, j} : p ? ocr_coded_frame{OCR_FRAME_PNG, p} : ocr_coded_frame{OCR_FRAME_RAW, r};
   }
-  return stage_validated(h, slot, jpegs, pngs, raws, count);
+  return stage_validated(h, slot, t);
+}
+
+int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, int count) {
+  if (!stage_args_ok(h, frames, slot, count)) return fail(OCR_ERR_ARG, "bad argument");
+  for (int i = 0; i < count; ++i) {
+    const void* f = frames[i].frame;
+    if (!f) return fail(OCR_ERR_ARG, "null frame in the batch");
+    const char* fault;
+    switch (frames[i].kind) {
+      case OCR_FRAME_JPEG: fault = jpeg_frame_fault(*(const ocr_jpeg_frame*)f); break;
+      case OCR_FRAME_PNG: fault = png_frame_fault(*(const ocr_png_frame*)f); break;
+      case OCR_FRAME_RAW: fault = raw_frame_fault(*(const ocr_raw_frame*)f); break;
+      case OCR_FRAME_TIFF: fault = tiff_frame_fault(*(const ocr_tiff_frame*)f); break;
+      default: fault = "frame kind is not an ocr_frame_kind"; break;
+    }
+    if (fault) return fail(OCR_ERR_ARG, fault);
+  }
+  return stage_validated(h, slot, std::vector<ocr_coded_frame>(frames, frames + count));
 }
 
 int ocr_pipe_stage_coded(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs, int count) {

@@ -22,6 +22,12 @@
 // decode_tool --time <iters> <bmp or pnm file> [<batch>]: the same for a BMP / PNM (ocr_raw_time / ocr_raw_time_batch: upload
 // of the stored rows, pixel stage), and "host_pixels_ms": raw::pixels of the same frame(s) on one host thread, the stage
 // the device stage would replace.
+// A TIFF's pixel half (predictor, tile placement, planar to chunky, bit expansion, palette, 16 -> 8 bits, CMYK, alpha) runs on
+// the GPU with --device / --frame too, through ocr_tiff_decode (whatever OCR_DEVICE_TIFF says); --stage takes TIFFs in the mix
+// (ocr_pipe_stage_batch); --time <iters> <tiff file> [<batch>]: ocr_tiff_time / ocr_tiff_time_batch (upload of the expanded
+// chunks, pixel stage), "host_pixels_ms" (tiff::pixels on one host thread), "bytes_in" / "bytes_out" (what the kernel reads and
+// writes) and "copy_ms": a plain copy kernel that reads and writes as many bytes in all (ocr_dev_copy_time), timed in the same run.
+// decode_tool --stage-frames <model dir> ...: as --stage, through ocr_pipe_stage_frames (the three-array entry point: no TIFFs).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -58,6 +64,38 @@ static int time_device(int iters, const char* in, int batch) {
     if ((batch > 1 ? ocr_png_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_png_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
     printf("{\"size\": [%d, %d], \"color_type\": %d, \"bit_depth\": %d, \"interlace\": %d, \"segments\": %d, \"batch\": %d, \"iters\": %d, "
            "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f}\n", d.height, d.width, d.color_type, d.bit_depth, d.interlace, d.nsegments, (int)all.size(), iters, ms[0], ms[1]);
+    return 0;
+  }
+  if (PaddleOCR::ipc::is_tiff(bytes.data(), bytes.size())) {
+    auto f = std::make_shared<PaddleOCR::tiff::Frame>();
+    if (!PaddleOCR::tiff::parse(bytes.data(), bytes.size(), *f)) { fprintf(stderr, "decode failed\n"); return 1; }
+    im.rows = f->height; im.cols = f->width;
+    im.tiff = f;
+    const ocr_tiff_frame d = im.tiff_frame();
+    std::vector<const ocr_tiff_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
+    double ms[2];
+    if ((batch > 1 ? ocr_tiff_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_tiff_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    std::vector<uint8_t> px;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < iters; ++i)
+      for (size_t k = 0; k < all.size(); ++k) PaddleOCR::tiff::pixels(*f, px);
+    const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+    // the yardstick of the same run: a plain copy kernel that reads and writes as many bytes in all as the pixel stage (chunks in, BGR out)
+    const size_t in = f->data.size() * all.size(), out = (size_t)d.width * d.height * 3 * all.size(), half = (in + out) / 2;
+    double copy_ms = -1;
+    void *a = nullptr, *b = nullptr;
+    if (ocr_dev_alloc(&a, half) == OCR_OK && ocr_dev_alloc(&b, half) == OCR_OK) {
+      std::vector<uint8_t> zero(half);
+      ocr_dev_upload(a, zero.data(), half);
+      copy_ms = 0;
+      if (ocr_dev_copy_time(b, a, half, iters, &copy_ms) != OCR_OK) copy_ms = -1;
+    }
+    if (a) ocr_dev_free(a);
+    if (b) ocr_dev_free(b);
+    printf("{\"size\": [%d, %d], \"photometric\": %d, \"bits\": %d, \"samples\": %d, \"planar\": %d, \"predictor\": %d, \"tile\": [%d, %d], \"batch\": %d, \"iters\": %d, "
+           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"bytes_in\": %zu, \"bytes_out\": %zu, \"copy_ms\": %.5f}\n",
+           d.height, d.width, d.photometric, d.bits_per_sample, d.samples_per_pixel, d.planar, d.predictor, d.tile_width, d.tile_height, (int)all.size(), iters,
+           ms[0], ms[1], host_ms, in, out, copy_ms);
     return 0;
   }
   if (bytes.size() > 2 && ((bytes[0] == 'B' && bytes[1] == 'M') || (bytes[0] == 'P' && bytes[1] >= '1' && bytes[1] <= '6'))) {
@@ -136,7 +174,22 @@ static int read_back(ocr_pipe* pipe, const Batch& b, const std::string& suffix) 
   return 0;
 }
 
-static int stage_batches(const std::string& model_dir, int nargs, char** args, bool ways) {
+// the batch through ocr_pipe_stage_frames, the entry point of three arrays (JPEG, PNG and raw frames only)
+static int stage_three_arrays(ocr_pipe* pipe, const Batch& b) {
+  const size_t n = b.frames.list.size();
+  std::vector<const ocr_jpeg_frame*> jp(n, nullptr);
+  std::vector<const ocr_png_frame*> pp(n, nullptr);
+  std::vector<const ocr_raw_frame*> rp(n, nullptr);
+  for (size_t i = 0; i < n; ++i) {
+    const ocr_coded_frame& f = b.frames.list[i];
+    if (f.kind == OCR_FRAME_JPEG) jp[i] = (const ocr_jpeg_frame*)f.frame;
+    else if (f.kind == OCR_FRAME_PNG) pp[i] = (const ocr_png_frame*)f.frame;
+    else if (f.kind == OCR_FRAME_RAW) rp[i] = (const ocr_raw_frame*)f.frame;
+  }
+  return ocr_pipe_stage_frames(pipe, 0, jp.data(), pp.data(), rp.data(), (int)n);
+}
+
+static int stage_batches(const std::string& model_dir, int nargs, char** args, bool ways, bool three_arrays = false) {
   std::vector<Batch> batches(1);
   for (int a = 0; a < nargs; ++a) {
     if (!strcmp(args[a], "--")) { batches.emplace_back(); continue; }
@@ -175,7 +228,7 @@ static int stage_batches(const std::string& model_dir, int nargs, char** args, b
     }
   } else {
     for (const Batch& b : batches) {
-      if (b.frames.stage(pipe, 0) != OCR_OK) { fprintf(stderr, "staging failed: %s\n", ocr_last_error()); rc = 1; }
+      if ((three_arrays ? stage_three_arrays(pipe, b) : b.frames.stage(pipe, 0)) != OCR_OK) { fprintf(stderr, "staging failed: %s\n", ocr_last_error()); rc = 1; }
       if (!rc) rc = read_back(pipe, b, "");
       if (rc) break;
     }
@@ -188,6 +241,11 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
+  if (im.device_decodable() && im.tiff) {
+    const ocr_tiff_frame d = im.tiff_frame();
+    im.pixels.resize((size_t)d.height * d.width * 3);
+    if (ocr_tiff_decode(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+  } else
   if (im.device_decodable() && im.raw) {
     const ocr_raw_frame d = im.raw_frame();
     im.pixels.resize((size_t)d.height * d.width * 3);
@@ -215,6 +273,7 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
 
 int main(int argc, char** argv) {
   if ((argc == 4 || argc == 5) && !strcmp(argv[1], "--time")) return time_device(atoi(argv[2]), argv[3], argc == 5 ? atoi(argv[4]) : 1);
+  if (argc >= 5 && !strcmp(argv[1], "--stage-frames")) return stage_batches(argv[2], argc - 3, argv + 3, false, true);
   if (argc >= 5 && (!strcmp(argv[1], "--stage") || !strcmp(argv[1], "--stage-ways"))) return stage_batches(argv[2], argc - 3, argv + 3, argv[1][7] != 0);
   const bool frame = argc > 1 && !strcmp(argv[1], "--frame");
   const bool device = frame || (argc > 1 && !strcmp(argv[1], "--device"));

@@ -44,6 +44,7 @@
 #include "paddle_ocr_hip.h"
 #include "png_decode.h"
 #include "raw_decode.h"
+#include "tiff_decode.h"
 
 namespace PaddleOCR {
 namespace ipc {
@@ -212,6 +213,28 @@ inline bool decode_ppm(const std::vector<uint8_t>& d, Image& im, bool device_pix
 inline bool decode_bmp(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false) {
   return d.size() >= 2 && d[0] == 'B' && d[1] == 'M' && decode_raw(d, im, device_pixels, force_device);
 }
+// TIFF as cv::imdecode(IMREAD_COLOR) returns it (tiff_decode.h: classic TIFF, strips and tiles, uncompressed / PackBits / LZW /
+// Deflate, the sample forms libtiff's RGBA interface reads).  device_pixels / force_device as for BMP and PNM; the switch is
+// OCR_DEVICE_TIFF, read once: =1 stops after the chunks are expanded and leaves predictor, conversion and placement to the
+// worker (frames within the device stage's bounds, tiff::Frame::device_ok), =0 or unset finishes every file on this host thread.
+constexpr bool TIFF_DEVICE_DEFAULT = false;
+inline bool tiff_device_enabled() {
+  static const char* env = getenv("OCR_DEVICE_TIFF");
+  return env && env[0] ? env[0] != '0' : TIFF_DEVICE_DEFAULT;
+}
+inline bool is_tiff(const uint8_t* d, size_t n) {
+  return n >= 4 && ((d[0] == 'I' && d[1] == 'I' && d[2] == 42 && d[3] == 0) || (d[0] == 'M' && d[1] == 'M' && d[2] == 0 && d[3] == 42));
+}
+inline bool decode_tiff(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false) {
+  if (!is_tiff(d.data(), d.size())) return false;
+  auto f = std::make_shared<tiff::Frame>();
+  if (!tiff::parse(d.data(), d.size(), *f)) return false;
+  im.pixels.clear();
+  im.rows = f->height; im.cols = f->width;
+  if (device_pixels && f->device_ok && (force_device || tiff_device_enabled())) { im.tiff = std::move(f); return true; }
+  if (!tiff::pixels(*f, im.pixels)) { im = Image(); return false; }
+  return true;
+}
 // libpng16 simplified API (png.h: png_image, PNG_IMAGE_VERSION 1, PNG_FORMAT_BGR = 0x12), resolved at run time
 struct PngImage {
   void* opaque;
@@ -285,10 +308,11 @@ inline bool decode_jpeg(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!dec.decode(d.data(), d.size(), im.pixels, im.rows, im.cols)) { im = Image(); return false; }
   return true;
 }
-// force_device: PNG and BMP / PNM take the device route whatever OCR_DEVICE_PNG / OCR_DEVICE_RAW say (decode_tool)
+// force_device: PNG, BMP / PNM and TIFF take the device route whatever OCR_DEVICE_PNG / OCR_DEVICE_RAW / OCR_DEVICE_TIFF say (decode_tool)
 inline bool decode_image(const std::vector<uint8_t>& bytes, Image& im, bool device_pixels = false, bool force_device = false) {
   return decode_png(bytes, im, device_pixels, force_device) || decode_jpeg(bytes, im, device_pixels) ||
-         decode_ppm(bytes, im, device_pixels, force_device) || decode_bmp(bytes, im, device_pixels, force_device);
+         decode_ppm(bytes, im, device_pixels, force_device) || decode_bmp(bytes, im, device_pixels, force_device) ||
+         decode_tiff(bytes, im, device_pixels, force_device);
 }
 inline bool read_file(const std::string& path, std::vector<uint8_t>& out) {
   std::ifstream f(path, std::ios::binary);

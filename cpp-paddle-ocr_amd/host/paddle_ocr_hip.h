@@ -32,6 +32,7 @@
 #include "jpeg_decode.h"
 #include "png_decode.h"
 #include "raw_decode.h"
+#include "tiff_decode.h"
 
 namespace PaddleOCR {
 
@@ -58,6 +59,9 @@ struct Image {
   // a BMP / PNM whose container has been parsed (and run-length stream or ASCII numbers expanded): the worker converts the
   // stored rows on the device (ocr_pipe_stage_frames)
   std::shared_ptr<raw::Frame> raw;
+  // a TIFF whose container has been parsed and whose chunks have been expanded (PackBits / LZW / Deflate): the worker undoes
+  // the predictor, converts and places the chunks on the device (ocr_pipe_stage_batch)
+  std::shared_ptr<tiff::Frame> tiff;
   Image() = default;
   explicit Image(const ImageView& v) : rows(v.rows), cols(v.cols) {
     if (!v.empty()) {
@@ -66,10 +70,15 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg && !png && !raw; }
-  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw); }
-  void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM on the host
+  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff); }
+  void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM / TIFF on the host
     if (!device_decodable()) return;
+    if (tiff) {
+      if (!tiff::pixels(*tiff, pixels)) throw std::runtime_error("TIFF conversion failed");
+      tiff.reset();
+      return;
+    }
     if (raw) {
       if (!raw::pixels(*raw, pixels)) throw std::runtime_error("BMP / PNM conversion failed");
       raw.reset();
@@ -103,6 +112,16 @@ struct Image {
     d.data = raw->data.data(); d.data_len = raw->data.size();
     return d;
   }
+  ocr_tiff_frame tiff_frame() const {  // only when tiff
+    ocr_tiff_frame d;
+    memset(&d, 0, sizeof d);
+    d.width = tiff->width; d.height = tiff->height; d.photometric = tiff->photometric; d.bits_per_sample = tiff->bits;
+    d.samples_per_pixel = tiff->samples; d.planar = tiff->planar; d.predictor = tiff->predictor; d.big_endian = tiff->big_endian;
+    d.premultiply = tiff->premultiply; d.tile_width = tiff->tile_width; d.tile_height = tiff->tile_height;
+    memcpy(d.palette, tiff->palette, sizeof d.palette);
+    d.data = tiff->data.data(); d.data_len = tiff->data.size();
+    return d;
+  }
   ocr_jpeg_frame jpeg_frame() const {  // only when jpeg: every file the host half reads (any sampling, grey, YCbCr, RGB, CMYK, YCCK)
     ocr_jpeg_frame d;
     memset(&d, 0, sizeof d);
@@ -117,22 +136,21 @@ struct Image {
   }
 };
 
-// The descriptors of device-decodable images as ocr_pipe_stage_frames takes them: image i is exactly one of jp[i], pp[i], rp[i].
+// The descriptors of device-decodable images as ocr_pipe_stage_batch takes them: image i is list[i], tagged with its kind.
 // The images must outlive the batch (the descriptors point into them).
 struct DeviceFrames {
   std::deque<ocr_jpeg_frame> jf;  // (deques: a descriptor stays where it is when the next one is added)
   std::deque<ocr_png_frame> pf;
   std::deque<ocr_raw_frame> rf;
-  std::vector<const ocr_jpeg_frame*> jp;
-  std::vector<const ocr_png_frame*> pp;
-  std::vector<const ocr_raw_frame*> rp;
+  std::deque<ocr_tiff_frame> tf;
+  std::vector<ocr_coded_frame> list;
   void add(const Image& im) {  // only when im.device_decodable()
-    jp.push_back(nullptr); pp.push_back(nullptr); rp.push_back(nullptr);
-    if (im.raw) { rf.push_back(im.raw_frame()); rp.back() = &rf.back(); }
-    else if (im.png) { pf.push_back(im.png_frame()); pp.back() = &pf.back(); }
-    else { jf.push_back(im.jpeg_frame()); jp.back() = &jf.back(); }
+    if (im.tiff) { tf.push_back(im.tiff_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF, &tf.back()}); }
+    else if (im.raw) { rf.push_back(im.raw_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_RAW, &rf.back()}); }
+    else if (im.png) { pf.push_back(im.png_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_PNG, &pf.back()}); }
+    else { jf.push_back(im.jpeg_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_JPEG, &jf.back()}); }
   }
-  int stage(ocr_pipe* pipe, int slot) const { return ocr_pipe_stage_frames(pipe, slot, jp.data(), pp.data(), rp.data(), (int)jp.size()); }
+  int stage(ocr_pipe* pipe, int slot) const { return ocr_pipe_stage_batch(pipe, slot, list.data(), (int)list.size()); }
 };
 
 inline void check_ocr(int rc, const char* what) {
@@ -554,8 +572,8 @@ class OCRWorker {
     std::vector<ocr_img> imgs;
     DeviceFrames frames;
     std::vector<size_t> owner;
-    // a batch of JPEGs, PNGs and raw BMP / PNM frames only (of the last there are none unless OCR_DEVICE_RAW=1: the IPC layer
-    // finishes those files on the host) is decoded on the device, in one ocr_pipe_stage_frames call whatever the mix; a batch
+    // a batch of JPEGs, PNGs, raw BMP / PNM frames and TIFF frames only (of the last two there are none unless OCR_DEVICE_RAW=1 /
+    // OCR_DEVICE_TIFF=1: the IPC layer finishes those files on the host) is decoded on the device, in one ocr_pipe_stage_batch call whatever the mix; a batch
     // with other host pixels in it takes the host path for all its images
     bool on_device = !char_boxes_;
     for (size_t i = 0; i < requests.size(); ++i)

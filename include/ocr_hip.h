@@ -385,6 +385,41 @@ int ocr_raw_time_batch(const ocr_raw_frame* const* frames, int count, int device
  * code, with the same bytes in the slot. */
 int ocr_pipe_stage_frames(ocr_pipe* h, int slot, const ocr_jpeg_frame* const* jpegs, const ocr_png_frame* const* pngs,
                           const ocr_raw_frame* const* raws, int count);
+/* TIFF inputs with the pixel half of the decoder on the device: the caller parses the container and does what is serial
+ * (the IFD, PackBits / LZW / Deflate expansion, FillOrder: host/tiff_decode.h, tiff::parse); the horizontal-differencing
+ * predictor (a scan along each chunk row), tile placement with clipped edge tiles, planar to chunky, 1- / 2- / 4-bit expansion,
+ * palette, MinIsWhite, 16 -> 8 bits, CMYK and alpha run on the copy stream straight into the slot.  The pixels are
+ * cv::imdecode(IMREAD_COLOR)'s as libtiff's RGBA interface makes them.  Every field is checked on the host before anything
+ * is launched (OCR_ERR_ARG, ocr_last_error says which rule). */
+typedef struct ocr_tiff_frame {
+  int width, height;       /* width * height <= 64 Mpixel */
+  int photometric;         /* 0 MinIsWhite, 1 MinIsBlack, 2 RGB, 3 palette, 5 CMYK */
+  int bits_per_sample;     /* 1, 2, 4 (grey, palette: one sample, chunky, no predictor), 8, 16 (not palette, not CMYK) */
+  int samples_per_pixel;   /* as stored, extra samples included: 1 .. 16, at least the photometric's 1 / 3 / 4 */
+  int planar;              /* 1 chunky; 2 one plane of chunks per sample (RGB, or grey with extra samples) */
+  int predictor;           /* 1; 2: samples are differences from the pixel before in the chunk's row (8 and 16 bits) */
+  int big_endian;          /* of 16-bit samples: the predictor's sum runs on the words in this order */
+  int premultiply;         /* 1: the sample behind the colour is unassociated alpha, c = (c * a + 127) / 255 (RGB; grey in planes) */
+  int tile_width, tile_height; /* a chunk; a strip is a chunk as wide as the image and min(RowsPerStrip, height) high */
+  uint8_t palette[1024];   /* B,G,R,x times 256, reduced to 8 bits */
+  const uint8_t* data;     /* host: the expanded chunks, each at its nominal size tile_height * row bytes, plane by plane, row of
+                            * chunks by row of chunks */
+  size_t data_len;         /* >= planes * chunks * tile_height * row bytes, which is <= 1 GiB */
+} ocr_tiff_frame;
+int ocr_tiff_decode(const ocr_tiff_frame* frame, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time), as ocr_raw_time: ms[0] = the upload of the chunks from pinned memory, ms[1] = the
+ * pixel-stage kernel; ocr_tiff_time_batch: `count` frames as ONE batch (one upload, one launch per sample width). */
+int ocr_tiff_time(const ocr_tiff_frame* frame, int device_id, int iters, double ms[2]);
+int ocr_tiff_time_batch(const ocr_tiff_frame* const* frames, int count, int device_id, int iters, double ms[2]);
+/* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw and TIFF
+ * frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
+ * all five validate their own argument list and stage through the same code, with the same bytes in the slot. */
+typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3 } ocr_frame_kind;
+typedef struct ocr_coded_frame {
+  int kind;           /* ocr_frame_kind */
+  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame or ocr_tiff_frame */
+} ocr_coded_frame;
+int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
 /* network input size the detector uses for a rows x cols image (ResizeImgType0) */
 int ocr_pipe_det_shape(ocr_pipe* h, int rows, int cols, int* net_rows, int* net_cols);
@@ -421,6 +456,9 @@ int ocr_dev_free(void* p);
 int ocr_dev_upload(void* dst, const void* src, size_t bytes);
 int ocr_dev_download(void* dst, const void* src, size_t bytes);
 int ocr_dev_sync(void);
+/* measurement aid (decode_tool --time): *ms = the device time of ONE plain copy kernel over `bytes` (dst, src from
+ * ocr_dev_alloc; 16 bytes a lane), the mean of `iters` - the yardstick a streaming kernel's time is set against in the same run */
+int ocr_dev_copy_time(void* dst, const void* src, size_t bytes, int iters, double* ms);
 
 /* ---------------------------------------------------------------- raw network taps (parity tests) */
 typedef struct ocr_net ocr_net;

@@ -153,6 +153,23 @@ def png_mode(clients, per):
             run(16, clients, per, path, fmt, workers=2, extra_env=dict(op, OCR_DEVICE_PNG=dev), tag="device_png" if dev == "1" else "host_png")
 
 
+def tiff_mode(clients, per):
+    """960x960 8-bit RGB TIFF requests (the configs[1] card of jpeg_mode; LZW with the horizontal predictor, strips of 16 rows,
+    written by Pillow) against a service with two GPU workers: OCR_DEVICE_TIFF=1 (opt-in: container and LZW on the client's
+    service thread, predictor scan, conversion and placement on the worker's copy stream) and 0 (the default: the whole decode
+    on the host thread).  The line's "sys_threads_per_1000rps" is the host-cores-per-1000-requests/s figure."""
+    import numpy as np
+    from PIL import Image
+    from synth_data import cfg2_sample
+    img = cfg2_sample(0, 960, 960, 32)[0]
+    path = f"/tmp/ocr_load_{os.getpid()}.tif"
+    Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(path, format="TIFF", compression="tiff_lzw", tiffinfo={317: 2})
+    fmt = "tiff 8-bit RGB LZW predictor 960x960 (%d KB)" % (os.path.getsize(path) // 1024)
+    op = {"OCR_WORKER_DET_LIMIT": "960", "OCR_WORKER_REC_H": "48", "OCR_WORKER_REC_W": "320", "OCR_WORKER_CLS": "1"}
+    for dev in ("1", "0"):
+        run(16, clients, per, path, fmt, workers=2, extra_env=dict(op, OCR_DEVICE_TIFF=dev), tag="device_tiff" if dev == "1" else "host_tiff")
+
+
 def bmp_mode(clients, per):
     """960x960 8-bit paletted BMP requests (the configs[1] card of jpeg_mode through a 256-colour palette, written by Pillow)
     against a service with two GPU workers: OCR_DEVICE_RAW=1 (opt-in: container on the client's service thread, palette
@@ -215,6 +232,12 @@ if __name__ == "__main__":
         import synth_weights
         synth_weights.ensure(ROOT)
         jpeg_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "tiff":
+        subprocess.check_call(["make", "-s", "-C", HOST])
+        import synth_weights
+        synth_weights.ensure(ROOT)
+        tiff_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "bmp":
         subprocess.check_call(["make", "-s", "-C", HOST])
