@@ -576,6 +576,7 @@ EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_
             "ocr_png_decode", "ocr_png_time", "ocr_png_time_batch", "ocr_pipe_stage_coded",
             "ocr_raw_decode", "ocr_raw_time", "ocr_raw_time_batch", "ocr_pipe_stage_frames",
             "ocr_tiff_decode", "ocr_tiff_time", "ocr_tiff_time_batch", "ocr_pipe_stage_batch",
+            "ocr_webp_decode", "ocr_webp_time", "ocr_webp_time_batch",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_dev_copy_time", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
@@ -703,7 +704,7 @@ class ocr_coded_frame(C.Structure):
     _fields_ = [("kind", C.c_int), ("frame", C.c_void_p)]
 
 
-FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF = 0, 1, 2, 3
+FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP = 0, 1, 2, 3, 4
 
 
 class TiffFrame:
@@ -730,6 +731,49 @@ class TiffFrame:
         h, w = self.c.height, self.c.width
         out = np.zeros((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), np.uint8)
         rc = L.ocr_tiff_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
+            err.code = rc
+            raise err
+        return out
+
+
+class ocr_webp_transform(C.Structure):
+    _fields_ = [("kind", C.c_int), ("bits", C.c_int), ("data", C.c_void_p), ("data_len", C.c_size_t)]
+
+
+class ocr_webp_frame(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("argb", C.c_void_p), ("argb_len", C.c_size_t), ("ntransforms", C.c_int),
+                ("transforms", ocr_webp_transform * 4)]
+
+
+class WebpFrame:
+    """an ocr_webp_frame over Python-owned memory.  coded: the entropy-decoded image (uint32 A << 24 | R << 16 | G << 8 | B, coded
+    width x height); transforms: up to four (kind, bits, data) in file order, data a uint32 array (sub-image or palette) or None.
+    Fields of .c may be changed before a call (the tests' tampering)."""
+
+    def __init__(self, width, height, coded, transforms=()):
+        self._coded = np.ascontiguousarray(coded, np.uint32).reshape(-1).copy()
+        self._data = []
+        c = ocr_webp_frame()
+        c.width, c.height = width, height
+        c.argb, c.argb_len = self._coded.ctypes.data, len(self._coded)
+        c.ntransforms = len(transforms)
+        for k, (kind, bits, data) in enumerate(list(transforms)[:4]):
+            c.transforms[k].kind, c.transforms[k].bits = kind, bits
+            if data is not None:
+                a = np.ascontiguousarray(data, np.uint32).reshape(-1).copy()
+                self._data.append(a)
+                c.transforms[k].data, c.transforms[k].data_len = a.ctypes.data, len(a)
+        self.c = c
+
+    def decode(self, device_id=0):
+        """ocr_webp_decode: the (height, width, 3) BGR image; OcrError where the call refuses"""
+        L = lib()
+        L.ocr_webp_decode.argtypes = [C.POINTER(ocr_webp_frame), C.c_int, C.c_void_p, C.c_size_t]
+        h, w = self.c.height, self.c.width
+        out = np.zeros((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), np.uint8)
+        rc = L.ocr_webp_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
         if rc != 0:
             err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
             err.code = rc

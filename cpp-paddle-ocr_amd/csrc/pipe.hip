@@ -15,6 +15,7 @@
 #include "png_stage.h"
 #include "raw_stage.h"
 #include "tiff_stage.h"
+#include "webp_stage.h"
 #include "stages.h"
 
 using namespace ocr;
@@ -431,6 +432,7 @@ struct ocr_pipe {
   PngScratch png;
   RawScratch raw;
   TiffScratch tiff;
+  WebpScratch webp;
   DevBuf<uint8_t> work;  // the requests' clones (OCRRequest copies the Mat, ocr_worker.h:28-29): cls rotates in place on them
   // Two batches in flight (round 5, ocr_pipe_run_device_on / ocr_pipe_run_staged_on): a call that names a chain runs its WHOLE
   // batch on that chain's worker, with a clone buffer of the chain's own; calls on different chains may run concurrently from
@@ -501,8 +503,8 @@ struct ocr_pipe {
     return OCR_OK;
   }
 
-  // ---- stage a batch of JPEG coefficients, inflated PNG streams, stored BMP / PNM rows and expanded TIFF chunks, in any mix: the
-  // four pixel stages run on the copy stream, into the slot.  Image i is frames[i], a tagged descriptor (validated by the caller
+  // ---- stage a batch of JPEG coefficients, inflated PNG streams, stored BMP / PNM rows, expanded TIFF chunks and entropy-decoded
+  // WebP images, in any mix: the five pixel stages run on the copy stream, into the slot.  Image i is frames[i], a tagged descriptor (validated by the caller
   // before the sizes are used - a refused batch leaves the slot as it was: a known kind, and a sound descriptor)
   int stage_coded(int si, const ocr_coded_frame* frames, int count, std::string& err) {
     StageSlot& S = slots[si];
@@ -510,13 +512,15 @@ struct ocr_pipe {
     auto pn = [&](int i) { return (const ocr_png_frame*)frames[i].frame; };
     auto rw = [&](int i) { return (const ocr_raw_frame*)frames[i].frame; };
     auto tf = [&](int i) { return (const ocr_tiff_frame*)frames[i].frame; };
+    auto wf = [&](int i) { return (const ocr_webp_frame*)frames[i].frame; };
     int rc = layout(S, count, [&](int i, int& r, int& c) {
       // the oriented size: a 40 x 72 image and a 72 x 40 one that EXIF turns by 90 degrees share a size group and a det pass
       switch (frames[i].kind) {
         case OCR_FRAME_JPEG: r = jpeg_out_rows(*jp(i)); c = jpeg_out_cols(*jp(i)); break;
         case OCR_FRAME_PNG: r = pn(i)->height; c = pn(i)->width; break;
         case OCR_FRAME_RAW: r = rw(i)->height; c = rw(i)->width; break;
-        default: r = tf(i)->height; c = tf(i)->width; break;
+        case OCR_FRAME_TIFF: r = tf(i)->height; c = tf(i)->width; break;
+        default: r = wf(i)->height; c = wf(i)->width; break;
       }
     }, err);
     if (rc) return rc;
@@ -524,7 +528,8 @@ struct ocr_pipe {
     std::vector<const ocr_png_frame*> pf;
     std::vector<const ocr_raw_frame*> rf;
     std::vector<const ocr_tiff_frame*> tff;
-    std::vector<uint8_t*> jdst, pdst, rdst, tdst;
+    std::vector<const ocr_webp_frame*> wff;
+    std::vector<uint8_t*> jdst, pdst, rdst, tdst, wdst;
     for (int k = 0; k < count; ++k) {
       const int i = S.imgs[k].orig;
       uint8_t* d = S.dev.p + S.imgs[k].off;
@@ -532,13 +537,15 @@ struct ocr_pipe {
         case OCR_FRAME_JPEG: jf.push_back(*jp(i)); jdst.push_back(d); break;
         case OCR_FRAME_PNG: pf.push_back(pn(i)); pdst.push_back(d); break;
         case OCR_FRAME_RAW: rf.push_back(rw(i)); rdst.push_back(d); break;
-        default: tff.push_back(tf(i)); tdst.push_back(d); break;
+        case OCR_FRAME_TIFF: tff.push_back(tf(i)); tdst.push_back(d); break;
+        default: wff.push_back(wf(i)); wdst.push_back(d); break;
       }
     }
     if (!jf.empty()) rc = jpeg_decode_async(jf.data(), (int)jf.size(), jdst.data(), jpeg, copy_stream, err);
     if (!rc && !pf.empty()) rc = png_decode_async(pf.data(), (int)pf.size(), pdst.data(), png, copy_stream, err);
     if (!rc && !rf.empty()) rc = raw_decode_async(rf.data(), (int)rf.size(), rdst.data(), raw, copy_stream, err);
     if (!rc && !tff.empty()) rc = tiff_decode_async(tff.data(), (int)tff.size(), tdst.data(), tiff, copy_stream, err);
+    if (!rc && !wff.empty()) rc = webp_decode_async(wff.data(), (int)wff.size(), wdst.data(), webp, copy_stream, err);
     if (rc) return rc;
     if (hipEventRecord(S.ready, copy_stream) != hipSuccess) { err = "hipEventRecord failed"; return OCR_ERR_DEVICE; }
     S.staged = true;
@@ -881,6 +888,7 @@ int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, i
       case OCR_FRAME_PNG: fault = png_frame_fault(*(const ocr_png_frame*)f); break;
       case OCR_FRAME_RAW: fault = raw_frame_fault(*(const ocr_raw_frame*)f); break;
       case OCR_FRAME_TIFF: fault = tiff_frame_fault(*(const ocr_tiff_frame*)f); break;
+      case OCR_FRAME_WEBP: fault = webp_frame_fault(*(const ocr_webp_frame*)f); break;
       default: fault = "frame kind is not an ocr_frame_kind"; break;
     }
     if (fault) return fail(OCR_ERR_ARG, fault);

@@ -28,6 +28,10 @@
 // chunks, pixel stage), "host_pixels_ms" (tiff::pixels on one host thread), "bytes_in" / "bytes_out" (what the kernel reads and
 // writes) and "copy_ms": a plain copy kernel that reads and writes as many bytes in all (ocr_dev_copy_time), timed in the same run.
 // decode_tool --stage-frames <model dir> ...: as --stage, through ocr_pipe_stage_frames (the three-array entry point: no TIFFs).
+// A lossless WebP's pixel half (the inverse transforms: predictor, cross-colour, add-green, palette) runs on the GPU with
+// --device / --frame too, through ocr_webp_decode (whatever OCR_DEVICE_WEBP says; a file outside the device stage's scope stays
+// on the host); --stage takes WebPs in the mix; --time <iters> <webp file> [<batch>]: ocr_webp_time / ocr_webp_time_batch (upload
+// of the coded data, pixel stage), "host_pixels_ms" (webp::pixels on one host thread), "bytes_in" / "bytes_out".
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -64,6 +68,29 @@ static int time_device(int iters, const char* in, int batch) {
     if ((batch > 1 ? ocr_png_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_png_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
     printf("{\"size\": [%d, %d], \"color_type\": %d, \"bit_depth\": %d, \"interlace\": %d, \"segments\": %d, \"batch\": %d, \"iters\": %d, "
            "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f}\n", d.height, d.width, d.color_type, d.bit_depth, d.interlace, d.nsegments, (int)all.size(), iters, ms[0], ms[1]);
+    return 0;
+  }
+  if (PaddleOCR::ipc::is_webp(bytes.data(), bytes.size())) {
+    auto f = std::make_shared<PaddleOCR::webp::Frame>();
+    if (!PaddleOCR::webp::parse(bytes.data(), bytes.size(), *f) || !f->device_ok) { fprintf(stderr, "decode failed: %s\n", f->error ? f->error : "outside the device stage's scope"); return 1; }
+    im.rows = f->height; im.cols = f->width;
+    im.webp = f;
+    const ocr_webp_frame d = im.webp_frame();
+    std::vector<const ocr_webp_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
+    double ms[2];
+    if ((batch > 1 ? ocr_webp_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_webp_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    std::vector<uint8_t> px;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < iters; ++i)
+      for (size_t k = 0; k < all.size(); ++k) PaddleOCR::webp::pixels(*f, px);
+    const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+    size_t in = f->argb.size() * 4;
+    std::string kinds;
+    for (const auto& t : f->transforms) { in += t.data.size() * 4; kinds += (kinds.empty() ? "" : ", ") + std::to_string(t.kind); }
+    printf("{\"size\": [%d, %d], \"coded_width\": %d, \"transforms\": [%s], \"batch\": %d, \"iters\": %d, "
+           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"bytes_in\": %zu, \"bytes_out\": %zu}\n",
+           d.height, d.width, PaddleOCR::webp::coded_width(*f), kinds.c_str(), (int)all.size(), iters, ms[0], ms[1], host_ms, in * all.size(),
+           (size_t)d.width * d.height * 3 * all.size());
     return 0;
   }
   if (PaddleOCR::ipc::is_tiff(bytes.data(), bytes.size())) {
@@ -241,6 +268,11 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
+  if (im.device_decodable() && im.webp) {
+    const ocr_webp_frame d = im.webp_frame();
+    im.pixels.resize((size_t)d.height * d.width * 3);
+    if (ocr_webp_decode(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+  } else
   if (im.device_decodable() && im.tiff) {
     const ocr_tiff_frame d = im.tiff_frame();
     im.pixels.resize((size_t)d.height * d.width * 3);

@@ -45,6 +45,7 @@
 #include "png_decode.h"
 #include "raw_decode.h"
 #include "tiff_decode.h"
+#include "webp_decode.h"
 
 namespace PaddleOCR {
 namespace ipc {
@@ -235,6 +236,29 @@ inline bool decode_tiff(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!tiff::pixels(*f, im.pixels)) { im = Image(); return false; }
   return true;
 }
+// Lossless WebP as cv::imdecode(IMREAD_COLOR) returns it (webp_decode.h: a VP8L chunk under RIFF / WEBP or in a VP8X container;
+// lossy and animated files are refused, *why says so).  device_pixels / force_device as for TIFF; the switch is
+// OCR_DEVICE_WEBP, read once: =1 stops after the entropy-coded image is decoded and leaves the inverse transforms to the
+// worker (frames in the device stage's scope, webp::Frame::device_ok), =0 or unset finishes every file on this host thread.
+constexpr bool WEBP_DEVICE_DEFAULT = false;
+inline bool webp_device_enabled() {
+  static const char* env = getenv("OCR_DEVICE_WEBP");
+  return env && env[0] ? env[0] != '0' : WEBP_DEVICE_DEFAULT;
+}
+inline bool is_webp(const uint8_t* d, size_t n) { return webp::is_webp(d, n); }
+inline bool decode_webp(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false, const char** why = nullptr) {
+  if (!is_webp(d.data(), d.size())) return false;
+  auto f = std::make_shared<webp::Frame>();
+  if (!webp::parse(d.data(), d.size(), *f)) {
+    if (why) *why = f->error;
+    return false;
+  }
+  im.pixels.clear();
+  im.rows = f->height; im.cols = f->width;
+  if (device_pixels && f->device_ok && (force_device || webp_device_enabled())) { im.webp = std::move(f); return true; }
+  if (!webp::pixels(*f, im.pixels)) { im = Image(); return false; }
+  return true;
+}
 // libpng16 simplified API (png.h: png_image, PNG_IMAGE_VERSION 1, PNG_FORMAT_BGR = 0x12), resolved at run time
 struct PngImage {
   void* opaque;
@@ -308,11 +332,13 @@ inline bool decode_jpeg(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!dec.decode(d.data(), d.size(), im.pixels, im.rows, im.cols)) { im = Image(); return false; }
   return true;
 }
-// force_device: PNG, BMP / PNM and TIFF take the device route whatever OCR_DEVICE_PNG / OCR_DEVICE_RAW / OCR_DEVICE_TIFF say (decode_tool)
-inline bool decode_image(const std::vector<uint8_t>& bytes, Image& im, bool device_pixels = false, bool force_device = false) {
+// force_device: PNG, BMP / PNM, TIFF and WebP take the device route whatever OCR_DEVICE_PNG / OCR_DEVICE_RAW / OCR_DEVICE_TIFF /
+// OCR_DEVICE_WEBP say (decode_tool).  why: set where a file is refused for a reason its sender should read (a lossy or
+// animated WebP), left alone otherwise
+inline bool decode_image(const std::vector<uint8_t>& bytes, Image& im, bool device_pixels = false, bool force_device = false, const char** why = nullptr) {
   return decode_png(bytes, im, device_pixels, force_device) || decode_jpeg(bytes, im, device_pixels) ||
          decode_ppm(bytes, im, device_pixels, force_device) || decode_bmp(bytes, im, device_pixels, force_device) ||
-         decode_tiff(bytes, im, device_pixels, force_device);
+         decode_tiff(bytes, im, device_pixels, force_device) || decode_webp(bytes, im, device_pixels, force_device, why);
 }
 inline bool read_file(const std::string& path, std::vector<uint8_t>& out) {
   std::ifstream f(path, std::ios::binary);
@@ -391,17 +417,19 @@ class OCRIPCService {
         const std::string image_path = req.get("image_path"), image_base64 = req.get("image_data");
         Image image;
         std::string error_msg;
+        const char* why = nullptr;  // what a decoder has to say to the sender: a lossy or animated WebP is refused in so many words
         if (!image_path.empty()) {
           std::vector<uint8_t> bytes;
-          if (!ipc::read_file(image_path, bytes) || !ipc::decode_image(bytes, image, gpu_worker_pool_ != nullptr) || image.empty())
+          if (!ipc::read_file(image_path, bytes) || !ipc::decode_image(bytes, image, gpu_worker_pool_ != nullptr, false, &why) || image.empty())
             error_msg = "Failed to load image from path: " + image_path;
         } else if (!image_base64.empty()) {
           std::vector<uint8_t> bytes;
           if (!ipc::base64_decode(image_base64, bytes)) error_msg = "Base64 decode error: invalid character";
-          else if (!ipc::decode_image(bytes, image, gpu_worker_pool_ != nullptr) || image.empty()) error_msg = "Failed to decode base64 image data";
+          else if (!ipc::decode_image(bytes, image, gpu_worker_pool_ != nullptr, false, &why) || image.empty()) error_msg = "Failed to decode base64 image data";
         } else {
           error_msg = "Missing image_path or image_data";
         }
+        if (!error_msg.empty() && why) error_msg += std::string(": ") + why;
         if (!error_msg.empty()) return ipc::error_reply(error_msg);
         if (!gpu_worker_pool_) return ipc::error_reply("No GPU workers configured (this build has no CPU path)");
         const int request_id = request_counter_.fetch_add(1);

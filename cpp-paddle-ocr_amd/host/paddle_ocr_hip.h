@@ -33,6 +33,7 @@
 #include "png_decode.h"
 #include "raw_decode.h"
 #include "tiff_decode.h"
+#include "webp_decode.h"
 
 namespace PaddleOCR {
 
@@ -62,6 +63,9 @@ struct Image {
   // a TIFF whose container has been parsed and whose chunks have been expanded (PackBits / LZW / Deflate): the worker undoes
   // the predictor, converts and places the chunks on the device (ocr_pipe_stage_batch)
   std::shared_ptr<tiff::Frame> tiff;
+  // a lossless WebP whose entropy-coded image has been decoded (prefix codes, LZ77, colour cache): the worker undoes the
+  // transforms on the device (ocr_pipe_stage_batch)
+  std::shared_ptr<webp::Frame> webp;
   Image() = default;
   explicit Image(const ImageView& v) : rows(v.rows), cols(v.cols) {
     if (!v.empty()) {
@@ -70,10 +74,15 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff; }
-  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff); }
-  void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM / TIFF on the host
+  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp); }
+  void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM / TIFF / WebP on the host
     if (!device_decodable()) return;
+    if (webp) {
+      if (!webp::pixels(*webp, pixels)) throw std::runtime_error("WebP conversion failed");
+      webp.reset();
+      return;
+    }
     if (tiff) {
       if (!tiff::pixels(*tiff, pixels)) throw std::runtime_error("TIFF conversion failed");
       tiff.reset();
@@ -122,6 +131,19 @@ struct Image {
     d.data = tiff->data.data(); d.data_len = tiff->data.size();
     return d;
   }
+  ocr_webp_frame webp_frame() const {  // only when webp
+    ocr_webp_frame d;
+    memset(&d, 0, sizeof d);
+    d.width = webp->width; d.height = webp->height;
+    d.argb = webp->argb.data(); d.argb_len = webp->argb.size();
+    d.ntransforms = (int)webp->transforms.size();
+    for (int t = 0; t < d.ntransforms && t < 4; ++t) {
+      const webp::Transform& tr = webp->transforms[(size_t)t];
+      d.transforms[t].kind = tr.kind; d.transforms[t].bits = tr.bits;
+      d.transforms[t].data = tr.data.empty() ? nullptr : tr.data.data(); d.transforms[t].data_len = tr.data.size();
+    }
+    return d;
+  }
   ocr_jpeg_frame jpeg_frame() const {  // only when jpeg: every file the host half reads (any sampling, grey, YCbCr, RGB, CMYK, YCCK)
     ocr_jpeg_frame d;
     memset(&d, 0, sizeof d);
@@ -143,9 +165,11 @@ struct DeviceFrames {
   std::deque<ocr_png_frame> pf;
   std::deque<ocr_raw_frame> rf;
   std::deque<ocr_tiff_frame> tf;
+  std::deque<ocr_webp_frame> wf;
   std::vector<ocr_coded_frame> list;
   void add(const Image& im) {  // only when im.device_decodable()
-    if (im.tiff) { tf.push_back(im.tiff_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF, &tf.back()}); }
+    if (im.webp) { wf.push_back(im.webp_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_WEBP, &wf.back()}); }
+    else if (im.tiff) { tf.push_back(im.tiff_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF, &tf.back()}); }
     else if (im.raw) { rf.push_back(im.raw_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_RAW, &rf.back()}); }
     else if (im.png) { pf.push_back(im.png_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_PNG, &pf.back()}); }
     else { jf.push_back(im.jpeg_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_JPEG, &jf.back()}); }
@@ -572,8 +596,8 @@ class OCRWorker {
     std::vector<ocr_img> imgs;
     DeviceFrames frames;
     std::vector<size_t> owner;
-    // a batch of JPEGs, PNGs, raw BMP / PNM frames and TIFF frames only (of the last two there are none unless OCR_DEVICE_RAW=1 /
-    // OCR_DEVICE_TIFF=1: the IPC layer finishes those files on the host) is decoded on the device, in one ocr_pipe_stage_batch call whatever the mix; a batch
+    // a batch of JPEGs, PNGs, raw BMP / PNM frames, TIFF and WebP frames only (of the last three there are none unless OCR_DEVICE_RAW=1 /
+    // OCR_DEVICE_TIFF=1 / OCR_DEVICE_WEBP=1: the IPC layer finishes those files on the host) is decoded on the device, in one ocr_pipe_stage_batch call whatever the mix; a batch
     // with other host pixels in it takes the host path for all its images
     bool on_device = !char_boxes_;
     for (size_t i = 0; i < requests.size(); ++i)

@@ -411,13 +411,43 @@ int ocr_tiff_decode(const ocr_tiff_frame* frame, int device_id, uint8_t* bgr, si
  * pixel-stage kernel; ocr_tiff_time_batch: `count` frames as ONE batch (one upload, one launch per sample width). */
 int ocr_tiff_time(const ocr_tiff_frame* frame, int device_id, int iters, double ms[2]);
 int ocr_tiff_time_batch(const ocr_tiff_frame* const* frames, int count, int device_id, int iters, double ms[2]);
-/* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw and TIFF
- * frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
+/* Lossless WebP inputs with the pixel half of the decoder on the device: the caller parses the container and does what is
+ * serial (prefix codes, LZ77, the colour cache: host/webp_decode.h, webp::parse); the inverse transforms - spatial predictor,
+ * cross-colour, add-green, palette with pixel bundling - run on the copy stream straight into the slot.  The pixels are
+ * cv::imdecode(IMREAD_COLOR)'s as libwebp's WebPDecodeBGR makes them (alpha dropped).  The device stage takes every order of
+ * transforms in which colour indexing, if present, is the FIRST of the file (every order libwebp's encoder writes); another
+ * order is refused here and finished on the host (webp::pixels).  Every field is checked on the host before anything is
+ * launched (OCR_ERR_ARG, ocr_last_error says which rule). */
+typedef struct ocr_webp_transform {
+  int kind;              /* 0 predictor, 1 cross-colour, 2 add-green, 3 colour indexing; each at most once */
+  int bits;              /* predictor, cross-colour: blocks of 2^bits pixels square, 2 .. 9; add-green: 0; colour indexing: a coded
+                          * pixel holds 2^bits indices - 3 / 2 / 1 / 0 for <= 2 / <= 4 / <= 16 / more colours */
+  const uint32_t* data;  /* host: predictor - the sub-image, mode in bits 8 .. 11; cross-colour - the sub-image, green-to-red,
+                          * green-to-blue, red-to-blue in bytes 0, 1, 2; colour indexing - the palette, A << 24 | R << 16 | G << 8 | B,
+                          * delta coding undone; add-green: unused */
+  size_t data_len;       /* dwords: >= ceil(w / 2^bits) * ceil(height / 2^bits) for a sub-image (w: the width the transform works
+                          * on - the coded width behind colour indexing); 1 .. 256 for the palette */
+} ocr_webp_transform;
+typedef struct ocr_webp_frame {
+  int width, height;     /* 1 .. 16384 each, width * height <= 64 Mpixel */
+  const uint32_t* argb;  /* host: the entropy-decoded image, A << 24 | R << 16 | G << 8 | B, coded width x height; the coded width
+                          * is ceil(width / 2^bits) of the colour indexing transform, the width without one */
+  size_t argb_len;       /* dwords: >= coded width * height */
+  int ntransforms;       /* 0 .. 4 */
+  ocr_webp_transform transforms[4]; /* in file order: they are undone last to first */
+} ocr_webp_frame;
+int ocr_webp_decode(const ocr_webp_frame* frame, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time), as ocr_tiff_time: ms[0] = the upload of the coded data from pinned memory, ms[1] = the
+ * pixel-stage kernels; ocr_webp_time_batch: `count` frames as ONE batch (one upload, one launch per kernel kind). */
+int ocr_webp_time(const ocr_webp_frame* frame, int device_id, int iters, double ms[2]);
+int ocr_webp_time_batch(const ocr_webp_frame* const* frames, int count, int device_id, int iters, double ms[2]);
+/* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw, TIFF
+ * and WebP frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
  * all five validate their own argument list and stage through the same code, with the same bytes in the slot. */
-typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3 } ocr_frame_kind;
+typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4 } ocr_frame_kind;
 typedef struct ocr_coded_frame {
   int kind;           /* ocr_frame_kind */
-  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame or ocr_tiff_frame */
+  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame or ocr_webp_frame */
 } ocr_coded_frame;
 int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);

@@ -170,6 +170,23 @@ def tiff_mode(clients, per):
         run(16, clients, per, path, fmt, workers=2, extra_env=dict(op, OCR_DEVICE_TIFF=dev), tag="device_tiff" if dev == "1" else "host_tiff")
 
 
+def webp_mode(clients, per):
+    """960x960 lossless WebP requests (the configs[1] card of jpeg_mode, written by Pillow with libwebp's encoder at method 4:
+    subtract-green, predictor and cross-colour) against a service with two GPU workers: OCR_DEVICE_WEBP=1 (opt-in: container,
+    prefix codes, LZ77 and colour cache on the client's service thread, the inverse transforms on the worker's copy stream) and 0
+    (the default: the whole decode on the host thread).  The line's "sys_threads_per_1000rps" is the host-cores-per-1000-requests/s figure."""
+    import numpy as np
+    from PIL import Image
+    from synth_data import cfg2_sample
+    img = cfg2_sample(0, 960, 960, 32)[0]
+    path = f"/tmp/ocr_load_{os.getpid()}.webp"
+    Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(path, format="WEBP", lossless=True, method=4)
+    fmt = "webp lossless method 4 960x960 (%d KB)" % (os.path.getsize(path) // 1024)
+    op = {"OCR_WORKER_DET_LIMIT": "960", "OCR_WORKER_REC_H": "48", "OCR_WORKER_REC_W": "320", "OCR_WORKER_CLS": "1"}
+    for dev in ("1", "0"):
+        run(16, clients, per, path, fmt, workers=2, extra_env=dict(op, OCR_DEVICE_WEBP=dev), tag="device_webp" if dev == "1" else "host_webp")
+
+
 def bmp_mode(clients, per):
     """960x960 8-bit paletted BMP requests (the configs[1] card of jpeg_mode through a 256-colour palette, written by Pillow)
     against a service with two GPU workers: OCR_DEVICE_RAW=1 (opt-in: container on the client's service thread, palette
@@ -238,6 +255,12 @@ if __name__ == "__main__":
         import synth_weights
         synth_weights.ensure(ROOT)
         tiff_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "webp":
+        subprocess.check_call(["make", "-s", "-C", HOST])
+        import synth_weights
+        synth_weights.ensure(ROOT)
+        webp_mode(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 16)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "bmp":
         subprocess.check_call(["make", "-s", "-C", HOST])
