@@ -576,7 +576,7 @@ EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_
             "ocr_png_decode", "ocr_png_time", "ocr_png_time_batch", "ocr_pipe_stage_coded",
             "ocr_raw_decode", "ocr_raw_time", "ocr_raw_time_batch", "ocr_pipe_stage_frames",
             "ocr_tiff_decode", "ocr_tiff_time", "ocr_tiff_time_batch", "ocr_pipe_stage_batch",
-            "ocr_webp_decode", "ocr_webp_time", "ocr_webp_time_batch",
+            "ocr_webp_decode", "ocr_webp_time", "ocr_webp_time_batch", "ocr_vp8_decode", "ocr_vp8_time", "ocr_vp8_time_batch",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_dev_copy_time", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
@@ -704,7 +704,7 @@ class ocr_coded_frame(C.Structure):
     _fields_ = [("kind", C.c_int), ("frame", C.c_void_p)]
 
 
-FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP = 0, 1, 2, 3, 4
+FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP, FRAME_VP8 = 0, 1, 2, 3, 4, 5
 
 
 class TiffFrame:
@@ -777,6 +777,45 @@ class WebpFrame:
         if rc != 0:
             err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
             err.code = rc
+            raise err
+        return out
+
+
+class ocr_vp8_frame(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("filter_type", C.c_int), ("mbs", C.c_void_p), ("mbs_len", C.c_size_t),
+                ("coeffs", C.c_void_p), ("coeffs_len", C.c_size_t)]
+
+
+# ocr_vp8_mb as a numpy record (40 bytes)
+VP8_MB = np.dtype([("modes", "u1", 16), ("is_i4x4", "u1"), ("uvmode", "u1"), ("level", "u1"), ("ilevel", "u1"), ("hev", "u1"), ("inner", "u1"),
+                   ("segment", "u1"), ("skip", "u1"), ("nz_y", "<u4"), ("nz_uv", "<u4"), ("present", "<u4"), ("coeff_off", "<u4")])
+
+
+class Vp8Frame:
+    """an ocr_vp8_frame over Python-owned memory.  mbs: the macroblock records (VP8_MB, raster order); coeffs: the int16
+    coefficients of the shipped blocks.  .mbs / .coeffs and the fields of .c may be changed before a call (the tests' tampering)."""
+
+    def __init__(self, width, height, filter_type, mbs, coeffs):
+        self.mbs = np.array(mbs, VP8_MB).reshape(-1)
+        self.coeffs = np.ascontiguousarray(coeffs, np.int16).reshape(-1).copy()
+        c = ocr_vp8_frame()
+        c.width, c.height, c.filter_type = width, height, filter_type
+        c.mbs, c.mbs_len = self.mbs.ctypes.data, len(self.mbs)
+        c.coeffs, c.coeffs_len = self.coeffs.ctypes.data if len(self.coeffs) else None, len(self.coeffs)
+        self.c = c
+
+    def decode(self, device_id=0, fill=0):
+        """ocr_vp8_decode: the (height, width, 3) BGR image; OcrError where the call refuses (err.out: the buffer as the call left
+        it, pre-filled with `fill`)"""
+        L = lib()
+        L.ocr_vp8_decode.argtypes = [C.POINTER(ocr_vp8_frame), C.c_int, C.c_void_p, C.c_size_t]
+        h, w = self.c.height, self.c.width
+        out = np.full((h, w, 3) if 0 < h <= 16383 and 0 < w <= 16383 else (1, 1, 3), fill, np.uint8)
+        rc = L.ocr_vp8_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
+            err.code = rc
+            err.out = out
             raise err
         return out
 

@@ -16,6 +16,7 @@
 #include "raw_stage.h"
 #include "tiff_stage.h"
 #include "webp_stage.h"
+#include "vp8_stage.h"
 #include "stages.h"
 
 using namespace ocr;
@@ -433,6 +434,7 @@ struct ocr_pipe {
   RawScratch raw;
   TiffScratch tiff;
   WebpScratch webp;
+  Vp8Scratch vp8;
   DevBuf<uint8_t> work;  // the requests' clones (OCRRequest copies the Mat, ocr_worker.h:28-29): cls rotates in place on them
   // Two batches in flight (round 5, ocr_pipe_run_device_on / ocr_pipe_run_staged_on): a call that names a chain runs its WHOLE
   // batch on that chain's worker, with a clone buffer of the chain's own; calls on different chains may run concurrently from
@@ -504,7 +506,7 @@ struct ocr_pipe {
   }
 
   // ---- stage a batch of JPEG coefficients, inflated PNG streams, stored BMP / PNM rows, expanded TIFF chunks and entropy-decoded
-  // WebP images, in any mix: the five pixel stages run on the copy stream, into the slot.  Image i is frames[i], a tagged descriptor (validated by the caller
+  // WebP images and VP8 frame descriptors, in any mix: the six pixel stages run on the copy stream, into the slot.  Image i is frames[i], a tagged descriptor (validated by the caller
   // before the sizes are used - a refused batch leaves the slot as it was: a known kind, and a sound descriptor)
   int stage_coded(int si, const ocr_coded_frame* frames, int count, std::string& err) {
     StageSlot& S = slots[si];
@@ -513,6 +515,7 @@ struct ocr_pipe {
     auto rw = [&](int i) { return (const ocr_raw_frame*)frames[i].frame; };
     auto tf = [&](int i) { return (const ocr_tiff_frame*)frames[i].frame; };
     auto wf = [&](int i) { return (const ocr_webp_frame*)frames[i].frame; };
+    auto vf = [&](int i) { return (const ocr_vp8_frame*)frames[i].frame; };
     int rc = layout(S, count, [&](int i, int& r, int& c) {
       // the oriented size: a 40 x 72 image and a 72 x 40 one that EXIF turns by 90 degrees share a size group and a det pass
       switch (frames[i].kind) {
@@ -520,7 +523,8 @@ struct ocr_pipe {
         case OCR_FRAME_PNG: r = pn(i)->height; c = pn(i)->width; break;
         case OCR_FRAME_RAW: r = rw(i)->height; c = rw(i)->width; break;
         case OCR_FRAME_TIFF: r = tf(i)->height; c = tf(i)->width; break;
-        default: r = wf(i)->height; c = wf(i)->width; break;
+        case OCR_FRAME_WEBP: r = wf(i)->height; c = wf(i)->width; break;
+        default: r = vf(i)->height; c = vf(i)->width; break;
       }
     }, err);
     if (rc) return rc;
@@ -529,7 +533,8 @@ struct ocr_pipe {
     std::vector<const ocr_raw_frame*> rf;
     std::vector<const ocr_tiff_frame*> tff;
     std::vector<const ocr_webp_frame*> wff;
-    std::vector<uint8_t*> jdst, pdst, rdst, tdst, wdst;
+    std::vector<const ocr_vp8_frame*> vff;
+    std::vector<uint8_t*> jdst, pdst, rdst, tdst, wdst, vdst;
     for (int k = 0; k < count; ++k) {
       const int i = S.imgs[k].orig;
       uint8_t* d = S.dev.p + S.imgs[k].off;
@@ -538,7 +543,8 @@ struct ocr_pipe {
         case OCR_FRAME_PNG: pf.push_back(pn(i)); pdst.push_back(d); break;
         case OCR_FRAME_RAW: rf.push_back(rw(i)); rdst.push_back(d); break;
         case OCR_FRAME_TIFF: tff.push_back(tf(i)); tdst.push_back(d); break;
-        default: wff.push_back(wf(i)); wdst.push_back(d); break;
+        case OCR_FRAME_WEBP: wff.push_back(wf(i)); wdst.push_back(d); break;
+        default: vff.push_back(vf(i)); vdst.push_back(d); break;
       }
     }
     if (!jf.empty()) rc = jpeg_decode_async(jf.data(), (int)jf.size(), jdst.data(), jpeg, copy_stream, err);
@@ -546,6 +552,7 @@ struct ocr_pipe {
     if (!rc && !rf.empty()) rc = raw_decode_async(rf.data(), (int)rf.size(), rdst.data(), raw, copy_stream, err);
     if (!rc && !tff.empty()) rc = tiff_decode_async(tff.data(), (int)tff.size(), tdst.data(), tiff, copy_stream, err);
     if (!rc && !wff.empty()) rc = webp_decode_async(wff.data(), (int)wff.size(), wdst.data(), webp, copy_stream, err);
+    if (!rc && !vff.empty()) rc = vp8_decode_async(vff.data(), (int)vff.size(), vdst.data(), vp8, copy_stream, err);
     if (rc) return rc;
     if (hipEventRecord(S.ready, copy_stream) != hipSuccess) { err = "hipEventRecord failed"; return OCR_ERR_DEVICE; }
     S.staged = true;
@@ -889,6 +896,7 @@ int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, i
       case OCR_FRAME_RAW: fault = raw_frame_fault(*(const ocr_raw_frame*)f); break;
       case OCR_FRAME_TIFF: fault = tiff_frame_fault(*(const ocr_tiff_frame*)f); break;
       case OCR_FRAME_WEBP: fault = webp_frame_fault(*(const ocr_webp_frame*)f); break;
+      case OCR_FRAME_VP8: fault = vp8_frame_fault(*(const ocr_vp8_frame*)f); break;
       default: fault = "frame kind is not an ocr_frame_kind"; break;
     }
     if (fault) return fail(OCR_ERR_ARG, fault);

@@ -32,6 +32,8 @@
 // --device / --frame too, through ocr_webp_decode (whatever OCR_DEVICE_WEBP says; a file outside the device stage's scope stays
 // on the host); --stage takes WebPs in the mix; --time <iters> <webp file> [<batch>]: ocr_webp_time / ocr_webp_time_batch (upload
 // of the coded data, pixel stage), "host_pixels_ms" (webp::pixels on one host thread), "bytes_in" / "bytes_out".
+// A lossy WebP takes the same switches: --device / --frame through ocr_vp8_decode, --stage in the mix, --time through
+// ocr_vp8_time / ocr_vp8_time_batch ("host_pixels_ms": vp8::pixels on one host thread, "descriptor_bytes": what one image uploads).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -71,6 +73,25 @@ static int time_device(int iters, const char* in, int batch) {
     return 0;
   }
   if (PaddleOCR::ipc::is_webp(bytes.data(), bytes.size())) {
+    auto v = std::make_shared<PaddleOCR::vp8::Frame>();
+    if (PaddleOCR::vp8::parse_file(bytes.data(), bytes.size(), *v)) {  // lossy
+      im.rows = v->height; im.cols = v->width;
+      im.vp8 = v;
+      const ocr_vp8_frame d = im.vp8_frame();
+      std::vector<const ocr_vp8_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
+      double ms[2];
+      if ((batch > 1 ? ocr_vp8_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_vp8_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+      std::vector<uint8_t> px;
+      const auto t0 = std::chrono::steady_clock::now();
+      for (int i = 0; i < iters; ++i)
+        for (size_t k = 0; k < all.size(); ++k) PaddleOCR::vp8::pixels(*v, px);
+      const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+      printf("{\"size\": [%d, %d], \"lossy\": true, \"filter_type\": %d, \"batch\": %d, \"iters\": %d, "
+             "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"descriptor_bytes\": %zu, \"bytes_out\": %zu}\n",
+             d.height, d.width, d.filter_type, (int)all.size(), iters, ms[0], ms[1], host_ms, v->mbs.size() * sizeof(PaddleOCR::vp8::Mb) + v->coeffs.size() * 2,
+             (size_t)d.width * d.height * 3 * all.size());
+      return 0;
+    }
     auto f = std::make_shared<PaddleOCR::webp::Frame>();
     if (!PaddleOCR::webp::parse(bytes.data(), bytes.size(), *f) || !f->device_ok) { fprintf(stderr, "decode failed: %s\n", f->error ? f->error : "outside the device stage's scope"); return 1; }
     im.rows = f->height; im.cols = f->width;
@@ -268,6 +289,11 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
+  if (im.device_decodable() && im.vp8) {
+    const ocr_vp8_frame d = im.vp8_frame();
+    im.pixels.resize((size_t)d.height * d.width * 3);
+    if (ocr_vp8_decode(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+  } else
   if (im.device_decodable() && im.webp) {
     const ocr_webp_frame d = im.webp_frame();
     im.pixels.resize((size_t)d.height * d.width * 3);

@@ -46,6 +46,7 @@
 #include "raw_decode.h"
 #include "tiff_decode.h"
 #include "webp_decode.h"
+#include "vp8_decode.h"
 
 namespace PaddleOCR {
 namespace ipc {
@@ -236,8 +237,10 @@ inline bool decode_tiff(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!tiff::pixels(*f, im.pixels)) { im = Image(); return false; }
   return true;
 }
-// Lossless WebP as cv::imdecode(IMREAD_COLOR) returns it (webp_decode.h: a VP8L chunk under RIFF / WEBP or in a VP8X container;
-// lossy and animated files are refused, *why says so).  device_pixels / force_device as for TIFF; the switch is
+// WebP as cv::imdecode(IMREAD_COLOR) returns it: lossless (webp_decode.h: a VP8L chunk under RIFF / WEBP or in a VP8X container)
+// and lossy (vp8_decode.h: a VP8 chunk, with or without ALPH; OCR_DEVICE_WEBP=1 stops after modes and tokens and leaves
+// reconstruction, loop filter and conversion to the worker).  Animated files and lossy data without a key frame are refused,
+// *why says so.  device_pixels / force_device as for TIFF; the switch is
 // OCR_DEVICE_WEBP, read once: =1 stops after the entropy-coded image is decoded and leaves the inverse transforms to the
 // worker (frames in the device stage's scope, webp::Frame::device_ok), =0 or unset finishes every file on this host thread.
 constexpr bool WEBP_DEVICE_DEFAULT = false;
@@ -250,6 +253,18 @@ inline bool decode_webp(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!is_webp(d.data(), d.size())) return false;
   auto f = std::make_shared<webp::Frame>();
   if (!webp::parse(d.data(), d.size(), *f)) {
+    if (f->vp8) {  // lossy: the payload goes to the VP8 decoder
+      auto v = std::make_shared<vp8::Frame>();
+      if (!vp8::parse(f->vp8, f->vp8_size, *v) || (f->canvas_width && (f->canvas_width != v->width || f->canvas_height != v->height))) {
+        if (why) *why = v->error;
+        return false;
+      }
+      im.pixels.clear();
+      im.rows = v->height; im.cols = v->width;
+      if (device_pixels && (force_device || webp_device_enabled())) { im.vp8 = std::move(v); return true; }
+      if (!vp8::pixels(*v, im.pixels)) { im = Image(); return false; }
+      return true;
+    }
     if (why) *why = f->error;
     return false;
   }

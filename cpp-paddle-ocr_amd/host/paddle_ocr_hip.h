@@ -34,6 +34,7 @@
 #include "raw_decode.h"
 #include "tiff_decode.h"
 #include "webp_decode.h"
+#include "vp8_decode.h"
 
 namespace PaddleOCR {
 
@@ -66,6 +67,9 @@ struct Image {
   // a lossless WebP whose entropy-coded image has been decoded (prefix codes, LZ77, colour cache): the worker undoes the
   // transforms on the device (ocr_pipe_stage_batch)
   std::shared_ptr<webp::Frame> webp;
+  // a lossy WebP whose key frame has been parsed (boolean decoder, modes, tokens): the worker reconstructs, filters and
+  // converts on the device (ocr_pipe_stage_batch)
+  std::shared_ptr<vp8::Frame> vp8;
   Image() = default;
   explicit Image(const ImageView& v) : rows(v.rows), cols(v.cols) {
     if (!v.empty()) {
@@ -74,10 +78,15 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp; }
-  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp); }
+  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8); }
   void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM / TIFF / WebP on the host
     if (!device_decodable()) return;
+    if (vp8) {
+      if (!vp8::pixels(*vp8, pixels)) throw std::runtime_error("WebP conversion failed");
+      vp8.reset();
+      return;
+    }
     if (webp) {
       if (!webp::pixels(*webp, pixels)) throw std::runtime_error("WebP conversion failed");
       webp.reset();
@@ -131,6 +140,14 @@ struct Image {
     d.data = tiff->data.data(); d.data_len = tiff->data.size();
     return d;
   }
+  ocr_vp8_frame vp8_frame() const {  // only when vp8
+    ocr_vp8_frame d;
+    memset(&d, 0, sizeof d);
+    d.width = vp8->width; d.height = vp8->height; d.filter_type = vp8->filter_type;
+    d.mbs = (const ocr_vp8_mb*)vp8->mbs.data(); d.mbs_len = vp8->mbs.size();
+    d.coeffs = vp8->coeffs.empty() ? nullptr : vp8->coeffs.data(); d.coeffs_len = vp8->coeffs.size();
+    return d;
+  }
   ocr_webp_frame webp_frame() const {  // only when webp
     ocr_webp_frame d;
     memset(&d, 0, sizeof d);
@@ -166,9 +183,11 @@ struct DeviceFrames {
   std::deque<ocr_raw_frame> rf;
   std::deque<ocr_tiff_frame> tf;
   std::deque<ocr_webp_frame> wf;
+  std::deque<ocr_vp8_frame> vf;
   std::vector<ocr_coded_frame> list;
   void add(const Image& im) {  // only when im.device_decodable()
-    if (im.webp) { wf.push_back(im.webp_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_WEBP, &wf.back()}); }
+    if (im.vp8) { vf.push_back(im.vp8_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_VP8, &vf.back()}); }
+    else if (im.webp) { wf.push_back(im.webp_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_WEBP, &wf.back()}); }
     else if (im.tiff) { tf.push_back(im.tiff_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF, &tf.back()}); }
     else if (im.raw) { rf.push_back(im.raw_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_RAW, &rf.back()}); }
     else if (im.png) { pf.push_back(im.png_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_PNG, &pf.back()}); }

@@ -9,8 +9,9 @@
 // Container: "RIFF" size "WEBP", then either a "VP8L" chunk or a "VP8X" chunk followed by any chunks, of which the first
 // "VP8L" is the image ("ICCP", "EXIF", "XMP " and unknown chunks are skipped: libwebp ignores them, the ICC profile is not
 // applied).  The RIFF size and every chunk size are checked against the bytes present; odd-sized chunks are padded.  A file
-// whose VP8X flags say animation, or that holds "ANIM" / "ANMF", and a file whose image is a lossy "VP8 " chunk (with or
-// without "ALPH") are refused with kNotLossless: no lossy decoder is here.
+// whose VP8X flags say animation, or that holds "ANIM" / "ANMF", is refused with kNotLossless.  A file whose image is a lossy
+// "VP8 " chunk (with or without "ALPH" in front, which is skipped) is not parse()'s either - it answers kNotLossless - but the
+// chunk's payload and the VP8X canvas are handed over in Frame::vp8 for vp8_decode.h, which decodes it.
 // VP8L: signature 0x2f, 14 bits width - 1, 14 bits height - 1, alpha_is_used (read, ignored), version 0; width * height
 // <= 64 Mpixel.  Bits are read from the least significant bit of each byte on; a prefix code's bits arrive most significant
 // first (as in Deflate).  Reading a bit the chunk does not have refuses the file.
@@ -53,7 +54,7 @@ constexpr long kMaxPixels = 64L << 20;  // the cap of the service's other decode
 constexpr int kMaxTransforms = 4;
 enum Kind { PREDICTOR = 0, CROSS_COLOUR = 1, ADD_GREEN = 2, COLOUR_INDEXING = 3 };
 // what a refused lossy or animated file is answered with
-constexpr const char* kNotLossless = "lossy or animated WebP is not decoded (only still lossless VP8L files are)";
+constexpr const char* kNotLossless = "lossy or animated WebP is not decoded (animated files, and lossy data without a key frame)";
 
 struct Transform {
   int kind = 0;
@@ -67,6 +68,10 @@ struct Frame {  // ocr_webp_frame of include/ocr_hip.h, field for field
   std::vector<Transform> transforms;   // in file order; pixels() undoes them last to first
   bool device_ok = false;              // colour indexing, if present, is the file's first transform: the device stage may take it
   const char* error = nullptr;         // why parse() refused
+  // a refused file whose image is a lossy "VP8 " chunk: its payload (inside the caller's bytes), and the VP8X canvas or 0 x 0
+  const uint8_t* vp8 = nullptr;
+  size_t vp8_size = 0;
+  int canvas_width = 0, canvas_height = 0;
 };
 
 inline int ceil_shift(int v, int bits) { return (v + (1 << bits) - 1) >> bits; }
@@ -392,7 +397,7 @@ inline bool parse(const uint8_t* d, size_t n, Frame& f) {
   if (riff < 12 || riff > n - 8) return fail("webp: the RIFF size is beyond the file");
   n = riff + 8;  // what follows the RIFF chunk is not the file's
   size_t pos = 12;
-  bool vp8x = false, first = true;
+  bool vp8x = false, first = true, alph = false;
   int canvas_w = 0, canvas_h = 0;
   while (pos + 8 <= n) {
     const uint8_t* tag = d + pos;
@@ -405,9 +410,18 @@ inline bool parse(const uint8_t* d, size_t n, Frame& f) {
       canvas_w = 1 + (body[4] | (body[5] << 8) | (body[6] << 16));
       canvas_h = 1 + (body[7] | (body[8] << 8) | (body[9] << 16));
       vp8x = true;
-    } else if (!memcmp(tag, "ANIM", 4) || !memcmp(tag, "ANMF", 4) || !memcmp(tag, "VP8 ", 4) || !memcmp(tag, "ALPH", 4)) {
+    } else if (!memcmp(tag, "ANIM", 4) || !memcmp(tag, "ANMF", 4)) {
       return fail(kNotLossless);
+    } else if (!memcmp(tag, "VP8 ", 4)) {
+      f.vp8 = body;
+      f.vp8_size = size;
+      if (vp8x) { f.canvas_width = canvas_w; f.canvas_height = canvas_h; }
+      return fail(kNotLossless);
+    } else if (!memcmp(tag, "ALPH", 4)) {
+      if (!vp8x) return fail(kNotLossless);
+      alph = true;
     } else if (!memcmp(tag, "VP8L", 4)) {
+      if (alph) return fail(kNotLossless);
       if (!parse_vp8l(body, size, f)) return false;
       if (vp8x && (canvas_w != f.width || canvas_h != f.height)) return fail("webp: the VP8X canvas is not the image's size");
       return true;
@@ -417,7 +431,7 @@ inline bool parse(const uint8_t* d, size_t n, Frame& f) {
     first = false;
     pos += 8 + size + (size & 1);
   }
-  return fail("webp: no image chunk");
+  return fail(alph ? kNotLossless : "webp: no image chunk");
 }
 
 // ----------------------------------------------------------------------------------------------------------- the pixel half

@@ -441,13 +441,48 @@ int ocr_webp_decode(const ocr_webp_frame* frame, int device_id, uint8_t* bgr, si
  * pixel-stage kernels; ocr_webp_time_batch: `count` frames as ONE batch (one upload, one launch per kernel kind). */
 int ocr_webp_time(const ocr_webp_frame* frame, int device_id, int iters, double ms[2]);
 int ocr_webp_time_batch(const ocr_webp_frame* const* frames, int count, int device_id, int iters, double ms[2]);
-/* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw, TIFF
- * and WebP frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
+/* Lossy WebP inputs (VP8 key frames) with the pixel half of the decoder on the device: the caller parses the container and
+ * does what is serial (boolean decoder, headers, modes, tokens: host/vp8_decode.h, vp8::parse); inverse WHT and DCT, intra
+ * prediction, the loop filter, fancy upsampling and the BGR conversion run on the copy stream straight into the slot.  The
+ * pixels are cv::imdecode(IMREAD_COLOR)'s as libwebp's WebPDecodeBGR makes them.  The device stage takes every frame the host
+ * half produces: nothing is left to the host.  Every field is checked on the host before anything is launched (OCR_ERR_ARG,
+ * ocr_last_error says which rule). */
+typedef struct ocr_vp8_mb {
+  uint8_t modes[16];     /* is_i4x4: the sub-block modes 0 .. 9 (DC TM VE HE RD VR LD VL HD HU) in raster order; else modes[0] is the
+                          * 16x16 mode 0 .. 3 (DC TM V H) */
+  uint8_t is_i4x4;       /* 0 or 1 */
+  uint8_t uvmode;        /* 0 .. 3 */
+  uint8_t level;         /* loop filter level 0 .. 63 of this macroblock (segment and deltas applied); 0: not filtered */
+  uint8_t ilevel;        /* interior limit, 0 .. 63 */
+  uint8_t hev;           /* high edge variance threshold, 0 .. 2 */
+  uint8_t inner;         /* 1: the inner edges are filtered too */
+  uint8_t segment, skip; /* as coded; not read */
+  uint32_t nz_y;         /* 2 bits a luma block, block 0 in bits 31 .. 30: 3 the full inverse DCT, 2 its three-coefficient form, else
+                          * the DC form when the DC is not zero */
+  uint32_t nz_uv;        /* the same for U (block 0 in bits 7 .. 6) and V (15 .. 14); a plane with any 2 or 3 is transformed in full */
+  uint32_t present;      /* bit b: block b is shipped (0 .. 15 luma, 16 .. 19 U, 20 .. 23 V, 24 Y2; Y2 only when !is_i4x4) */
+  uint32_t coeff_off;    /* in blocks of 16: the shipped blocks follow one another from here, in the order of their bits */
+} ocr_vp8_mb;
+typedef struct ocr_vp8_frame {
+  int width, height;     /* 1 .. 16383 each */
+  int filter_type;       /* 0 none, 1 simple (luma only), 2 normal */
+  const ocr_vp8_mb* mbs; /* host: ceil(width / 16) * ceil(height / 16) records in raster order */
+  size_t mbs_len;        /* records: >= that product */
+  const int16_t* coeffs; /* host: dequantised coefficients, 16 a block in raster (not zigzag) order, as libwebp's int16_t holds them */
+  size_t coeffs_len;     /* int16 values */
+} ocr_vp8_frame;
+int ocr_vp8_decode(const ocr_vp8_frame* frame, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time), as ocr_webp_time: ms[0] = the upload of the descriptor from pinned memory, ms[1] = the
+ * three kernels; ocr_vp8_time_batch: `count` frames as ONE batch (one upload, one launch per kernel kind). */
+int ocr_vp8_time(const ocr_vp8_frame* frame, int device_id, int iters, double ms[2]);
+int ocr_vp8_time_batch(const ocr_vp8_frame* const* frames, int count, int device_id, int iters, double ms[2]);
+/* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw, TIFF,
+ * WebP and VP8 frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
  * all five validate their own argument list and stage through the same code, with the same bytes in the slot. */
-typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4 } ocr_frame_kind;
+typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5 } ocr_frame_kind;
 typedef struct ocr_coded_frame {
   int kind;           /* ocr_frame_kind */
-  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame or ocr_webp_frame */
+  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame or ocr_vp8_frame */
 } ocr_coded_frame;
 int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
