@@ -576,7 +576,7 @@ EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_
             "ocr_png_decode", "ocr_png_time", "ocr_png_time_batch", "ocr_pipe_stage_coded",
             "ocr_raw_decode", "ocr_raw_time", "ocr_raw_time_batch", "ocr_pipe_stage_frames",
             "ocr_tiff_decode", "ocr_tiff_time", "ocr_tiff_time_batch", "ocr_pipe_stage_batch",
-            "ocr_webp_decode", "ocr_webp_time", "ocr_webp_time_batch", "ocr_vp8_decode", "ocr_vp8_time", "ocr_vp8_time_batch",
+            "ocr_webp_decode", "ocr_webp_time", "ocr_webp_time_batch", "ocr_vp8_decode", "ocr_vp8_time", "ocr_vp8_time_batch", "ocr_j2k_decode", "ocr_j2k_time", "ocr_j2k_time_batch",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_dev_copy_time", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
@@ -704,7 +704,7 @@ class ocr_coded_frame(C.Structure):
     _fields_ = [("kind", C.c_int), ("frame", C.c_void_p)]
 
 
-FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP, FRAME_VP8 = 0, 1, 2, 3, 4, 5
+FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP, FRAME_VP8, FRAME_J2K = 0, 1, 2, 3, 4, 5, 6
 
 
 class TiffFrame:
@@ -812,6 +812,50 @@ class Vp8Frame:
         h, w = self.c.height, self.c.width
         out = np.full((h, w, 3) if 0 < h <= 16383 and 0 < w <= 16383 else (1, 1, 3), fill, np.uint8)
         rc = L.ocr_vp8_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
+            err.code = rc
+            err.out = out
+            raise err
+        return out
+
+
+class ocr_j2k_frame(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("ncomp", C.c_int), ("prec", C.c_int), ("transform", C.c_int),
+                ("mct", C.c_int), ("chan", C.c_int * 3), ("tcs", C.c_void_p), ("tcs_len", C.c_size_t), ("steps", C.c_void_p), ("steps_len", C.c_size_t),
+                ("coeffs", C.c_void_p), ("coeffs_len", C.c_size_t)]
+
+
+# ocr_j2k_tilecomp as a numpy record (40 bytes)
+J2K_TC = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("levels", "<i4"), ("comp", "<i4"), ("step_off", "<u4"), ("reserved", "<u4"),
+                   ("coeff_off", "<u8")])
+
+
+class J2kFrame:
+    """an ocr_j2k_frame over Python-owned memory.  tcs: the tile-component records (J2K_TC, ncomp a tile, tiles in raster order);
+    steps: float32 step sizes; coeffs: int32 coefficients in the band arrangement.  .tcs / .steps / .coeffs and the fields of
+    .c may be changed before a call (the tests' tampering)."""
+
+    def __init__(self, width, height, x0, y0, ncomp, prec, transform, mct, chan, tcs, steps, coeffs):
+        self.tcs = np.array(tcs, J2K_TC).reshape(-1)
+        self.steps = np.ascontiguousarray(steps, np.float32).reshape(-1).copy()
+        self.coeffs = np.ascontiguousarray(coeffs, np.int32).reshape(-1).copy()
+        c = ocr_j2k_frame()
+        c.width, c.height, c.x0, c.y0, c.ncomp, c.prec, c.transform, c.mct = width, height, x0, y0, ncomp, prec, transform, mct
+        c.chan[0], c.chan[1], c.chan[2] = chan
+        c.tcs, c.tcs_len = self.tcs.ctypes.data, len(self.tcs)
+        c.steps, c.steps_len = self.steps.ctypes.data, len(self.steps)
+        c.coeffs, c.coeffs_len = self.coeffs.ctypes.data, len(self.coeffs)
+        self.c = c
+
+    def decode(self, device_id=0, fill=0):
+        """ocr_j2k_decode: the (height, width, 3) BGR image; OcrError where the call refuses (err.out: the buffer as the call left
+        it, pre-filled with `fill`)"""
+        L = lib()
+        L.ocr_j2k_decode.argtypes = [C.POINTER(ocr_j2k_frame), C.c_int, C.c_void_p, C.c_size_t]
+        h, w = self.c.height, self.c.width
+        out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= 1 << 26 else (1, 1, 3), fill, np.uint8)
+        rc = L.ocr_j2k_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
         if rc != 0:
             err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
             err.code = rc

@@ -32,6 +32,9 @@
 // --device / --frame too, through ocr_webp_decode (whatever OCR_DEVICE_WEBP says; a file outside the device stage's scope stays
 // on the host); --stage takes WebPs in the mix; --time <iters> <webp file> [<batch>]: ocr_webp_time / ocr_webp_time_batch (upload
 // of the coded data, pixel stage), "host_pixels_ms" (webp::pixels on one host thread), "bytes_in" / "bytes_out".
+// A JPEG 2000 file takes the same switches: --device / --frame through ocr_j2k_decode (a file outside the device stage's scope
+// stays on the host), --stage in the mix, --time through ocr_j2k_time / ocr_j2k_time_batch ("host_pixels_ms": j2k::pixels on one
+// host thread, "host_tier1_ms_per_image": j2k::parse, which is what bounds a request).
 // A lossy WebP takes the same switches: --device / --frame through ocr_vp8_decode, --stage in the mix, --time through
 // ocr_vp8_time / ocr_vp8_time_batch ("host_pixels_ms": vp8::pixels on one host thread, "descriptor_bytes": what one image uploads).
 #include <chrono>
@@ -70,6 +73,28 @@ static int time_device(int iters, const char* in, int batch) {
     if ((batch > 1 ? ocr_png_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_png_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
     printf("{\"size\": [%d, %d], \"color_type\": %d, \"bit_depth\": %d, \"interlace\": %d, \"segments\": %d, \"batch\": %d, \"iters\": %d, "
            "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f}\n", d.height, d.width, d.color_type, d.bit_depth, d.interlace, d.nsegments, (int)all.size(), iters, ms[0], ms[1]);
+    return 0;
+  }
+  if (PaddleOCR::ipc::is_j2k(bytes.data(), bytes.size())) {
+    auto v = std::make_shared<PaddleOCR::j2k::Frame>();
+    const auto p0 = std::chrono::steady_clock::now();
+    if (!PaddleOCR::j2k::parse(bytes.data(), bytes.size(), *v) || !v->device_ok) { fprintf(stderr, "decode failed: %s\n", v->error ? v->error : "outside the device stage's scope"); return 1; }
+    const double parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p0).count();
+    im.rows = v->height; im.cols = v->width;
+    im.j2k = v;
+    const ocr_j2k_frame d = im.j2k_frame();
+    std::vector<const ocr_j2k_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
+    double ms[2];
+    if ((batch > 1 ? ocr_j2k_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_j2k_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    std::vector<uint8_t> px;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < iters; ++i)
+      for (size_t k = 0; k < all.size(); ++k) PaddleOCR::j2k::pixels(*v, px);
+    const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+    printf("{\"size\": [%d, %d], \"j2k\": true, \"transform\": \"%s\", \"levels\": %d, \"batch\": %d, \"iters\": %d, "
+           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"host_tier1_ms_per_image\": %.5f, \"descriptor_bytes\": %zu, \"bytes_out\": %zu}\n",
+           d.height, d.width, d.transform ? "9/7" : "5/3", v->tcs[0].levels, (int)all.size(), iters, ms[0], ms[1], host_ms, parse_ms,
+           v->coeffs.size() * 4 + v->steps.size() * 4 + v->tcs.size() * sizeof(PaddleOCR::j2k::TileComp), (size_t)d.width * d.height * 3 * all.size());
     return 0;
   }
   if (PaddleOCR::ipc::is_webp(bytes.data(), bytes.size())) {
@@ -289,6 +314,11 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
+  if (im.device_decodable() && im.j2k) {
+    const ocr_j2k_frame d = im.j2k_frame();
+    im.pixels.resize((size_t)d.height * d.width * 3);
+    if (ocr_j2k_decode(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+  } else
   if (im.device_decodable() && im.vp8) {
     const ocr_vp8_frame d = im.vp8_frame();
     im.pixels.resize((size_t)d.height * d.width * 3);

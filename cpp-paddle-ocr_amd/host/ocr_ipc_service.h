@@ -47,6 +47,7 @@
 #include "tiff_decode.h"
 #include "webp_decode.h"
 #include "vp8_decode.h"
+#include "j2k_decode.h"
 
 namespace PaddleOCR {
 namespace ipc {
@@ -274,6 +275,30 @@ inline bool decode_webp(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!webp::pixels(*f, im.pixels)) { im = Image(); return false; }
   return true;
 }
+// JPEG 2000 (a JP2 file or a bare codestream) as cv::imdecode(IMREAD_COLOR) returns it through OpenJPEG (j2k_decode.h).  What
+// the decoder refuses - code-block styles, HT, POC / PPM / PPT / RGN, palettes, other colour spaces, signed or subsampled
+// components - it refuses with a reason, *why.  device_pixels / force_device as for TIFF; the switch is OCR_DEVICE_J2K, read
+// once: =1 stops after tier-1 and leaves dequantisation, the inverse wavelet and component transforms and the conversion to
+// the worker (frames in the device stage's scope, j2k::Frame::device_ok), =0 or unset finishes every file on this host thread.
+constexpr bool J2K_DEVICE_DEFAULT = false;
+inline bool j2k_device_enabled() {
+  static const char* env = getenv("OCR_DEVICE_J2K");
+  return env && env[0] ? env[0] != '0' : J2K_DEVICE_DEFAULT;
+}
+inline bool is_j2k(const uint8_t* d, size_t n) { return j2k::is_j2k(d, n); }
+inline bool decode_j2k(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false, const char** why = nullptr) {
+  if (!is_j2k(d.data(), d.size())) return false;
+  auto f = std::make_shared<j2k::Frame>();
+  if (!j2k::parse(d.data(), d.size(), *f)) {
+    if (why) *why = f->error;
+    return false;
+  }
+  im.pixels.clear();
+  im.rows = f->height; im.cols = f->width;
+  if (device_pixels && f->device_ok && (force_device || j2k_device_enabled())) { im.j2k = std::move(f); return true; }
+  if (!j2k::pixels(*f, im.pixels)) { im = Image(); return false; }
+  return true;
+}
 // libpng16 simplified API (png.h: png_image, PNG_IMAGE_VERSION 1, PNG_FORMAT_BGR = 0x12), resolved at run time
 struct PngImage {
   void* opaque;
@@ -347,13 +372,14 @@ inline bool decode_jpeg(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!dec.decode(d.data(), d.size(), im.pixels, im.rows, im.cols)) { im = Image(); return false; }
   return true;
 }
-// force_device: PNG, BMP / PNM, TIFF and WebP take the device route whatever OCR_DEVICE_PNG / OCR_DEVICE_RAW / OCR_DEVICE_TIFF /
-// OCR_DEVICE_WEBP say (decode_tool).  why: set where a file is refused for a reason its sender should read (a lossy or
+// force_device: PNG, BMP / PNM, TIFF, WebP and JPEG 2000 take the device route whatever OCR_DEVICE_PNG / OCR_DEVICE_RAW / OCR_DEVICE_TIFF /
+// OCR_DEVICE_WEBP / OCR_DEVICE_J2K say (decode_tool).  why: set where a file is refused for a reason its sender should read (a lossy or
 // animated WebP), left alone otherwise
 inline bool decode_image(const std::vector<uint8_t>& bytes, Image& im, bool device_pixels = false, bool force_device = false, const char** why = nullptr) {
   return decode_png(bytes, im, device_pixels, force_device) || decode_jpeg(bytes, im, device_pixels) ||
          decode_ppm(bytes, im, device_pixels, force_device) || decode_bmp(bytes, im, device_pixels, force_device) ||
-         decode_tiff(bytes, im, device_pixels, force_device) || decode_webp(bytes, im, device_pixels, force_device, why);
+         decode_tiff(bytes, im, device_pixels, force_device) || decode_webp(bytes, im, device_pixels, force_device, why) ||
+         decode_j2k(bytes, im, device_pixels, force_device, why);
 }
 inline bool read_file(const std::string& path, std::vector<uint8_t>& out) {
   std::ifstream f(path, std::ios::binary);

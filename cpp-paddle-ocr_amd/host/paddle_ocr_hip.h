@@ -35,6 +35,7 @@
 #include "tiff_decode.h"
 #include "webp_decode.h"
 #include "vp8_decode.h"
+#include "j2k_decode.h"
 
 namespace PaddleOCR {
 
@@ -70,6 +71,9 @@ struct Image {
   // a lossy WebP whose key frame has been parsed (boolean decoder, modes, tokens): the worker reconstructs, filters and
   // converts on the device (ocr_pipe_stage_batch)
   std::shared_ptr<vp8::Frame> vp8;
+  // a JPEG 2000 file after tier-1 (boxes, markers, packet headers, MQ decoding): the worker dequantises, undoes the wavelet and
+  // component transforms and converts on the device (ocr_pipe_stage_batch)
+  std::shared_ptr<j2k::Frame> j2k;
   Image() = default;
   explicit Image(const ImageView& v) : rows(v.rows), cols(v.cols) {
     if (!v.empty()) {
@@ -78,10 +82,15 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8; }
-  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8); }
+  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8 && !j2k; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8 || j2k); }
   void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM / TIFF / WebP on the host
     if (!device_decodable()) return;
+    if (j2k) {
+      if (!j2k::pixels(*j2k, pixels)) throw std::runtime_error("JPEG 2000 conversion failed");
+      j2k.reset();
+      return;
+    }
     if (vp8) {
       if (!vp8::pixels(*vp8, pixels)) throw std::runtime_error("WebP conversion failed");
       vp8.reset();
@@ -140,6 +149,17 @@ struct Image {
     d.data = tiff->data.data(); d.data_len = tiff->data.size();
     return d;
   }
+  ocr_j2k_frame j2k_frame() const {  // only when j2k
+    ocr_j2k_frame d;
+    memset(&d, 0, sizeof d);
+    d.width = j2k->width; d.height = j2k->height; d.x0 = j2k->x0; d.y0 = j2k->y0;
+    d.ncomp = j2k->ncomp; d.prec = j2k->prec; d.transform = j2k->transform; d.mct = j2k->mct;
+    for (int k = 0; k < 3; ++k) d.chan[k] = j2k->chan[k];
+    d.tcs = (const ocr_j2k_tilecomp*)j2k->tcs.data(); d.tcs_len = j2k->tcs.size();
+    d.steps = j2k->steps.data(); d.steps_len = j2k->steps.size();
+    d.coeffs = j2k->coeffs.data(); d.coeffs_len = j2k->coeffs.size();
+    return d;
+  }
   ocr_vp8_frame vp8_frame() const {  // only when vp8
     ocr_vp8_frame d;
     memset(&d, 0, sizeof d);
@@ -184,9 +204,11 @@ struct DeviceFrames {
   std::deque<ocr_tiff_frame> tf;
   std::deque<ocr_webp_frame> wf;
   std::deque<ocr_vp8_frame> vf;
+  std::deque<ocr_j2k_frame> kf;
   std::vector<ocr_coded_frame> list;
   void add(const Image& im) {  // only when im.device_decodable()
-    if (im.vp8) { vf.push_back(im.vp8_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_VP8, &vf.back()}); }
+    if (im.j2k) { kf.push_back(im.j2k_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K, &kf.back()}); }
+    else if (im.vp8) { vf.push_back(im.vp8_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_VP8, &vf.back()}); }
     else if (im.webp) { wf.push_back(im.webp_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_WEBP, &wf.back()}); }
     else if (im.tiff) { tf.push_back(im.tiff_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF, &tf.back()}); }
     else if (im.raw) { rf.push_back(im.raw_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_RAW, &rf.back()}); }

@@ -476,13 +476,49 @@ int ocr_vp8_decode(const ocr_vp8_frame* frame, int device_id, uint8_t* bgr, size
  * three kernels; ocr_vp8_time_batch: `count` frames as ONE batch (one upload, one launch per kernel kind). */
 int ocr_vp8_time(const ocr_vp8_frame* frame, int device_id, int iters, double ms[2]);
 int ocr_vp8_time_batch(const ocr_vp8_frame* const* frames, int count, int device_id, int iters, double ms[2]);
+/* JPEG 2000 inputs with the sample half of the decoder on the device: the caller parses boxes and markers and does what is
+ * serial (tier-2 packet headers, tier-1 MQ decoding: host/j2k_decode.h, j2k::parse); dequantisation, the multi-level inverse
+ * wavelet transform (5/3 in int32, 9/7 in float32 in OpenJPEG's operation order), the inverse component transform, level shift,
+ * clamp and the BGR store run on the copy stream straight into the slot.  The pixels are those of j2k::pixels, byte for byte.
+ * A band's rectangle and the parity of its origin follow from the tile-component's rectangle (j2k::band_rect, j2k::res_rect).
+ * The device stage takes frames of up to 8 decomposition levels whose tile's components share one level count; j2k::parse
+ * says so in Frame::device_ok, other frames are finished on the host.  Every field is checked on the host before anything is
+ * launched (OCR_ERR_ARG, ocr_last_error says which rule). */
+typedef struct ocr_j2k_tilecomp {
+  int x0, y0, x1, y1;   /* the tile-component's rectangle on the reference grid: inside the image, the same for the components of a tile */
+  int levels;           /* decomposition levels, 0 .. 32 (the device stage: 0 .. 8) */
+  int comp;             /* the file's component index; not read */
+  uint32_t step_off;    /* into steps: 1 + 3 * levels values - LL, then HL, LH, HH of resolution 1, 2, ... (read by the 9/7 only) */
+  uint32_t reserved;
+  uint64_t coeff_off;   /* into coeffs: (x1 - x0) * (y1 - y0) values in the band arrangement, row stride x1 - x0 */
+} ocr_j2k_tilecomp;
+typedef struct ocr_j2k_frame {
+  int width, height;    /* of the image; width * height <= 64 Mi */
+  int x0, y0;           /* the image's origin on the reference grid (XOsiz, YOsiz) */
+  int ncomp;            /* carried components per tile: 1 or 3 */
+  int prec;             /* 1 .. 16; above 8 the samples are reduced by >> (prec - 8) */
+  int transform;        /* 0: 5/3 reversible, 1: 9/7 */
+  int mct;              /* 1: inverse component transform (RCT / ICT) over the three carried components */
+  int chan[3];          /* which carried component is R, G, B */
+  const ocr_j2k_tilecomp* tcs; /* host: ncomp records a tile, tiles in raster order, covering the image exactly */
+  size_t tcs_len;
+  const float* steps;   /* host: quantiser step sizes */
+  size_t steps_len;
+  const int32_t* coeffs; /* host: tier-1's integers with their half bit (units of half a step) */
+  size_t coeffs_len;
+} ocr_j2k_frame;
+int ocr_j2k_decode(const ocr_j2k_frame* frame, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time), as ocr_vp8_time: ms[0] = the upload of the descriptor from pinned memory, ms[1] = the
+ * kernels; ocr_j2k_time_batch: `count` frames as ONE batch (one upload, two launches per level and one to finish). */
+int ocr_j2k_time(const ocr_j2k_frame* frame, int device_id, int iters, double ms[2]);
+int ocr_j2k_time_batch(const ocr_j2k_frame* const* frames, int count, int device_id, int iters, double ms[2]);
 /* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw, TIFF,
- * WebP and VP8 frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
+ * WebP, VP8 and JPEG 2000 frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
  * all five validate their own argument list and stage through the same code, with the same bytes in the slot. */
-typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5 } ocr_frame_kind;
+typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5, OCR_FRAME_J2K = 6 } ocr_frame_kind;
 typedef struct ocr_coded_frame {
   int kind;           /* ocr_frame_kind */
-  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame or ocr_vp8_frame */
+  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame, ocr_vp8_frame or ocr_j2k_frame */
 } ocr_coded_frame;
 int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
