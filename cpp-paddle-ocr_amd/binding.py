@@ -577,6 +577,7 @@ EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_
             "ocr_raw_decode", "ocr_raw_time", "ocr_raw_time_batch", "ocr_pipe_stage_frames",
             "ocr_tiff_decode", "ocr_tiff_time", "ocr_tiff_time_batch", "ocr_pipe_stage_batch",
             "ocr_webp_decode", "ocr_webp_time", "ocr_webp_time_batch", "ocr_vp8_decode", "ocr_vp8_time", "ocr_vp8_time_batch", "ocr_j2k_decode", "ocr_j2k_time", "ocr_j2k_time_batch",
+            "ocr_j2k_tier1", "ocr_j2k_decode_coded", "ocr_j2k_time_coded", "ocr_j2k_time_coded_batch",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_dev_copy_time", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
@@ -704,7 +705,7 @@ class ocr_coded_frame(C.Structure):
     _fields_ = [("kind", C.c_int), ("frame", C.c_void_p)]
 
 
-FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP, FRAME_VP8, FRAME_J2K = 0, 1, 2, 3, 4, 5, 6
+FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP, FRAME_VP8, FRAME_J2K, FRAME_J2K_CODED = 0, 1, 2, 3, 4, 5, 6, 7
 
 
 class TiffFrame:
@@ -862,6 +863,88 @@ class J2kFrame:
             err.out = out
             raise err
         return out
+
+
+class ocr_j2k_coded(C.Structure):
+    _fields_ = [("frame", ocr_j2k_frame), ("cblks", C.c_void_p), ("cblks_len", C.c_size_t), ("bytes", C.c_void_p), ("bytes_len", C.c_size_t)]
+
+
+# ocr_j2k_cblk as a numpy record (32 bytes)
+J2K_CBLK = np.dtype([("tc", "<u4"), ("at", "<u4"), ("byte_off", "<u8"), ("byte_len", "<u4"), ("w", "<u2"), ("h", "<u2"), ("orient", "u1"), ("numbps", "u1"),
+                     ("passes", "u1"), ("reserved", "u1"), ("reserved2", "<u4")])
+
+
+def _raise(L, rc, out):
+    err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
+    err.code = rc
+    err.out = out
+    raise err
+
+
+class J2kCoded:
+    """an ocr_j2k_coded over Python-owned memory: the frame before tier-1.  tcs, steps as for J2kFrame; ncoeffs: the size of the
+    coefficient plane; cblks: the code-block records (J2K_CBLK); data: the blocks' bytes.  .tcs / .steps / .cblks / .data and
+    the fields of .c may be changed before a call (the tests' tampering)."""
+
+    def __init__(self, width, height, x0, y0, ncomp, prec, transform, mct, chan, tcs, steps, ncoeffs, cblks, data):
+        self.tcs = np.array(tcs, J2K_TC).reshape(-1)
+        self.steps = np.ascontiguousarray(steps, np.float32).reshape(-1).copy()
+        self.cblks = np.array(cblks, J2K_CBLK).reshape(-1)
+        self.data = np.frombuffer(bytes(data), np.uint8).copy() if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8).reshape(-1).copy()
+        c = ocr_j2k_coded()
+        f = c.frame
+        f.width, f.height, f.x0, f.y0, f.ncomp, f.prec, f.transform, f.mct = width, height, x0, y0, ncomp, prec, transform, mct
+        f.chan[0], f.chan[1], f.chan[2] = chan
+        f.tcs, f.tcs_len = self.tcs.ctypes.data, len(self.tcs)
+        f.steps, f.steps_len = self.steps.ctypes.data, len(self.steps)
+        f.coeffs, f.coeffs_len = None, int(ncoeffs)
+        c.cblks, c.cblks_len = self.cblks.ctypes.data if len(self.cblks) else None, len(self.cblks)
+        c.bytes, c.bytes_len = self.data.ctypes.data if len(self.data) else None, len(self.data)
+        self.c = c
+
+    def tier1(self, device_id=0, fill=0):
+        """ocr_j2k_tier1: the int32 coefficient plane; OcrError where the call refuses (err.out: the buffer as the call left it)"""
+        L = lib()
+        L.ocr_j2k_tier1.argtypes = [C.POINTER(ocr_j2k_coded), C.c_int, C.c_void_p, C.c_size_t]
+        n = self.c.frame.coeffs_len
+        out = np.full(n if 0 < n <= 1 << 28 else 1, fill, np.int32)
+        rc = L.ocr_j2k_tier1(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            _raise(L, rc, out)
+        return out
+
+    def decode(self, device_id=0, fill=0):
+        """ocr_j2k_decode_coded: the (height, width, 3) BGR image; OcrError where the call refuses (err.out: the buffer as the
+        call left it, pre-filled with `fill`)"""
+        L = lib()
+        L.ocr_j2k_decode_coded.argtypes = [C.POINTER(ocr_j2k_coded), C.c_int, C.c_void_p, C.c_size_t]
+        h, w = self.c.frame.height, self.c.frame.width
+        out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= 1 << 26 else (1, 1, 3), fill, np.uint8)
+        rc = L.ocr_j2k_decode_coded(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            _raise(L, rc, out)
+        return out
+
+    def time(self, iters=3, device_id=0):
+        """ocr_j2k_time_coded: [upload, tier-1, pixel stage] in ms"""
+        return time_j2k_coded([self], iters, device_id, single=True)
+
+
+def time_j2k_coded(coded, iters=3, device_id=0, single=False):
+    """ocr_j2k_time_coded_batch over J2kCoded objects as one batch (single: ocr_j2k_time_coded of the first):
+    [upload, tier-1, pixel stage] in ms"""
+    L = lib()
+    ms = (C.c_double * 3)()
+    if single:
+        L.ocr_j2k_time_coded.argtypes = [C.POINTER(ocr_j2k_coded), C.c_int, C.c_int, C.POINTER(C.c_double)]
+        rc = L.ocr_j2k_time_coded(C.byref(coded[0].c), device_id, iters, ms)
+    else:
+        L.ocr_j2k_time_coded_batch.argtypes = [C.POINTER(C.POINTER(ocr_j2k_coded)), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        ptrs = (C.POINTER(ocr_j2k_coded) * len(coded))(*[C.pointer(k.c) for k in coded])
+        rc = L.ocr_j2k_time_coded_batch(ptrs, len(coded), device_id, iters, ms)
+    if rc != 0:
+        _raise(L, rc, None)
+    return list(ms)
 
 
 def rotate_crop_shape(rows, cols, box):

@@ -34,7 +34,11 @@
 // of the coded data, pixel stage), "host_pixels_ms" (webp::pixels on one host thread), "bytes_in" / "bytes_out".
 // A JPEG 2000 file takes the same switches: --device / --frame through ocr_j2k_decode (a file outside the device stage's scope
 // stays on the host), --stage in the mix, --time through ocr_j2k_time / ocr_j2k_time_batch ("host_pixels_ms": j2k::pixels on one
-// host thread, "host_tier1_ms_per_image": j2k::parse, which is what bounds a request).
+// host thread, "host_tier1_ms_per_image": j2k::parse, which is what bounds a request).  The coded route - tier-1 on the device
+// too, ocr_j2k_decode_coded - is taken by --device / --frame / --stage when OCR_DEVICE_J2K=2, and by --stage for an input
+// written "coded:<file>" whatever the switch says (so that one batch can mix both forms); --time measures both routes in one
+// run: "coded_upload_ms", "tier1_stage_ms", "coded_pixel_stage_ms" (ocr_j2k_time_coded / _batch), "coded_descriptor_bytes"
+// (what one image uploads that way) and "host_tier2_ms_per_image" (j2k::parse_coded: what stays on the host).
 // A lossy WebP takes the same switches: --device / --frame through ocr_vp8_decode, --stage in the mix, --time through
 // ocr_vp8_time / ocr_vp8_time_batch ("host_pixels_ms": vp8::pixels on one host thread, "descriptor_bytes": what one image uploads).
 #include <chrono>
@@ -91,10 +95,24 @@ static int time_device(int iters, const char* in, int batch) {
     for (int i = 0; i < iters; ++i)
       for (size_t k = 0; k < all.size(); ++k) PaddleOCR::j2k::pixels(*v, px);
     const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+    // the coded route
+    auto c = std::make_shared<PaddleOCR::j2k::Coded>();
+    const auto c0 = std::chrono::steady_clock::now();
+    if (!PaddleOCR::j2k::parse_coded(bytes.data(), bytes.size(), *c)) { fprintf(stderr, "decode failed: %s\n", c->frame.error ? c->frame.error : "tier-2"); return 1; }
+    const double tier2_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+    im.j2k_coded = c;
+    const ocr_j2k_coded cd = im.j2k_coded_frame();
+    std::vector<const ocr_j2k_coded*> call(all.size(), &cd);
+    double cms[3];
+    if ((batch > 1 ? ocr_j2k_time_coded_batch(call.data(), (int)call.size(), 0, iters, cms) : ocr_j2k_time_coded(&cd, 0, iters, cms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
     printf("{\"size\": [%d, %d], \"j2k\": true, \"transform\": \"%s\", \"levels\": %d, \"batch\": %d, \"iters\": %d, "
-           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"host_tier1_ms_per_image\": %.5f, \"descriptor_bytes\": %zu, \"bytes_out\": %zu}\n",
+           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"host_tier1_ms_per_image\": %.5f, \"descriptor_bytes\": %zu, \"bytes_out\": %zu, "
+           "\"coded_upload_ms\": %.5f, \"tier1_stage_ms\": %.5f, \"coded_pixel_stage_ms\": %.5f, \"coded_descriptor_bytes\": %zu, \"code_blocks\": %zu, "
+           "\"host_tier2_ms_per_image\": %.5f}\n",
            d.height, d.width, d.transform ? "9/7" : "5/3", v->tcs[0].levels, (int)all.size(), iters, ms[0], ms[1], host_ms, parse_ms,
-           v->coeffs.size() * 4 + v->steps.size() * 4 + v->tcs.size() * sizeof(PaddleOCR::j2k::TileComp), (size_t)d.width * d.height * 3 * all.size());
+           v->coeffs.size() * 4 + v->steps.size() * 4 + v->tcs.size() * sizeof(PaddleOCR::j2k::TileComp), (size_t)d.width * d.height * 3 * all.size(),
+           cms[0], cms[1], cms[2], c->bytes.size() + c->cblks.size() * sizeof(PaddleOCR::j2k::CodedBlock) + v->steps.size() * 4 + v->tcs.size() * sizeof(PaddleOCR::j2k::TileComp),
+           c->cblks.size(), tier2_ms);
     return 0;
   }
   if (PaddleOCR::ipc::is_webp(bytes.data(), bytes.size())) {
@@ -276,6 +294,17 @@ static int stage_batches(const std::string& model_dir, int nargs, char** args, b
     b.ims.resize(b.in.size());
     for (size_t i = 0; i < b.in.size(); ++i) {
       std::vector<uint8_t> bytes;
+      if (!b.in[i].compare(0, 6, "coded:")) {  // a JPEG 2000 file in the coded form, whatever OCR_DEVICE_J2K says
+        auto c = std::make_shared<PaddleOCR::j2k::Coded>();
+        if (!PaddleOCR::ipc::read_file(b.in[i].substr(6), bytes) || !PaddleOCR::j2k::parse_coded(bytes.data(), bytes.size(), *c) || !c->frame.device_ok) {
+          fprintf(stderr, "decode failed: %s\n", b.in[i].c_str());
+          return 1;
+        }
+        b.ims[i].rows = c->frame.height; b.ims[i].cols = c->frame.width;
+        b.ims[i].j2k_coded = c;
+        b.frames.add(b.ims[i]);
+        continue;
+      }
       if (!PaddleOCR::ipc::read_file(b.in[i], bytes) || !PaddleOCR::ipc::decode_image(bytes, b.ims[i], true, true) || !b.ims[i].device_decodable() ||
           (ways && !(b.ims[i].jpeg && b.ims[i].jpeg->classic()))) {
         fprintf(stderr, "decode failed: %s\n", b.in[i].c_str());
@@ -314,6 +343,11 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
+  if (im.device_decodable() && im.j2k_coded) {
+    const ocr_j2k_coded d = im.j2k_coded_frame();
+    im.pixels.resize((size_t)d.frame.height * d.frame.width * 3);
+    if (ocr_j2k_decode_coded(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+  } else
   if (im.device_decodable() && im.j2k) {
     const ocr_j2k_frame d = im.j2k_frame();
     im.pixels.resize((size_t)d.height * d.width * 3);

@@ -91,6 +91,28 @@ struct Frame {
   const char* error = nullptr;  // why parse() refused (nullptr: a bare decode failure)
 };
 
+// The frame BEFORE tier-1 (parse_coded): the frame without its coefficients, every coded block with where its samples go, and
+// the blocks' bytes.  What is left to do has no serial part: a block depends on no other (tier1(), or the device).
+struct CodedBlock {  // ocr_j2k_cblk of include/ocr_hip.h, field for field
+  uint32_t tc;        // index into Frame::tcs
+  uint32_t at;        // sample offset of the block's top-left corner within its tile-component's plane (row stride x1 - x0)
+  uint64_t byte_off;  // into Coded::bytes
+  uint32_t byte_len;  // the block's chunks one after another, in layer order
+  uint16_t w, h;      // 1 .. 1024 each, w * h <= 4096
+  uint8_t orient;     // 0 LL, 1 HL, 2 LH, 3 HH
+  uint8_t numbps;     // magnitude bit planes, 1 .. 30
+  uint8_t passes;     // coding passes, 1 .. 3 * numbps - 2
+  uint8_t reserved;
+  uint32_t reserved2;
+};
+static_assert(sizeof(CodedBlock) == 32, "CodedBlock is part of the C ABI");
+struct Coded {
+  Frame frame;          // coeffs stays empty
+  size_t ncoeffs = 0;   // what tier-1 fills: the sum of the tile-components' planes
+  std::vector<CodedBlock> cblks;
+  std::vector<uint8_t> bytes;
+};
+
 // ------------------------------------------------------------------------------------------------------------- geometry
 J2K_FN int ceil_shift(int64_t a, int b) { return (int)((a + (((int64_t)1 << b) - 1)) >> b); }
 // resolution with `lev` decompositions still to undo below the full size (lev = levels - r)
@@ -197,6 +219,24 @@ inline const char* device_fault(int width, int height, int ncomp, const TileComp
   for (size_t t = 0; t < ntcs; ++t) {
     if (tcs[t].levels > kDeviceMaxLevels) return "j2k frame: more decomposition levels than the device stage runs";
     if (tcs[t].levels != tcs[t - t % (size_t)ncomp].levels) return "j2k frame: the device stage wants one level count per tile";
+  }
+  return nullptr;
+}
+
+// why tier1() (and the device's tier-1, over ocr_j2k_coded) refuses a block list; nullptr when sound.  The tile-components
+// are those of a frame that passed fault_of().  Two blocks may overlap: they race on values, never out of bounds.
+inline const char* coded_fault(const TileComp* tcs, size_t ntcs, const CodedBlock* cblks, size_t ncblks, size_t nbytes) {
+  if (ncblks && !cblks) return "j2k coded: the block list is missing";
+  for (size_t i = 0; i < ncblks; ++i) {
+    const CodedBlock& k = cblks[i];
+    if (k.w < 1 || k.h < 1 || k.w > 1024 || k.h > 1024 || (int)k.w * k.h > 4096) return "j2k coded: a block must be 1 .. 1024 on a side and at most 4096 samples";
+    if (k.orient > 3) return "j2k coded: a block's orientation must be 0 .. 3";
+    if (k.numbps < 1 || k.numbps > 30) return "j2k coded: a block's bit planes must be 1 .. 30";
+    if (k.passes < 1 || k.passes > 3 * k.numbps - 2) return "j2k coded: a block's passes must be 1 .. 3 * numbps - 2";
+    if (k.tc >= ntcs) return "j2k coded: a block's tile-component lies beyond the list";
+    const int64_t W = (int64_t)tcs[k.tc].x1 - tcs[k.tc].x0, H = (int64_t)tcs[k.tc].y1 - tcs[k.tc].y0;
+    if (W < 1 || H < 1 || (int64_t)k.at % W + k.w > W || (int64_t)k.at / W + k.h > H) return "j2k coded: a block's rectangle leaves its tile-component";
+    if (k.byte_len > 0x7fffffffu || k.byte_off > nbytes || k.byte_len > nbytes - k.byte_off) return "j2k coded: a block's bytes lie beyond the pool";
   }
   return nullptr;
 }
@@ -332,9 +372,24 @@ struct Params {  // of the main header, copied per tile and overridden by the ti
   Qnt qnt[kMaxComps];
 };
 
-// the MQ arithmetic decoder (software conventions); bytes beyond the segment read as ff ff, which feeds ones
+}  // namespace detail
+
+// ------------------------------------------------------------------------------------------------------------------ tier-1
+// Tier-1 of one code block is stated ONCE, as templates over the block's storage S, and compiled twice: for the host over
+// vectors (detail::T1 below) and for the device over LDS (csrc/kernels_j2k_t1.hip).  S provides
+//   int flag(x, y), void set_flag(x, y, v)   the sample's flags; x in -1 .. w, y in -1 .. h (a border of one sample, never set)
+//   uint32_t mag(x, y), void set_mag(x, y, m)
+//   int cx(i), void set_cx(i, v)             MQ context i of 19: state << 1 | mps
+//   int at(uint32_t i)                       byte i of the block's segment; 0xff at or beyond its end (which feeds ones)
+//   void clear(), void clear_visited()       all flags, magnitudes to zero; VISITED off everywhere
+//   int width(), int height()
+enum : int { kSig = 1, kNeg = 2, kVisited = 4, kRefined = 8 };
+constexpr int kCxAgg = 17, kCxUni = 18, kCxMag = 14, kCxCount = 19;
+
+// the MQ arithmetic decoder's probability table (software conventions)
 struct MqState { uint16_t qe; uint8_t nmps, nlps, sw; };
-constexpr MqState kMq[47] = {
+J2K_FN MqState mq_row(int i) {
+  static constexpr MqState kMq[47] = {
     {0x5601, 1, 1, 1},    {0x3401, 2, 6, 0},    {0x1801, 3, 9, 0},    {0x0ac1, 4, 12, 0},   {0x0521, 5, 29, 0},   {0x0221, 38, 33, 0},
     {0x5601, 7, 6, 1},    {0x5401, 8, 14, 0},   {0x4801, 9, 14, 0},   {0x3801, 10, 14, 0},  {0x3001, 11, 17, 0},  {0x2401, 12, 18, 0},
     {0x1c01, 13, 20, 0},  {0x1601, 29, 21, 0},  {0x5601, 15, 14, 1},  {0x5401, 16, 14, 0},  {0x5101, 17, 15, 0},  {0x4801, 18, 16, 0},
@@ -343,145 +398,187 @@ constexpr MqState kMq[47] = {
     {0x0ac1, 31, 28, 0},  {0x09c1, 32, 29, 0},  {0x08a1, 33, 30, 0},  {0x0521, 34, 31, 0},  {0x0441, 35, 32, 0},  {0x02a1, 36, 33, 0},
     {0x0221, 37, 34, 0},  {0x0141, 38, 35, 0},  {0x0111, 39, 36, 0},  {0x0085, 40, 37, 0},  {0x0049, 41, 38, 0},  {0x0025, 42, 39, 0},
     {0x0015, 43, 40, 0},  {0x0009, 44, 41, 0},  {0x0005, 45, 42, 0},  {0x0001, 45, 43, 0},  {0x5601, 46, 46, 0}};
+  return kMq[i];
+}
 
-struct Mq {
-  const uint8_t* d;
-  size_t n, pos = 0;
-  uint32_t a = 0x8000, c = 0;
-  int ct = 0;
-  uint8_t state[19], mps[19];
-  uint8_t at(size_t i) const { return i < n ? d[i] : 0xff; }
-  void bytein() {
-    if (at(pos) == 0xff) {
-      if (at(pos + 1) > 0x8f) { c += 0xff00; ct = 8; }
-      else { ++pos; c += (uint32_t)at(pos) << 9; ct = 7; }
-    } else { ++pos; c += (uint32_t)at(pos) << 8; ct = 8; }
+// the decoder's registers; pos never passes the segment's length (beyond it every byte reads ff, which does not advance)
+struct Mq { uint32_t pos, a, c; int ct; };
+template <class S> J2K_FN void mq_bytein(S& s, Mq& q) {
+  if (s.at(q.pos) == 0xff) {
+    if (s.at(q.pos + 1) > 0x8f) { q.c += 0xff00; q.ct = 8; }  // a marker: not consumed
+    else { ++q.pos; q.c += (uint32_t)s.at(q.pos) << 9; q.ct = 7; }
+  } else { ++q.pos; q.c += (uint32_t)s.at(q.pos) << 8; q.ct = 8; }
+}
+template <class S> J2K_FN void mq_init(S& s, Mq& q) {
+  for (int i = 0; i < kCxCount; ++i) s.set_cx(i, 0);
+  s.set_cx(0, 4 << 1); s.set_cx(kCxAgg, 3 << 1); s.set_cx(kCxUni, 46 << 1);
+  q.pos = 0; q.a = 0x8000; q.ct = 0;
+  q.c = (uint32_t)s.at(0) << 16;
+  mq_bytein(s, q);
+  q.c <<= 7;
+  q.ct -= 7;
+}
+// at most 15 shifts: a >= qe >= 1 on entry and the loop ends at a >= 0x8000
+template <class S> J2K_FN void mq_renorm(S& s, Mq& q) {
+  do {
+    if (q.ct == 0) mq_bytein(s, q);
+    q.a <<= 1; q.c <<= 1; --q.ct;
+  } while (q.a < 0x8000);
+}
+template <class S> J2K_FN int mq_decode(S& s, Mq& q, int cx) {
+  const int v = s.cx(cx), mps = v & 1;
+  const MqState r = mq_row(v >> 1);
+  const uint32_t qe = r.qe;
+  bool lps;  // the less probable symbol came out
+  q.a -= qe;
+  if ((q.c >> 16) < qe) {
+    lps = q.a >= qe;
+    q.a = qe;
+  } else {
+    q.c -= qe << 16;
+    if (q.a & 0x8000) return mps;
+    lps = q.a < qe;
   }
-  Mq(const uint8_t* data, size_t len) : d(data), n(len) {
-    memset(state, 0, sizeof state);
-    memset(mps, 0, sizeof mps);
-    state[0] = 4; state[17] = 3; state[18] = 46;
-    c = (uint32_t)at(0) << 16;
-    bytein();
-    c <<= 7;
-    ct -= 7;
-  }
-  void renorm() {
-    do {
-      if (ct == 0) bytein();
-      a <<= 1; c <<= 1; --ct;
-    } while (a < 0x8000);
-  }
-  int decode(int cx) {
-    const MqState& s = kMq[state[cx]];
-    int bit;
-    a -= s.qe;
-    if ((c >> 16) < s.qe) {
-      if (a < s.qe) { bit = mps[cx]; state[cx] = s.nmps; }
-      else { bit = 1 - mps[cx]; if (s.sw) mps[cx] ^= 1; state[cx] = s.nlps; }
-      a = s.qe;
-      renorm();
-    } else {
-      c -= (uint32_t)s.qe << 16;
-      if (a & 0x8000) return mps[cx];
-      if (a < s.qe) { bit = 1 - mps[cx]; if (s.sw) mps[cx] ^= 1; state[cx] = s.nlps; }
-      else { bit = mps[cx]; state[cx] = s.nmps; }
-      renorm();
-    }
-    return bit;
-  }
-};
+  s.set_cx(cx, lps ? (r.nlps << 1 | (mps ^ r.sw)) : (r.nmps << 1 | mps));
+  mq_renorm(s, q);
+  return lps ? 1 - mps : mps;
+}
 
-// tier-1 of one code block: w x h samples, `numbps` magnitude planes, `passes` coding passes out of `data`; out: the signed
-// integers with their half bit, row stride `stride`
-struct T1 {
-  enum { SIG = 1, NEG = 2, VISITED = 4, REFINED = 8 };
-  std::vector<uint8_t> fl;
-  std::vector<uint32_t> mag;
-  int w = 0, h = 0, fw = 0;
-  uint8_t& F(int x, int y) { return fl[(size_t)(y + 1) * fw + x + 1]; }
-  int zc(int x, int y, int orient) {
-    int hz = (F(x - 1, y) & SIG) + (F(x + 1, y) & SIG), v = (F(x, y - 1) & SIG) + (F(x, y + 1) & SIG);
-    const int d = (F(x - 1, y - 1) & SIG) + (F(x + 1, y - 1) & SIG) + (F(x - 1, y + 1) & SIG) + (F(x + 1, y + 1) & SIG);
-    if (orient == 3) {
-      const int hv = hz + v;
-      if (d >= 3) return 8;
-      if (d == 2) return hv >= 1 ? 7 : 6;
-      if (d == 1) return hv >= 2 ? 5 : hv == 1 ? 4 : 3;
-      return hv >= 2 ? 2 : hv;
-    }
-    if (orient == 1) std::swap(hz, v);
-    if (hz == 2) return 8;
-    if (hz == 1) return v >= 1 ? 7 : d >= 1 ? 6 : 5;
-    if (v == 2) return 4;
-    if (v == 1) return 3;
-    return d >= 2 ? 2 : d;
+// the zero-coding context of a sample from how many of its horizontal (0 .. 2), vertical (0 .. 2) and diagonal (0 .. 4)
+// neighbours are significant
+J2K_FN int zc_ctx(int hz, int v, int d, int orient) {
+  if (orient == 3) {
+    const int hv = hz + v;
+    if (d >= 3) return 8;
+    if (d == 2) return hv >= 1 ? 7 : 6;
+    if (d == 1) return hv >= 2 ? 5 : hv == 1 ? 4 : 3;
+    return hv >= 2 ? 2 : hv;
   }
-  bool any(int x, int y) {
-    return ((F(x - 1, y) | F(x + 1, y) | F(x, y - 1) | F(x, y + 1) | F(x - 1, y - 1) | F(x + 1, y - 1) | F(x - 1, y + 1) | F(x + 1, y + 1)) & SIG) != 0;
-  }
-  int contrib(int x, int y) { const uint8_t f = F(x, y); return (f & SIG) ? ((f & NEG) ? -1 : 1) : 0; }
-  void sign(Mq& mq, int x, int y) {
-    const int hc = std::max(-1, std::min(1, contrib(x - 1, y) + contrib(x + 1, y))), vc = std::max(-1, std::min(1, contrib(x, y - 1) + contrib(x, y + 1)));
-    static const uint8_t ctx[3][3] = {{13, 12, 11}, {10, 9, 10}, {11, 12, 13}};  // [h + 1][v + 1]
-    static const uint8_t flip[3][3] = {{1, 1, 1}, {1, 0, 0}, {0, 0, 0}};
-    const int bit = mq.decode(ctx[hc + 1][vc + 1]) ^ flip[hc + 1][vc + 1];
-    F(x, y) |= bit ? (SIG | NEG) : SIG;
-  }
-  void run(const uint8_t* data, size_t len, int numbps, int passes, int orient, int cw, int chh, int32_t* out, size_t stride) {
-    w = cw; h = chh; fw = w + 2;
-    fl.assign((size_t)fw * (h + 2), 0);
-    mag.assign((size_t)w * h, 0);
-    Mq mq(data, len);
-    int bp1 = numbps, type = 2;
-    for (int p = 0; p < passes && bp1 >= 1; ++p) {
-      const uint32_t one = 1u << bp1, half = one >> 1, oph = one | half;
-      if (type == 0) {
-        for (int y0 = 0; y0 < h; y0 += 4)
-          for (int x = 0; x < w; ++x)
-            for (int y = y0; y < std::min(h, y0 + 4); ++y) {
-              if ((F(x, y) & SIG) || !any(x, y)) continue;
-              if (mq.decode(zc(x, y, orient))) { sign(mq, x, y); mag[(size_t)y * w + x] = oph; }
-              F(x, y) |= VISITED;
-            }
-      } else if (type == 1) {
-        for (int y0 = 0; y0 < h; y0 += 4)
-          for (int x = 0; x < w; ++x)
-            for (int y = y0; y < std::min(h, y0 + 4); ++y) {
-              const uint8_t f = F(x, y);
-              if ((f & (SIG | VISITED)) != SIG) continue;
-              const int cx = (f & REFINED) ? 16 : any(x, y) ? 15 : 14;
-              if (mq.decode(cx)) mag[(size_t)y * w + x] += half; else mag[(size_t)y * w + x] -= half;
-              F(x, y) |= REFINED;
-            }
-      } else {
-        for (int y0 = 0; y0 < h; y0 += 4)
-          for (int x = 0; x < w; ++x) {
-            int y = y0;
-            if (y0 + 4 <= h && !((F(x, y0) | F(x, y0 + 1) | F(x, y0 + 2) | F(x, y0 + 3)) & (SIG | VISITED)) && !any(x, y0) && !any(x, y0 + 1) &&
-                !any(x, y0 + 2) && !any(x, y0 + 3)) {
-              if (!mq.decode(17)) continue;
-              int run = mq.decode(18) << 1;
-              run |= mq.decode(18);
-              y = y0 + run;
-              sign(mq, x, y);
-              mag[(size_t)y * w + x] = oph;
-              ++y;
-            }
-            for (; y < std::min(h, y0 + 4); ++y) {
-              if (F(x, y) & (SIG | VISITED)) continue;
-              if (mq.decode(zc(x, y, orient))) { sign(mq, x, y); mag[(size_t)y * w + x] = oph; }
-            }
-          }
-        for (auto& f : fl) f &= (uint8_t)~VISITED;
-      }
-      if (++type == 3) { type = 0; --bp1; }
-    }
-    for (int y = 0; y < h; ++y)
+  if (orient == 1) { const int t = hz; hz = v; v = t; }
+  if (hz == 2) return 8;
+  if (hz == 1) return v >= 1 ? 7 : d >= 1 ? 6 : 5;
+  if (v == 2) return 4;
+  if (v == 1) return 3;
+  return d >= 2 ? 2 : d;
+}
+// the sign's context and whether the decoded bit is flipped, from the neighbours' contributions hc, vc in -1 .. 1
+J2K_FN int sign_ctx(int hc, int vc) {
+  static constexpr uint8_t ctx[3][3] = {{13, 12, 11}, {10, 9, 10}, {11, 12, 13}};  // [h + 1][v + 1]
+  return ctx[hc + 1][vc + 1];
+}
+J2K_FN int sign_flip(int hc, int vc) {
+  static constexpr uint8_t flip[3][3] = {{1, 1, 1}, {1, 0, 0}, {0, 0, 0}};
+  return flip[hc + 1][vc + 1];
+}
+// the pass order: a block starts with the cleanup pass of its top plane, then significance, refinement, cleanup per plane
+enum : int { kPassSig = 0, kPassRef = 1, kPassClean = 2 };
+J2K_FN void pass_first(int numbps, int& bp1, int& type) { bp1 = numbps; type = kPassClean; }
+J2K_FN void pass_next(int& bp1, int& type) { if (++type == 3) { type = kPassSig; --bp1; } }
+J2K_FN int max_passes(int numbps) { return 3 * numbps - 2; }
+
+namespace t1 {
+template <class S> J2K_FN int sig(S& s, int x, int y) { return s.flag(x, y) & kSig; }
+template <class S> J2K_FN int zc(S& s, int x, int y, int orient) {
+  return zc_ctx(sig(s, x - 1, y) + sig(s, x + 1, y), sig(s, x, y - 1) + sig(s, x, y + 1),
+                sig(s, x - 1, y - 1) + sig(s, x + 1, y - 1) + sig(s, x - 1, y + 1) + sig(s, x + 1, y + 1), orient);
+}
+template <class S> J2K_FN bool any(S& s, int x, int y) {
+  return ((s.flag(x - 1, y) | s.flag(x + 1, y) | s.flag(x, y - 1) | s.flag(x, y + 1) | s.flag(x - 1, y - 1) | s.flag(x + 1, y - 1) | s.flag(x - 1, y + 1) |
+           s.flag(x + 1, y + 1)) & kSig) != 0;
+}
+template <class S> J2K_FN int contrib(S& s, int x, int y) { const int f = s.flag(x, y); return (f & kSig) ? ((f & kNeg) ? -1 : 1) : 0; }
+J2K_FN int clamp1(int v) { return v < -1 ? -1 : v > 1 ? 1 : v; }
+template <class S> J2K_FN void sign(S& s, Mq& q, int x, int y) {
+  const int hc = clamp1(contrib(s, x - 1, y) + contrib(s, x + 1, y)), vc = clamp1(contrib(s, x, y - 1) + contrib(s, x, y + 1));
+  const int bit = mq_decode(s, q, sign_ctx(hc, vc)) ^ sign_flip(hc, vc);
+  s.set_flag(x, y, s.flag(x, y) | (bit ? (kSig | kNeg) : kSig));
+}
+// The coding passes of one block into S: `numbps` magnitude planes, `passes` coding passes.  Every loop is bounded by the
+// descriptor: at most max_passes(30) = 88 passes, width * height samples a pass and at most four decoded symbols a sample;
+// no byte sequence changes how often a loop runs, only what it decodes.
+template <class S> J2K_FN void decode(S& s, int numbps, int passes, int orient) {
+  const int w = s.width(), h = s.height();
+  s.clear();
+  Mq q;
+  mq_init(s, q);
+  int bp1, type;
+  pass_first(numbps, bp1, type);
+  for (int p = 0; p < passes && bp1 >= 1; ++p) {
+    const uint32_t one = 1u << bp1, half = one >> 1, oph = one | half;
+    for (int y0 = 0; y0 < h; y0 += 4) {
+      const int y1 = y0 + 4 < h ? y0 + 4 : h;
       for (int x = 0; x < w; ++x) {
-        const int32_t m = (int32_t)(mag[(size_t)y * w + x] & 0x7fffffffu);
-        out[(size_t)y * stride + x] = (F(x, y) & NEG) ? -m : m;
+        if (type == kPassSig) {
+          for (int y = y0; y < y1; ++y) {
+            if ((s.flag(x, y) & kSig) || !any(s, x, y)) continue;
+            if (mq_decode(s, q, zc(s, x, y, orient))) { sign(s, q, x, y); s.set_mag(x, y, oph); }
+            s.set_flag(x, y, s.flag(x, y) | kVisited);
+          }
+        } else if (type == kPassRef) {
+          for (int y = y0; y < y1; ++y) {
+            const int f = s.flag(x, y);
+            if ((f & (kSig | kVisited)) != kSig) continue;
+            const int cx = (f & kRefined) ? kCxMag + 2 : any(s, x, y) ? kCxMag + 1 : kCxMag;
+            if (mq_decode(s, q, cx)) s.set_mag(x, y, s.mag(x, y) + half); else s.set_mag(x, y, s.mag(x, y) - half);
+            s.set_flag(x, y, f | kRefined);
+          }
+        } else {
+          int y = y0;
+          if (y0 + 4 <= h && !((s.flag(x, y0) | s.flag(x, y0 + 1) | s.flag(x, y0 + 2) | s.flag(x, y0 + 3)) & (kSig | kVisited)) && !any(s, x, y0) &&
+              !any(s, x, y0 + 1) && !any(s, x, y0 + 2) && !any(s, x, y0 + 3)) {
+            if (!mq_decode(s, q, kCxAgg)) continue;
+            int run = mq_decode(s, q, kCxUni) << 1;
+            run |= mq_decode(s, q, kCxUni);
+            y = y0 + run;
+            sign(s, q, x, y);
+            s.set_mag(x, y, oph);
+            ++y;
+          }
+          for (; y < y1; ++y) {
+            if (s.flag(x, y) & (kSig | kVisited)) continue;
+            if (mq_decode(s, q, zc(s, x, y, orient))) { sign(s, q, x, y); s.set_mag(x, y, oph); }
+          }
+        }
       }
+    }
+    if (type == kPassClean) s.clear_visited();
+    pass_next(bp1, type);
+  }
+}
+// what a sample's state comes to: the signed integer with its half bit
+J2K_FN int32_t coefficient(int flag, uint32_t mag) {
+  const int32_t m = (int32_t)(mag & 0x7fffffffu);
+  return (flag & kNeg) ? -m : m;
+}
+}  // namespace t1
+
+namespace detail {
+
+// tier-1's storage on the host: one code block of w x h samples over `len` bytes at `data`
+struct T1 {
+  std::vector<uint8_t> fl;
+  std::vector<uint32_t> mg;
+  uint8_t ctx[kCxCount];
+  const uint8_t* data = nullptr;
+  uint32_t len = 0;
+  int w = 0, h = 0, fw = 0;
+  int width() const { return w; }
+  int height() const { return h; }
+  int flag(int x, int y) const { return fl[(size_t)(y + 1) * fw + x + 1]; }
+  void set_flag(int x, int y, int v) { fl[(size_t)(y + 1) * fw + x + 1] = (uint8_t)v; }
+  uint32_t mag(int x, int y) const { return mg[(size_t)y * w + x]; }
+  void set_mag(int x, int y, uint32_t m) { mg[(size_t)y * w + x] = m; }
+  int cx(int i) const { return ctx[i]; }
+  void set_cx(int i, int v) { ctx[i] = (uint8_t)v; }
+  int at(uint32_t i) const { return i < len ? data[i] : 0xff; }
+  void clear() { fl.assign((size_t)fw * (h + 2), 0); mg.assign((size_t)w * h, 0); }
+  void clear_visited() { for (auto& f : fl) f &= (uint8_t)~kVisited; }
+  // out: the signed integers with their half bit, row stride `stride`
+  void run(const uint8_t* bytes, uint32_t n, int numbps, int passes, int orient, int cw, int chh, int32_t* out, size_t stride) {
+    data = bytes; len = n; w = cw; h = chh; fw = w + 2;
+    t1::decode(*this, numbps, passes, orient);
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x) out[(size_t)y * stride + x] = t1::coefficient(flag(x, y), mag(x, y));
   }
 };
 
@@ -576,11 +673,12 @@ inline int floor_log2(uint32_t v) { int l = 0; while (v > 1) { v >>= 1; ++l; } r
 
 }  // namespace detail
 
-// One tile: structure, tier-2 over `data` (the tile-parts' bodies one after another), tier-1 into the frame's coefficients.
-// `carried[c]`: the slot of component c among the carried ones, or -1.
-inline bool decode_tile(Frame& f, const detail::Params& P, int ncomps, const Rect& tile, const std::vector<uint8_t>& data, const int* carried, size_t tc_base,
+// One tile: structure, tier-2 over `data` (the tile-parts' bodies one after another), then the blocks tier-1 is to decode, with
+// their bytes, for the carried components.  `carried[c]`: the slot of component c among the carried ones, or -1.
+inline bool decode_tile(Coded& cd, const detail::Params& P, int ncomps, const Rect& tile, const std::vector<uint8_t>& data, const int* carried, size_t tc_base,
                         const char*& error) {
   using namespace detail;
+  Frame& f = cd.frame;
   auto fail = [&](const char* why) { error = why; return false; };
   std::vector<std::vector<Res>> comps((size_t)ncomps);
   int64_t npackets = 0;
@@ -742,10 +840,8 @@ inline bool decode_tile(Frame& f, const detail::Params& P, int ncomps, const Rec
       pos += g.len;
     }
   }
-  // tier-1, into the carried components' coefficients
+  // what tier-1 decodes, into the carried components' coefficients
   const int w = tile.x1 - tile.x0, h = tile.y1 - tile.y0;
-  T1 t1;
-  std::vector<uint8_t> seg;
   for (int c = 0; c < ncomps; ++c) {
     if (carried[c] < 0) continue;
     TileComp& tc = f.tcs[tc_base + (size_t)carried[c]];
@@ -754,34 +850,38 @@ inline bool decode_tile(Frame& f, const detail::Params& P, int ncomps, const Rec
     tc.comp = c;
     tc.reserved = 0;
     tc.step_off = (uint32_t)f.steps.size();
-    tc.coeff_off = f.coeffs.size();
+    tc.coeff_off = cd.ncoeffs;
     const Qnt& q = P.qnt[c];
     for (int bi = 0; bi < 3 * tc.levels + 1; ++bi) {
       const int expn = q.style == 1 ? std::max(0, (int)q.expn[0] - (bi ? (bi - 1) / 3 : 0)) : q.expn[bi];
       const int mant = q.style == 1 ? q.mant[0] : q.style == 2 ? q.mant[bi] : 0;
       f.steps.push_back((float)((1.0 + mant / 2048.0) * std::pow(2.0, f.prec - expn)));
     }
-    f.coeffs.resize(f.coeffs.size() + (size_t)w * h, 0);
-    int32_t* plane = f.coeffs.data() + tc.coeff_off;
+    cd.ncoeffs += (size_t)w * h;
     for (Res& R : comps[(size_t)c])
       for (size_t pi = 0; pi < R.prec.size(); ++pi) {
         const Band& B = R.band[pi % (size_t)R.nbands];
         for (const Cblk& k : R.prec[pi].cblks) {
           if (!k.included || k.passes == 0 || k.numbps == 0) continue;
-          seg.clear();
-          for (int32_t id = k.first; id >= 0; id = chunks[(size_t)id].next) seg.insert(seg.end(), d + chunks[(size_t)id].off, d + chunks[(size_t)id].off + chunks[(size_t)id].len);
-          t1.run(seg.data(), seg.size(), k.numbps, k.passes, B.orient, k.x1 - k.x0, k.y1 - k.y0,
-                 plane + (size_t)(B.oy + k.y0 - B.r.y0) * w + (size_t)(B.ox + k.x0 - B.r.x0), (size_t)w);
+          const size_t from = cd.bytes.size();
+          for (int32_t id = k.first; id >= 0; id = chunks[(size_t)id].next) cd.bytes.insert(cd.bytes.end(), d + chunks[(size_t)id].off, d + chunks[(size_t)id].off + chunks[(size_t)id].len);
+          if (cd.bytes.size() - from > 0x7fffffffu) return fail("j2k: a code block of more than 2 GiB");
+          // (passes beyond max_passes are never run: t1::decode stops at the last plane)
+          cd.cblks.push_back(CodedBlock{(uint32_t)(tc_base + (size_t)carried[c]), (uint32_t)((size_t)(B.oy + k.y0 - B.r.y0) * w + (size_t)(B.ox + k.x0 - B.r.x0)), from,
+                                        (uint32_t)(cd.bytes.size() - from), (uint16_t)(k.x1 - k.x0), (uint16_t)(k.y1 - k.y0), (uint8_t)B.orient, (uint8_t)k.numbps,
+                                        (uint8_t)std::min(k.passes, max_passes(k.numbps)), 0, 0});
         }
       }
   }
   return true;
 }
 
-// The serial half: container, headers, tier-2, tier-1.  false: refused, Frame::error says why where a reason is known.
-inline bool parse(const uint8_t* d, size_t n, Frame& f) {
+// The serial half up to the seam between tier-2 and tier-1: container, headers, packets.  false: refused, Frame::error says
+// why where a reason is known.
+inline bool parse_coded(const uint8_t* d, size_t n, Coded& cd) {
   using namespace detail;
-  f = Frame();
+  cd = Coded();
+  Frame& f = cd.frame;
   auto fail = [&](const char* why) { f.error = why; return false; };
   if (!is_j2k(d, n)) return fail("j2k: neither a JP2 signature nor a codestream");
   int colours = 0;              // 1 grey, 3 RGB; 0: guessed from the component count
@@ -1054,19 +1154,49 @@ inline bool parse(const uint8_t* d, size_t n, Frame& f) {
   f.sop = P0.sop; f.eph = P0.eph;
   // ---- tiles
   f.tcs.assign(ntiles * (size_t)f.ncomp, TileComp());
-  f.coeffs.reserve((size_t)f.width * f.height * f.ncomp);
   for (size_t t = 0; t < ntiles; ++t) {
     const uint64_t p = t % tw, q = t / tw;
     Rect tile;
     tile.x0 = (int)std::max<uint64_t>(XTO + p * XT, XO); tile.y0 = (int)std::max<uint64_t>(YTO + q * YT, YO);
     tile.x1 = (int)std::min<uint64_t>(XTO + (p + 1) * XT, X); tile.y1 = (int)std::min<uint64_t>(YTO + (q + 1) * YT, Y);
     if (tile.x0 >= tile.x1 || tile.y0 >= tile.y1) return fail("j2k: an empty tile");
-    if (!decode_tile(f, tiles[t].P, ncomps, tile, tiles[t].data, carried, t * (size_t)f.ncomp, f.error)) return false;
+    if (!decode_tile(cd, tiles[t].P, ncomps, tile, tiles[t].data, carried, t * (size_t)f.ncomp, f.error)) return false;
     tiles[t].data = std::vector<uint8_t>();
   }
-  if (fault(f)) return fail(fault(f));
+  if (const char* why = fault_of(f.width, f.height, f.x0, f.y0, f.ncomp, f.prec, f.transform, f.mct, f.chan, f.tcs.data(), f.tcs.size(), f.steps.size(), cd.ncoeffs))
+    return fail(why);
   f.device_ok = device_fault(f.width, f.height, f.ncomp, f.tcs.data(), f.tcs.size()) == nullptr;
   return true;
+}
+
+// Tier-1 on the host: every block of `cd` into `coeffs` (cd.ncoeffs values, zeroed here).  false: the block list breaks a rule
+// (coded_fault()).
+inline bool tier1(const Coded& cd, int32_t* coeffs) {
+  if (coded_fault(cd.frame.tcs.data(), cd.frame.tcs.size(), cd.cblks.data(), cd.cblks.size(), cd.bytes.size())) return false;
+  std::fill(coeffs, coeffs + cd.ncoeffs, 0);
+  detail::T1 t1;
+  for (const CodedBlock& k : cd.cblks) {
+    const TileComp& tc = cd.frame.tcs[k.tc];
+    t1.run(cd.bytes.data() + k.byte_off, k.byte_len, k.numbps, k.passes, k.orient, k.w, k.h, coeffs + tc.coeff_off + k.at, (size_t)(tc.x1 - tc.x0));
+  }
+  return true;
+}
+
+// What parse_coded left to do, on this thread: `f` becomes cd's frame with its coefficients (cd gives its frame up).
+inline bool finish_coded(Coded& cd, Frame& f) {
+  std::vector<int32_t> coeffs(cd.ncoeffs);
+  const bool ok = tier1(cd, coeffs.data());
+  if (!ok) cd.frame.error = coded_fault(cd.frame.tcs.data(), cd.frame.tcs.size(), cd.cblks.data(), cd.cblks.size(), cd.bytes.size());
+  f = std::move(cd.frame);
+  if (ok) f.coeffs = std::move(coeffs);
+  return ok;
+}
+
+// The serial half: parse_coded, then tier-1 on this thread.
+inline bool parse(const uint8_t* d, size_t n, Frame& f) {
+  Coded cd;
+  if (!parse_coded(d, n, cd)) { f = std::move(cd.frame); return false; }
+  return finish_coded(cd, f);
 }
 
 }  // namespace j2k

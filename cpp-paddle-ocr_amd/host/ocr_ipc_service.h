@@ -279,17 +279,33 @@ inline bool decode_webp(const std::vector<uint8_t>& d, Image& im, bool device_pi
 // the decoder refuses - code-block styles, HT, POC / PPM / PPT / RGN, palettes, other colour spaces, signed or subsampled
 // components - it refuses with a reason, *why.  device_pixels / force_device as for TIFF; the switch is OCR_DEVICE_J2K, read
 // once: =1 stops after tier-1 and leaves dequantisation, the inverse wavelet and component transforms and the conversion to
-// the worker (frames in the device stage's scope, j2k::Frame::device_ok), =0 or unset finishes every file on this host thread.
+// the worker (frames in the device stage's scope, j2k::Frame::device_ok), =2 stops after tier-2 already and leaves the code
+// blocks to the worker as well (j2k::parse_coded; the same scope, other frames are finished here), =0 or unset finishes every
+// file on this host thread.
 constexpr bool J2K_DEVICE_DEFAULT = false;
-inline bool j2k_device_enabled() {
+inline int j2k_device_mode() {  // 0 host, 1 coefficients to the device, 2 coded blocks to the device
   static const char* env = getenv("OCR_DEVICE_J2K");
-  return env && env[0] ? env[0] != '0' : J2K_DEVICE_DEFAULT;
+  return env && env[0] ? (env[0] == '0' ? 0 : env[0] == '2' && !env[1] ? 2 : 1) : (J2K_DEVICE_DEFAULT ? 1 : 0);
 }
+inline bool j2k_device_enabled() { return j2k_device_mode() != 0; }
 inline bool is_j2k(const uint8_t* d, size_t n) { return j2k::is_j2k(d, n); }
 inline bool decode_j2k(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false, const char** why = nullptr) {
   if (!is_j2k(d.data(), d.size())) return false;
   auto f = std::make_shared<j2k::Frame>();
-  if (!j2k::parse(d.data(), d.size(), *f)) {
+  if (device_pixels && j2k_device_mode() == 2) {
+    auto c = std::make_shared<j2k::Coded>();
+    if (!j2k::parse_coded(d.data(), d.size(), *c)) {
+      if (why) *why = c->frame.error;
+      return false;
+    }
+    if (c->frame.device_ok) {
+      im.pixels.clear();
+      im.rows = c->frame.height; im.cols = c->frame.width;
+      im.j2k_coded = std::move(c);
+      return true;
+    }
+    if (!j2k::finish_coded(*c, *f)) return false;
+  } else if (!j2k::parse(d.data(), d.size(), *f)) {
     if (why) *why = f->error;
     return false;
   }

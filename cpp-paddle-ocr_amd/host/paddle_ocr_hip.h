@@ -74,6 +74,9 @@ struct Image {
   // a JPEG 2000 file after tier-1 (boxes, markers, packet headers, MQ decoding): the worker dequantises, undoes the wavelet and
   // component transforms and converts on the device (ocr_pipe_stage_batch)
   std::shared_ptr<j2k::Frame> j2k;
+  // a JPEG 2000 file after tier-2 only (boxes, markers, packet headers): the worker decodes the code blocks on the device as
+  // well, then goes on as for j2k (ocr_pipe_stage_batch, OCR_FRAME_J2K_CODED)
+  std::shared_ptr<j2k::Coded> j2k_coded;
   Image() = default;
   explicit Image(const ImageView& v) : rows(v.rows), cols(v.cols) {
     if (!v.empty()) {
@@ -82,10 +85,16 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8 && !j2k; }
-  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8 || j2k); }
+  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8 && !j2k && !j2k_coded; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8 || j2k || j2k_coded); }
   void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM / TIFF / WebP on the host
     if (!device_decodable()) return;
+    if (j2k_coded) {
+      j2k::Frame f;
+      if (!j2k::finish_coded(*j2k_coded, f) || !j2k::pixels(f, pixels)) throw std::runtime_error("JPEG 2000 conversion failed");
+      j2k_coded.reset();
+      return;
+    }
     if (j2k) {
       if (!j2k::pixels(*j2k, pixels)) throw std::runtime_error("JPEG 2000 conversion failed");
       j2k.reset();
@@ -160,6 +169,21 @@ struct Image {
     d.coeffs = j2k->coeffs.data(); d.coeffs_len = j2k->coeffs.size();
     return d;
   }
+  ocr_j2k_coded j2k_coded_frame() const {  // only when j2k_coded
+    static_assert(sizeof(j2k::CodedBlock) == sizeof(ocr_j2k_cblk), "j2k::CodedBlock is ocr_j2k_cblk");
+    const j2k::Frame& f = j2k_coded->frame;
+    ocr_j2k_coded d;
+    memset(&d, 0, sizeof d);
+    d.frame.width = f.width; d.frame.height = f.height; d.frame.x0 = f.x0; d.frame.y0 = f.y0;
+    d.frame.ncomp = f.ncomp; d.frame.prec = f.prec; d.frame.transform = f.transform; d.frame.mct = f.mct;
+    for (int k = 0; k < 3; ++k) d.frame.chan[k] = f.chan[k];
+    d.frame.tcs = (const ocr_j2k_tilecomp*)f.tcs.data(); d.frame.tcs_len = f.tcs.size();
+    d.frame.steps = f.steps.data(); d.frame.steps_len = f.steps.size();
+    d.frame.coeffs = nullptr; d.frame.coeffs_len = j2k_coded->ncoeffs;
+    d.cblks = (const ocr_j2k_cblk*)j2k_coded->cblks.data(); d.cblks_len = j2k_coded->cblks.size();
+    d.bytes = j2k_coded->bytes.empty() ? nullptr : j2k_coded->bytes.data(); d.bytes_len = j2k_coded->bytes.size();
+    return d;
+  }
   ocr_vp8_frame vp8_frame() const {  // only when vp8
     ocr_vp8_frame d;
     memset(&d, 0, sizeof d);
@@ -205,9 +229,11 @@ struct DeviceFrames {
   std::deque<ocr_webp_frame> wf;
   std::deque<ocr_vp8_frame> vf;
   std::deque<ocr_j2k_frame> kf;
+  std::deque<ocr_j2k_coded> kcf;
   std::vector<ocr_coded_frame> list;
   void add(const Image& im) {  // only when im.device_decodable()
-    if (im.j2k) { kf.push_back(im.j2k_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K, &kf.back()}); }
+    if (im.j2k_coded) { kcf.push_back(im.j2k_coded_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K_CODED, &kcf.back()}); }
+    else if (im.j2k) { kf.push_back(im.j2k_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K, &kf.back()}); }
     else if (im.vp8) { vf.push_back(im.vp8_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_VP8, &vf.back()}); }
     else if (im.webp) { wf.push_back(im.webp_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_WEBP, &wf.back()}); }
     else if (im.tiff) { tf.push_back(im.tiff_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF, &tf.back()}); }

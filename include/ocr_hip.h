@@ -512,13 +512,46 @@ int ocr_j2k_decode(const ocr_j2k_frame* frame, int device_id, uint8_t* bgr, size
  * kernels; ocr_j2k_time_batch: `count` frames as ONE batch (one upload, two launches per level and one to finish). */
 int ocr_j2k_time(const ocr_j2k_frame* frame, int device_id, int iters, double ms[2]);
 int ocr_j2k_time_batch(const ocr_j2k_frame* const* frames, int count, int device_id, int iters, double ms[2]);
+/* JPEG 2000 inputs with tier-1 on the device as well: the caller stops at the seam between tier-2 and tier-1
+ * (host/j2k_decode.h, j2k::parse_coded) and hands over compressed bytes, not coefficients - the frame without `coeffs`, every
+ * coded block with where its samples go, and one pool of the blocks' bytes.  A block is decoded by one wavefront, its state in
+ * LDS (csrc/kernels_j2k_t1.hip); the coefficients are those of j2k::tier1, integer for integer.  Code-block style 0 only, as
+ * j2k::parse.  Every field is checked on the host before anything is launched (j2k::coded_fault: OCR_ERR_ARG, ocr_last_error
+ * says which rule); two blocks that overlap race on values and never leave the plane. */
+typedef struct ocr_j2k_cblk {
+  uint32_t tc;        /* index into the frame's tcs */
+  uint32_t at;        /* sample offset of the block's top-left corner within its tile-component's plane (row stride x1 - x0) */
+  uint64_t byte_off;  /* into bytes */
+  uint32_t byte_len;  /* the block's chunks one after another, in layer order; bytes beyond read as ff */
+  uint16_t w, h;      /* 1 .. 1024 each, w * h <= 4096, the rectangle inside the tile-component */
+  uint8_t orient;     /* 0 LL, 1 HL, 2 LH, 3 HH */
+  uint8_t numbps;     /* magnitude bit planes, 1 .. 30 */
+  uint8_t passes;     /* coding passes, 1 .. 3 * numbps - 2 */
+  uint8_t reserved;
+  uint32_t reserved2;
+} ocr_j2k_cblk;
+typedef struct ocr_j2k_coded {
+  ocr_j2k_frame frame;        /* coeffs is NULL, coeffs_len is the size of the coefficient plane tier-1 fills */
+  const ocr_j2k_cblk* cblks;  /* host */
+  size_t cblks_len;
+  const uint8_t* bytes;       /* host */
+  size_t bytes_len;
+} ocr_j2k_coded;
+/* tier-1 alone: coeffs[0 .. frame.coeffs_len) as j2k::tier1 fills them (samples outside every block: 0); cap in values */
+int ocr_j2k_tier1(const ocr_j2k_coded* coded, int device_id, int32_t* coeffs, size_t cap);
+/* tier-1, then the launches of ocr_j2k_decode, on one stream with no host round trip in between */
+int ocr_j2k_decode_coded(const ocr_j2k_coded* coded, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time): ms[0] = the upload of blocks, bytes and descriptors from pinned memory, ms[1] = zeroing
+ * the plane and tier-1, ms[2] = the pixel stage's kernels; ocr_j2k_time_coded_batch: `count` frames as ONE batch. */
+int ocr_j2k_time_coded(const ocr_j2k_coded* coded, int device_id, int iters, double ms[3]);
+int ocr_j2k_time_coded_batch(const ocr_j2k_coded* const* coded, int count, int device_id, int iters, double ms[3]);
 /* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw, TIFF,
- * WebP, VP8 and JPEG 2000 frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
+ * WebP, VP8 and JPEG 2000 frames (coefficient form and coded form) in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
  * all five validate their own argument list and stage through the same code, with the same bytes in the slot. */
-typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5, OCR_FRAME_J2K = 6 } ocr_frame_kind;
+typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5, OCR_FRAME_J2K = 6, OCR_FRAME_J2K_CODED = 7 } ocr_frame_kind;
 typedef struct ocr_coded_frame {
   int kind;           /* ocr_frame_kind */
-  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame, ocr_vp8_frame or ocr_j2k_frame */
+  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame, ocr_vp8_frame, ocr_j2k_frame or ocr_j2k_coded */
 } ocr_coded_frame;
 int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
