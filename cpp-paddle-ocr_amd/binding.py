@@ -578,6 +578,7 @@ EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_
             "ocr_tiff_decode", "ocr_tiff_time", "ocr_tiff_time_batch", "ocr_pipe_stage_batch",
             "ocr_webp_decode", "ocr_webp_time", "ocr_webp_time_batch", "ocr_vp8_decode", "ocr_vp8_time", "ocr_vp8_time_batch", "ocr_j2k_decode", "ocr_j2k_time", "ocr_j2k_time_batch",
             "ocr_j2k_tier1", "ocr_j2k_decode_coded", "ocr_j2k_time_coded", "ocr_j2k_time_coded_batch",
+            "ocr_tiff_expand", "ocr_tiff_decode_coded", "ocr_tiff_time_coded", "ocr_tiff_time_coded_batch",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_dev_copy_time", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
@@ -705,7 +706,7 @@ class ocr_coded_frame(C.Structure):
     _fields_ = [("kind", C.c_int), ("frame", C.c_void_p)]
 
 
-FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP, FRAME_VP8, FRAME_J2K, FRAME_J2K_CODED = 0, 1, 2, 3, 4, 5, 6, 7
+FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP, FRAME_VP8, FRAME_J2K, FRAME_J2K_CODED, FRAME_TIFF_CODED = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
 
 class TiffFrame:
@@ -737,6 +738,109 @@ class TiffFrame:
             err.code = rc
             raise err
         return out
+
+
+class ocr_tiff_coded(C.Structure):
+    _fields_ = [("frame", ocr_tiff_frame), ("compression", C.c_int), ("chunks", C.c_void_p), ("chunks_len", C.c_size_t), ("bytes", C.c_void_p),
+                ("bytes_len", C.c_size_t)]
+
+
+# ocr_tiff_chunk as a numpy record (16 bytes)
+TIFF_CHUNK = np.dtype([("byte_off", "<u8"), ("byte_len", "<u4"), ("rows", "<u4")])
+
+
+def _raise_tiff(L, rc, out):
+    err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
+    err.code = rc
+    err.out = out  # the buffer as the call left it
+    raise err
+
+
+class TiffCoded:
+    """an ocr_tiff_coded over Python-owned memory: the frame before its chunks are expanded.  compression: 1, 5 or 32773;
+    chunks: the records (TIFF_CHUNK: byte_off, byte_len, rows) in the order of the expanded chunks; data: the byte pool; the
+    rest as for TiffFrame.  .chunks / .data and the fields of .c may be changed before a call (the tests' tampering)."""
+
+    def __init__(self, width, height, photometric, bits, samples, compression, chunks, data, tile=None, planar=1, predictor=1, big_endian=0, premultiply=0,
+                 palette=None):
+        self.chunks = np.array(chunks, TIFF_CHUNK).reshape(-1)
+        self.data = np.frombuffer(bytes(data), np.uint8).copy() if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8).reshape(-1).copy()
+        c = ocr_tiff_coded()
+        f = c.frame
+        f.width, f.height, f.photometric, f.bits_per_sample, f.samples_per_pixel = width, height, photometric, bits, samples
+        f.planar, f.predictor, f.big_endian, f.premultiply = planar, predictor, int(big_endian), premultiply
+        f.tile_width, f.tile_height = tile if tile else (width, height)
+        if palette is not None:
+            flat = np.ascontiguousarray(palette, np.uint8).reshape(-1)
+            C.memmove(f.palette, flat.ctypes.data, min(1024, len(flat)))
+        f.data, f.data_len = None, 0
+        c.compression = compression
+        c.chunks, c.chunks_len = self.chunks.ctypes.data if len(self.chunks) else None, len(self.chunks)
+        c.bytes, c.bytes_len = self.data.ctypes.data if len(self.data) else None, len(self.data)
+        self.c = c
+
+    def nominal(self):
+        """the bytes of the expanded chunks at their nominal size (0 where the geometry is out of range)"""
+        f = self.c.frame
+        if min(f.width, f.height, f.tile_width, f.tile_height, f.bits_per_sample, f.samples_per_pixel) <= 0:
+            return 0
+        planes = f.samples_per_pixel if f.planar == 2 else 1
+        row = (f.tile_width * (1 if f.planar == 2 else f.samples_per_pixel) * f.bits_per_sample + 7) // 8
+        return row * f.tile_height * (-(-f.width // f.tile_width)) * (-(-f.height // f.tile_height)) * planes
+
+    def expand(self, device_id=0, fill=0):
+        """ocr_tiff_expand: the chunks as tiff::parse fills Frame::data (uint8 array); OcrError where the call refuses"""
+        L = lib()
+        L.ocr_tiff_expand.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_void_p, C.c_size_t]
+        n = self.nominal()
+        out = np.full(n if 0 < n <= 1 << 30 else 1, fill, np.uint8)
+        rc = L.ocr_tiff_expand(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            _raise_tiff(L, rc, out)
+        return out
+
+    def decode(self, device_id=0, fill=0):
+        """ocr_tiff_decode_coded: the (height, width, 3) BGR image; OcrError where the call refuses (err.out: the buffer as the
+        call left it, pre-filled with `fill`)"""
+        L = lib()
+        L.ocr_tiff_decode_coded.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_void_p, C.c_size_t]
+        h, w = self.c.frame.height, self.c.frame.width
+        out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), fill, np.uint8)
+        rc = L.ocr_tiff_decode_coded(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            _raise_tiff(L, rc, out)
+        return out
+
+    def time(self, iters=3, device_id=0):
+        """ocr_tiff_time_coded: [upload, expansion, pixel stage] in ms"""
+        return time_tiff_coded([self], iters, device_id, single=True)
+
+
+def tiff_expand(coded, device_id=0):
+    """ocr_tiff_expand of a TiffCoded"""
+    return coded.expand(device_id)
+
+
+def tiff_decode_coded(coded, device_id=0):
+    """ocr_tiff_decode_coded of a TiffCoded"""
+    return coded.decode(device_id)
+
+
+def time_tiff_coded(coded, iters=3, device_id=0, single=False):
+    """ocr_tiff_time_coded_batch over TiffCoded objects as one batch (single: ocr_tiff_time_coded of the first):
+    [upload, expansion, pixel stage] in ms"""
+    L = lib()
+    ms = (C.c_double * 3)()
+    if single:
+        L.ocr_tiff_time_coded.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_int, C.POINTER(C.c_double)]
+        rc = L.ocr_tiff_time_coded(C.byref(coded[0].c), device_id, iters, ms)
+    else:
+        L.ocr_tiff_time_coded_batch.argtypes = [C.POINTER(C.POINTER(ocr_tiff_coded)), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        ptrs = (C.POINTER(ocr_tiff_coded) * len(coded))(*[C.pointer(k.c) for k in coded])
+        rc = L.ocr_tiff_time_coded_batch(ptrs, len(coded), device_id, iters, ms)
+    if rc != 0:
+        _raise_tiff(L, rc, None)
+    return list(ms)
 
 
 class ocr_webp_transform(C.Structure):

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../host/tiff_decode.h"  // coded_fault_of and the extent scans: the rules of a coded frame, stated once
 #include "capi_common.h"
 #include "tiff_stage.h"
 
@@ -9,14 +10,22 @@ namespace ocr {
 
 namespace {
 
+namespace tiff = PaddleOCR::tiff;
+
+static_assert(sizeof(ocr_tiff_chunk) == sizeof(tiff::Chunk) && offsetof(ocr_tiff_chunk, byte_off) == offsetof(tiff::Chunk, byte_off) &&
+                  offsetof(ocr_tiff_chunk, byte_len) == offsetof(tiff::Chunk, byte_len) && offsetof(ocr_tiff_chunk, rows) == offsetof(tiff::Chunk, rows),
+              "ocr_tiff_chunk is tiff::Chunk");
+
+size_t pad256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
 // host/tiff_decode.h Geometry: what follows from a (sound) descriptor
 struct TiffGeometry {
   int across = 0, down = 0, planes = 1, colour = 1, used = 1;
   size_t row_bytes = 0, chunk_bytes = 0, total = 0;
 };
 
-// host/tiff_decode.h fault(), rule for rule
-const char* tiff_fault(const ocr_tiff_frame& f, TiffGeometry& g) {
+// host/tiff_decode.h fault(), rule for rule; with_data: the frame carries its expanded chunks (a coded frame does not)
+const char* tiff_fault(const ocr_tiff_frame& f, TiffGeometry& g, bool with_data = true) {
   if (f.width <= 0 || f.height <= 0 || (long)f.width * f.height > (64L << 20)) return "tiff frame: width and height must be positive and at most 64 Mpixel together";
   if (f.bits_per_sample != 1 && f.bits_per_sample != 2 && f.bits_per_sample != 4 && f.bits_per_sample != 8 && f.bits_per_sample != 16)
     return "tiff frame: bits per sample must be 1, 2, 4, 8 or 16";
@@ -43,8 +52,59 @@ const char* tiff_fault(const ocr_tiff_frame& f, TiffGeometry& g) {
   g.chunk_bytes = g.row_bytes * (size_t)f.tile_height;                              // <= 2^26 * 32 + 2^26
   g.total = g.chunk_bytes * (size_t)g.across * g.down * g.planes;                   // < 2^32 * 2^26 * 2^4
   if (g.total > ((size_t)1 << 30)) return "tiff frame: the chunks at their nominal size exceed 1 GiB";
-  if (!f.data || f.data_len < g.total) return "tiff frame: data_len is less than the chunks at their nominal size";
+  if (with_data && (!f.data || f.data_len < g.total)) return "tiff frame: data_len is less than the chunks at their nominal size";
   return nullptr;
+}
+
+// host/tiff_decode.h coded_fault(): fault(), the records and the extent scan of every chunk, and the device bounds
+const char* tiff_coded_fault_of(const ocr_tiff_coded& c, TiffGeometry& g) {
+  const ocr_tiff_frame& f = c.frame;
+  if (f.data) return "tiff coded: a coded frame carries no expanded chunks";
+  if (const char* why = tiff_fault(f, g, false)) return why;
+  tiff::Frame h;
+  h.width = f.width; h.height = f.height; h.photometric = f.photometric; h.bits = f.bits_per_sample; h.samples = f.samples_per_pixel;
+  h.planar = f.planar; h.predictor = f.predictor; h.big_endian = f.big_endian; h.premultiply = f.premultiply;
+  h.tile_width = f.tile_width; h.tile_height = f.tile_height;
+  tiff::Geometry hg;
+  if (const char* why = tiff::coded_fault_of(h, c.compression, (const tiff::Chunk*)c.chunks, c.chunks_len, c.bytes, c.bytes_len, hg)) return why;
+  if (c.chunks_len > tiff::kMaxDeviceChunks || g.total > tiff::kMaxDeviceBytes) return "tiff coded: beyond the device bounds (2^20 chunks, 512 MiB at their nominal size)";
+  return nullptr;
+}
+
+int kind_of(const ocr_tiff_frame& f) { return f.bits_per_sample < 8 ? 0 : f.bits_per_sample == 8 ? 1 : 2; }
+
+// The descriptors of validated frames ordered by the kernel that takes them, the units of a kind numbered through its
+// frames; frame i's chunks lie at data + off[i].  Fills L's counts and units.
+std::vector<TiffImageDesc> describe(const ocr_tiff_frame* const* imgs, int count, const std::vector<TiffGeometry>& geo, const std::vector<size_t>& off,
+                                    uint8_t* const* dst, const uint8_t* data, TiffLaunch& L) {
+  for (int i = 0; i < count; ++i) L.count[kind_of(*imgs[i])]++;
+  for (int k = 1; k < kTiffKinds; ++k) L.first[k] = L.first[k - 1] + L.count[k - 1];
+  int next[kTiffKinds];
+  std::copy(L.first, L.first + kTiffKinds, next);
+  std::vector<TiffImageDesc> id((size_t)count);
+  for (int i = 0; i < count; ++i) {
+    const ocr_tiff_frame& f = *imgs[i];
+    const TiffGeometry& g = geo[i];
+    const int kind = kind_of(f);
+    TiffImageDesc& d = id[next[kind]++];
+    memset(&d, 0, sizeof d);
+    d.data = data + off[i];
+    d.bgr = dst ? dst[i] : nullptr;
+    d.first_unit = L.units[kind];
+    d.chunk_bytes = g.chunk_bytes;
+    d.plane_bytes = f.planar == 2 ? g.chunk_bytes * (size_t)g.across * g.down : 0;
+    d.row_bytes = g.row_bytes;
+    d.width = f.width; d.height = f.height; d.tile_width = f.tile_width; d.tile_height = f.tile_height; d.across = g.across; d.down = g.down;
+    d.bits = f.bits_per_sample; d.samples = f.samples_per_pixel; d.used = g.used;
+    d.mode = f.photometric == 3 ? TIFF_PALETTE : f.photometric == 5 ? TIFF_CMYK : f.photometric == 2 ? TIFF_RGB : f.planar == 2 ? TIFF_GREY_PLANES : TIFF_GREY;
+    d.predictor = f.predictor; d.big_endian = f.big_endian; d.invert = f.photometric == 0; d.premultiply = f.premultiply;
+    d.lanes_per_row = tiff_lanes_per_row(std::min(f.tile_width, f.width));
+    d.rows_per_unit = 64 / d.lanes_per_row;
+    d.units_per_chunk = (unsigned)((std::min(f.tile_height, f.height) + d.rows_per_unit - 1) / d.rows_per_unit);
+    L.units[kind] += (unsigned long long)g.across * g.down * d.units_per_chunk;  // <= chunks * rows of a chunk: < 2^27
+    for (int k = 0; k < 256; ++k) d.palette[k] = (uint32_t)f.palette[4 * k] | ((uint32_t)f.palette[4 * k + 1] << 8) | ((uint32_t)f.palette[4 * k + 2] << 16);
+  }
+  return id;
 }
 
 }  // namespace
@@ -65,45 +125,17 @@ int tiff_decode_async(const ocr_tiff_frame* const* imgs, int count, uint8_t* con
   std::vector<TiffGeometry> geo((size_t)count);
   size_t bytes = 0;
   TiffLaunch L;
-  auto kind_of = [](const ocr_tiff_frame& f) { return f.bits_per_sample < 8 ? 0 : f.bits_per_sample == 8 ? 1 : 2; };
   for (int i = 0; i < count; ++i) {
     if (!imgs[i]) { err = "null tiff frame"; return OCR_ERR_ARG; }
     if (const char* fault = tiff_fault(*imgs[i], geo[i])) { err = fault; return OCR_ERR_ARG; }
     off[i] = bytes;
-    bytes += (geo[i].total + 255) & ~(size_t)255;
-    L.count[kind_of(*imgs[i])]++;
+    bytes += pad256(geo[i].total);
   }
   L.bytes = bytes;
   if (!sc.data.ensure(bytes + 256, err) || !sc.id.ensure((size_t)count, err)) return OCR_ERR_DEVICE;
   if (!sc.stage.reserve(bytes, err)) return OCR_ERR_DEVICE;
   parallel_copy((size_t)count, bytes, [&](size_t i) { memcpy(sc.stage.p + off[i], imgs[i]->data, geo[i].total); });  // chunks -> pinned memory
-  // the descriptors ordered by the kernel that takes them, the units of a kind numbered through its frames
-  for (int k = 1; k < kTiffKinds; ++k) L.first[k] = L.first[k - 1] + L.count[k - 1];
-  int next[kTiffKinds];
-  std::copy(L.first, L.first + kTiffKinds, next);
-  std::vector<TiffImageDesc> id((size_t)count);
-  for (int i = 0; i < count; ++i) {
-    const ocr_tiff_frame& f = *imgs[i];
-    const TiffGeometry& g = geo[i];
-    const int kind = kind_of(f);
-    TiffImageDesc& d = id[next[kind]++];
-    memset(&d, 0, sizeof d);
-    d.data = sc.data.p + off[i];
-    d.bgr = dst[i];
-    d.first_unit = L.units[kind];
-    d.chunk_bytes = g.chunk_bytes;
-    d.plane_bytes = f.planar == 2 ? g.chunk_bytes * (size_t)g.across * g.down : 0;
-    d.row_bytes = g.row_bytes;
-    d.width = f.width; d.height = f.height; d.tile_width = f.tile_width; d.tile_height = f.tile_height; d.across = g.across; d.down = g.down;
-    d.bits = f.bits_per_sample; d.samples = f.samples_per_pixel; d.used = g.used;
-    d.mode = f.photometric == 3 ? TIFF_PALETTE : f.photometric == 5 ? TIFF_CMYK : f.photometric == 2 ? TIFF_RGB : f.planar == 2 ? TIFF_GREY_PLANES : TIFF_GREY;
-    d.predictor = f.predictor; d.big_endian = f.big_endian; d.invert = f.photometric == 0; d.premultiply = f.premultiply;
-    d.lanes_per_row = tiff_lanes_per_row(std::min(f.tile_width, f.width));
-    d.rows_per_unit = 64 / d.lanes_per_row;
-    d.units_per_chunk = (unsigned)((std::min(f.tile_height, f.height) + d.rows_per_unit - 1) / d.rows_per_unit);
-    L.units[kind] += (unsigned long long)g.across * g.down * d.units_per_chunk;  // <= chunks * rows of a chunk: < 2^27
-    for (int k = 0; k < 256; ++k) d.palette[k] = (uint32_t)f.palette[4 * k] | ((uint32_t)f.palette[4 * k + 1] << 8) | ((uint32_t)f.palette[4 * k + 2] << 16);
-  }
+  const std::vector<TiffImageDesc> id = describe(imgs, count, geo, off, dst, sc.data.p, L);
   if (!sc.stage.upload(sc.data.p, bytes, s, err) ||
       hipMemcpyAsync(sc.id.p, id.data(), id.size() * sizeof(TiffImageDesc), hipMemcpyHostToDevice, s) != hipSuccess) {
     err = "tiff chunks upload failed";
@@ -112,6 +144,72 @@ int tiff_decode_async(const ocr_tiff_frame* const* imgs, int count, uint8_t* con
   tiff_relaunch(sc, L, s);
   if (launched) *launched = L;
   if (hipGetLastError() != hipSuccess) { err = "tiff pixel kernels failed to launch"; return OCR_ERR_DEVICE; }
+  return OCR_OK;
+}
+
+const char* tiff_coded_fault(const ocr_tiff_coded& c) {
+  TiffGeometry g;
+  return tiff_coded_fault_of(c, g);
+}
+
+void tiff_expand_relaunch(const TiffScratch& sc, const TiffLaunch& L, hipStream_t s) { launch_tiff_expand(L.chunks, L.lzw, L.runs, L.pool, sc.data.p, s); }
+
+int tiff_coded_decode_async(const ocr_tiff_coded* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
+                            TiffLaunch* launched, bool pixels) {
+  std::vector<size_t> off((size_t)count), pool_at((size_t)count);
+  std::vector<TiffGeometry> geo((size_t)count);
+  std::vector<const ocr_tiff_frame*> frames((size_t)count);
+  size_t bytes = 0, nchunks = 0, pool = 0;
+  TiffLaunch L;
+  for (int i = 0; i < count; ++i) {
+    if (!imgs[i]) { err = "null tiff frame"; return OCR_ERR_ARG; }
+    if (const char* fault = tiff_coded_fault_of(*imgs[i], geo[i])) { err = fault; return OCR_ERR_ARG; }
+    frames[i] = &imgs[i]->frame;
+    off[i] = bytes;
+    pool_at[i] = pool;
+    bytes += pad256(geo[i].total);
+    nchunks += imgs[i]->chunks_len;
+    pool += imgs[i]->bytes_len;
+  }
+  if (nchunks > 0x7fffffffu) { err = "tiff batch: more chunks than a launch has workgroups"; return OCR_ERR_ARG; }
+  // the batch's chunks: the LZW ones, then the others; within each the long streams first, so that they do not form the tail
+  std::vector<TiffChunkDesc> cd;
+  cd.reserve(nchunks);
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int i = 0; i < count; ++i) {
+      const ocr_tiff_coded& c = *imgs[i];
+      if ((c.compression == 5) != (pass == 0)) continue;
+      for (size_t k = 0; k < c.chunks_len; ++k)
+        cd.push_back(TiffChunkDesc{pool_at[i] + c.chunks[k].byte_off, off[i] + k * geo[i].chunk_bytes, c.chunks[k].byte_len,
+                                   (uint32_t)(c.chunks[k].rows * geo[i].row_bytes), (uint32_t)geo[i].chunk_bytes, (uint32_t)c.compression});
+    }
+    if (pass == 0) L.lzw = (uint32_t)cd.size();
+  }
+  L.runs = (uint32_t)cd.size() - L.lzw;
+  auto longer = [](const TiffChunkDesc& a, const TiffChunkDesc& b) { return a.byte_len > b.byte_len; };
+  std::stable_sort(cd.begin(), cd.begin() + L.lzw, longer);
+  std::stable_sort(cd.begin() + L.lzw, cd.end(), longer);
+  const size_t at_pool = pad256(cd.size() * sizeof(TiffChunkDesc)), coded_bytes = at_pool + pad256(pool);
+  L.bytes = coded_bytes;
+  if (!sc.data.ensure(bytes + 256, err) || !sc.coded.ensure(coded_bytes + 256, err) || !sc.id.ensure((size_t)count, err)) return OCR_ERR_DEVICE;
+  if (!sc.stage.reserve(coded_bytes, err)) return OCR_ERR_DEVICE;
+  if (!cd.empty()) memcpy(sc.stage.p, cd.data(), cd.size() * sizeof(TiffChunkDesc));
+  parallel_copy((size_t)count, pool, [&](size_t i) { if (imgs[i]->bytes_len) memcpy(sc.stage.p + at_pool + pool_at[i], imgs[i]->bytes, imgs[i]->bytes_len); });
+  L.chunks = (const TiffChunkDesc*)sc.coded.p;
+  L.pool = sc.coded.p + at_pool;
+  const std::vector<TiffImageDesc> id = describe(frames.data(), count, geo, off, dst, sc.data.p, L);
+  if (!sc.stage.upload(sc.coded.p, coded_bytes, s, err) ||
+      hipMemcpyAsync(sc.id.p, id.data(), id.size() * sizeof(TiffImageDesc), hipMemcpyHostToDevice, s) != hipSuccess) {
+    err = "tiff coded chunks upload failed";
+    return OCR_ERR_DEVICE;
+  }
+  tiff_expand_relaunch(sc, L, s);
+  if (hipGetLastError() != hipSuccess) { err = "tiff expansion kernels failed to launch"; return OCR_ERR_DEVICE; }
+  if (pixels) {
+    tiff_relaunch(sc, L, s);
+    if (hipGetLastError() != hipSuccess) { err = "tiff pixel kernels failed to launch"; return OCR_ERR_DEVICE; }
+  }
+  if (launched) *launched = L;
   return OCR_OK;
 }
 
@@ -143,7 +241,73 @@ int time_batch(const ocr_tiff_frame* const* frames, int count, int device_id, in
                      [&] { tiff_relaunch(sc, L, nullptr); return hipSuccess; });
 }
 
+// the coded route: upload, expansion, pixel stage
+int time_coded_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
+  for (int i = 0; i < count; ++i) {
+    if (!coded[i]) return fail(OCR_ERR_ARG, "null argument");
+    if (const char* fault = tiff_coded_fault(*coded[i])) return fail(OCR_ERR_ARG, fault);
+  }
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  std::vector<DevBuf<uint8_t>> out((size_t)count);
+  std::vector<uint8_t*> dst((size_t)count);
+  std::string err;
+  for (int i = 0; i < count; ++i) {
+    if (!out[i].ensure((size_t)coded[i]->frame.width * coded[i]->frame.height * 3, err)) return fail(OCR_ERR_DEVICE, err);
+    dst[i] = out[i].p;
+  }
+  TiffScratch sc;
+  TiffLaunch L;
+  rc = tiff_coded_decode_async(coded, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
+  if (rc) return fail(rc, err);
+  double t[2];
+  rc = time_phases(iters, t, [&] { return hipMemcpyAsync(sc.coded.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
+                   [&] { tiff_expand_relaunch(sc, L, nullptr); return hipGetLastError(); });
+  if (rc) return rc;
+  ms[0] = t[0]; ms[1] = t[1];
+  rc = time_phases(iters, t, [&] { tiff_relaunch(sc, L, nullptr); return hipGetLastError(); }, [] { return hipSuccess; });
+  ms[2] = t[0];
+  return rc;
+}
+
 }  // namespace
+
+extern "C" int ocr_tiff_expand(const ocr_tiff_coded* coded, int device_id, uint8_t* out, size_t cap) {
+  if (!coded || !out) return fail(OCR_ERR_ARG, "null argument");
+  TiffGeometry g;
+  if (const char* fault = tiff_coded_fault_of(*coded, g)) return fail(OCR_ERR_ARG, fault);
+  if (g.total > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  TiffScratch sc;
+  std::string err;
+  rc = tiff_coded_decode_async(&coded, 1, nullptr, sc, nullptr, err, nullptr, false);
+  if (rc) return fail(rc, err);
+  CAPI_HIP(hipStreamSynchronize(nullptr));
+  CAPI_HIP(g_memcpy(out, sc.data.p, g.total, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
+extern "C" int ocr_tiff_decode_coded(const ocr_tiff_coded* coded, int device_id, uint8_t* bgr, size_t cap) {
+  if (!coded || !bgr) return fail(OCR_ERR_ARG, "null argument");
+  if (const char* fault = tiff_coded_fault(*coded)) return fail(OCR_ERR_ARG, fault);
+  const size_t bytes = (size_t)coded->frame.width * coded->frame.height * 3;
+  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  TiffScratch sc;
+  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return tiff_coded_decode_async(&coded, 1, dst, sc, nullptr, err); });
+}
+
+extern "C" int ocr_tiff_time_coded(const ocr_tiff_coded* coded, int device_id, int iters, double ms[3]) {
+  if (!coded || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
+  return time_coded_batch(&coded, 1, device_id, iters, ms);
+}
+
+extern "C" int ocr_tiff_time_coded_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
+  if (!coded || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
+  return time_coded_batch(coded, count, device_id, iters, ms);
+}
 
 extern "C" int ocr_tiff_decode(const ocr_tiff_frame* frame, int device_id, uint8_t* bgr, size_t cap) {
   if (!frame || !bgr) return fail(OCR_ERR_ARG, "null argument");

@@ -433,7 +433,7 @@ struct ocr_pipe {
   JpegScratch jpeg;
   PngScratch png;
   RawScratch raw;
-  TiffScratch tiff;
+  TiffScratch tiff, tiff_coded;  // expanded frames and coded ones are two batches: their uploads differ
   WebpScratch webp;
   Vp8Scratch vp8;
   J2kScratch j2k, j2k_coded;  // coefficient-form frames and coded ones are two batches: their uploads differ
@@ -508,7 +508,7 @@ struct ocr_pipe {
   }
 
   // ---- stage a batch of JPEG coefficients, inflated PNG streams, stored BMP / PNM rows, expanded TIFF chunks and entropy-decoded
-  // WebP images, VP8 and JPEG 2000 frame descriptors (coefficients or coded blocks), in any mix: the seven pixel stages run on the copy stream, into the slot.  Image i is frames[i], a tagged descriptor (validated by the caller
+  // WebP images, VP8 and JPEG 2000 frame descriptors (coefficients or coded blocks) and coded TIFF chunks, in any mix: the seven pixel stages run on the copy stream, into the slot.  Image i is frames[i], a tagged descriptor (validated by the caller
   // before the sizes are used - a refused batch leaves the slot as it was: a known kind, and a sound descriptor)
   int stage_coded(int si, const ocr_coded_frame* frames, int count, std::string& err) {
     StageSlot& S = slots[si];
@@ -525,7 +525,7 @@ struct ocr_pipe {
         case OCR_FRAME_JPEG: r = jpeg_out_rows(*jp(i)); c = jpeg_out_cols(*jp(i)); break;
         case OCR_FRAME_PNG: r = pn(i)->height; c = pn(i)->width; break;
         case OCR_FRAME_RAW: r = rw(i)->height; c = rw(i)->width; break;
-        case OCR_FRAME_TIFF: r = tf(i)->height; c = tf(i)->width; break;
+        case OCR_FRAME_TIFF: case OCR_FRAME_TIFF_CODED: r = tf(i)->height; c = tf(i)->width; break;  // (an ocr_tiff_coded starts with its ocr_tiff_frame)
         case OCR_FRAME_WEBP: r = wf(i)->height; c = wf(i)->width; break;
         case OCR_FRAME_VP8: r = vf(i)->height; c = vf(i)->width; break;
         default: r = kf(i)->height; c = kf(i)->width; break;  // (an ocr_j2k_coded starts with its ocr_j2k_frame)
@@ -540,7 +540,8 @@ struct ocr_pipe {
     std::vector<const ocr_vp8_frame*> vff;
     std::vector<const ocr_j2k_frame*> kff;
     std::vector<const ocr_j2k_coded*> kcf;
-    std::vector<uint8_t*> jdst, pdst, rdst, tdst, wdst, vdst, kdst, kcdst;
+    std::vector<const ocr_tiff_coded*> tcf;
+    std::vector<uint8_t*> jdst, pdst, rdst, tdst, wdst, vdst, kdst, kcdst, tcdst;
     for (int k = 0; k < count; ++k) {
       const int i = S.imgs[k].orig;
       uint8_t* d = S.dev.p + S.imgs[k].off;
@@ -552,6 +553,7 @@ struct ocr_pipe {
         case OCR_FRAME_WEBP: wff.push_back(wf(i)); wdst.push_back(d); break;
         case OCR_FRAME_VP8: vff.push_back(vf(i)); vdst.push_back(d); break;
         case OCR_FRAME_J2K_CODED: kcf.push_back((const ocr_j2k_coded*)frames[i].frame); kcdst.push_back(d); break;
+        case OCR_FRAME_TIFF_CODED: tcf.push_back((const ocr_tiff_coded*)frames[i].frame); tcdst.push_back(d); break;
         default: kff.push_back(kf(i)); kdst.push_back(d); break;
       }
     }
@@ -563,6 +565,7 @@ struct ocr_pipe {
     if (!rc && !vff.empty()) rc = vp8_decode_async(vff.data(), (int)vff.size(), vdst.data(), vp8, copy_stream, err);
     if (!rc && !kff.empty()) rc = j2k_decode_async(kff.data(), (int)kff.size(), kdst.data(), j2k, copy_stream, err);
     if (!rc && !kcf.empty()) rc = j2k_coded_decode_async(kcf.data(), (int)kcf.size(), kcdst.data(), j2k_coded, copy_stream, err);
+    if (!rc && !tcf.empty()) rc = tiff_coded_decode_async(tcf.data(), (int)tcf.size(), tcdst.data(), tiff_coded, copy_stream, err);
     if (rc) return rc;
     if (hipEventRecord(S.ready, copy_stream) != hipSuccess) { err = "hipEventRecord failed"; return OCR_ERR_DEVICE; }
     S.staged = true;
@@ -909,6 +912,7 @@ int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, i
       case OCR_FRAME_VP8: fault = vp8_frame_fault(*(const ocr_vp8_frame*)f); break;
       case OCR_FRAME_J2K: fault = j2k_frame_fault(*(const ocr_j2k_frame*)f); break;
       case OCR_FRAME_J2K_CODED: fault = j2k_coded_fault(*(const ocr_j2k_coded*)f); break;
+      case OCR_FRAME_TIFF_CODED: fault = tiff_coded_fault(*(const ocr_tiff_coded*)f); break;
       default: fault = "frame kind is not an ocr_frame_kind"; break;
     }
     if (fault) return fail(OCR_ERR_ARG, fault);

@@ -24,7 +24,12 @@
 // the device stage would replace.
 // A TIFF's pixel half (predictor, tile placement, planar to chunky, bit expansion, palette, 16 -> 8 bits, CMYK, alpha) runs on
 // the GPU with --device / --frame too, through ocr_tiff_decode (whatever OCR_DEVICE_TIFF says); --stage takes TIFFs in the mix
-// (ocr_pipe_stage_batch); --time <iters> <tiff file> [<batch>]: ocr_tiff_time / ocr_tiff_time_batch (upload of the expanded
+// (ocr_pipe_stage_batch).  The coded route - the chunks' LZW / PackBits expansion on the device too, ocr_tiff_decode_coded - is
+// taken by --device / --frame / --stage when OCR_DEVICE_TIFF=2, and by --stage for an input written "coded:<file>" whatever
+// the switch says; --time measures both routes in one run: "coded_upload_ms", "expand_stage_ms", "coded_pixel_stage_ms"
+// (ocr_tiff_time_coded / _batch), "coded_bytes", "host_scan_ms_per_image" (tiff::coded_fault: the extent scans, which both
+// routes pay) and "host_expand_ms_per_image" (tiff::expand on one host thread, which the coded route saves).
+// --time <iters> <tiff file> [<batch>]: ocr_tiff_time / ocr_tiff_time_batch (upload of the expanded
 // chunks, pixel stage), "host_pixels_ms" (tiff::pixels on one host thread), "bytes_in" / "bytes_out" (what the kernel reads and
 // writes) and "copy_ms": a plain copy kernel that reads and writes as many bytes in all (ocr_dev_copy_time), timed in the same run.
 // decode_tool --stage-frames <model dir> ...: as --stage, through ocr_pipe_stage_frames (the three-array entry point: no TIFFs).
@@ -184,9 +189,34 @@ static int time_device(int iters, const char* in, int batch) {
     if (a) ocr_dev_free(a);
     if (b) ocr_dev_free(b);
     printf("{\"size\": [%d, %d], \"photometric\": %d, \"bits\": %d, \"samples\": %d, \"planar\": %d, \"predictor\": %d, \"tile\": [%d, %d], \"batch\": %d, \"iters\": %d, "
-           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"bytes_in\": %zu, \"bytes_out\": %zu, \"copy_ms\": %.5f}\n",
+           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"bytes_in\": %zu, \"bytes_out\": %zu, \"copy_ms\": %.5f",
            d.height, d.width, d.photometric, d.bits_per_sample, d.samples_per_pixel, d.planar, d.predictor, d.tile_width, d.tile_height, (int)all.size(), iters,
            ms[0], ms[1], host_ms, in, out, copy_ms);
+    // the coded route (Compression 1, LZW, PackBits): upload of the coded chunks, expansion and pixel stage on the device, and
+    // what the host pays either way, per image on one thread: the extent scan (both routes) and tiff::expand (the =1 route)
+    auto c = std::make_shared<PaddleOCR::tiff::Coded>();
+    if (PaddleOCR::tiff::parse_coded(bytes.data(), bytes.size(), *c) == PaddleOCR::tiff::kCoded && c->frame.device_ok) {
+      im.tiff_coded = c;
+      const ocr_tiff_coded cd = im.tiff_coded_frame();
+      std::vector<const ocr_tiff_coded*> call(all.size(), &cd);
+      double cms[3];
+      if ((batch > 1 ? ocr_tiff_time_coded_batch(call.data(), (int)call.size(), 0, iters, cms) : ocr_tiff_time_coded(&cd, 0, iters, cms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+      PaddleOCR::tiff::Geometry g;
+      const int reps = iters < 3 ? 3 : iters;
+      auto t1 = std::chrono::steady_clock::now();
+      bool sound = true;
+      for (int i = 0; i < reps; ++i) sound = sound && !PaddleOCR::tiff::coded_fault(*c, g);
+      const double scan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() / reps;
+      PaddleOCR::tiff::Frame ef;
+      t1 = std::chrono::steady_clock::now();
+      for (int i = 0; i < reps; ++i) sound = sound && PaddleOCR::tiff::expand(*c, ef);
+      const double expand_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() / reps;
+      if (!sound) { fprintf(stderr, "host expansion failed\n"); return 1; }
+      printf(", \"compression\": %d, \"chunks\": %zu, \"coded_bytes\": %zu, \"coded_upload_ms\": %.5f, \"expand_stage_ms\": %.5f, \"coded_pixel_stage_ms\": %.5f, "
+             "\"host_scan_ms_per_image\": %.5f, \"host_expand_ms_per_image\": %.5f",
+             c->compression, c->chunks.size(), c->bytes.size(), cms[0], cms[1], cms[2], scan_ms, expand_ms);
+    }
+    printf("}\n");
     return 0;
   }
   if (bytes.size() > 2 && ((bytes[0] == 'B' && bytes[1] == 'M') || (bytes[0] == 'P' && bytes[1] >= '1' && bytes[1] <= '6'))) {
@@ -294,7 +324,18 @@ static int stage_batches(const std::string& model_dir, int nargs, char** args, b
     b.ims.resize(b.in.size());
     for (size_t i = 0; i < b.in.size(); ++i) {
       std::vector<uint8_t> bytes;
-      if (!b.in[i].compare(0, 6, "coded:")) {  // a JPEG 2000 file in the coded form, whatever OCR_DEVICE_J2K says
+      if (!b.in[i].compare(0, 6, "coded:")) {  // a JPEG 2000 or TIFF file in the coded form, whatever OCR_DEVICE_J2K / OCR_DEVICE_TIFF say
+        if (PaddleOCR::ipc::read_file(b.in[i].substr(6), bytes) && PaddleOCR::ipc::is_tiff(bytes.data(), bytes.size())) {
+          auto t = std::make_shared<PaddleOCR::tiff::Coded>();
+          if (PaddleOCR::tiff::parse_coded(bytes.data(), bytes.size(), *t) != PaddleOCR::tiff::kCoded || !t->frame.device_ok) {
+            fprintf(stderr, "decode failed: %s\n", b.in[i].c_str());
+            return 1;
+          }
+          b.ims[i].rows = t->frame.height; b.ims[i].cols = t->frame.width;
+          b.ims[i].tiff_coded = t;
+          b.frames.add(b.ims[i]);
+          continue;
+        }
         auto c = std::make_shared<PaddleOCR::j2k::Coded>();
         if (!PaddleOCR::ipc::read_file(b.in[i].substr(6), bytes) || !PaddleOCR::j2k::parse_coded(bytes.data(), bytes.size(), *c) || !c->frame.device_ok) {
           fprintf(stderr, "decode failed: %s\n", b.in[i].c_str());
@@ -343,6 +384,11 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
+  if (im.device_decodable() && im.tiff_coded) {
+    const ocr_tiff_coded d = im.tiff_coded_frame();
+    im.pixels.resize((size_t)d.frame.height * d.frame.width * 3);
+    if (ocr_tiff_decode_coded(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+  } else
   if (im.device_decodable() && im.j2k_coded) {
     const ocr_j2k_coded d = im.j2k_coded_frame();
     im.pixels.resize((size_t)d.frame.height * d.frame.width * 3);

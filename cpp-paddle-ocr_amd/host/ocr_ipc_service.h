@@ -219,19 +219,38 @@ inline bool decode_bmp(const std::vector<uint8_t>& d, Image& im, bool device_pix
 // TIFF as cv::imdecode(IMREAD_COLOR) returns it (tiff_decode.h: classic TIFF, strips and tiles, uncompressed / PackBits / LZW /
 // Deflate, the sample forms libtiff's RGBA interface reads).  device_pixels / force_device as for BMP and PNM; the switch is
 // OCR_DEVICE_TIFF, read once: =1 stops after the chunks are expanded and leaves predictor, conversion and placement to the
-// worker (frames within the device stage's bounds, tiff::Frame::device_ok), =0 or unset finishes every file on this host thread.
+// worker (frames within the device stage's bounds, tiff::Frame::device_ok), =2 stops before the expansion already and leaves
+// the chunks' LZW / PackBits streams to the worker as well (tiff::parse_coded, which still scans every stream; Deflate files and
+// frames beyond the bounds go the =1 route), =0 or unset finishes every file on this host thread.
 constexpr bool TIFF_DEVICE_DEFAULT = false;
-inline bool tiff_device_enabled() {
+inline int tiff_device_mode() {  // 0 host, 1 expanded chunks to the device, 2 coded chunks to the device
   static const char* env = getenv("OCR_DEVICE_TIFF");
-  return env && env[0] ? env[0] != '0' : TIFF_DEVICE_DEFAULT;
+  return env && env[0] ? (env[0] == '0' ? 0 : env[0] == '2' && !env[1] ? 2 : 1) : (TIFF_DEVICE_DEFAULT ? 1 : 0);
 }
+inline bool tiff_device_enabled() { return tiff_device_mode() != 0; }
 inline bool is_tiff(const uint8_t* d, size_t n) {
   return n >= 4 && ((d[0] == 'I' && d[1] == 'I' && d[2] == 42 && d[3] == 0) || (d[0] == 'M' && d[1] == 'M' && d[2] == 0 && d[3] == 42));
 }
 inline bool decode_tiff(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false) {
   if (!is_tiff(d.data(), d.size())) return false;
   auto f = std::make_shared<tiff::Frame>();
-  if (!tiff::parse(d.data(), d.size(), *f)) return false;
+  bool parsed = false;
+  if (device_pixels && tiff_device_mode() == 2) {
+    auto c = std::make_shared<tiff::Coded>();
+    const tiff::Route route = tiff::parse_coded(d.data(), d.size(), *c);
+    if (route == tiff::kRefused) return false;
+    if (route == tiff::kCoded) {
+      if (c->frame.device_ok) {
+        im.pixels.clear();
+        im.rows = c->frame.height; im.cols = c->frame.width;
+        im.tiff_coded = std::move(c);
+        return true;
+      }
+      if (!tiff::expand(*c, *f)) return false;
+      parsed = true;
+    }
+  }
+  if (!parsed && !tiff::parse(d.data(), d.size(), *f)) return false;
   im.pixels.clear();
   im.rows = f->height; im.cols = f->width;
   if (device_pixels && f->device_ok && (force_device || tiff_device_enabled())) { im.tiff = std::move(f); return true; }

@@ -65,6 +65,9 @@ struct Image {
   // a TIFF whose container has been parsed and whose chunks have been expanded (PackBits / LZW / Deflate): the worker undoes
   // the predictor, converts and places the chunks on the device (ocr_pipe_stage_batch)
   std::shared_ptr<tiff::Frame> tiff;
+  // a TIFF whose container alone has been parsed (Compression 1, LZW, PackBits): the worker expands the chunks on the device
+  // as well, then goes on as for tiff (ocr_pipe_stage_batch, OCR_FRAME_TIFF_CODED)
+  std::shared_ptr<tiff::Coded> tiff_coded;
   // a lossless WebP whose entropy-coded image has been decoded (prefix codes, LZ77, colour cache): the worker undoes the
   // transforms on the device (ocr_pipe_stage_batch)
   std::shared_ptr<webp::Frame> webp;
@@ -85,8 +88,8 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8 && !j2k && !j2k_coded; }
-  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8 || j2k || j2k_coded); }
+  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8 && !j2k && !j2k_coded && !tiff_coded; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8 || j2k || j2k_coded || tiff_coded); }
   void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM / TIFF / WebP on the host
     if (!device_decodable()) return;
     if (j2k_coded) {
@@ -108,6 +111,12 @@ struct Image {
     if (webp) {
       if (!webp::pixels(*webp, pixels)) throw std::runtime_error("WebP conversion failed");
       webp.reset();
+      return;
+    }
+    if (tiff_coded) {
+      tiff::Frame f;
+      if (!tiff::expand(*tiff_coded, f) || !tiff::pixels(f, pixels)) throw std::runtime_error("TIFF conversion failed");
+      tiff_coded.reset();
       return;
     }
     if (tiff) {
@@ -146,6 +155,20 @@ struct Image {
     d.width = raw->width; d.height = raw->height; d.kind = raw->kind; d.bottom_up = raw->bottom_up; d.row_stride = raw->row_stride;
     memcpy(d.palette, raw->palette, sizeof d.palette);
     d.data = raw->data.data(); d.data_len = raw->data.size();
+    return d;
+  }
+  ocr_tiff_coded tiff_coded_frame() const {  // only when tiff_coded
+    static_assert(sizeof(tiff::Chunk) == sizeof(ocr_tiff_chunk), "tiff::Chunk is ocr_tiff_chunk");
+    const tiff::Frame& f = tiff_coded->frame;
+    ocr_tiff_coded d;
+    memset(&d, 0, sizeof d);
+    d.frame.width = f.width; d.frame.height = f.height; d.frame.photometric = f.photometric; d.frame.bits_per_sample = f.bits;
+    d.frame.samples_per_pixel = f.samples; d.frame.planar = f.planar; d.frame.predictor = f.predictor; d.frame.big_endian = f.big_endian;
+    d.frame.premultiply = f.premultiply; d.frame.tile_width = f.tile_width; d.frame.tile_height = f.tile_height;
+    memcpy(d.frame.palette, f.palette, sizeof d.frame.palette);
+    d.compression = tiff_coded->compression;
+    d.chunks = (const ocr_tiff_chunk*)tiff_coded->chunks.data(); d.chunks_len = tiff_coded->chunks.size();
+    d.bytes = tiff_coded->bytes.empty() ? nullptr : tiff_coded->bytes.data(); d.bytes_len = tiff_coded->bytes.size();
     return d;
   }
   ocr_tiff_frame tiff_frame() const {  // only when tiff
@@ -230,12 +253,14 @@ struct DeviceFrames {
   std::deque<ocr_vp8_frame> vf;
   std::deque<ocr_j2k_frame> kf;
   std::deque<ocr_j2k_coded> kcf;
+  std::deque<ocr_tiff_coded> tcf;
   std::vector<ocr_coded_frame> list;
   void add(const Image& im) {  // only when im.device_decodable()
     if (im.j2k_coded) { kcf.push_back(im.j2k_coded_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K_CODED, &kcf.back()}); }
     else if (im.j2k) { kf.push_back(im.j2k_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K, &kf.back()}); }
     else if (im.vp8) { vf.push_back(im.vp8_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_VP8, &vf.back()}); }
     else if (im.webp) { wf.push_back(im.webp_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_WEBP, &wf.back()}); }
+    else if (im.tiff_coded) { tcf.push_back(im.tiff_coded_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF_CODED, &tcf.back()}); }
     else if (im.tiff) { tf.push_back(im.tiff_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF, &tf.back()}); }
     else if (im.raw) { rf.push_back(im.raw_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_RAW, &rf.back()}); }
     else if (im.png) { pf.push_back(im.png_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_PNG, &pf.back()}); }

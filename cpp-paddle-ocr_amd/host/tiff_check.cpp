@@ -9,6 +9,16 @@
 //   out: the BGR images one after another (nothing for a refused frame: the exit status is 1 then).
 // tiff_check --reject <dir>: every file of the directory must be refused; prints "refused <n> accepted <m>" and the names
 //   of the accepted ones; exit status 1 when there are any.
+// tiff_check --chunks <file> <out> [<file> <out> ...]: tiff::parse; out: Frame::data, the expanded chunks at their nominal size.
+// tiff_check --coded <file> <out> [<file> <out> ...]: tiff::parse_coded; out: the Coded in a flat little-endian form - [i32 width, height,
+//   photometric, bits, samples, planar, predictor, big_endian, premultiply, tile_width, tile_height][1024 palette bytes]
+//   [i32 compression][u64 chunks][per chunk: u64 byte_off, u32 byte_len, u32 rows][u64 length][that many pool bytes].  Exit
+//   status 1 for a refused file, 3 for one that takes the other route (Deflate).
+// tiff_check --expand <in> <out>: tiff::expand over Codeds of that form, one after another; out: Frame::data of each (nothing
+//   for a refused one: the exit status is 1 then) - what the device expansion is compared with.  Prints "ok" or "refused" per frame.
+// tiff_check --why <file> [...]: per file "<file>: ok", "refused" or "other route" (parse_coded's answer).
+// tiff_check --extents <streams> <out>: streams: repeated [u32 compression (5 or 32773), u32 need, u32 length][the bytes];
+//   out: per stream two bytes, the verdict of lzw_extent / packbits_extent and that of unlzw / unpack_bits for the same need.
 #include <dirent.h>
 
 #include <cstdio>
@@ -67,6 +77,92 @@ static int pixels_of_frames(const char* in, const char* outp) {
   return rc;
 }
 
+static const char* const kRouteName[] = {"refused", "ok", "other route"};
+
+static int coded_of_file(const char* in, const char* outp) {
+  std::unique_ptr<uint8_t[]> buf;
+  size_t n = 0;
+  if (!read_exact(in, buf, n)) { fprintf(stderr, "cannot read %s\n", in); return 2; }
+  tiff::Coded c;
+  const tiff::Route route = tiff::parse_coded(buf.get(), n, c);
+  if (route != tiff::kCoded) { fprintf(stderr, "%s: %s\n", kRouteName[route], in); return route == tiff::kRefused ? 1 : 3; }
+  FILE* o = fopen(outp, "wb");
+  if (!o) return 2;
+  const tiff::Frame& f = c.frame;
+  const int32_t head[11] = {f.width, f.height, f.photometric, f.bits, f.samples, f.planar, f.predictor, f.big_endian, f.premultiply, f.tile_width, f.tile_height};
+  const int32_t comp = c.compression;
+  const uint64_t nchunks = c.chunks.size(), len = c.bytes.size();
+  fwrite(head, 1, sizeof head, o);
+  fwrite(f.palette, 1, 1024, o);
+  fwrite(&comp, 1, 4, o);
+  fwrite(&nchunks, 1, 8, o);
+  for (const tiff::Chunk& k : c.chunks) { fwrite(&k.byte_off, 1, 8, o); fwrite(&k.byte_len, 1, 4, o); fwrite(&k.rows, 1, 4, o); }
+  fwrite(&len, 1, 8, o);
+  fwrite(c.bytes.data(), 1, c.bytes.size(), o);
+  fclose(o);
+  printf("%d %d %d %zu %zu\n", f.width, f.height, c.compression, c.chunks.size(), c.bytes.size());
+  return 0;
+}
+
+static int expand_codeds(const char* in, const char* outp) {
+  FILE* f = fopen(in, "rb");
+  FILE* o = fopen(outp, "wb");
+  if (!f || !o) return 2;
+  int rc = 0;
+  for (;;) {
+    int32_t head[11], comp;
+    uint64_t nchunks, len;
+    tiff::Coded c;
+    const size_t got = fread(head, 1, sizeof head, f);
+    if (got == 0) break;
+    if (got != sizeof head || fread(c.frame.palette, 1, 1024, f) != 1024 || fread(&comp, 1, 4, f) != 4 || fread(&nchunks, 1, 8, f) != 8) return 2;
+    tiff::Frame& fr = c.frame;
+    fr.width = head[0]; fr.height = head[1]; fr.photometric = head[2]; fr.bits = head[3]; fr.samples = head[4];
+    fr.planar = head[5]; fr.predictor = head[6]; fr.big_endian = head[7]; fr.premultiply = head[8];
+    fr.tile_width = head[9]; fr.tile_height = head[10];
+    c.compression = comp;
+    if (nchunks > ((uint64_t)1 << 24)) return 2;
+    c.chunks.resize((size_t)nchunks);
+    for (tiff::Chunk& k : c.chunks)
+      if (fread(&k.byte_off, 1, 8, f) != 8 || fread(&k.byte_len, 1, 4, f) != 4 || fread(&k.rows, 1, 4, f) != 4) return 2;
+    if (fread(&len, 1, 8, f) != 8 || len > ((uint64_t)1 << 31)) return 2;
+    // (a heap block of exactly the pool's size: a read past it is the sanitizer's to see)
+    std::unique_ptr<uint8_t[]> pool(new uint8_t[len ? len : 1]);
+    if (fread(pool.get(), 1, (size_t)len, f) != len) return 2;
+    c.bytes.assign(pool.get(), pool.get() + len);
+    c.bytes.shrink_to_fit();
+    tiff::Frame out;
+    if (!tiff::expand(c, out)) { rc = 1; printf("refused\n"); continue; }
+    printf("ok\n");
+    fwrite(out.data.data(), 1, out.data.size(), o);
+  }
+  fclose(f);
+  fclose(o);
+  return rc;
+}
+
+static int extents_of_streams(const char* in, const char* outp) {
+  FILE* f = fopen(in, "rb");
+  FILE* o = fopen(outp, "wb");
+  if (!f || !o) return 2;
+  for (;;) {
+    uint32_t head[3];
+    const size_t got = fread(head, 1, sizeof head, f);
+    if (got == 0) break;
+    if (got != sizeof head || head[1] > (1u << 26) || head[2] > (1u << 26)) return 2;
+    const size_t need = head[1], len = head[2];
+    std::unique_ptr<uint8_t[]> s(new uint8_t[len ? len : 1]), out(new uint8_t[need ? need : 1]);  // exactly their sizes
+    if (fread(s.get(), 1, len, f) != len) return 2;
+    uint8_t verdict[2];
+    if (head[0] == 5) { verdict[0] = tiff::detail::lzw_extent(s.get(), len, need); verdict[1] = tiff::detail::unlzw(s.get(), len, out.get(), need); }
+    else { verdict[0] = tiff::detail::packbits_extent(s.get(), len, need); verdict[1] = tiff::detail::unpack_bits(s.get(), len, out.get(), need); }
+    fwrite(verdict, 1, 2, o);
+  }
+  fclose(f);
+  fclose(o);
+  return 0;
+}
+
 static int reject_dir(const char* dir) {
   DIR* d = opendir(dir);
   if (!d) return 2;
@@ -88,6 +184,37 @@ int main(int argc, char** argv) {
   const std::string mode = argc > 1 ? argv[1] : "";
   if (mode == "--pixels" && argc == 4) return pixels_of_frames(argv[2], argv[3]);
   if (mode == "--reject" && argc == 3) return reject_dir(argv[2]);
+  if (mode == "--coded" && argc >= 4 && argc % 2 == 0) {
+    for (int i = 2; i < argc; i += 2)
+      if (const int rc = coded_of_file(argv[i], argv[i + 1])) return rc;
+    return 0;
+  }
+  if (mode == "--chunks" && argc >= 4 && argc % 2 == 0) {
+    for (int i = 2; i < argc; i += 2) {
+      std::unique_ptr<uint8_t[]> buf;
+      size_t n = 0;
+      if (!read_exact(argv[i], buf, n)) { fprintf(stderr, "cannot read %s\n", argv[i]); return 2; }
+      tiff::Frame frame;
+      if (!tiff::parse(buf.get(), n, frame)) { fprintf(stderr, "refused: %s\n", argv[i]); return 1; }
+      FILE* o = fopen(argv[i + 1], "wb");
+      if (!o) return 2;
+      fwrite(frame.data.data(), 1, frame.data.size(), o);
+      fclose(o);
+    }
+    return 0;
+  }
+  if (mode == "--expand" && argc == 4) return expand_codeds(argv[2], argv[3]);
+  if (mode == "--extents" && argc == 4) return extents_of_streams(argv[2], argv[3]);
+  if (mode == "--why" && argc >= 3) {
+    for (int i = 2; i < argc; ++i) {
+      std::unique_ptr<uint8_t[]> buf;
+      size_t n = 0;
+      if (!read_exact(argv[i], buf, n)) { fprintf(stderr, "cannot read %s\n", argv[i]); return 2; }
+      tiff::Coded c;
+      printf("%s: %s\n", argv[i], kRouteName[tiff::parse_coded(buf.get(), n, c)]);
+    }
+    return 0;
+  }
   if (mode == "--decode" && argc >= 4 && argc % 2 == 0) {
     for (int i = 2; i < argc; i += 2) {
       tiff::Frame frame;
@@ -101,6 +228,7 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  fprintf(stderr, "usage: tiff_check --decode <file> <out> [...] | --pixels <descriptors> <out> | --reject <dir>\n");
+  fprintf(stderr, "usage: tiff_check --decode <file> <out> [...] | --pixels <descriptors> <out> | --reject <dir> | --chunks <file> <out> [...] | --coded <file> <out> [...] | --expand <codeds> <out> | "
+                  "--why <file> [...] | --extents <streams> <out>\n");
   return 2;
 }

@@ -107,6 +107,21 @@ inline const char* fault(const Frame& f, Geometry& g) {
 }
 inline bool sound(const Frame& f, Geometry& g) { return !fault(f, g) && f.data.size() >= g.total; }
 
+// A file before its chunks are expanded (Compression 1, 5 and 32773): parse() is parse_coded() + expand(), and the device
+// takes the second half too (csrc/kernels_tiff_lzw.hip through ocr_tiff_coded).
+struct Chunk {  // ocr_tiff_chunk of include/ocr_hip.h, field for field
+  uint64_t byte_off = 0;  // into Coded::bytes
+  uint32_t byte_len = 0;
+  uint32_t rows = 0;      // the rows the chunk really holds: 1 .. tile_height (the last strip may have fewer)
+};
+struct Coded {
+  Frame frame;                // data empty
+  int compression = 1;        // 1, 5 (LZW) or 32773 (PackBits)
+  std::vector<Chunk> chunks;  // in the order Frame::data has them: plane by plane, row of chunks by row of chunks
+  std::vector<uint8_t> bytes; // the coded chunks one after another, MSB first (FillOrder 2 is undone)
+};
+enum Route { kRefused = 0, kCoded = 1, kOtherRoute = 2 };  // of parse_coded; kOtherRoute: Deflate, which goes through parse()
+
 namespace detail {
 
 struct Reader {  // the file, in its byte order
@@ -184,6 +199,61 @@ inline bool unlzw(const uint8_t* s, size_t n, uint8_t* out, size_t need) {
   return o == need;
 }
 
+// The extent scans: the walks of unpack_bits and unlzw over the lengths alone - no byte is copied, no chain is followed.
+// They say true exactly where the expander says true for the same `need`, and stop where it stops: what lies behind the
+// code that completes `need` is not looked at.  A chunk that passed is what the device expander is given.
+inline bool packbits_extent(const uint8_t* s, size_t n, size_t need) {
+  size_t i = 0, o = 0;
+  while (o < need && i < n) {
+    const int c = (int8_t)s[i++];
+    if (c >= 0) {
+      size_t k = (size_t)c + 1;
+      if (n - i < k) k = n - i;
+      if (k > need - o) k = need - o;
+      i += (size_t)c + 1; o += k;
+      if (i > n) break;
+    } else if (c != -128) {
+      if (i >= n) break;
+      ++i;
+      const size_t k = (size_t)(1 - c);
+      o += k > need - o ? need - o : k;
+    }
+  }
+  return o == need;
+}
+
+inline bool lzw_extent(const uint8_t* s, size_t n, size_t need) {
+  if (need == 0) return true;
+  if (n >= 2 && s[0] == 0 && (s[1] & 1)) return false;
+  uint16_t len[4096];  // of an entry's string; an entry below `next` alone is read
+  for (int i = 0; i < 258; ++i) len[i] = 1;
+  int bits = 9, next = 258, old = -1;
+  uint64_t acc = 0;
+  int have = 0;
+  size_t i = 0, o = 0;
+  while (o < need) {
+    while (have < bits && i < n) { acc = (acc << 8) | s[i++]; have += 8; }
+    if (have < bits) break;
+    const int code = (int)((acc >> (have - bits)) & ((1u << bits) - 1));
+    have -= bits;
+    if (code == 256) { bits = 9; next = 258; old = -1; continue; }
+    if (code == 257) break;
+    if (old < 0) {
+      if (code > 255) return false;
+      ++o;
+      old = code;
+      continue;
+    }
+    if (code > next || next >= 4096) return false;
+    len[next] = (uint16_t)(len[old] + 1);
+    ++next;
+    if (next > (1 << bits) - 2 && bits < 12) ++bits;
+    o += len[code] < need - o ? len[code] : need - o;
+    old = code;
+  }
+  return o == need;
+}
+
 inline bool inflate(const uint8_t* s, size_t n, uint8_t* out, size_t need) {
   const png::Zlib& z = png::zlib();
   if (!z.ok() || n > 0xFFFFFFFFu) return false;
@@ -209,13 +279,32 @@ inline bool inflate(const uint8_t* s, size_t n, uint8_t* out, size_t need) {
 
 }  // namespace detail
 
-// The container and the expansion: everything but the pixels.  false = not a TIFF file, or one that is refused.
-inline bool parse(const uint8_t* d, size_t n, Frame& f) {
-  using namespace detail;
+namespace detail {
+
+// What the container says beyond the frame: where the chunks lie and how they are coded.
+struct Head {
+  Reader r{nullptr, 0, false};
+  Geometry g;
+  uint32_t comp = 1, fill = 1;
+  bool tiled = false;
+  size_t chunks = 0;
+  Tag offs, counts;
+  // chunk c of the file: where its bytes lie, and the rows it really holds
+  size_t at(size_t c) const { return value(r, offs, c); }
+  size_t len(size_t c) const { return value(r, counts, c); }
+  size_t rows(const Frame& f, size_t c) const {
+    const size_t cy = (c / g.across) % g.down;
+    return cy + 1 == (size_t)g.down && !tiled ? (size_t)f.height - cy * f.tile_height : (size_t)f.tile_height;
+  }
+};
+
+// The container up to the expansion: the IFD, the frame, the chunk tables.  false = not a TIFF file, or one that is refused.
+inline bool parse_head(const uint8_t* d, size_t n, Frame& f, Head& hd) {
   if (n < 8) return false;
   const bool be = d[0] == 'M';
   if (!((d[0] == 'I' && d[1] == 'I') || (d[0] == 'M' && d[1] == 'M'))) return false;
   const Reader r{d, n, be};
+  hd.r = r;
   if (r.u16(2) != 42) return false;  // (43: BigTIFF)
   const size_t ifd = r.u32(4);
   if (ifd < 8 || ifd > n - 2) return false;
@@ -286,12 +375,12 @@ inline bool parse(const uint8_t* d, size_t n, Frame& f) {
     if (rps == 0) return false;
     f.tile_width = (int)w; f.tile_height = (int)(rps < h ? rps : h);
   }
-  Geometry g;
+  Geometry& g = hd.g;
   if (fault(f, g)) return false;
   // the chunk tables: as many entries as the geometry has chunks (they lie in the file: that bounds the number)
   const Tag& offs = tag[tiled ? TOFFS : OFFS];
   const Tag& counts = tag[tiled ? TCOUNTS : COUNTS];
-  const size_t chunks = (size_t)g.across * g.down * g.planes;
+  const size_t chunks = hd.chunks = (size_t)g.across * g.down * g.planes;
   if (!offs.present || !counts.present || offs.count != chunks || counts.count != chunks) return false;
   if (photo == 3) {
     const size_t entries3 = (size_t)1 << bits;
@@ -317,29 +406,128 @@ inline bool parse(const uint8_t* d, size_t n, Frame& f) {
     coded += len;
   }
   if (comp != 1 && coded == 0) return false;
+  hd.comp = comp; hd.fill = fill; hd.tiled = tiled; hd.offs = offs; hd.counts = counts;
+  return true;
+}
+
+inline const char* structure_fault(const Frame& f, int compression, const Chunk* chunks, size_t nchunks, size_t pool, Geometry& g) {
+  if (const char* why = fault(f, g)) return why;
+  if (compression != 1 && compression != 5 && compression != 32773) return "coded: compression must be 1 (none), 5 (LZW) or 32773 (PackBits)";
+  if (nchunks != (size_t)g.across * g.down * g.planes || (nchunks && !chunks)) return "coded: as many chunk records as the geometry has chunks";
+  for (size_t c = 0; c < nchunks; ++c) {
+    if (chunks[c].rows < 1 || chunks[c].rows > (uint32_t)f.tile_height) return "coded: a chunk's rows must be 1 .. tile_height";
+    if (chunks[c].byte_off > pool || pool - chunks[c].byte_off < chunks[c].byte_len) return "coded: a chunk's bytes lie outside the pool";
+  }
+  return nullptr;
+}
+
+}  // namespace detail
+
+// The rules a coded frame satisfies, over its parts (csrc/capi_tiff.hip runs the same text on its side of the ABI): fault(),
+// the records, and the extent scan of every chunk - a faulty stream is found here, on the host, because the device expander
+// cannot refuse a file.  nullptr when it is sound.
+inline const char* coded_fault_of(const Frame& f, int compression, const Chunk* chunks, size_t nchunks, const uint8_t* bytes, size_t pool, Geometry& g) {
+  if (const char* why = detail::structure_fault(f, compression, chunks, nchunks, pool, g)) return why;
+  if (pool && !bytes) return "coded: the byte pool is missing";
+  for (size_t c = 0; c < nchunks; ++c) {
+    const uint8_t* s = bytes + chunks[c].byte_off;
+    const size_t len = chunks[c].byte_len, need = (size_t)chunks[c].rows * g.row_bytes;
+    const bool ok = compression == 1 ? len >= need : compression == 5 ? detail::lzw_extent(s, len, need) : detail::packbits_extent(s, len, need);
+    if (!ok) return "coded: a chunk's stream does not hold the bytes its rows need";
+  }
+  return nullptr;
+}
+inline const char* coded_fault(const Coded& c, Geometry& g) {
+  if (!c.frame.data.empty()) return "coded: a coded frame carries no expanded chunks";
+  return coded_fault_of(c.frame, c.compression, c.chunks.data(), c.chunks.size(), c.bytes.data(), c.bytes.size(), g);
+}
+
+// The expansion: every chunk of a coded frame to its nominal size, as Frame::data holds them.  The records are checked here,
+// the streams by the expanders themselves; false where coded_fault() would have refused.
+inline bool expand(const Coded& c, Frame& f) {
+  Geometry g;
+  if (!c.frame.data.empty() || detail::structure_fault(c.frame, c.compression, c.chunks.data(), c.chunks.size(), c.bytes.size(), g)) { f = Frame(); return false; }
+  f = c.frame;
+  f.data.assign(g.total, 0);  // (rows of a strip the image does not have stay zero)
+  for (size_t k = 0; k < c.chunks.size(); ++k) {
+    const uint8_t* s = c.bytes.data() + c.chunks[k].byte_off;
+    const size_t len = c.chunks[k].byte_len, need = (size_t)c.chunks[k].rows * g.row_bytes;
+    uint8_t* out = f.data.data() + k * g.chunk_bytes;
+    bool ok;
+    if (c.compression == 1) { ok = len >= need; if (ok) memcpy(out, s, need); }
+    else if (c.compression == 32773) ok = detail::unpack_bits(s, len, out, need);
+    else ok = detail::unlzw(s, len, out, need);
+    if (!ok) { f = Frame(); return false; }
+  }
+  f.device_ok = c.chunks.size() <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
+  return true;
+}
+
+namespace detail {
+// the coded chunks of a parsed head into one pool (an uncompressed chunk: the bytes its rows need, no more).  scan: with the
+// extent scan of every stream (coded_fault); without, the records alone are checked - for a caller that expands at once, whose
+// expanders refuse exactly what the scan refuses
+inline bool gather(const uint8_t* d, const Head& h, Coded& c, bool scan) {
+  c.compression = (int)h.comp;
+  c.chunks.resize(h.chunks);
+  size_t pool = 0;
+  for (size_t k = 0; k < h.chunks; ++k) {
+    const size_t rows = h.rows(c.frame, k), len = h.comp == 1 ? rows * h.g.row_bytes : h.len(k);
+    c.chunks[k].byte_off = pool; c.chunks[k].byte_len = (uint32_t)len; c.chunks[k].rows = (uint32_t)rows;
+    pool += len;
+  }
+  c.bytes.resize(pool);
+  for (size_t k = 0; k < h.chunks; ++k) {
+    const uint8_t* s = d + h.at(k);
+    uint8_t* o = c.bytes.data() + c.chunks[k].byte_off;
+    if (h.fill == 2) for (size_t i = 0; i < c.chunks[k].byte_len; ++i) o[i] = reverse_bits(s[i]);  // FillOrder 2: the coded bytes with their bits reversed
+    else memcpy(o, s, c.chunks[k].byte_len);
+  }
+  Geometry g;
+  if (scan ? coded_fault(c, g) : structure_fault(c.frame, c.compression, c.chunks.data(), c.chunks.size(), c.bytes.size(), g)) return false;
+  c.frame.device_ok = h.chunks <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
+  return true;
+}
+}  // namespace detail
+
+// The container alone, for the files whose expansion the device can take: Compression 1, 5 and 32773.  Every chunk's stream
+// is scanned (coded_fault), so that kCoded means expand() - on the host or on the device - has what it needs.  Deflate answers
+// kOtherRoute: parse() is the way.
+inline Route parse_coded(const uint8_t* d, size_t n, Coded& c) {
+  c = Coded();
+  detail::Head h;
+  if (!detail::parse_head(d, n, c.frame, h)) { c = Coded(); return kRefused; }
+  if (h.comp != 1 && h.comp != 5 && h.comp != 32773) { c = Coded(); return kOtherRoute; }
+  if (!detail::gather(d, h, c, true)) { c = Coded(); return kRefused; }
+  return kCoded;
+}
+
+// The container and the expansion: everything but the pixels.  false = not a TIFF file, or one that is refused.
+inline bool parse(const uint8_t* d, size_t n, Frame& f) {
+  using namespace detail;
+  Head h;
+  if (!parse_head(d, n, f, h)) return false;
+  if (h.comp == 1 || h.comp == 5 || h.comp == 32773) {
+    Coded c;  // parse_coded + expand, less the scan: unlzw / unpack_bits refuse what lzw_extent / packbits_extent refuse
+    c.frame = f;
+    if (!gather(d, h, c, false) || !expand(c, f)) { f = Frame(); return false; }
+    return true;
+  }
+  const Geometry& g = h.g;
   std::vector<uint8_t> turned;  // FillOrder 2: the coded bytes of a chunk with their bits reversed
-  for (size_t c = 0; c < chunks; ++c) {
-    const size_t at = value(r, offs, c), len = value(r, counts, c);
-    const size_t cy = (c / g.across) % g.down;
-    const size_t rows = cy + 1 == (size_t)g.down && !tiled ? (size_t)h - cy * f.tile_height : (size_t)f.tile_height;
-    const size_t need = rows * g.row_bytes;
-    const uint8_t* s = d + at;
-    if (fill == 2) {
+  for (size_t c = 0; c < h.chunks; ++c) {
+    const size_t len = h.len(c), need = h.rows(f, c) * g.row_bytes;
+    const uint8_t* s = d + h.at(c);
+    if (h.fill == 2) {
       turned.resize(len);
       for (size_t i = 0; i < len; ++i) turned[i] = reverse_bits(s[i]);
       s = turned.data();
     }
     // the buffer grows chunk by chunk - a header's claim alone allocates nothing - to g.total at most
     f.data.resize((c + 1) * g.chunk_bytes, 0);
-    uint8_t* out = f.data.data() + c * g.chunk_bytes;
-    bool ok;
-    if (comp == 1) { memcpy(out, s, need); ok = true; }
-    else if (comp == 32773) ok = unpack_bits(s, len, out, need);
-    else if (comp == 5) ok = unlzw(s, len, out, need);
-    else ok = inflate(s, len, out, need);
-    if (!ok) { f = Frame(); return false; }
+    if (!inflate(s, len, f.data.data() + c * g.chunk_bytes, need)) { f = Frame(); return false; }
   }
-  f.device_ok = chunks <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
+  f.device_ok = h.chunks <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
   return true;
 }
 

@@ -411,6 +411,35 @@ int ocr_tiff_decode(const ocr_tiff_frame* frame, int device_id, uint8_t* bgr, si
  * pixel-stage kernel; ocr_tiff_time_batch: `count` frames as ONE batch (one upload, one launch per sample width). */
 int ocr_tiff_time(const ocr_tiff_frame* frame, int device_id, int iters, double ms[2]);
 int ocr_tiff_time_batch(const ocr_tiff_frame* const* frames, int count, int device_id, int iters, double ms[2]);
+/* TIFF inputs with the expansion of the chunks on the device as well (Compression 1, 5 = LZW, 32773 = PackBits): the caller
+ * stops before the expansion (host/tiff_decode.h, tiff::parse_coded) and hands over coded bytes - the frame without `data`, one
+ * record per chunk in the order `data` would have them, and one pool of the chunks' bytes, MSB first (FillOrder 2 undone).  A
+ * chunk is expanded by one wavefront (csrc/kernels_tiff_lzw.hip) into device scratch, to the bytes of tiff::expand.  Every
+ * field and every stream is checked on the host before anything is launched (tiff::coded_fault, which scans each chunk's codes
+ * for the bytes its rows need: OCR_ERR_ARG, ocr_last_error says which rule); a frame of more than 2^20 chunks or 512 MiB of
+ * chunks at their nominal size is refused here - tiff::expand and ocr_tiff_decode take it. */
+typedef struct ocr_tiff_chunk {
+  uint64_t byte_off;  /* into bytes */
+  uint32_t byte_len;
+  uint32_t rows;      /* the rows the chunk really holds, 1 .. tile_height (the last strip may have fewer) */
+} ocr_tiff_chunk;
+typedef struct ocr_tiff_coded {
+  ocr_tiff_frame frame;          /* data is NULL (data_len is not read) */
+  int compression;               /* 1, 5 or 32773 */
+  const ocr_tiff_chunk* chunks;  /* host: plane by plane, row of chunks by row of chunks */
+  size_t chunks_len;
+  const uint8_t* bytes;          /* host */
+  size_t bytes_len;
+} ocr_tiff_coded;
+/* the expansion alone: out[0 .. chunks * tile_height * row bytes) as tiff::parse fills Frame::data, zero rows behind a short
+ * last strip included; cap in bytes */
+int ocr_tiff_expand(const ocr_tiff_coded* coded, int device_id, uint8_t* out, size_t cap);
+/* the expansion, then the launches of ocr_tiff_decode, on one stream with no host round trip in between */
+int ocr_tiff_decode_coded(const ocr_tiff_coded* coded, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time): ms[0] = the upload of the pool, records and descriptors from pinned memory, ms[1] = the
+ * expansion, ms[2] = the pixel stage's kernels; ocr_tiff_time_coded_batch: `count` frames as ONE batch. */
+int ocr_tiff_time_coded(const ocr_tiff_coded* coded, int device_id, int iters, double ms[3]);
+int ocr_tiff_time_coded_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]);
 /* Lossless WebP inputs with the pixel half of the decoder on the device: the caller parses the container and does what is
  * serial (prefix codes, LZ77, the colour cache: host/webp_decode.h, webp::parse); the inverse transforms - spatial predictor,
  * cross-colour, add-green, palette with pixel bundling - run on the copy stream straight into the slot.  The pixels are
@@ -546,12 +575,12 @@ int ocr_j2k_decode_coded(const ocr_j2k_coded* coded, int device_id, uint8_t* bgr
 int ocr_j2k_time_coded(const ocr_j2k_coded* coded, int device_id, int iters, double ms[3]);
 int ocr_j2k_time_coded_batch(const ocr_j2k_coded* const* coded, int count, int device_id, int iters, double ms[3]);
 /* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw, TIFF,
- * WebP, VP8 and JPEG 2000 frames (coefficient form and coded form) in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
+ * WebP, VP8 and JPEG 2000 frames (coefficient form and coded form) and coded TIFF frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
  * all five validate their own argument list and stage through the same code, with the same bytes in the slot. */
-typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5, OCR_FRAME_J2K = 6, OCR_FRAME_J2K_CODED = 7 } ocr_frame_kind;
+typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5, OCR_FRAME_J2K = 6, OCR_FRAME_J2K_CODED = 7, OCR_FRAME_TIFF_CODED = 8 } ocr_frame_kind;
 typedef struct ocr_coded_frame {
   int kind;           /* ocr_frame_kind */
-  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame, ocr_vp8_frame, ocr_j2k_frame or ocr_j2k_coded */
+  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame, ocr_vp8_frame, ocr_j2k_frame, ocr_j2k_coded or ocr_tiff_coded */
 } ocr_coded_frame;
 int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);

@@ -156,8 +156,9 @@ def png_mode(clients, per):
 def tiff_mode(clients, per):
     """960x960 8-bit RGB TIFF requests (the configs[1] card of jpeg_mode; LZW with the horizontal predictor, strips of 16 rows,
     written by Pillow) against a service with two GPU workers: OCR_DEVICE_TIFF=1 (opt-in: container and LZW on the client's
-    service thread, predictor scan, conversion and placement on the worker's copy stream) and 0 (the default: the whole decode
-    on the host thread).  The line's "sys_threads_per_1000rps" is the host-cores-per-1000-requests/s figure."""
+    service thread, predictor scan, conversion and placement on the worker's copy stream), 2 (opt-in: the container and the
+    extent scan of every strip on the service thread, LZW expansion too on the worker's copy stream) and 0 (the default: the
+    whole decode on the host thread).  The line's "sys_threads_per_1000rps" is the host-cores-per-1000-requests/s figure."""
     import numpy as np
     from PIL import Image
     from synth_data import cfg2_sample
@@ -166,8 +167,8 @@ def tiff_mode(clients, per):
     Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(path, format="TIFF", compression="tiff_lzw", tiffinfo={317: 2})
     fmt = "tiff 8-bit RGB LZW predictor 960x960 (%d KB)" % (os.path.getsize(path) // 1024)
     op = {"OCR_WORKER_DET_LIMIT": "960", "OCR_WORKER_REC_H": "48", "OCR_WORKER_REC_W": "320", "OCR_WORKER_CLS": "1"}
-    for dev in ("1", "0"):
-        run(16, clients, per, path, fmt, workers=2, extra_env=dict(op, OCR_DEVICE_TIFF=dev), tag="device_tiff" if dev == "1" else "host_tiff")
+    for dev, tag in (("1", "device_tiff"), ("2", "device_tiff_coded"), ("0", "host_tiff")):
+        run(16, clients, per, path, fmt, workers=2, extra_env=dict(op, OCR_DEVICE_TIFF=dev), tag=tag)
 
 
 def webp_mode(clients, per):
