@@ -56,6 +56,7 @@ EXPORTS = [
     "ocr_net_create", "ocr_net_create_precision", "ocr_net_destroy", "ocr_net_forward", "ocr_net_forward_ragged", "ocr_net_forward_ragged_images", "ocr_net_num_tensors", "ocr_net_tensor_exists", "ocr_net_fetch",
     "ocr_net_timing", "ocr_net_timing_report", "ocr_probe", "ocr_selftest_refuse_launch", "ocr_selftest_lds_memo",
     "ocr_selftest_unclip", "ocr_selftest_unclip_box",
+    "ocr_selftest_det_pre", "ocr_selftest_line_pre", "ocr_selftest_line_pre_ragged",
     "ocr_srv_net_create", "ocr_srv_net_destroy", "ocr_srv_net_forward", "ocr_srv_net_rerun", "ocr_srv_net_num_tensors", "ocr_srv_net_fetch",
     "ocr_srv_net_timing", "ocr_srv_net_timing_report", "ocr_srv_net_num_launches", "ocr_srv_net_launch_info", "ocr_srv_net_run_launches",
     "ocr_srv_net_upload",
@@ -231,6 +232,83 @@ def selftest_topk(rows, p0, k, ncols=None):
                                     C.c_void_p, C.c_void_p]
     check(L.ocr_selftest_topk(rows.ctypes.data, n, C_, pitch, p0.ctypes.data, int(k), ids.ctypes.data, probs.ctypes.data))
     return ids, probs
+
+
+SELFTEST_FILL, SELFTEST_GUARD = 0xA5, 256   # include/ocr_hip.h OCR_SELFTEST_FILL / OCR_SELFTEST_GUARD
+PAD_REC, PAD_CLS = 0, 1                      # OCR_PAD_REC / OCR_PAD_CLS
+STAGE_REC, STAGE_CLS = 1, 2                  # OCR_STAGE_REC / OCR_STAGE_CLS
+
+
+def _split_guard(raw, count, dtype):
+    """the first `count` elements of a self-test output and the guard bytes behind them"""
+    n = count * np.dtype(dtype).itemsize
+    return raw[:n].view(dtype), raw[n:]
+
+
+def selftest_det_pre(buf, src_offset, src_stride, src_image_bytes, N, sh, sw, dh, dw):
+    """launch_det_pre alone (ocr_selftest_det_pre): buf a flat uint8 buffer; image i at byte src_offset + i * src_image_bytes of its
+    256-byte-aligned device copy -> (f32 [N, dh, dw, 3], u8 tap [N, dh, dw, 3], guard bytes behind the f32, guard bytes behind the tap)"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+    cnt = max(0, N) * max(0, dh) * max(0, dw) * 3
+    if cnt > 1 << 26:
+        cnt = 0  # (the call refuses such sizes before it writes)
+    out = np.zeros(cnt * 4 + SELFTEST_GUARD, np.uint8)
+    res = np.zeros(cnt + SELFTEST_GUARD, np.uint8)
+    L = lib()
+    L.ocr_selftest_det_pre.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.c_void_p]
+    check(L.ocr_selftest_det_pre(buf.ctypes.data, buf.size, int(src_offset), int(src_stride), int(src_image_bytes), int(N), int(sh),
+                                 int(sw), int(dh), int(dw), out.ctypes.data, res.ctypes.data))
+    x, gx = _split_guard(out, cnt, np.float32)
+    r, gr = _split_guard(res, cnt, np.uint8)
+    return x.reshape(N, dh, dw, 3), r.reshape(N, dh, dw, 3), gx, gr
+
+
+def _parent_rows(img):
+    img = np.asarray(img)
+    assert img.dtype == np.uint8 and img.ndim == 2 and img.flags.c_contiguous, "parent image: uint8 [rows, stride] with the pad bytes"
+    return img
+
+
+def selftest_line_pre(parent, cols, lines, imgH, imgW, nslots, pad_mode, stage=STAGE_REC):
+    """launch_line_pre alone (ocr_selftest_line_pre): parent uint8 [rows, stride] holding `cols` BGR pixels per row; lines: rows of
+    (x, y, w, h, resize_w, slot) -> (f32 [nslots, imgH, imgW, 3], guard bytes behind it)"""
+    parent = _parent_rows(parent)
+    lines = np.ascontiguousarray(lines, dtype=np.int32).reshape(-1, 6)
+    cnt = max(0, nslots) * max(0, imgH) * max(0, imgW) * 3
+    if cnt > 1 << 26:
+        cnt = 0
+    out = np.zeros(cnt * 4 + SELFTEST_GUARD, np.uint8)
+    L = lib()
+    L.ocr_selftest_line_pre.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_void_p]
+    check(L.ocr_selftest_line_pre(parent.ctypes.data, parent.shape[0], int(cols), parent.shape[1], lines.ctypes.data, len(lines), int(imgH),
+                                  int(imgW), int(nslots), int(pad_mode), int(stage), out.ctypes.data))
+    x, g = _split_guard(out, cnt, np.float32)
+    return x.reshape(nslots, imgH, imgW, 3), g
+
+
+def selftest_line_pre_ragged(parent, cols, lines, imgH, stage=STAGE_REC):
+    """launch_line_pre_ragged alone (ocr_selftest_line_pre_ragged): lines: rows of (x, y, w, h, resize_w, tensor_w) -> (list of f32
+    [imgH, tensor_w, 3] per line, guard bytes behind the last)"""
+    parent = _parent_rows(parent)
+    lines = np.ascontiguousarray(lines, dtype=np.int32).reshape(-1, 6)
+    ok = imgH > 0 and len(lines) and (lines[:, 5] > 0).all() and (lines[:, 5] <= 8192).all() and imgH <= 8192
+    widths = [int(w) for w in lines[:, 5]] if ok else []
+    cnt = imgH * sum(widths) * 3 if ok else 0
+    if cnt > 1 << 26:
+        cnt, widths = 0, []
+    out = np.zeros(cnt * 4 + SELFTEST_GUARD, np.uint8)
+    L = lib()
+    L.ocr_selftest_line_pre_ragged.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    check(L.ocr_selftest_line_pre_ragged(parent.ctypes.data, parent.shape[0], int(cols), parent.shape[1], lines.ctypes.data, len(lines),
+                                         int(imgH), int(stage), out.ctypes.data))
+    x, g = _split_guard(out, cnt, np.float32)
+    outs, at = [], 0
+    for w in widths:
+        outs.append(x[at:at + imgH * w * 3].reshape(imgH, w, 3))
+        at += imgH * w * 3
+    return outs, g
 
 
 def probe(a, b):

@@ -135,6 +135,148 @@ int ocr_selftest_unclip_box(const float* boxes, float unclip_ratio, int n, float
   return OCR_OK;
 }
 
+// ---- self-test taps: the resize-and-normalise launches of kernels_pre.hip alone.  Outputs are pre-filled with
+// OCR_SELFTEST_FILL and handed back with OCR_SELFTEST_GUARD bytes from behind their last element; whatever the launchers
+// leave undefined is refused here, before the device sees it.
+namespace {
+const int kPreMaxSide = 8192, kPreMaxCount = 1024;
+const size_t kPreMaxBytes = (size_t)1 << 28;
+
+bool upload_norm_lut(NormStage st, DevBuf<float>& lut, std::string& err) {
+  const std::vector<float> h = stage_norm_lut(st);
+  if (!lut.ensure(h.size(), err)) return false;
+  if (g_memcpy(lut.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { err = "lut upload failed"; return false; }
+  return true;
+}
+// the parent image and the ROIs (x, y, w, h, resize_w, .) of a line launch
+const char* check_lines(const uint8_t* img, int rows, int cols, size_t stride, const int32_t* lines, int n, int imgH, int stage, const float* out) {
+  if (!img || !lines || !out) return "null argument";
+  if (rows < 1 || cols < 1 || rows > kPreMaxSide || cols > kPreMaxSide) return "parent image size out of range";
+  if (stride < (size_t)cols * 3 || stride > (size_t)kPreMaxSide * 4) return "stride below 3 * cols";
+  if (n < 1 || n > kPreMaxCount) return "line count out of range";
+  if (imgH < 1 || imgH > kPreMaxSide) return "imgH out of range";
+  if (stage != OCR_STAGE_REC && stage != OCR_STAGE_CLS) return "stage is neither OCR_STAGE_REC nor OCR_STAGE_CLS";
+  for (int i = 0; i < n; ++i) {
+    const int32_t* q = lines + (size_t)i * 6;
+    if (q[2] < 1 || q[3] < 1) return "empty ROI";
+    if (q[0] < 0 || q[1] < 0 || q[0] > cols - q[2] || q[1] > rows - q[3]) return "ROI outside the parent image";
+    if (q[4] < 1) return "resize_w < 1";
+  }
+  return nullptr;
+}
+}  // namespace
+
+int ocr_selftest_det_pre(const uint8_t* buf, size_t buf_bytes, size_t src_offset, size_t src_stride, size_t src_image_bytes, int N,
+                         int sh, int sw, int dh, int dw, float* out, uint8_t* resized) {
+  if (!buf || !out || !resized) return fail(OCR_ERR_ARG, "null argument");
+  if (N < 1 || N > kPreMaxCount || sh < 1 || sw < 1 || dh < 1 || dw < 1 || sh > kPreMaxSide || sw > kPreMaxSide || dh > kPreMaxSide ||
+      dw > kPreMaxSide)
+    return fail(OCR_ERR_ARG, "image count or size out of range");
+  if (buf_bytes < 1 || buf_bytes > kPreMaxBytes) return fail(OCR_ERR_ARG, "buffer size out of range");
+  if (src_stride < (size_t)sw * 3 || src_stride > buf_bytes) return fail(OCR_ERR_ARG, "src_stride below 3 * sw");
+  const size_t one = (size_t)(sh - 1) * src_stride + (size_t)sw * 3;  // bytes from an image's first to behind its last
+  if (N > 1 && src_image_bytes < one) return fail(OCR_ERR_ARG, "src_image_bytes below the size of one image");
+  if (src_image_bytes > buf_bytes || src_offset > buf_bytes || one > buf_bytes - src_offset ||
+      (size_t)(N - 1) * src_image_bytes > buf_bytes - src_offset - one)
+    return fail(OCR_ERR_ARG, "the images do not lie inside the buffer");
+  const size_t nel = (size_t)N * dh * dw * 3;
+  if (nel * sizeof(float) > kPreMaxBytes) return fail(OCR_ERR_ARG, "output too large");
+  std::string err;
+  DevBuf<uint8_t> dsrc, dres;
+  DevBuf<float> dout, lut;
+  const size_t out_bytes = nel * sizeof(float) + OCR_SELFTEST_GUARD, res_bytes = nel + OCR_SELFTEST_GUARD;
+  if (!dsrc.ensure(buf_bytes, err) || !dres.ensure(res_bytes, err) || !dout.ensure(out_bytes / sizeof(float), err) ||
+      !upload_norm_lut(NormStage::Det, lut, err))
+    return fail(OCR_ERR_DEVICE, err);
+  CAPI_HIP(g_memcpy(dsrc.p, buf, buf_bytes, hipMemcpyHostToDevice));
+  CAPI_HIP(hipMemset(dout.p, OCR_SELFTEST_FILL, out_bytes));
+  CAPI_HIP(hipMemset(dres.p, OCR_SELFTEST_FILL, res_bytes));
+  DetPreArgs pa{};
+  pa.src = dsrc.p + src_offset; pa.src_image_bytes = src_image_bytes; pa.src_stride = src_stride;
+  pa.N = N; pa.sh = sh; pa.sw = sw; pa.dh = dh; pa.dw = dw; pa.lut = lut.p; pa.out = dout.p; pa.resized = dres.p;
+  launch_det_pre(pa, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(g_memcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+  CAPI_HIP(g_memcpy(resized, dres.p, res_bytes, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
+int ocr_selftest_line_pre(const uint8_t* img, int rows, int cols, size_t stride, const int32_t* lines, int n, int imgH, int imgW,
+                          int nslots, int pad_mode, int stage, float* out) {
+  if (const char* why = check_lines(img, rows, cols, stride, lines, n, imgH, stage, out)) return fail(OCR_ERR_ARG, why);
+  if (imgW < 1 || imgW > kPreMaxSide) return fail(OCR_ERR_ARG, "imgW out of range");
+  if (pad_mode != OCR_PAD_REC && pad_mode != OCR_PAD_CLS) return fail(OCR_ERR_ARG, "pad_mode is neither OCR_PAD_REC nor OCR_PAD_CLS");
+  if (nslots < n || nslots > kPreMaxCount) return fail(OCR_ERR_ARG, "fewer slots than lines");
+  std::vector<char> taken(nslots, 0);
+  for (int i = 0; i < n; ++i) {
+    const int32_t* q = lines + (size_t)i * 6;
+    if (q[4] > imgW) return fail(OCR_ERR_ARG, "resize_w above the tensor width");
+    if (q[5] < 0 || q[5] >= nslots) return fail(OCR_ERR_ARG, "slot outside the tensor");
+    if (taken[q[5]]) return fail(OCR_ERR_ARG, "two lines name one slot");
+    taken[q[5]] = 1;
+  }
+  const size_t nel = (size_t)nslots * imgH * imgW * 3;
+  if (nel * sizeof(float) > kPreMaxBytes) return fail(OCR_ERR_ARG, "output too large");
+  std::string err;
+  DevBuf<uint8_t> dimg;
+  DevBuf<float> dout, lut;
+  DevBuf<LineDesc> ddesc;
+  const size_t out_bytes = nel * sizeof(float) + OCR_SELFTEST_GUARD;
+  if (!dimg.ensure((size_t)rows * stride, err) || !dout.ensure(out_bytes / sizeof(float), err) || !ddesc.ensure(n, err) ||
+      !upload_norm_lut(stage == OCR_STAGE_REC ? NormStage::Rec : NormStage::Cls, lut, err))
+    return fail(OCR_ERR_DEVICE, err);
+  std::vector<LineDesc> d(n);
+  for (int i = 0; i < n; ++i) {
+    const int32_t* q = lines + (size_t)i * 6;
+    d[i] = LineDesc::make(dimg.p, stride, q[0], q[1], q[2], q[3], q[4], q[5], imgH);
+  }
+  CAPI_HIP(g_memcpy(dimg.p, img, (size_t)rows * stride, hipMemcpyHostToDevice));
+  CAPI_HIP(g_memcpy(ddesc.p, d.data(), (size_t)n * sizeof(LineDesc), hipMemcpyHostToDevice));
+  CAPI_HIP(hipMemset(dout.p, OCR_SELFTEST_FILL, out_bytes));
+  launch_line_pre(ddesc.p, n, imgH, imgW, lut.p, pad_mode == OCR_PAD_CLS, dout.p, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(g_memcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
+int ocr_selftest_line_pre_ragged(const uint8_t* img, int rows, int cols, size_t stride, const int32_t* lines, int n, int imgH,
+                                 int stage, float* out) {
+  if (const char* why = check_lines(img, rows, cols, stride, lines, n, imgH, stage, out)) return fail(OCR_ERR_ARG, why);
+  long pix = 0;
+  for (int i = 0; i < n; ++i) {
+    const int32_t* q = lines + (size_t)i * 6;
+    if (q[5] < 1 || q[5] > kPreMaxSide) return fail(OCR_ERR_ARG, "tensor_w out of range");
+    if (q[4] > q[5]) return fail(OCR_ERR_ARG, "resize_w above the tensor width");
+    pix += (long)imgH * q[5];
+  }
+  const size_t nel = (size_t)pix * 3;
+  if (nel * sizeof(float) > kPreMaxBytes) return fail(OCR_ERR_ARG, "output too large");
+  std::string err;
+  DevBuf<uint8_t> dimg;
+  DevBuf<float> dout, lut;
+  DevBuf<LineDesc> ddesc;
+  const size_t out_bytes = nel * sizeof(float) + OCR_SELFTEST_GUARD;
+  if (!dimg.ensure((size_t)rows * stride, err) || !dout.ensure(out_bytes / sizeof(float), err) || !ddesc.ensure(n, err) ||
+      !upload_norm_lut(stage == OCR_STAGE_REC ? NormStage::Rec : NormStage::Cls, lut, err))
+    return fail(OCR_ERR_DEVICE, err);
+  std::vector<LineDesc> d(n);
+  long at = 0;
+  for (int i = 0; i < n; ++i) {
+    const int32_t* q = lines + (size_t)i * 6;
+    d[i] = LineDesc::make(dimg.p, stride, q[0], q[1], q[2], q[3], q[4], i, imgH);
+    d[i].tensor_w = q[5];
+    d[i].pix0 = (int)at;
+    at += (long)imgH * q[5];
+  }
+  CAPI_HIP(g_memcpy(dimg.p, img, (size_t)rows * stride, hipMemcpyHostToDevice));
+  CAPI_HIP(g_memcpy(ddesc.p, d.data(), (size_t)n * sizeof(LineDesc), hipMemcpyHostToDevice));
+  CAPI_HIP(hipMemset(dout.p, OCR_SELFTEST_FILL, out_bytes));
+  launch_line_pre_ragged(ddesc.p, n, pix, imgH, lut.p, dout.p, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(g_memcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
 void ocr_cls_cfg_default(ocr_cls_cfg* c) {
   if (!c) return;
   memset(c, 0, sizeof(*c));

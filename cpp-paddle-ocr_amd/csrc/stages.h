@@ -238,5 +238,9 @@ bool upload_lines(const ocr_img* imgs, int n, DevBuf<uint8_t>& staging, std::vec
 
 // 3x256 normalisation LUT: Normalize::Run per byte value (convertTo 1/255, then scale/shift)
 std::vector<float> make_norm_lut(const float mean[3], const float scale[3]);
+// the table of one stage (its mean / scale literals live here alone): the stages upload it at create, the
+// ocr_selftest_*_pre taps launch the pre-processing kernels with it
+enum class NormStage { Det, Rec, Cls };
+std::vector<float> stage_norm_lut(NormStage st);
 
 }  // namespace ocr

@@ -50,6 +50,15 @@ std::vector<float> make_norm_lut(const float mean[3], const float scale[3]) {
   }
   return lut;
 }
+std::vector<float> stage_norm_lut(NormStage st) {
+  if (st == NormStage::Det) {
+    const float mean[3] = {0.485f, 0.456f, 0.406f};                      // ocr_det.h:121
+    const float scale[3] = {1 / 0.229f, 1 / 0.224f, 1 / 0.225f};        // ocr_det.h:122
+    return make_norm_lut(mean, scale);
+  }
+  const float mean[3] = {0.5f, 0.5f, 0.5f}, scale[3] = {1 / 0.5f, 1 / 0.5f, 1 / 0.5f};  // ocr_rec.h:108-109, ocr_cls.h:93-94
+  return make_norm_lut(mean, scale);
+}
 
 bool upload_lines(const ocr_img* imgs, int n, DevBuf<uint8_t>& staging, std::vector<LineSrc>& out, hipStream_t s,
                   std::string& err) {
@@ -126,9 +135,7 @@ bool DetStage::create(const DetConfig& cfg, std::string& err, int& code) {
   code = OCR_ERR_DEVICE;
   if (g_stream_create(&stream_) != hipSuccess) { err = "hipStreamCreate failed"; return false; }
   if (!timer_.init(err)) return false;
-  const float mean[3] = {0.485f, 0.456f, 0.406f};                      // ocr_det.h:121
-  const float scale[3] = {1 / 0.229f, 1 / 0.224f, 1 / 0.225f};        // ocr_det.h:122
-  const auto lut = make_norm_lut(mean, scale);
+  const auto lut = stage_norm_lut(NormStage::Det);
   if (!lut_.ensure(lut.size(), err)) return false;
   if (g_memcpy(lut_.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { err = "lut upload failed"; return false; }
   ithresh_ = (int)std::floor(cfg.thresh * 255);  // cv::threshold on 8U floors the threshold (ocr_det.cpp:151-154)
@@ -454,8 +461,7 @@ bool RecStage::create(const RecConfig& cfg, std::string& err, int& code) {
   code = OCR_ERR_DEVICE;
   if (g_stream_create(&stream_) != hipSuccess) { err = "hipStreamCreate failed"; return false; }
   if (!timer_.init(err)) return false;
-  const float mean[3] = {0.5f, 0.5f, 0.5f}, scale[3] = {1 / 0.5f, 1 / 0.5f, 1 / 0.5f};  // ocr_rec.h:108-109
-  const auto lut = make_norm_lut(mean, scale);
+  const auto lut = stage_norm_lut(NormStage::Rec);
   if (!lut_.ensure(lut.size(), err)) return false;
   if (g_memcpy(lut_.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { err = "lut upload failed"; return false; }
   code = OCR_OK;
@@ -815,8 +821,7 @@ bool ClsStage::create(const ClsConfig& cfg, std::string& err, int& code) {
   code = OCR_ERR_DEVICE;
   if (g_stream_create(&stream_) != hipSuccess) { err = "hipStreamCreate failed"; return false; }
   if (!timer_.init(err)) return false;
-  const float mean[3] = {0.5f, 0.5f, 0.5f}, scale[3] = {1 / 0.5f, 1 / 0.5f, 1 / 0.5f};  // ocr_cls.h:93-94
-  const auto lut = make_norm_lut(mean, scale);
+  const auto lut = stage_norm_lut(NormStage::Cls);
   if (!lut_.ensure(lut.size(), err)) return false;
   if (g_memcpy(lut_.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { err = "lut upload failed"; return false; }
   code = OCR_OK;

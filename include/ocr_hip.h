@@ -709,6 +709,32 @@ int ocr_selftest_lds_memo(void);
 int ocr_selftest_unclip(const int32_t* quads, const double* deltas, int n, int64_t* out, int cap, int* counts, double* trig);
 int ocr_selftest_unclip_box(const float* boxes, float unclip_ratio, int n, float* out14, int* status);
 
+/* The resize-and-normalise launches of csrc/kernels_pre.hip alone (tests/test_gpu_pre_ops.py), each with the named stage's own
+ * normalisation table.  Every output buffer is pre-filled on the device with the byte OCR_SELFTEST_FILL and comes back with
+ * OCR_SELFTEST_GUARD more bytes than the launch may write, taken from device memory right behind its last element: what no
+ * descriptor names, guard included, must still hold the fill.  Arguments the launchers do not define are refused with
+ * OCR_ERR_ARG before anything reaches the device.
+ * ocr_selftest_det_pre: launch_det_pre (detector table) on the device copy of buf[buf_bytes]; image i starts at byte src_offset +
+ * i * src_image_bytes of that copy (the copy itself is 256-byte aligned, so src_offset % 4 is the alignment of the first
+ * image), rows src_stride apart.  out: N*dh*dw*3 floats + guard, resized: N*dh*dw*3 bytes + guard.
+ * ocr_selftest_line_pre: launch_line_pre on ROIs of one parent image (rows x cols BGR, rows stride apart, rows*stride bytes);
+ * lines: n x 6 int32 (x, y, w, h, resize_w, slot), slots distinct and < nslots; pad_mode OCR_PAD_REC (byte 0 before
+ * normalising) | OCR_PAD_CLS (0.0f after); stage OCR_STAGE_REC | OCR_STAGE_CLS.  out: nslots*imgH*imgW*3 floats + guard.
+ * ocr_selftest_line_pre_ragged: launch_line_pre_ragged (the recognizer's pad); lines: n x 6 int32 (x, y, w, h, resize_w,
+ * tensor_w), line i at pixel imgH * (tensor widths before it).  out: imgH * sum(tensor_w) * 3 floats + guard. */
+#define OCR_SELFTEST_FILL 0xA5
+#define OCR_SELFTEST_GUARD 256
+#define OCR_PAD_REC 0
+#define OCR_PAD_CLS 1
+#define OCR_STAGE_REC 1
+#define OCR_STAGE_CLS 2
+int ocr_selftest_det_pre(const uint8_t* buf, size_t buf_bytes, size_t src_offset, size_t src_stride, size_t src_image_bytes, int N,
+                         int sh, int sw, int dh, int dw, float* out, uint8_t* resized);
+int ocr_selftest_line_pre(const uint8_t* img, int rows, int cols, size_t stride, const int32_t* lines, int n, int imgH, int imgW,
+                          int nslots, int pad_mode, int stage, float* out);
+int ocr_selftest_line_pre_ragged(const uint8_t* img, int rows, int cols, size_t stride, const int32_t* lines, int n, int imgH,
+                                 int stage, float* out);
+
 /* numerics probe (tests): out[8*n] = a/b, sqrt|a|, ocr_expf(a), fma(a,b,a), a*b+a, rint(a*log2e), hswish(a), hswish(b) */
 int ocr_probe(const float* a, const float* b, float* out, int n);
 

@@ -1,10 +1,15 @@
 """Properties and cross-checks of the oracle's OpenCV-semantics restatements (no OpenCV exists in
 the container: these pin internal consistency, not OpenCV itself — see oracle/oracle_post.cpp header)."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
 from hypothesis import given, settings, strategies as st
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bilinear_exact import fixed_against_exact  # noqa: E402
 
 
 def _contours(O, bm):
@@ -226,7 +231,6 @@ def test_fixed_point_resize_against_exact_rational_bilinear(built):
     interpolation itself in exact rational arithmetic.  The fixed-point result must be within 1 of the exactly
     rounded value everywhere and equal to it at more than 4 of 5 positions; plus a plain-Python big-int restatement of the
     fixed-point formula (written from the formula, not from the oracle's C) that must match bit for bit."""
-    from fractions import Fraction
     import oracle as O
     rs = np.random.RandomState(3)
     for (sh, sw, dh, dw) in [(9, 13, 17, 31), (20, 24, 11, 7), (6, 40, 48, 57), (31, 5, 12, 23), (8, 8, 9, 8)]:
@@ -234,42 +238,5 @@ def test_fixed_point_resize_against_exact_rational_bilinear(built):
         got = O.resize_u8c3(img, dh, dw)
         if dh * 2 == sh and dw * 2 == sw:
             continue
-        sx_, sy_ = 1.0 / (np.float64(dw) / sw), 1.0 / (np.float64(dh) / sh)   # resize.cpp: scale = 1 / inv_scale
-
-        def coords(n_dst, n_src, scale, clamp):
-            # x: positions left of the first / right of the last pixel centre take that pixel alone (weight 0 on the
-            # neighbour); y: the fraction is kept and the two ROWS are clipped instead (resize.cpp, resizeGeneric_)
-            out = []
-            for d in range(n_dst):
-                f = np.float32((d + 0.5) * scale - 0.5)
-                s = int(np.floor(f))
-                f = np.float32(f - np.float32(s))
-                if clamp and s < 0:
-                    s, f = 0, np.float32(0)
-                if clamp and s >= n_src - 1:
-                    s, f = n_src - 1, np.float32(0)
-                out.append((s, f))
-            return out
-        cx, cy = coords(dw, sw, sx_, True), coords(dh, sh, sy_, False)
-        sat = lambda v: int(max(-32768, min(32767, int(np.rint(np.float32(v))))))
-        worst, exact_hits, total = 0, 0, 0
-        for y, (sy, fy) in enumerate(cy):
-            for x, (sx, fx) in enumerate(cx):
-                x1 = min(sx + 1, sw - 1)
-                y0, y1 = min(max(sy, 0), sh - 1), min(max(sy + 1, 0), sh - 1)
-                a0, a1 = sat((np.float32(1) - fx) * np.float32(2048)), sat(fx * np.float32(2048))
-                b0, b1 = sat((np.float32(1) - fy) * np.float32(2048)), sat(fy * np.float32(2048))
-                for c in range(3):
-                    p00, p01, p10, p11 = (int(img[y0, sx, c]), int(img[y0, x1, c]), int(img[y1, sx, c]), int(img[y1, x1, c]))
-                    # plain big-int restatement of the fixed-point formula
-                    r0, r1 = p00 * a0 + p01 * a1, p10 * a0 + p11 * a1
-                    v = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2
-                    assert got[y, x, c] == max(0, min(255, v))
-                    # exact rational bilinear at the same float32 sample offsets
-                    FX, FY = Fraction(float(fx)), Fraction(float(fy))
-                    e = (p00 * (1 - FX) + p01 * FX) * (1 - FY) + (p10 * (1 - FX) + p11 * FX) * FY
-                    r = int(e + Fraction(1, 2))
-                    worst = max(worst, abs(int(got[y, x, c]) - r))
-                    exact_hits += int(got[y, x, c]) == r
-                    total += 1
+        worst, exact_hits, total = fixed_against_exact(img, got, dh, dw)   # (asserts the big-int restatement bit for bit)
         assert worst <= 1 and exact_hits / total > 0.8, (worst, exact_hits / total)
