@@ -657,6 +657,7 @@ EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_
             "ocr_webp_decode", "ocr_webp_time", "ocr_webp_time_batch", "ocr_vp8_decode", "ocr_vp8_time", "ocr_vp8_time_batch", "ocr_j2k_decode", "ocr_j2k_time", "ocr_j2k_time_batch",
             "ocr_j2k_tier1", "ocr_j2k_decode_coded", "ocr_j2k_time_coded", "ocr_j2k_time_coded_batch",
             "ocr_tiff_expand", "ocr_tiff_decode_coded", "ocr_tiff_time_coded", "ocr_tiff_time_coded_batch",
+            "ocr_tiff_inflate", "ocr_tiff_decode_deflate", "ocr_tiff_time_deflate", "ocr_tiff_time_deflate_batch",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_dev_copy_time", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
@@ -785,6 +786,7 @@ class ocr_coded_frame(C.Structure):
 
 
 FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP, FRAME_VP8, FRAME_J2K, FRAME_J2K_CODED, FRAME_TIFF_CODED = 0, 1, 2, 3, 4, 5, 6, 7, 8
+FRAME_TIFF_DEFLATE = 9
 
 
 class TiffFrame:
@@ -893,6 +895,31 @@ class TiffCoded:
         """ocr_tiff_time_coded: [upload, expansion, pixel stage] in ms"""
         return time_tiff_coded([self], iters, device_id, single=True)
 
+    # the Deflate route (compression 8 or 32946)
+    def inflate(self, device_id=0, fill=0):
+        """ocr_tiff_inflate: (the chunks as tiff::parse fills Frame::data, the bytes each chunk's stream gave); OcrError where
+        the call refuses (err.out: the buffer as the call left it, pre-filled with `fill`)"""
+        L = lib()
+        L.ocr_tiff_inflate.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        n = self.nominal()
+        out = np.full(n if 0 < n <= 1 << 30 else 1, fill, np.uint8)
+        produced = np.zeros(max(1, len(self.chunks)), np.uint32)
+        rc = L.ocr_tiff_inflate(C.byref(self.c), device_id, out.ctypes.data, out.size, produced.ctypes.data)
+        if rc != 0:
+            _raise_tiff(L, rc, out)
+        return out, produced[:len(self.chunks)]
+
+    def decode_deflate(self, device_id=0, fill=0):
+        """ocr_tiff_decode_deflate: the (height, width, 3) BGR image; OcrError where the call refuses (err.out as for decode)"""
+        L = lib()
+        L.ocr_tiff_decode_deflate.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_void_p, C.c_size_t]
+        h, w = self.c.frame.height, self.c.frame.width
+        out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), fill, np.uint8)
+        rc = L.ocr_tiff_decode_deflate(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            _raise_tiff(L, rc, out)
+        return out
+
 
 def tiff_expand(coded, device_id=0):
     """ocr_tiff_expand of a TiffCoded"""
@@ -916,6 +943,33 @@ def time_tiff_coded(coded, iters=3, device_id=0, single=False):
         L.ocr_tiff_time_coded_batch.argtypes = [C.POINTER(C.POINTER(ocr_tiff_coded)), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
         ptrs = (C.POINTER(ocr_tiff_coded) * len(coded))(*[C.pointer(k.c) for k in coded])
         rc = L.ocr_tiff_time_coded_batch(ptrs, len(coded), device_id, iters, ms)
+    if rc != 0:
+        _raise_tiff(L, rc, None)
+    return list(ms)
+
+
+def tiff_inflate(coded, device_id=0):
+    """ocr_tiff_inflate of a TiffCoded with a Deflate compression: (chunks, produced)"""
+    return coded.inflate(device_id)
+
+
+def tiff_decode_deflate(coded, device_id=0):
+    """ocr_tiff_decode_deflate of a TiffCoded with a Deflate compression"""
+    return coded.decode_deflate(device_id)
+
+
+def time_tiff_deflate(coded, iters=3, device_id=0, single=False):
+    """ocr_tiff_time_deflate_batch over TiffCoded objects as one batch (single: ocr_tiff_time_deflate of the first):
+    [upload, inflate with its read-back, pixel stage] in ms"""
+    L = lib()
+    ms = (C.c_double * 3)()
+    if single:
+        L.ocr_tiff_time_deflate.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_int, C.POINTER(C.c_double)]
+        rc = L.ocr_tiff_time_deflate(C.byref(coded[0].c), device_id, iters, ms)
+    else:
+        L.ocr_tiff_time_deflate_batch.argtypes = [C.POINTER(C.POINTER(ocr_tiff_coded)), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        ptrs = (C.POINTER(ocr_tiff_coded) * len(coded))(*[C.pointer(k.c) for k in coded])
+        rc = L.ocr_tiff_time_deflate_batch(ptrs, len(coded), device_id, iters, ms)
     if rc != 0:
         _raise_tiff(L, rc, None)
     return list(ms)

@@ -71,6 +71,21 @@ const char* tiff_coded_fault_of(const ocr_tiff_coded& c, TiffGeometry& g) {
   return nullptr;
 }
 
+// host/tiff_decode.h deflate_fault_of(): fault(), the records, the device bounds; no stream is looked at
+const char* tiff_deflate_fault_of(const ocr_tiff_coded& c, TiffGeometry& g) {
+  const ocr_tiff_frame& f = c.frame;
+  if (f.data) return "tiff coded: a coded frame carries no expanded chunks";
+  if (const char* why = tiff_fault(f, g, false)) return why;
+  tiff::Frame h;
+  h.width = f.width; h.height = f.height; h.photometric = f.photometric; h.bits = f.bits_per_sample; h.samples = f.samples_per_pixel;
+  h.planar = f.planar; h.predictor = f.predictor; h.big_endian = f.big_endian; h.premultiply = f.premultiply;
+  h.tile_width = f.tile_width; h.tile_height = f.tile_height;
+  tiff::Geometry hg;
+  if (const char* why = tiff::deflate_fault_of(h, c.compression, (const tiff::Chunk*)c.chunks, c.chunks_len, c.bytes, c.bytes_len, hg)) return why;
+  if (c.chunks_len > tiff::kMaxDeviceChunks || g.total > tiff::kMaxDeviceBytes) return "tiff coded: beyond the device bounds (2^20 chunks, 512 MiB at their nominal size)";
+  return nullptr;
+}
+
 int kind_of(const ocr_tiff_frame& f) { return f.bits_per_sample < 8 ? 0 : f.bits_per_sample == 8 ? 1 : 2; }
 
 // The descriptors of validated frames ordered by the kernel that takes them, the units of a kind numbered through its
@@ -213,6 +228,91 @@ int tiff_coded_decode_async(const ocr_tiff_coded* const* imgs, int count, uint8_
   return OCR_OK;
 }
 
+const char* tiff_deflate_fault(const ocr_tiff_coded& c) {
+  TiffGeometry g;
+  return tiff_deflate_fault_of(c, g);
+}
+
+int tiff_inflate_relaunch(TiffScratch& sc, const TiffLaunch& L, hipStream_t s) {
+  launch_inflate(L.streams, L.nstreams, L.pool, sc.data.p, sc.produced.p, s);
+  if (hipGetLastError() != hipSuccess) return OCR_ERR_DEVICE;
+  if (L.nstreams && hipMemcpyAsync(sc.counts.p, sc.produced.p, (size_t)L.nstreams * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return OCR_ERR_DEVICE;
+  return hipStreamSynchronize(s) == hipSuccess ? OCR_OK : OCR_ERR_DEVICE;
+}
+
+int tiff_deflate_decode_async(const ocr_tiff_coded* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
+                              TiffLaunch* launched, bool pixels, uint32_t* const* produced, const int* ids) {
+  std::vector<size_t> off((size_t)count), pool_at((size_t)count);
+  std::vector<TiffGeometry> geo((size_t)count);
+  std::vector<const ocr_tiff_frame*> frames((size_t)count);
+  size_t bytes = 0, nchunks = 0, pool = 0;
+  TiffLaunch L;
+  for (int i = 0; i < count; ++i) {
+    if (!imgs[i]) { err = "null tiff frame"; return OCR_ERR_ARG; }
+    if (const char* fault = tiff_deflate_fault_of(*imgs[i], geo[i])) { err = fault; return OCR_ERR_ARG; }
+    frames[i] = &imgs[i]->frame;
+    off[i] = bytes;
+    pool_at[i] = pool;
+    bytes += pad256(geo[i].total);
+    nchunks += imgs[i]->chunks_len;
+    pool += imgs[i]->bytes_len;
+  }
+  if (nchunks > 0x7fffffffu) { err = "tiff batch: more chunks than a launch has workgroups"; return OCR_ERR_ARG; }
+  // the batch's streams, the long ones first, so that they do not form the tail; whose[k]: the frame and chunk of record k
+  struct Whose { int frame; uint32_t chunk; };
+  std::vector<uint32_t> order;
+  std::vector<InflateDesc> sd;
+  std::vector<Whose> whose;
+  order.reserve(nchunks); sd.reserve(nchunks); whose.reserve(nchunks);
+  for (int i = 0; i < count; ++i) {
+    const ocr_tiff_coded& c = *imgs[i];
+    for (size_t k = 0; k < c.chunks_len; ++k) {
+      order.push_back((uint32_t)sd.size());
+      sd.push_back(InflateDesc{pool_at[i] + c.chunks[k].byte_off, off[i] + k * geo[i].chunk_bytes, c.chunks[k].byte_len,
+                               (uint32_t)(c.chunks[k].rows * geo[i].row_bytes), (uint32_t)geo[i].chunk_bytes});
+      whose.push_back(Whose{i, (uint32_t)k});
+    }
+  }
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return sd[a].byte_len > sd[b].byte_len; });
+  std::vector<InflateDesc> sorted(sd.size());
+  for (size_t k = 0; k < order.size(); ++k) sorted[k] = sd[order[k]];
+  L.nstreams = (uint32_t)sorted.size();
+  const size_t at_pool = pad256(sorted.size() * sizeof(InflateDesc)), coded_bytes = at_pool + pad256(pool);
+  L.bytes = coded_bytes;
+  if (!sc.data.ensure(bytes + 256, err) || !sc.coded.ensure(coded_bytes + 256, err) || !sc.id.ensure((size_t)count, err) || !sc.produced.ensure(sorted.size() + 1, err)) return OCR_ERR_DEVICE;
+  if (!sc.stage.reserve(coded_bytes, err) || !sc.counts.reserve((sorted.size() + 1) * 4, err)) return OCR_ERR_DEVICE;
+  if (!sorted.empty()) memcpy(sc.stage.p, sorted.data(), sorted.size() * sizeof(InflateDesc));
+  parallel_copy((size_t)count, pool, [&](size_t i) { if (imgs[i]->bytes_len) memcpy(sc.stage.p + at_pool + pool_at[i], imgs[i]->bytes, imgs[i]->bytes_len); });
+  L.streams = (const InflateDesc*)sc.coded.p;
+  L.pool = sc.coded.p + at_pool;
+  const std::vector<TiffImageDesc> id = describe(frames.data(), count, geo, off, dst, sc.data.p, L);
+  if (!sc.stage.upload(sc.coded.p, coded_bytes, s, err) ||
+      hipMemcpyAsync(sc.id.p, id.data(), id.size() * sizeof(TiffImageDesc), hipMemcpyHostToDevice, s) != hipSuccess) {
+    err = "tiff deflate chunks upload failed";
+    return OCR_ERR_DEVICE;
+  }
+  if (tiff_inflate_relaunch(sc, L, s) != OCR_OK) { err = "tiff inflate kernel failed"; return OCR_ERR_DEVICE; }
+  for (size_t k = 0; k < order.size(); ++k) {
+    const Whose w = whose[order[k]];
+    if (produced && produced[w.frame]) produced[w.frame][w.chunk] = sc.produced_host()[k];
+  }
+  if (pixels) {
+    // the first chunk, in the order of the batch, whose stream fell short
+    size_t bad = sd.size();
+    for (size_t k = 0; k < order.size(); ++k)
+      if (sc.produced_host()[k] != sorted[k].need && order[k] < bad) bad = order[k];
+    if (bad < sd.size()) {
+      const Whose w = whose[bad];
+      err = "deflate: a chunk's stream does not hold the bytes its rows need (frame " + std::to_string(ids ? ids[w.frame] : w.frame) + ", chunk " + std::to_string(w.chunk) + ")";
+      return OCR_ERR_ARG;
+    }
+    tiff_relaunch(sc, L, s);
+    if (hipGetLastError() != hipSuccess) { err = "tiff pixel kernels failed to launch"; return OCR_ERR_DEVICE; }
+  }
+  if (launched) *launched = L;
+  return OCR_OK;
+}
+
 }  // namespace ocr
 
 using namespace ocr;
@@ -270,7 +370,72 @@ int time_coded_batch(const ocr_tiff_coded* const* coded, int count, int device_i
   return rc;
 }
 
+// the Deflate route: upload, the inflate launch with its read-back, pixel stage
+int time_deflate_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
+  for (int i = 0; i < count; ++i) {
+    if (!coded[i]) return fail(OCR_ERR_ARG, "null argument");
+    if (const char* fault = tiff_deflate_fault(*coded[i])) return fail(OCR_ERR_ARG, fault);
+  }
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  std::vector<DevBuf<uint8_t>> out((size_t)count);
+  std::vector<uint8_t*> dst((size_t)count);
+  std::string err;
+  for (int i = 0; i < count; ++i) {
+    if (!out[i].ensure((size_t)coded[i]->frame.width * coded[i]->frame.height * 3, err)) return fail(OCR_ERR_DEVICE, err);
+    dst[i] = out[i].p;
+  }
+  TiffScratch sc;
+  TiffLaunch L;
+  rc = tiff_deflate_decode_async(coded, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
+  if (rc) return fail(rc, err);
+  double t[2];
+  rc = time_phases(iters, t, [&] { return hipMemcpyAsync(sc.coded.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
+                   [&] { return tiff_inflate_relaunch(sc, L, nullptr) == OCR_OK ? hipSuccess : hipErrorUnknown; });
+  if (rc) return rc;
+  ms[0] = t[0]; ms[1] = t[1];
+  rc = time_phases(iters, t, [&] { tiff_relaunch(sc, L, nullptr); return hipGetLastError(); }, [] { return hipSuccess; });
+  ms[2] = t[0];
+  return rc;
+}
+
 }  // namespace
+
+extern "C" int ocr_tiff_inflate(const ocr_tiff_coded* coded, int device_id, uint8_t* out, size_t cap, uint32_t* produced) {
+  if (!coded || !out) return fail(OCR_ERR_ARG, "null argument");
+  TiffGeometry g;
+  if (const char* fault = tiff_deflate_fault_of(*coded, g)) return fail(OCR_ERR_ARG, fault);
+  if (g.total > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  TiffScratch sc;
+  std::string err;
+  rc = tiff_deflate_decode_async(&coded, 1, nullptr, sc, nullptr, err, nullptr, false, produced ? &produced : nullptr);
+  if (rc) return fail(rc, err);
+  CAPI_HIP(g_memcpy(out, sc.data.p, g.total, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
+extern "C" int ocr_tiff_decode_deflate(const ocr_tiff_coded* coded, int device_id, uint8_t* bgr, size_t cap) {
+  if (!coded || !bgr) return fail(OCR_ERR_ARG, "null argument");
+  if (const char* fault = tiff_deflate_fault(*coded)) return fail(OCR_ERR_ARG, fault);
+  const size_t bytes = (size_t)coded->frame.width * coded->frame.height * 3;
+  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  TiffScratch sc;
+  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return tiff_deflate_decode_async(&coded, 1, dst, sc, nullptr, err); });
+}
+
+extern "C" int ocr_tiff_time_deflate(const ocr_tiff_coded* coded, int device_id, int iters, double ms[3]) {
+  if (!coded || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
+  return time_deflate_batch(&coded, 1, device_id, iters, ms);
+}
+
+extern "C" int ocr_tiff_time_deflate_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
+  if (!coded || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
+  return time_deflate_batch(coded, count, device_id, iters, ms);
+}
 
 extern "C" int ocr_tiff_expand(const ocr_tiff_coded* coded, int device_id, uint8_t* out, size_t cap) {
   if (!coded || !out) return fail(OCR_ERR_ARG, "null argument");

@@ -1,0 +1,25 @@
+// Host-visible launch interface of kernels_inflate.hip: zlib streams (RFC 1950 around RFC 1951) inflated on the device, one
+// stream per wavefront.  Nothing here knows what the bytes are for: a TIFF's Deflate chunks today (capi_tiff.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace ocr {
+
+constexpr int kInflateWave = 64;  // a stream belongs to one wavefront, and a workgroup is one wavefront
+
+struct InflateDesc {   // a stream of the batch; nobody has looked at its bytes
+  uint64_t src;        // into the batch's byte pool
+  uint64_t dst;        // into the batch's output
+  uint32_t byte_len;   // coded bytes
+  uint32_t need;       // the bytes the stream must give: what is asked of it, and no more is written
+  uint32_t nominal;    // >= need: what is written, zeros behind what the stream gave
+};
+
+// One workgroup a stream, in the order of the list.  Reads pool[src .. src + byte_len) and writes out[dst .. dst + nominal) and
+// produced[i] per stream and nothing else, whatever the bytes are.  produced[i]: the bytes that came out before the first fault,
+// the end of the final block or the end of the input, cut at min(need, nominal); the stream is good where that equals `need`
+// (the rule of tiff::detail::inflate, host/tiff_decode.h: the checksum behind the final block is not read).
+void launch_inflate(const InflateDesc* streams, uint32_t count, const uint8_t* pool, uint8_t* out, uint32_t* produced, hipStream_t s);
+
+}  // namespace ocr

@@ -433,7 +433,7 @@ struct ocr_pipe {
   JpegScratch jpeg;
   PngScratch png;
   RawScratch raw;
-  TiffScratch tiff, tiff_coded;  // expanded frames and coded ones are two batches: their uploads differ
+  TiffScratch tiff, tiff_coded, tiff_deflate;  // expanded frames, coded ones and Deflate ones are three batches: their uploads differ
   WebpScratch webp;
   Vp8Scratch vp8;
   J2kScratch j2k, j2k_coded;  // coefficient-form frames and coded ones are two batches: their uploads differ
@@ -525,7 +525,7 @@ struct ocr_pipe {
         case OCR_FRAME_JPEG: r = jpeg_out_rows(*jp(i)); c = jpeg_out_cols(*jp(i)); break;
         case OCR_FRAME_PNG: r = pn(i)->height; c = pn(i)->width; break;
         case OCR_FRAME_RAW: r = rw(i)->height; c = rw(i)->width; break;
-        case OCR_FRAME_TIFF: case OCR_FRAME_TIFF_CODED: r = tf(i)->height; c = tf(i)->width; break;  // (an ocr_tiff_coded starts with its ocr_tiff_frame)
+        case OCR_FRAME_TIFF: case OCR_FRAME_TIFF_CODED: case OCR_FRAME_TIFF_DEFLATE: r = tf(i)->height; c = tf(i)->width; break;  // (an ocr_tiff_coded starts with its ocr_tiff_frame)
         case OCR_FRAME_WEBP: r = wf(i)->height; c = wf(i)->width; break;
         case OCR_FRAME_VP8: r = vf(i)->height; c = vf(i)->width; break;
         default: r = kf(i)->height; c = kf(i)->width; break;  // (an ocr_j2k_coded starts with its ocr_j2k_frame)
@@ -540,7 +540,9 @@ struct ocr_pipe {
     std::vector<const ocr_vp8_frame*> vff;
     std::vector<const ocr_j2k_frame*> kff;
     std::vector<const ocr_j2k_coded*> kcf;
-    std::vector<const ocr_tiff_coded*> tcf;
+    std::vector<const ocr_tiff_coded*> tcf, tdf;
+    std::vector<uint8_t*> tddst;
+    std::vector<int> tdid;  // a Deflate frame's place in the batch: what a refusal names
     std::vector<uint8_t*> jdst, pdst, rdst, tdst, wdst, vdst, kdst, kcdst, tcdst;
     for (int k = 0; k < count; ++k) {
       const int i = S.imgs[k].orig;
@@ -554,10 +556,13 @@ struct ocr_pipe {
         case OCR_FRAME_VP8: vff.push_back(vf(i)); vdst.push_back(d); break;
         case OCR_FRAME_J2K_CODED: kcf.push_back((const ocr_j2k_coded*)frames[i].frame); kcdst.push_back(d); break;
         case OCR_FRAME_TIFF_CODED: tcf.push_back((const ocr_tiff_coded*)frames[i].frame); tcdst.push_back(d); break;
+        case OCR_FRAME_TIFF_DEFLATE: tdf.push_back((const ocr_tiff_coded*)frames[i].frame); tddst.push_back(d); tdid.push_back(i); break;
         default: kff.push_back(kf(i)); kdst.push_back(d); break;
       }
     }
-    if (!jf.empty()) rc = jpeg_decode_async(jf.data(), (int)jf.size(), jdst.data(), jpeg, copy_stream, err);
+    // (Deflate frames first: theirs is the one route that can refuse a stream, and it does so before anything else is enqueued)
+    if (!tdf.empty()) rc = tiff_deflate_decode_async(tdf.data(), (int)tdf.size(), tddst.data(), tiff_deflate, copy_stream, err, nullptr, true, nullptr, tdid.data());
+    if (!rc && !jf.empty()) rc = jpeg_decode_async(jf.data(), (int)jf.size(), jdst.data(), jpeg, copy_stream, err);
     if (!rc && !pf.empty()) rc = png_decode_async(pf.data(), (int)pf.size(), pdst.data(), png, copy_stream, err);
     if (!rc && !rf.empty()) rc = raw_decode_async(rf.data(), (int)rf.size(), rdst.data(), raw, copy_stream, err);
     if (!rc && !tff.empty()) rc = tiff_decode_async(tff.data(), (int)tff.size(), tdst.data(), tiff, copy_stream, err);
@@ -913,6 +918,7 @@ int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, i
       case OCR_FRAME_J2K: fault = j2k_frame_fault(*(const ocr_j2k_frame*)f); break;
       case OCR_FRAME_J2K_CODED: fault = j2k_coded_fault(*(const ocr_j2k_coded*)f); break;
       case OCR_FRAME_TIFF_CODED: fault = tiff_coded_fault(*(const ocr_tiff_coded*)f); break;
+      case OCR_FRAME_TIFF_DEFLATE: fault = tiff_deflate_fault(*(const ocr_tiff_coded*)f); break;
       default: fault = "frame kind is not an ocr_frame_kind"; break;
     }
     if (fault) return fail(OCR_ERR_ARG, fault);

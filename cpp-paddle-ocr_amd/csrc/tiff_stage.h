@@ -5,6 +5,7 @@
 
 #include "image_stage.h"
 #include "kernels_tiff.h"
+#include "kernels_inflate.h"
 #include "kernels_tiff_lzw.h"
 
 namespace ocr {
@@ -14,6 +15,9 @@ struct TiffScratch {
   DevBuf<TiffImageDesc> id;
   PinnedStage stage;  // of the expanded chunks; a coded batch: of its chunk records and their bytes
   DevBuf<uint8_t> coded;  // a coded batch: the chunk records, then the byte pool (data is then filled by the expansion)
+  DevBuf<uint32_t> produced;  // a Deflate batch: the bytes each chunk's stream gave, in the order of the records
+  PinnedStage counts;  // the same on the host, pinned: the read-back is then a plain asynchronous copy
+  const uint32_t* produced_host() const { return (const uint32_t*)counts.p; }
 };
 // what a batch launched, for a caller that repeats it (ocr_tiff_time): id[first[k]] .. + count[k] are the frames of kind k
 struct TiffLaunch {
@@ -24,6 +28,9 @@ struct TiffLaunch {
   const TiffChunkDesc* chunks = nullptr;
   uint32_t lzw = 0, runs = 0;
   const uint8_t* pool = nullptr;
+  // a Deflate batch: the streams the inflate launch goes over (device), instead of chunks / lzw / runs
+  const InflateDesc* streams = nullptr;
+  uint32_t nstreams = 0;
 };
 // why a frame is refused, nullptr when it is sound: a kernel only ever sees descriptors that passed
 const char* tiff_frame_fault(const ocr_tiff_frame& f);
@@ -39,5 +46,18 @@ const char* tiff_coded_fault(const ocr_tiff_coded& c);
 int tiff_coded_decode_async(const ocr_tiff_coded* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
                             TiffLaunch* launched = nullptr, bool pixels = true);
 void tiff_expand_relaunch(const TiffScratch& sc, const TiffLaunch& L, hipStream_t s);
+// Deflate frames (ocr_tiff_coded with compression 8 or 32946).  tiff_deflate_fault checks the frame and the chunk records - the
+// rules of a coded frame with that compression set and the same device bounds - and looks at no stream: the inflate kernel gives
+// a verdict per chunk.  tiff_deflate_decode_async, all on `s`: uploads the records and the pool, runs the inflate launch into
+// sc.data, copies the per-chunk counts back and WAITS for that copy (4 bytes a chunk: the one host round trip of this route),
+// and launches the pixel kernels only where every chunk gave the bytes its rows need; otherwise OCR_ERR_ARG "deflate: a
+// chunk's stream does not hold the bytes its rows need (frame F, chunk C)" - F is ids[i] where ids is given, else i - and no
+// pixel kernel is launched for the batch.  `pixels` false: the inflate launch and the read-back alone, no refusal; produced:
+// count pointers (or null), each to chunks_len words in the frame's chunk order.
+const char* tiff_deflate_fault(const ocr_tiff_coded& c);
+int tiff_deflate_decode_async(const ocr_tiff_coded* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
+                              TiffLaunch* launched = nullptr, bool pixels = true, uint32_t* const* produced = nullptr, const int* ids = nullptr);
+// the inflate launch and its read-back again (ocr_tiff_time_deflate)
+int tiff_inflate_relaunch(TiffScratch& sc, const TiffLaunch& L, hipStream_t s);  // (after a tiff_deflate_decode_async of the batch)
 
 }  // namespace ocr

@@ -29,6 +29,10 @@
 // the switch says; --time measures both routes in one run: "coded_upload_ms", "expand_stage_ms", "coded_pixel_stage_ms"
 // (ocr_tiff_time_coded / _batch), "coded_bytes", "host_scan_ms_per_image" (tiff::coded_fault: the extent scans, which both
 // routes pay) and "host_expand_ms_per_image" (tiff::expand on one host thread, which the coded route saves).
+// A Deflate TIFF goes coded under OCR_DEVICE_TIFF=3 (--device / --frame / --stage: ocr_tiff_decode_deflate,
+// OCR_FRAME_TIFF_DEFLATE) and by --stage for "coded:<file>"; --time on such a file adds "coded_upload_ms", "inflate_stage_ms"
+// (the inflate launch with the read-back of its counts), "coded_pixel_stage_ms" (ocr_tiff_time_deflate / _batch) and
+// "host_inflate_ms_per_image" (tiff::inflate_all: zlib on one host thread).
 // --time <iters> <tiff file> [<batch>]: ocr_tiff_time / ocr_tiff_time_batch (upload of the expanded
 // chunks, pixel stage), "host_pixels_ms" (tiff::pixels on one host thread), "bytes_in" / "bytes_out" (what the kernel reads and
 // writes) and "copy_ms": a plain copy kernel that reads and writes as many bytes in all (ocr_dev_copy_time), timed in the same run.
@@ -215,6 +219,24 @@ static int time_device(int iters, const char* in, int batch) {
       printf(", \"compression\": %d, \"chunks\": %zu, \"coded_bytes\": %zu, \"coded_upload_ms\": %.5f, \"expand_stage_ms\": %.5f, \"coded_pixel_stage_ms\": %.5f, "
              "\"host_scan_ms_per_image\": %.5f, \"host_expand_ms_per_image\": %.5f",
              c->compression, c->chunks.size(), c->bytes.size(), cms[0], cms[1], cms[2], scan_ms, expand_ms);
+    } else if (PaddleOCR::tiff::parse_deflate(bytes.data(), bytes.size(), *c) && c->frame.device_ok) {
+      // the Deflate route: upload of the coded chunks, the inflate launch with its read-back and the pixel stage on the device,
+      // against tiff::inflate_all - zlib on one thread - per image
+      im.tiff_deflate = c;
+      const ocr_tiff_coded cd = im.tiff_deflate_frame();
+      std::vector<const ocr_tiff_coded*> call(all.size(), &cd);
+      double cms[3];
+      if ((batch > 1 ? ocr_tiff_time_deflate_batch(call.data(), (int)call.size(), 0, iters, cms) : ocr_tiff_time_deflate(&cd, 0, iters, cms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+      const int reps = iters < 3 ? 3 : iters;
+      PaddleOCR::tiff::Frame ef;
+      bool sound = true;
+      const auto t1 = std::chrono::steady_clock::now();
+      for (int i = 0; i < reps; ++i) sound = sound && PaddleOCR::tiff::inflate_all(*c, ef);
+      const double inflate_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() / reps;
+      if (!sound) { fprintf(stderr, "host expansion failed\n"); return 1; }
+      printf(", \"compression\": %d, \"chunks\": %zu, \"coded_bytes\": %zu, \"coded_upload_ms\": %.5f, \"inflate_stage_ms\": %.5f, \"coded_pixel_stage_ms\": %.5f, "
+             "\"host_inflate_ms_per_image\": %.5f",
+             c->compression, c->chunks.size(), c->bytes.size(), cms[0], cms[1], cms[2], inflate_ms);
     }
     printf("}\n");
     return 0;
@@ -327,7 +349,14 @@ static int stage_batches(const std::string& model_dir, int nargs, char** args, b
       if (!b.in[i].compare(0, 6, "coded:")) {  // a JPEG 2000 or TIFF file in the coded form, whatever OCR_DEVICE_J2K / OCR_DEVICE_TIFF say
         if (PaddleOCR::ipc::read_file(b.in[i].substr(6), bytes) && PaddleOCR::ipc::is_tiff(bytes.data(), bytes.size())) {
           auto t = std::make_shared<PaddleOCR::tiff::Coded>();
-          if (PaddleOCR::tiff::parse_coded(bytes.data(), bytes.size(), *t) != PaddleOCR::tiff::kCoded || !t->frame.device_ok) {
+          const PaddleOCR::tiff::Route route = PaddleOCR::tiff::parse_coded(bytes.data(), bytes.size(), *t);
+          if (route == PaddleOCR::tiff::kOtherRoute && PaddleOCR::tiff::parse_deflate(bytes.data(), bytes.size(), *t) && t->frame.device_ok) {  // OCR_FRAME_TIFF_DEFLATE
+            b.ims[i].rows = t->frame.height; b.ims[i].cols = t->frame.width;
+            b.ims[i].tiff_deflate = t;
+            b.frames.add(b.ims[i]);
+            continue;
+          }
+          if (route != PaddleOCR::tiff::kCoded || !t->frame.device_ok) {
             fprintf(stderr, "decode failed: %s\n", b.in[i].c_str());
             return 1;
           }
@@ -384,6 +413,11 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (!PaddleOCR::ipc::read_file(in, bytes) || !PaddleOCR::ipc::decode_image(bytes, im, device, device) || im.empty()) { fprintf(stderr, "decode failed: %s\n", in); return 1; }
+  if (im.device_decodable() && im.tiff_deflate) {
+    const ocr_tiff_coded d = im.tiff_deflate_frame();
+    im.pixels.resize((size_t)d.frame.height * d.frame.width * 3);
+    if (ocr_tiff_decode_deflate(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+  } else
   if (im.device_decodable() && im.tiff_coded) {
     const ocr_tiff_coded d = im.tiff_coded_frame();
     im.pixels.resize((size_t)d.frame.height * d.frame.width * 3);

@@ -221,11 +221,14 @@ inline bool decode_bmp(const std::vector<uint8_t>& d, Image& im, bool device_pix
 // OCR_DEVICE_TIFF, read once: =1 stops after the chunks are expanded and leaves predictor, conversion and placement to the
 // worker (frames within the device stage's bounds, tiff::Frame::device_ok), =2 stops before the expansion already and leaves
 // the chunks' LZW / PackBits streams to the worker as well (tiff::parse_coded, which still scans every stream; Deflate files and
-// frames beyond the bounds go the =1 route), =0 or unset finishes every file on this host thread.
+// frames beyond the bounds go the =1 route), =3 is =2 and hands Deflate files within the bounds over coded too (tiff::parse_deflate, the
+// container alone: the device inflates the chunks and gives the verdict per stream; a batch with a faulty stream is refused at
+// staging and the worker's fallback, one request per image, gives that file the host's refusal through Image::materialise),
+// =0 or unset finishes every file on this host thread.
 constexpr bool TIFF_DEVICE_DEFAULT = false;
-inline int tiff_device_mode() {  // 0 host, 1 expanded chunks to the device, 2 coded chunks to the device
+inline int tiff_device_mode() {  // 0 host, 1 expanded chunks to the device, 2 coded chunks to the device, 3 Deflate chunks too
   static const char* env = getenv("OCR_DEVICE_TIFF");
-  return env && env[0] ? (env[0] == '0' ? 0 : env[0] == '2' && !env[1] ? 2 : 1) : (TIFF_DEVICE_DEFAULT ? 1 : 0);
+  return env && env[0] ? (env[0] == '0' ? 0 : (env[0] == '2' || env[0] == '3') && !env[1] ? env[0] - '0' : 1) : (TIFF_DEVICE_DEFAULT ? 1 : 0);
 }
 inline bool tiff_device_enabled() { return tiff_device_mode() != 0; }
 inline bool is_tiff(const uint8_t* d, size_t n) {
@@ -235,10 +238,21 @@ inline bool decode_tiff(const std::vector<uint8_t>& d, Image& im, bool device_pi
   if (!is_tiff(d.data(), d.size())) return false;
   auto f = std::make_shared<tiff::Frame>();
   bool parsed = false;
-  if (device_pixels && tiff_device_mode() == 2) {
+  if (device_pixels && tiff_device_mode() >= 2) {
     auto c = std::make_shared<tiff::Coded>();
-    const tiff::Route route = tiff::parse_coded(d.data(), d.size(), *c);
+    bool deflate = false;  // =3: the container is read once, whatever the compression
+    const tiff::Route route = tiff_device_mode() == 3 ? tiff::parse_any(d.data(), d.size(), *c, deflate) : tiff::parse_coded(d.data(), d.size(), *c);
     if (route == tiff::kRefused) return false;
+    if (deflate) {
+      if (c->frame.device_ok) {
+        im.pixels.clear();
+        im.rows = c->frame.height; im.cols = c->frame.width;
+        im.tiff_deflate = std::move(c);
+        return true;
+      }
+      if (!tiff::inflate_all(*c, *f)) return false;  // (beyond the device bounds: the =1 route, from the container already read)
+      parsed = true;
+    } else
     if (route == tiff::kCoded) {
       if (c->frame.device_ok) {
         im.pixels.clear();
@@ -509,9 +523,21 @@ class OCRIPCService {
         if (!error_msg.empty()) return ipc::error_reply(error_msg);
         if (!gpu_worker_pool_) return ipc::error_reply("No GPU workers configured (this build has no CPU path)");
         const int request_id = request_counter_.fetch_add(1);
+        // a Deflate TIFF handed over coded (OCR_DEVICE_TIFF=3): nobody has looked at its streams yet
+        const std::shared_ptr<tiff::Coded> deflate = image.tiff_deflate;
         auto request = std::make_shared<OCRRequest>(request_id, std::move(image));
         total_requests_.fetch_add(1);
         std::string result = gpu_worker_pool_->submitRequest(request).get();
+        if (deflate && result.find("\"success\":true") == std::string::npos) {
+          // the worker failed the request.  It has asked the host already where the device refused a stream (processRequest), so
+          // this is about the words alone: a file zlib refuses gets the reply it gets where it fails to decode on this thread
+          // (OCR_DEVICE_TIFF=0), and is not counted as a request either, as there
+          tiff::Frame f;
+          if (!tiff::inflate_all(*deflate, f)) {
+            total_requests_.fetch_sub(1);
+            return ipc::error_reply(!image_path.empty() ? "Failed to load image from path: " + image_path : "Failed to decode base64 image data");
+          }
+        }
         if (result.find("\"success\":true") != std::string::npos) successful_requests_.fetch_add(1);
         const size_t p = result.find("\"processing_time_ms\":");
         if (p != std::string::npos) {

@@ -68,6 +68,12 @@ struct Image {
   // a TIFF whose container alone has been parsed (Compression 1, LZW, PackBits): the worker expands the chunks on the device
   // as well, then goes on as for tiff (ocr_pipe_stage_batch, OCR_FRAME_TIFF_CODED)
   std::shared_ptr<tiff::Coded> tiff_coded;
+  // a Deflate TIFF whose container alone has been parsed (tiff::parse_deflate; no stream has been looked at): the worker
+  // inflates the chunks on the device and refuses the batch where a stream falls short (ocr_pipe_stage_batch,
+  // OCR_FRAME_TIFF_DEFLATE).  materialise() is the host's verdict on the same bytes (tiff::inflate_all) and THROWS where a
+  // stream is faulty - of all kinds this one alone can, the others were checked before they got here - so the worker calls it
+  // per request and fails that request alone; where the device refused, the worker asks it and the host's answer stands
+  std::shared_ptr<tiff::Coded> tiff_deflate;
   // a lossless WebP whose entropy-coded image has been decoded (prefix codes, LZ77, colour cache): the worker undoes the
   // transforms on the device (ocr_pipe_stage_batch)
   std::shared_ptr<webp::Frame> webp;
@@ -88,8 +94,8 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8 && !j2k && !j2k_coded && !tiff_coded; }
-  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8 || j2k || j2k_coded || tiff_coded); }
+  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8 && !j2k && !j2k_coded && !tiff_coded && !tiff_deflate; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8 || j2k || j2k_coded || tiff_coded || tiff_deflate); }
   void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM / TIFF / WebP on the host
     if (!device_decodable()) return;
     if (j2k_coded) {
@@ -111,6 +117,12 @@ struct Image {
     if (webp) {
       if (!webp::pixels(*webp, pixels)) throw std::runtime_error("WebP conversion failed");
       webp.reset();
+      return;
+    }
+    if (tiff_deflate) {
+      tiff::Frame f;
+      if (!tiff::inflate_all(*tiff_deflate, f) || !tiff::pixels(f, pixels)) throw std::runtime_error("TIFF conversion failed");
+      tiff_deflate.reset();
       return;
     }
     if (tiff_coded) {
@@ -157,18 +169,20 @@ struct Image {
     d.data = raw->data.data(); d.data_len = raw->data.size();
     return d;
   }
-  ocr_tiff_coded tiff_coded_frame() const {  // only when tiff_coded
+  ocr_tiff_coded tiff_coded_frame() const { return coded_frame_of(*tiff_coded); }      // only when tiff_coded
+  ocr_tiff_coded tiff_deflate_frame() const { return coded_frame_of(*tiff_deflate); }  // only when tiff_deflate
+  static ocr_tiff_coded coded_frame_of(const tiff::Coded& c) {
     static_assert(sizeof(tiff::Chunk) == sizeof(ocr_tiff_chunk), "tiff::Chunk is ocr_tiff_chunk");
-    const tiff::Frame& f = tiff_coded->frame;
+    const tiff::Frame& f = c.frame;
     ocr_tiff_coded d;
     memset(&d, 0, sizeof d);
     d.frame.width = f.width; d.frame.height = f.height; d.frame.photometric = f.photometric; d.frame.bits_per_sample = f.bits;
     d.frame.samples_per_pixel = f.samples; d.frame.planar = f.planar; d.frame.predictor = f.predictor; d.frame.big_endian = f.big_endian;
     d.frame.premultiply = f.premultiply; d.frame.tile_width = f.tile_width; d.frame.tile_height = f.tile_height;
     memcpy(d.frame.palette, f.palette, sizeof d.frame.palette);
-    d.compression = tiff_coded->compression;
-    d.chunks = (const ocr_tiff_chunk*)tiff_coded->chunks.data(); d.chunks_len = tiff_coded->chunks.size();
-    d.bytes = tiff_coded->bytes.empty() ? nullptr : tiff_coded->bytes.data(); d.bytes_len = tiff_coded->bytes.size();
+    d.compression = c.compression;
+    d.chunks = (const ocr_tiff_chunk*)c.chunks.data(); d.chunks_len = c.chunks.size();
+    d.bytes = c.bytes.empty() ? nullptr : c.bytes.data(); d.bytes_len = c.bytes.size();
     return d;
   }
   ocr_tiff_frame tiff_frame() const {  // only when tiff
@@ -253,13 +267,14 @@ struct DeviceFrames {
   std::deque<ocr_vp8_frame> vf;
   std::deque<ocr_j2k_frame> kf;
   std::deque<ocr_j2k_coded> kcf;
-  std::deque<ocr_tiff_coded> tcf;
+  std::deque<ocr_tiff_coded> tcf, tdf;
   std::vector<ocr_coded_frame> list;
   void add(const Image& im) {  // only when im.device_decodable()
     if (im.j2k_coded) { kcf.push_back(im.j2k_coded_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K_CODED, &kcf.back()}); }
     else if (im.j2k) { kf.push_back(im.j2k_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K, &kf.back()}); }
     else if (im.vp8) { vf.push_back(im.vp8_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_VP8, &vf.back()}); }
     else if (im.webp) { wf.push_back(im.webp_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_WEBP, &wf.back()}); }
+    else if (im.tiff_deflate) { tdf.push_back(im.tiff_deflate_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF_DEFLATE, &tdf.back()}); }
     else if (im.tiff_coded) { tcf.push_back(im.tiff_coded_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF_CODED, &tcf.back()}); }
     else if (im.tiff) { tf.push_back(im.tiff_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF, &tf.back()}); }
     else if (im.raw) { rf.push_back(im.raw_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_RAW, &rf.back()}); }
@@ -648,7 +663,7 @@ class OCRWorker {
     int off = 0, n = 0;
     int rc;
     if (char_boxes_) {
-      const_cast<OCRRequest&>(request).image_data.materialise();
+      if (!materialised(request, result)) return result;
       ocr_img im = request.image_data.view().c();
       rc = ocr_pipe_run_chars(pipe_, &im, 1, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), chars.data(), nullptr);
     } else
@@ -657,6 +672,13 @@ class OCRWorker {
       frames.add(request.image_data);
       rc = frames.stage(pipe_, 0);
       if (rc == OCR_OK) rc = ocr_pipe_run_staged(pipe_, 0, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), nullptr);
+      else if (rc == OCR_ERR_ARG && request.image_data.tiff_deflate) {
+        // the device refused a stream of a Deflate TIFF: the host is right where the two differ, so zlib decides - a file it
+        // refuses too fails here, one it accepts goes on from its pixels
+        if (!materialised(request, result)) return result;
+        ocr_img im = request.image_data.view().c();
+        rc = ocr_pipe_run(pipe_, &im, 1, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), nullptr);
+      }
     } else {
       ocr_img im = request.image_data.view().c();
       rc = ocr_pipe_run(pipe_, &im, 1, words.data(), (int)words.size(), &off, &n, ids.data(), (int)ids.size(), nullptr);
@@ -676,6 +698,18 @@ class OCRWorker {
     result.processing_time_ms =
         std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
     return result;
+  }
+
+  // Image::materialise() for a request; false, with the result's error set, where the host refuses the image (a Deflate TIFF
+  // with a faulty stream, which nobody has looked at before): that request fails, nothing else does
+  static bool materialised(const OCRRequest& request, OCRResult& result) {
+    try {
+      const_cast<OCRRequest&>(request).image_data.materialise();
+      return true;
+    } catch (const std::exception& e) {
+      result.error_message = e.what();
+      return false;
+    }
   }
 
   // The same for several requests in one pipeline run; results[i] belongs to requests[i].  A failure of
@@ -701,7 +735,7 @@ class OCRWorker {
       results[i].height = requests[i]->image_data.rows;
       if (on_device) frames.add(requests[i]->image_data);
       else {
-        const_cast<OCRRequest*>(requests[i])->image_data.materialise();
+        if (!materialised(*requests[i], results[i])) continue;  // (this request fails; the batch goes on without it)
         imgs.push_back(requests[i]->image_data.view().c());
       }
       owner.push_back(i);

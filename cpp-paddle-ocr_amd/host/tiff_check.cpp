@@ -19,6 +19,12 @@
 // tiff_check --why <file> [...]: per file "<file>: ok", "refused" or "other route" (parse_coded's answer).
 // tiff_check --extents <streams> <out>: streams: repeated [u32 compression (5 or 32773), u32 need, u32 length][the bytes];
 //   out: per stream two bytes, the verdict of lzw_extent / packbits_extent and that of unlzw / unpack_bits for the same need.
+// tiff_check --route-deflate <file> <out> [...]: tiff::parse_deflate; out: the Coded in the form of --coded.  Exit status 1 for a
+//   file that is refused or is not a Deflate one.
+// tiff_check --inflate <streams> <out>: streams: repeated [u32 need, u32 length][the bytes]; out: per stream [u8 good][u32
+//   produced][need bytes: what zlib wrote, zeros behind] - tiff::detail::inflate_count, the host's verdict the device's inflate
+//   kernel is held to (and the form of inflate_check).  Prints "<streams> <good>".
+// tiff_check --inflate-all <in> <out>: tiff::inflate_all over Codeds of that form; out and what is printed as --expand.
 #include <dirent.h>
 
 #include <cstdio>
@@ -79,13 +85,17 @@ static int pixels_of_frames(const char* in, const char* outp) {
 
 static const char* const kRouteName[] = {"refused", "ok", "other route"};
 
-static int coded_of_file(const char* in, const char* outp) {
+static int coded_of_file(const char* in, const char* outp, bool deflate = false) {
   std::unique_ptr<uint8_t[]> buf;
   size_t n = 0;
   if (!read_exact(in, buf, n)) { fprintf(stderr, "cannot read %s\n", in); return 2; }
   tiff::Coded c;
-  const tiff::Route route = tiff::parse_coded(buf.get(), n, c);
-  if (route != tiff::kCoded) { fprintf(stderr, "%s: %s\n", kRouteName[route], in); return route == tiff::kRefused ? 1 : 3; }
+  if (deflate) {
+    if (!tiff::parse_deflate(buf.get(), n, c)) { fprintf(stderr, "refused: %s\n", in); return 1; }
+  } else {
+    const tiff::Route route = tiff::parse_coded(buf.get(), n, c);
+    if (route != tiff::kCoded) { fprintf(stderr, "%s: %s\n", kRouteName[route], in); return route == tiff::kRefused ? 1 : 3; }
+  }
   FILE* o = fopen(outp, "wb");
   if (!o) return 2;
   const tiff::Frame& f = c.frame;
@@ -104,7 +114,7 @@ static int coded_of_file(const char* in, const char* outp) {
   return 0;
 }
 
-static int expand_codeds(const char* in, const char* outp) {
+static int expand_codeds(const char* in, const char* outp, bool deflate = false) {
   FILE* f = fopen(in, "rb");
   FILE* o = fopen(outp, "wb");
   if (!f || !o) return 2;
@@ -132,7 +142,7 @@ static int expand_codeds(const char* in, const char* outp) {
     c.bytes.assign(pool.get(), pool.get() + len);
     c.bytes.shrink_to_fit();
     tiff::Frame out;
-    if (!tiff::expand(c, out)) { rc = 1; printf("refused\n"); continue; }
+    if (!(deflate ? tiff::inflate_all(c, out) : tiff::expand(c, out))) { rc = 1; printf("refused\n"); continue; }
     printf("ok\n");
     fwrite(out.data.data(), 1, out.data.size(), o);
   }
@@ -160,6 +170,34 @@ static int extents_of_streams(const char* in, const char* outp) {
   }
   fclose(f);
   fclose(o);
+  return 0;
+}
+
+static int inflate_streams(const char* in, const char* outp) {
+  FILE* f = fopen(in, "rb");
+  FILE* o = fopen(outp, "wb");
+  if (!f || !o) return 2;
+  long streams = 0, good = 0;
+  for (;;) {
+    uint32_t head[2];
+    const size_t got = fread(head, 1, sizeof head, f);
+    if (got == 0) break;
+    if (got != sizeof head || head[0] > (1u << 26) || head[1] > (1u << 26)) return 2;
+    const size_t need = head[0], len = head[1];
+    std::unique_ptr<uint8_t[]> s(new uint8_t[len ? len : 1]), out(new uint8_t[need ? need : 1]);  // exactly their sizes
+    if (fread(s.get(), 1, len, f) != len) return 2;
+    memset(out.get(), 0, need);
+    const uint32_t produced = (uint32_t)tiff::detail::inflate_count(s.get(), len, out.get(), need);
+    const uint8_t ok = produced == need;
+    fwrite(&ok, 1, 1, o);
+    fwrite(&produced, 1, 4, o);
+    fwrite(out.get(), 1, need, o);
+    ++streams;
+    good += ok;
+  }
+  fclose(f);
+  fclose(o);
+  printf("%ld %ld\n", streams, good);
   return 0;
 }
 
@@ -204,6 +242,13 @@ int main(int argc, char** argv) {
     return 0;
   }
   if (mode == "--expand" && argc == 4) return expand_codeds(argv[2], argv[3]);
+  if (mode == "--inflate-all" && argc == 4) return expand_codeds(argv[2], argv[3], true);
+  if (mode == "--inflate" && argc == 4) return inflate_streams(argv[2], argv[3]);
+  if (mode == "--route-deflate" && argc >= 4 && argc % 2 == 0) {
+    for (int i = 2; i < argc; i += 2)
+      if (const int rc = coded_of_file(argv[i], argv[i + 1], true)) return rc;
+    return 0;
+  }
   if (mode == "--extents" && argc == 4) return extents_of_streams(argv[2], argv[3]);
   if (mode == "--why" && argc >= 3) {
     for (int i = 2; i < argc; ++i) {
@@ -229,6 +274,6 @@ int main(int argc, char** argv) {
     return 0;
   }
   fprintf(stderr, "usage: tiff_check --decode <file> <out> [...] | --pixels <descriptors> <out> | --reject <dir> | --chunks <file> <out> [...] | --coded <file> <out> [...] | --expand <codeds> <out> | "
-                  "--why <file> [...] | --extents <streams> <out>\n");
+                  "--why <file> [...] | --extents <streams> <out> | --route-deflate <file> <out> [...] | --inflate <streams> <out> | --inflate-all <codeds> <out>\n");
   return 2;
 }

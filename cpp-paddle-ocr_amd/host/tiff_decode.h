@@ -108,7 +108,8 @@ inline const char* fault(const Frame& f, Geometry& g) {
 inline bool sound(const Frame& f, Geometry& g) { return !fault(f, g) && f.data.size() >= g.total; }
 
 // A file before its chunks are expanded (Compression 1, 5 and 32773): parse() is parse_coded() + expand(), and the device
-// takes the second half too (csrc/kernels_tiff_lzw.hip through ocr_tiff_coded).
+// takes the second half too (csrc/kernels_tiff_lzw.hip through ocr_tiff_coded).  A Deflate file (8, 32946) has the same form
+// from parse_deflate(), whose second half is inflate_all() here and csrc/kernels_inflate.hip on the device.
 struct Chunk {  // ocr_tiff_chunk of include/ocr_hip.h, field for field
   uint64_t byte_off = 0;  // into Coded::bytes
   uint32_t byte_len = 0;
@@ -116,7 +117,7 @@ struct Chunk {  // ocr_tiff_chunk of include/ocr_hip.h, field for field
 };
 struct Coded {
   Frame frame;                // data empty
-  int compression = 1;        // 1, 5 (LZW) or 32773 (PackBits)
+  int compression = 1;        // 1, 5 (LZW) or 32773 (PackBits); 8 or 32946 (Deflate) from parse_deflate alone
   std::vector<Chunk> chunks;  // in the order Frame::data has them: plane by plane, row of chunks by row of chunks
   std::vector<uint8_t> bytes; // the coded chunks one after another, MSB first (FillOrder 2 is undone)
 };
@@ -254,12 +255,13 @@ inline bool lzw_extent(const uint8_t* s, size_t n, size_t need) {
   return o == need;
 }
 
-inline bool inflate(const uint8_t* s, size_t n, uint8_t* out, size_t need) {
+// the bytes zlib gives before its first error, the end of the stream or the end of the input, at most `need`
+inline size_t inflate_count(const uint8_t* s, size_t n, uint8_t* out, size_t need) {
   const png::Zlib& z = png::zlib();
-  if (!z.ok() || n > 0xFFFFFFFFu) return false;
+  if (!z.ok() || n > 0xFFFFFFFFu) return 0;
   png::ZStream zs;
   memset(&zs, 0, sizeof zs);
-  if (z.init(&zs, "1.2.11", (int)sizeof zs) != 0) return false;
+  if (z.init(&zs, "1.2.11", (int)sizeof zs) != 0) return 0;
   zs.next_in = s; zs.avail_in = (unsigned)n;
   size_t o = 0;
   bool ok = true;
@@ -274,8 +276,10 @@ inline bool inflate(const uint8_t* s, size_t n, uint8_t* out, size_t need) {
     if (rc != 0 || before == zs.avail_out) ok = false;  // an error, or no progress (the input is used up)
   }
   z.end(&zs);
-  return o == need;
+  return o;
 }
+// a chunk is good where `need` bytes come out; neither a wrong checksum nor a missing trailer behind them refuses it
+inline bool inflate(const uint8_t* s, size_t n, uint8_t* out, size_t need) { return inflate_count(s, n, out, need) == need; }
 
 }  // namespace detail
 
@@ -410,9 +414,11 @@ inline bool parse_head(const uint8_t* d, size_t n, Frame& f, Head& hd) {
   return true;
 }
 
-inline const char* structure_fault(const Frame& f, int compression, const Chunk* chunks, size_t nchunks, size_t pool, Geometry& g) {
+inline const char* structure_fault(const Frame& f, int compression, const Chunk* chunks, size_t nchunks, size_t pool, Geometry& g, bool deflate = false) {
   if (const char* why = fault(f, g)) return why;
-  if (compression != 1 && compression != 5 && compression != 32773) return "coded: compression must be 1 (none), 5 (LZW) or 32773 (PackBits)";
+  if (deflate) {
+    if (compression != 8 && compression != 32946) return "deflate: compression must be 8 or 32946 (Deflate)";
+  } else if (compression != 1 && compression != 5 && compression != 32773) return "coded: compression must be 1 (none), 5 (LZW) or 32773 (PackBits)";
   if (nchunks != (size_t)g.across * g.down * g.planes || (nchunks && !chunks)) return "coded: as many chunk records as the geometry has chunks";
   for (size_t c = 0; c < nchunks; ++c) {
     if (chunks[c].rows < 1 || chunks[c].rows > (uint32_t)f.tile_height) return "coded: a chunk's rows must be 1 .. tile_height";
@@ -467,7 +473,7 @@ namespace detail {
 // the coded chunks of a parsed head into one pool (an uncompressed chunk: the bytes its rows need, no more).  scan: with the
 // extent scan of every stream (coded_fault); without, the records alone are checked - for a caller that expands at once, whose
 // expanders refuse exactly what the scan refuses
-inline bool gather(const uint8_t* d, const Head& h, Coded& c, bool scan) {
+inline void gather_bytes(const uint8_t* d, const Head& h, Coded& c) {
   c.compression = (int)h.comp;
   c.chunks.resize(h.chunks);
   size_t pool = 0;
@@ -483,6 +489,9 @@ inline bool gather(const uint8_t* d, const Head& h, Coded& c, bool scan) {
     if (h.fill == 2) for (size_t i = 0; i < c.chunks[k].byte_len; ++i) o[i] = reverse_bits(s[i]);  // FillOrder 2: the coded bytes with their bits reversed
     else memcpy(o, s, c.chunks[k].byte_len);
   }
+}
+inline bool gather(const uint8_t* d, const Head& h, Coded& c, bool scan) {
+  gather_bytes(d, h, c);
   Geometry g;
   if (scan ? coded_fault(c, g) : structure_fault(c.frame, c.compression, c.chunks.data(), c.chunks.size(), c.bytes.size(), g)) return false;
   c.frame.device_ok = h.chunks <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
@@ -500,6 +509,54 @@ inline Route parse_coded(const uint8_t* d, size_t n, Coded& c) {
   if (h.comp != 1 && h.comp != 5 && h.comp != 32773) { c = Coded(); return kOtherRoute; }
   if (!detail::gather(d, h, c, true)) { c = Coded(); return kRefused; }
   return kCoded;
+}
+
+// The Deflate route (Compression 8 / 32946), reached by names of its own: the container alone - no stream is looked at, the
+// device's inflate kernel (csrc/kernels_inflate.hip) gives the verdict per chunk, and inflate_all() is the host's.
+inline const char* deflate_fault_of(const Frame& f, int compression, const Chunk* chunks, size_t nchunks, const uint8_t* bytes, size_t pool, Geometry& g) {
+  if (const char* why = detail::structure_fault(f, compression, chunks, nchunks, pool, g, true)) return why;
+  if (pool && !bytes) return "coded: the byte pool is missing";
+  return nullptr;
+}
+inline bool parse_deflate(const uint8_t* d, size_t n, Coded& c) {
+  c = Coded();
+  detail::Head h;
+  if (!detail::parse_head(d, n, c.frame, h) || (h.comp != 8 && h.comp != 32946)) { c = Coded(); return false; }
+  c.compression = (int)h.comp;
+  detail::gather_bytes(d, h, c);
+  Geometry g;
+  if (deflate_fault_of(c.frame, c.compression, c.chunks.data(), c.chunks.size(), c.bytes.data(), c.bytes.size(), g)) { c = Coded(); return false; }
+  c.frame.device_ok = h.chunks <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
+  return true;
+}
+// parse_coded() and parse_deflate() behind one reading of the container: kCoded with `deflate` false is parse_coded()'s answer,
+// kCoded with `deflate` true parse_deflate()'s; kOtherRoute does not occur.
+inline Route parse_any(const uint8_t* d, size_t n, Coded& c, bool& deflate) {
+  c = Coded();
+  detail::Head h;
+  if (!detail::parse_head(d, n, c.frame, h)) { c = Coded(); return kRefused; }
+  deflate = h.comp == 8 || h.comp == 32946;
+  if (!deflate) {
+    if (!detail::gather(d, h, c, true)) { c = Coded(); return kRefused; }
+    return kCoded;
+  }
+  detail::gather_bytes(d, h, c);
+  Geometry g;
+  if (deflate_fault_of(c.frame, c.compression, c.chunks.data(), c.chunks.size(), c.bytes.data(), c.bytes.size(), g)) { c = Coded(); return kRefused; }
+  c.frame.device_ok = h.chunks <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
+  return kCoded;
+}
+// The host expansion of such a frame: what parse() gives for the file.  false where a chunk's stream does not hold its bytes.
+inline bool inflate_all(const Coded& c, Frame& f) {
+  Geometry g;
+  if (!c.frame.data.empty() || deflate_fault_of(c.frame, c.compression, c.chunks.data(), c.chunks.size(), c.bytes.data(), c.bytes.size(), g)) { f = Frame(); return false; }
+  f = c.frame;
+  for (size_t k = 0; k < c.chunks.size(); ++k) {
+    f.data.resize((k + 1) * g.chunk_bytes, 0);  // (chunk by chunk, as parse() grows it)
+    if (!detail::inflate(c.bytes.data() + c.chunks[k].byte_off, c.chunks[k].byte_len, f.data.data() + k * g.chunk_bytes, (size_t)c.chunks[k].rows * g.row_bytes)) { f = Frame(); return false; }
+  }
+  f.device_ok = c.chunks.size() <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
+  return true;
 }
 
 // The container and the expansion: everything but the pixels.  false = not a TIFF file, or one that is refused.

@@ -425,7 +425,7 @@ typedef struct ocr_tiff_chunk {
 } ocr_tiff_chunk;
 typedef struct ocr_tiff_coded {
   ocr_tiff_frame frame;          /* data is NULL (data_len is not read) */
-  int compression;               /* 1, 5 or 32773 */
+  int compression;               /* 1, 5 or 32773; 8 or 32946 for the Deflate entry points alone */
   const ocr_tiff_chunk* chunks;  /* host: plane by plane, row of chunks by row of chunks */
   size_t chunks_len;
   const uint8_t* bytes;          /* host */
@@ -440,6 +440,23 @@ int ocr_tiff_decode_coded(const ocr_tiff_coded* coded, int device_id, uint8_t* b
  * expansion, ms[2] = the pixel stage's kernels; ocr_tiff_time_coded_batch: `count` frames as ONE batch. */
 int ocr_tiff_time_coded(const ocr_tiff_coded* coded, int device_id, int iters, double ms[3]);
 int ocr_tiff_time_coded_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]);
+/* Deflate TIFFs (Compression 8 and 32946) on the same structure: an ocr_tiff_coded with that compression (host/tiff_decode.h,
+ * tiff::parse_deflate: the container alone, one zlib stream per chunk, FillOrder 2 undone), through entry points of their own.
+ * Fields and chunk records are checked on the host before anything is launched (OCR_ERR_ARG, nothing launched, the output
+ * untouched); NO stream is looked at there.  One wavefront inflates one chunk (csrc/kernels_inflate.hip) and reports the bytes
+ * its stream gave; a chunk is good where that is what its rows need - zlib's verdict on the host (tiff::detail::inflate):
+ * neither a wrong Adler-32 nor a missing trailer behind those bytes refuses it.  The counts come back to the host (4 bytes a
+ * chunk, the one round trip of this route); where a chunk fell short the call returns OCR_ERR_ARG "deflate: a chunk's stream does
+ * not hold the bytes its rows need (frame F, chunk C)", no pixel kernel runs, the output's contents are unspecified and nothing
+ * beyond its cap is written.  The caller's fallback is the host: tiff::inflate_all.
+ * ocr_tiff_inflate: the expansion alone, out as ocr_tiff_expand's; produced (chunks_len words, may be NULL): the bytes each
+ * chunk's stream gave, cut at what its rows need - it returns OCR_OK whatever the streams are, the verdict is in `produced`. */
+int ocr_tiff_inflate(const ocr_tiff_coded* coded, int device_id, uint8_t* out, size_t cap, uint32_t* produced);
+int ocr_tiff_decode_deflate(const ocr_tiff_coded* coded, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time): ms[0] = the upload, ms[1] = the inflate launch with the read-back of its counts,
+ * ms[2] = the pixel stage's kernels; ocr_tiff_time_deflate_batch: `count` frames as ONE batch. */
+int ocr_tiff_time_deflate(const ocr_tiff_coded* coded, int device_id, int iters, double ms[3]);
+int ocr_tiff_time_deflate_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]);
 /* Lossless WebP inputs with the pixel half of the decoder on the device: the caller parses the container and does what is
  * serial (prefix codes, LZ77, the colour cache: host/webp_decode.h, webp::parse); the inverse transforms - spatial predictor,
  * cross-colour, add-green, palette with pixel bundling - run on the copy stream straight into the slot.  The pixels are
@@ -577,10 +594,10 @@ int ocr_j2k_time_coded_batch(const ocr_j2k_coded* const* coded, int count, int d
 /* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw, TIFF,
  * WebP, VP8 and JPEG 2000 frames (coefficient form and coded form) and coded TIFF frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
  * all five validate their own argument list and stage through the same code, with the same bytes in the slot. */
-typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5, OCR_FRAME_J2K = 6, OCR_FRAME_J2K_CODED = 7, OCR_FRAME_TIFF_CODED = 8 } ocr_frame_kind;
+typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5, OCR_FRAME_J2K = 6, OCR_FRAME_J2K_CODED = 7, OCR_FRAME_TIFF_CODED = 8, OCR_FRAME_TIFF_DEFLATE = 9 } ocr_frame_kind;
 typedef struct ocr_coded_frame {
   int kind;           /* ocr_frame_kind */
-  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame, ocr_vp8_frame, ocr_j2k_frame, ocr_j2k_coded or ocr_tiff_coded */
+  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame, ocr_vp8_frame, ocr_j2k_frame, ocr_j2k_coded or ocr_tiff_coded (TIFF_CODED and TIFF_DEFLATE) */
 } ocr_coded_frame;
 int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
