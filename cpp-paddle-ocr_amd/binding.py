@@ -95,6 +95,45 @@ def check(rc):
         raise OcrError("libocr_hip error %d: %s" % (rc, lib().ocr_last_error().decode(errors="replace")))
 
 
+def _raise(L, rc, out):
+    err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
+    err.code = rc
+    err.out = out  # the buffer as the call left it
+    raise err
+
+
+def _decode_frame(name, c, h, w, device_id, fill=0):
+    """L.<name>(&c, device_id, bgr, cap) - the ocr_X_decode of a format route - into an (h, w, 3) buffer pre-filled with `fill`;
+    (1, 1, 3) where h x w is no image size: the library refuses the descriptor before it looks at the capacity"""
+    L = lib()
+    fn = getattr(L, name)
+    fn.argtypes = [C.POINTER(type(c)), C.c_int, C.c_void_p, C.c_size_t]
+    out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), fill, np.uint8)
+    rc = fn(C.byref(c), device_id, out.ctypes.data, out.size)
+    if rc != 0:
+        _raise(L, rc, out)
+    return out
+
+
+def _time_coded(name, coded, iters, device_id, single):
+    """L.<name>_batch over the descriptors of `coded` as one batch (single: L.<name> of the first): three phases in ms"""
+    L = lib()
+    ctype = type(coded[0].c)
+    ms = (C.c_double * 3)()
+    if single:
+        fn = getattr(L, name)
+        fn.argtypes = [C.POINTER(ctype), C.c_int, C.c_int, C.POINTER(C.c_double)]
+        rc = fn(C.byref(coded[0].c), device_id, iters, ms)
+    else:
+        fn = getattr(L, name + "_batch")
+        fn.argtypes = [C.POINTER(C.POINTER(ctype)), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+        ptrs = (C.POINTER(ctype) * len(coded))(*[C.pointer(k.c) for k in coded])
+        rc = fn(ptrs, len(coded), device_id, iters, ms)
+    if rc != 0:
+        _raise(L, rc, None)
+    return list(ms)
+
+
 class SrvNet:
     """raw taps of a server network (BASELINE configs[4]; hand-written plans, seeded weights): kind "det" | "rec" """
 
@@ -728,15 +767,7 @@ class PngFrame:
 
     def decode(self, device_id=0):
         """ocr_png_decode: the (height, width, 3) BGR image; OcrError where the call refuses"""
-        L = lib()
-        L.ocr_png_decode.argtypes = [C.POINTER(ocr_png_frame), C.c_int, C.c_void_p, C.c_size_t]
-        out = np.zeros((max(1, self.c.height), max(1, self.c.width), 3), np.uint8)
-        rc = L.ocr_png_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
-            err.code = rc
-            raise err
-        return out
+        return _decode_frame("ocr_png_decode", self.c, self.c.height, self.c.width, device_id)
 
 
 class ocr_raw_frame(C.Structure):
@@ -763,16 +794,7 @@ class RawFrame:
 
     def decode(self, device_id=0):
         """ocr_raw_decode: the (height, width, 3) BGR image; OcrError where the call refuses"""
-        L = lib()
-        L.ocr_raw_decode.argtypes = [C.POINTER(ocr_raw_frame), C.c_int, C.c_void_p, C.c_size_t]
-        h, w = self.c.height, self.c.width
-        out = np.zeros((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), np.uint8)
-        rc = L.ocr_raw_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
-            err.code = rc
-            raise err
-        return out
+        return _decode_frame("ocr_raw_decode", self.c, self.c.height, self.c.width, device_id)
 
 
 class ocr_tiff_frame(C.Structure):
@@ -808,16 +830,7 @@ class TiffFrame:
 
     def decode(self, device_id=0):
         """ocr_tiff_decode: the (height, width, 3) BGR image; OcrError where the call refuses"""
-        L = lib()
-        L.ocr_tiff_decode.argtypes = [C.POINTER(ocr_tiff_frame), C.c_int, C.c_void_p, C.c_size_t]
-        h, w = self.c.height, self.c.width
-        out = np.zeros((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), np.uint8)
-        rc = L.ocr_tiff_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
-            err.code = rc
-            raise err
-        return out
+        return _decode_frame("ocr_tiff_decode", self.c, self.c.height, self.c.width, device_id)
 
 
 class ocr_tiff_coded(C.Structure):
@@ -827,13 +840,6 @@ class ocr_tiff_coded(C.Structure):
 
 # ocr_tiff_chunk as a numpy record (16 bytes)
 TIFF_CHUNK = np.dtype([("byte_off", "<u8"), ("byte_len", "<u4"), ("rows", "<u4")])
-
-
-def _raise_tiff(L, rc, out):
-    err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
-    err.code = rc
-    err.out = out  # the buffer as the call left it
-    raise err
 
 
 class TiffCoded:
@@ -876,20 +882,13 @@ class TiffCoded:
         out = np.full(n if 0 < n <= 1 << 30 else 1, fill, np.uint8)
         rc = L.ocr_tiff_expand(C.byref(self.c), device_id, out.ctypes.data, out.size)
         if rc != 0:
-            _raise_tiff(L, rc, out)
+            _raise(L, rc, out)
         return out
 
     def decode(self, device_id=0, fill=0):
         """ocr_tiff_decode_coded: the (height, width, 3) BGR image; OcrError where the call refuses (err.out: the buffer as the
         call left it, pre-filled with `fill`)"""
-        L = lib()
-        L.ocr_tiff_decode_coded.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_void_p, C.c_size_t]
-        h, w = self.c.frame.height, self.c.frame.width
-        out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), fill, np.uint8)
-        rc = L.ocr_tiff_decode_coded(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            _raise_tiff(L, rc, out)
-        return out
+        return _decode_frame("ocr_tiff_decode_coded", self.c, self.c.frame.height, self.c.frame.width, device_id, fill)
 
     def time(self, iters=3, device_id=0):
         """ocr_tiff_time_coded: [upload, expansion, pixel stage] in ms"""
@@ -906,19 +905,12 @@ class TiffCoded:
         produced = np.zeros(max(1, len(self.chunks)), np.uint32)
         rc = L.ocr_tiff_inflate(C.byref(self.c), device_id, out.ctypes.data, out.size, produced.ctypes.data)
         if rc != 0:
-            _raise_tiff(L, rc, out)
+            _raise(L, rc, out)
         return out, produced[:len(self.chunks)]
 
     def decode_deflate(self, device_id=0, fill=0):
         """ocr_tiff_decode_deflate: the (height, width, 3) BGR image; OcrError where the call refuses (err.out as for decode)"""
-        L = lib()
-        L.ocr_tiff_decode_deflate.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_void_p, C.c_size_t]
-        h, w = self.c.frame.height, self.c.frame.width
-        out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), fill, np.uint8)
-        rc = L.ocr_tiff_decode_deflate(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            _raise_tiff(L, rc, out)
-        return out
+        return _decode_frame("ocr_tiff_decode_deflate", self.c, self.c.frame.height, self.c.frame.width, device_id, fill)
 
 
 def tiff_expand(coded, device_id=0):
@@ -934,18 +926,7 @@ def tiff_decode_coded(coded, device_id=0):
 def time_tiff_coded(coded, iters=3, device_id=0, single=False):
     """ocr_tiff_time_coded_batch over TiffCoded objects as one batch (single: ocr_tiff_time_coded of the first):
     [upload, expansion, pixel stage] in ms"""
-    L = lib()
-    ms = (C.c_double * 3)()
-    if single:
-        L.ocr_tiff_time_coded.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_int, C.POINTER(C.c_double)]
-        rc = L.ocr_tiff_time_coded(C.byref(coded[0].c), device_id, iters, ms)
-    else:
-        L.ocr_tiff_time_coded_batch.argtypes = [C.POINTER(C.POINTER(ocr_tiff_coded)), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
-        ptrs = (C.POINTER(ocr_tiff_coded) * len(coded))(*[C.pointer(k.c) for k in coded])
-        rc = L.ocr_tiff_time_coded_batch(ptrs, len(coded), device_id, iters, ms)
-    if rc != 0:
-        _raise_tiff(L, rc, None)
-    return list(ms)
+    return _time_coded("ocr_tiff_time_coded", coded, iters, device_id, single)
 
 
 def tiff_inflate(coded, device_id=0):
@@ -961,18 +942,7 @@ def tiff_decode_deflate(coded, device_id=0):
 def time_tiff_deflate(coded, iters=3, device_id=0, single=False):
     """ocr_tiff_time_deflate_batch over TiffCoded objects as one batch (single: ocr_tiff_time_deflate of the first):
     [upload, inflate with its read-back, pixel stage] in ms"""
-    L = lib()
-    ms = (C.c_double * 3)()
-    if single:
-        L.ocr_tiff_time_deflate.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_int, C.POINTER(C.c_double)]
-        rc = L.ocr_tiff_time_deflate(C.byref(coded[0].c), device_id, iters, ms)
-    else:
-        L.ocr_tiff_time_deflate_batch.argtypes = [C.POINTER(C.POINTER(ocr_tiff_coded)), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
-        ptrs = (C.POINTER(ocr_tiff_coded) * len(coded))(*[C.pointer(k.c) for k in coded])
-        rc = L.ocr_tiff_time_deflate_batch(ptrs, len(coded), device_id, iters, ms)
-    if rc != 0:
-        _raise_tiff(L, rc, None)
-    return list(ms)
+    return _time_coded("ocr_tiff_time_deflate", coded, iters, device_id, single)
 
 
 class ocr_webp_transform(C.Structure):
@@ -1006,16 +976,7 @@ class WebpFrame:
 
     def decode(self, device_id=0):
         """ocr_webp_decode: the (height, width, 3) BGR image; OcrError where the call refuses"""
-        L = lib()
-        L.ocr_webp_decode.argtypes = [C.POINTER(ocr_webp_frame), C.c_int, C.c_void_p, C.c_size_t]
-        h, w = self.c.height, self.c.width
-        out = np.zeros((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), np.uint8)
-        rc = L.ocr_webp_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
-            err.code = rc
-            raise err
-        return out
+        return _decode_frame("ocr_webp_decode", self.c, self.c.height, self.c.width, device_id)
 
 
 class ocr_vp8_frame(C.Structure):
@@ -1044,17 +1005,7 @@ class Vp8Frame:
     def decode(self, device_id=0, fill=0):
         """ocr_vp8_decode: the (height, width, 3) BGR image; OcrError where the call refuses (err.out: the buffer as the call left
         it, pre-filled with `fill`)"""
-        L = lib()
-        L.ocr_vp8_decode.argtypes = [C.POINTER(ocr_vp8_frame), C.c_int, C.c_void_p, C.c_size_t]
-        h, w = self.c.height, self.c.width
-        out = np.full((h, w, 3) if 0 < h <= 16383 and 0 < w <= 16383 else (1, 1, 3), fill, np.uint8)
-        rc = L.ocr_vp8_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
-            err.code = rc
-            err.out = out
-            raise err
-        return out
+        return _decode_frame("ocr_vp8_decode", self.c, self.c.height, self.c.width, device_id, fill)
 
 
 class ocr_j2k_frame(C.Structure):
@@ -1088,17 +1039,7 @@ class J2kFrame:
     def decode(self, device_id=0, fill=0):
         """ocr_j2k_decode: the (height, width, 3) BGR image; OcrError where the call refuses (err.out: the buffer as the call left
         it, pre-filled with `fill`)"""
-        L = lib()
-        L.ocr_j2k_decode.argtypes = [C.POINTER(ocr_j2k_frame), C.c_int, C.c_void_p, C.c_size_t]
-        h, w = self.c.height, self.c.width
-        out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= 1 << 26 else (1, 1, 3), fill, np.uint8)
-        rc = L.ocr_j2k_decode(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
-            err.code = rc
-            err.out = out
-            raise err
-        return out
+        return _decode_frame("ocr_j2k_decode", self.c, self.c.height, self.c.width, device_id, fill)
 
 
 class ocr_j2k_coded(C.Structure):
@@ -1108,13 +1049,6 @@ class ocr_j2k_coded(C.Structure):
 # ocr_j2k_cblk as a numpy record (32 bytes)
 J2K_CBLK = np.dtype([("tc", "<u4"), ("at", "<u4"), ("byte_off", "<u8"), ("byte_len", "<u4"), ("w", "<u2"), ("h", "<u2"), ("orient", "u1"), ("numbps", "u1"),
                      ("passes", "u1"), ("reserved", "u1"), ("reserved2", "<u4")])
-
-
-def _raise(L, rc, out):
-    err = OcrError("libocr_hip error %d: %s" % (rc, L.ocr_last_error().decode(errors="replace")))
-    err.code = rc
-    err.out = out
-    raise err
 
 
 class J2kCoded:
@@ -1152,14 +1086,7 @@ class J2kCoded:
     def decode(self, device_id=0, fill=0):
         """ocr_j2k_decode_coded: the (height, width, 3) BGR image; OcrError where the call refuses (err.out: the buffer as the
         call left it, pre-filled with `fill`)"""
-        L = lib()
-        L.ocr_j2k_decode_coded.argtypes = [C.POINTER(ocr_j2k_coded), C.c_int, C.c_void_p, C.c_size_t]
-        h, w = self.c.frame.height, self.c.frame.width
-        out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= 1 << 26 else (1, 1, 3), fill, np.uint8)
-        rc = L.ocr_j2k_decode_coded(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            _raise(L, rc, out)
-        return out
+        return _decode_frame("ocr_j2k_decode_coded", self.c, self.c.frame.height, self.c.frame.width, device_id, fill)
 
     def time(self, iters=3, device_id=0):
         """ocr_j2k_time_coded: [upload, tier-1, pixel stage] in ms"""
@@ -1169,18 +1096,7 @@ class J2kCoded:
 def time_j2k_coded(coded, iters=3, device_id=0, single=False):
     """ocr_j2k_time_coded_batch over J2kCoded objects as one batch (single: ocr_j2k_time_coded of the first):
     [upload, tier-1, pixel stage] in ms"""
-    L = lib()
-    ms = (C.c_double * 3)()
-    if single:
-        L.ocr_j2k_time_coded.argtypes = [C.POINTER(ocr_j2k_coded), C.c_int, C.c_int, C.POINTER(C.c_double)]
-        rc = L.ocr_j2k_time_coded(C.byref(coded[0].c), device_id, iters, ms)
-    else:
-        L.ocr_j2k_time_coded_batch.argtypes = [C.POINTER(C.POINTER(ocr_j2k_coded)), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
-        ptrs = (C.POINTER(ocr_j2k_coded) * len(coded))(*[C.pointer(k.c) for k in coded])
-        rc = L.ocr_j2k_time_coded_batch(ptrs, len(coded), device_id, iters, ms)
-    if rc != 0:
-        _raise(L, rc, None)
-    return list(ms)
+    return _time_coded("ocr_j2k_time_coded", coded, iters, device_id, single)
 
 
 def rotate_crop_shape(rows, cols, box):

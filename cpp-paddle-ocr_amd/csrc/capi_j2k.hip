@@ -230,83 +230,49 @@ using namespace ocr;
 
 namespace {
 
-int time_batch(const ocr_j2k_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
-  for (int i = 0; i < count; ++i) {
-    if (!frames[i]) return fail(OCR_ERR_ARG, "null argument");
-    if (const char* fault = j2k_frame_fault(*frames[i])) return fail(OCR_ERR_ARG, fault);
+struct J2kRoute {
+  using Frame = ocr_j2k_frame;
+  using Scratch = J2kScratch;
+  using Launch = J2kLaunch;
+  static const char* fault(const Frame& f) { return j2k_frame_fault(f); }
+  static int rows(const Frame& f) { return f.height; }
+  static int cols(const Frame& f) { return f.width; }
+  static int decode(const Frame* const* frames, int count, uint8_t* const* dst, Scratch& sc, std::string& err, Launch* L) {
+    return j2k_decode_async(frames, count, dst, sc, nullptr, err, L);
   }
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  std::vector<DevBuf<uint8_t>> out((size_t)count);
-  std::vector<uint8_t*> dst((size_t)count);
-  std::string err;
-  for (int i = 0; i < count; ++i) {
-    if (!out[i].ensure((size_t)frames[i]->width * frames[i]->height * 3, err)) return fail(OCR_ERR_DEVICE, err);
-    dst[i] = out[i].p;
+  static uint8_t* uploaded(Scratch& sc, const Launch&) { return sc.data.p; }
+  static void pixels(Scratch&, const Launch& L) { j2k_relaunch(L, nullptr); }
+};
+
+// the coded route: upload (of what follows plane a), tier-1, pixel stage
+struct J2kCodedRoute {
+  using Frame = ocr_j2k_coded;
+  using Scratch = J2kScratch;
+  using Launch = J2kLaunch;
+  static const char* fault(const Frame& c) { return j2k_coded_fault(c); }
+  static int rows(const Frame& c) { return c.frame.height; }
+  static int cols(const Frame& c) { return c.frame.width; }
+  static int decode(const Frame* const* coded, int count, uint8_t* const* dst, Scratch& sc, std::string& err, Launch* L) {
+    return j2k_coded_decode_async(coded, count, dst, sc, nullptr, err, L);
   }
-  J2kScratch sc;
-  J2kLaunch L;
-  rc = j2k_decode_async(frames, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
-  if (rc) return fail(rc, err);
-  return time_phases(iters, ms, [&] { return hipMemcpyAsync(sc.data.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
-                     [&] { j2k_relaunch(L, nullptr); return hipSuccess; });
-}
+  static uint8_t* uploaded(Scratch& sc, const Launch& L) { return sc.data.p + L.upload_at; }
+  static hipError_t middle(Scratch&, const Launch& L) { return j2k_t1_relaunch(L, nullptr); }
+  static void pixels(Scratch&, const Launch& L) { j2k_relaunch(L, nullptr); }
+};
 
 }  // namespace
 
-extern "C" int ocr_j2k_decode(const ocr_j2k_frame* frame, int device_id, uint8_t* bgr, size_t cap) {
-  if (!frame || !bgr) return fail(OCR_ERR_ARG, "null argument");
-  // (the descriptor first: a bad one is an argument error wherever the call is made)
-  if (const char* fault = j2k_frame_fault(*frame)) return fail(OCR_ERR_ARG, fault);
-  const size_t bytes = (size_t)frame->width * frame->height * 3;
-  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  J2kScratch sc;
-  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return j2k_decode_async(&frame, 1, dst, sc, nullptr, err); });
-}
+extern "C" int ocr_j2k_decode(const ocr_j2k_frame* frame, int device_id, uint8_t* bgr, size_t cap) { return decode_frame<J2kRoute>(frame, device_id, bgr, cap); }
 
 extern "C" int ocr_j2k_time(const ocr_j2k_frame* frame, int device_id, int iters, double ms[2]) {
   if (!frame || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_batch(&frame, 1, device_id, iters, ms);
+  return time_frames<J2kRoute>(&frame, 1, device_id, iters, ms);
 }
 
 extern "C" int ocr_j2k_time_batch(const ocr_j2k_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
   if (!frames || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_batch(frames, count, device_id, iters, ms);
+  return time_frames<J2kRoute>(frames, count, device_id, iters, ms);
 }
-
-namespace {
-
-int time_coded_batch(const ocr_j2k_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
-  for (int i = 0; i < count; ++i) {
-    if (!coded[i]) return fail(OCR_ERR_ARG, "null argument");
-    if (const char* fault = j2k_coded_fault(*coded[i])) return fail(OCR_ERR_ARG, fault);
-  }
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  std::vector<DevBuf<uint8_t>> out((size_t)count);
-  std::vector<uint8_t*> dst((size_t)count);
-  std::string err;
-  for (int i = 0; i < count; ++i) {
-    if (!out[i].ensure((size_t)coded[i]->frame.width * coded[i]->frame.height * 3, err)) return fail(OCR_ERR_DEVICE, err);
-    dst[i] = out[i].p;
-  }
-  J2kScratch sc;
-  J2kLaunch L;
-  rc = j2k_coded_decode_async(coded, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
-  if (rc) return fail(rc, err);
-  double t[2];
-  rc = time_phases(iters, t, [&] { return hipMemcpyAsync(sc.data.p + L.upload_at, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
-                   [&] { return j2k_t1_relaunch(L, nullptr); });
-  if (rc) return rc;
-  ms[0] = t[0]; ms[1] = t[1];
-  rc = time_phases(iters, t, [&] { j2k_relaunch(L, nullptr); return hipGetLastError(); }, [] { return hipSuccess; });
-  ms[2] = t[0];
-  return rc;
-}
-
-}  // namespace
 
 extern "C" int ocr_j2k_tier1(const ocr_j2k_coded* coded, int device_id, int32_t* coeffs, size_t cap) {
   if (!coded || !coeffs) return fail(OCR_ERR_ARG, "null argument");
@@ -335,22 +301,15 @@ extern "C" int ocr_j2k_tier1(const ocr_j2k_coded* coded, int device_id, int32_t*
 }
 
 extern "C" int ocr_j2k_decode_coded(const ocr_j2k_coded* coded, int device_id, uint8_t* bgr, size_t cap) {
-  if (!coded || !bgr) return fail(OCR_ERR_ARG, "null argument");
-  if (const char* fault = j2k_coded_fault(*coded)) return fail(OCR_ERR_ARG, fault);
-  const size_t bytes = (size_t)coded->frame.width * coded->frame.height * 3;
-  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  J2kScratch sc;
-  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return j2k_coded_decode_async(&coded, 1, dst, sc, nullptr, err); });
+  return decode_frame<J2kCodedRoute>(coded, device_id, bgr, cap);
 }
 
 extern "C" int ocr_j2k_time_coded(const ocr_j2k_coded* coded, int device_id, int iters, double ms[3]) {
   if (!coded || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_coded_batch(&coded, 1, device_id, iters, ms);
+  return time_frames3<J2kCodedRoute>(&coded, 1, device_id, iters, ms);
 }
 
 extern "C" int ocr_j2k_time_coded_batch(const ocr_j2k_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
   if (!coded || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_coded_batch(coded, count, device_id, iters, ms);
+  return time_frames3<J2kCodedRoute>(coded, count, device_id, iters, ms);
 }

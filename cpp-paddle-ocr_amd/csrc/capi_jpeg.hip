@@ -88,7 +88,7 @@ int jpeg_frame_kind(const ocr_jpeg_frame& f) {
   return classic ? jpeg_output_kind(f.orientation) : jpeg_general_kind(f.orientation);
 }
 
-int jpeg_decode_async(const ocr_jpeg_frame* imgs, int count, uint8_t* const* dst, JpegScratch& sc, hipStream_t s, std::string& err,
+int jpeg_decode_async(const ocr_jpeg_frame* const* imgs, int count, uint8_t* const* dst, JpegScratch& sc, hipStream_t s, std::string& err,
                       JpegLaunch* launched) {
   std::vector<JpegPlaneDesc> pd;
   std::vector<size_t> coef_off, plane_off;
@@ -97,7 +97,7 @@ int jpeg_decode_async(const ocr_jpeg_frame* imgs, int count, uint8_t* const* dst
   JpegLaunch L;
   std::vector<int> kinds((size_t)count);
   for (int i = 0; i < count; ++i) {
-    const ocr_jpeg_frame& im = imgs[i];
+    const ocr_jpeg_frame& im = *imgs[i];
     if (const char* fault = jpeg_frame_fault(im)) { err = fault; return OCR_ERR_ARG; }
     kinds[i] = jpeg_frame_kind(im);
     L.count[kinds[i]]++;
@@ -128,7 +128,7 @@ int jpeg_decode_async(const ocr_jpeg_frame* imgs, int count, uint8_t* const* dst
     std::vector<Piece> pieces;
     size_t p = 0;
     for (int i = 0; i < count; ++i)
-      for (int c = 0; c < imgs[i].ncomp; ++c, ++p) pieces.push_back({imgs[i].comp[c].coef, coef_off[p], (size_t)imgs[i].comp[c].bw * imgs[i].comp[c].bh * 64});
+      for (int c = 0; c < imgs[i]->ncomp; ++c, ++p) pieces.push_back({imgs[i]->comp[c].coef, coef_off[p], (size_t)imgs[i]->comp[c].bw * imgs[i]->comp[c].bh * 64});
     int16_t* pinned = reinterpret_cast<int16_t*>(sc.stage.p);
     parallel_copy(pieces.size(), coef_bytes, [&](size_t k) { memcpy(pinned + pieces[k].off, pieces[k].src, pieces[k].n * sizeof(int16_t)); });
   }
@@ -142,7 +142,7 @@ int jpeg_decode_async(const ocr_jpeg_frame* imgs, int count, uint8_t* const* dst
   std::copy(L.first, L.first + kJpegKinds, next);
   size_t p = 0;
   for (int i = 0; i < count; ++i) {
-    const ocr_jpeg_frame& im = imgs[i];
+    const ocr_jpeg_frame& im = *imgs[i];
     const int kind = kinds[i];
     const int orient = im.orientation ? im.orientation : 1;
     const FrameMax m = frame_max(im);
@@ -212,7 +212,8 @@ int decode_frame(const ocr_jpeg_frame& f, int device_id, uint8_t* bgr, size_t ca
   const size_t bytes = (size_t)f.rows * f.cols * 3;
   if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
   JpegScratch sc;
-  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return jpeg_decode_async(&f, 1, dst, sc, nullptr, err); });
+  const ocr_jpeg_frame* frame = &f;
+  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return jpeg_decode_async(&frame, 1, dst, sc, nullptr, err); });
 }
 
 int time_frame(const ocr_jpeg_frame& f, int device_id, int iters, double ms[2]) {
@@ -225,7 +226,8 @@ int time_frame(const ocr_jpeg_frame& f, int device_id, int iters, double ms[2]) 
   if (!out.ensure((size_t)f.rows * f.cols * 3, err)) return fail(OCR_ERR_DEVICE, err);
   uint8_t* dst = out.p;
   JpegLaunch L;
-  rc = jpeg_decode_async(&f, 1, &dst, sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
+  const ocr_jpeg_frame* frame = &f;
+  rc = jpeg_decode_async(&frame, 1, &dst, sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
   if (rc) return fail(rc, err);
   return time_phases(iters, ms, [&] { launch_jpeg_idct(sc.pd.p, L.ndesc, L.idct_blocks, nullptr); return hipSuccess; },
                      [&] { launch_jpeg_output(sc.id.p, sc.gd.p, L, nullptr); return hipSuccess; });

@@ -146,47 +146,17 @@ int png_decode_async(const ocr_png_frame* const* imgs, int count, uint8_t* const
 using namespace ocr;
 
 namespace {
-
-int time_batch(const ocr_png_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  std::vector<DevBuf<uint8_t>> out((size_t)count);
-  std::vector<uint8_t*> dst((size_t)count);
-  std::string err;
-  for (int i = 0; i < count; ++i) {
-    if (!frames[i]) return fail(OCR_ERR_ARG, "null argument");
-    if (const char* fault = png_frame_fault(*frames[i])) return fail(OCR_ERR_ARG, fault);
-    if (!out[i].ensure((size_t)frames[i]->width * frames[i]->height * 3, err)) return fail(OCR_ERR_DEVICE, err);
-    dst[i] = out[i].p;
-  }
-  PngScratch sc;
-  PngLaunch L;
-  rc = png_decode_async(frames, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
-  if (rc) return fail(rc, err);
-  return time_phases(iters, ms, [&] { return hipMemcpyAsync(sc.data.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
-                     [&] { png_relaunch(sc, L, nullptr); return hipSuccess; });
-}
-
+struct PngRoute : PlainRoute<ocr_png_frame, PngScratch, PngLaunch, png_frame_fault, png_decode_async, png_relaunch> {};
 }  // namespace
 
-extern "C" int ocr_png_decode(const ocr_png_frame* frame, int device_id, uint8_t* bgr, size_t cap) {
-  if (!frame || !bgr) return fail(OCR_ERR_ARG, "null argument");
-  // (the descriptor first: a bad one is an argument error wherever the call is made)
-  if (const char* fault = png_frame_fault(*frame)) return fail(OCR_ERR_ARG, fault);
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  const size_t bytes = (size_t)frame->width * frame->height * 3;
-  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
-  PngScratch sc;
-  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return png_decode_async(&frame, 1, dst, sc, nullptr, err); });
-}
+extern "C" int ocr_png_decode(const ocr_png_frame* frame, int device_id, uint8_t* bgr, size_t cap) { return decode_frame<PngRoute>(frame, device_id, bgr, cap); }
 
 extern "C" int ocr_png_time(const ocr_png_frame* frame, int device_id, int iters, double ms[2]) {
   if (!frame || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_batch(&frame, 1, device_id, iters, ms);
+  return time_frames<PngRoute>(&frame, 1, device_id, iters, ms);
 }
 
 extern "C" int ocr_png_time_batch(const ocr_png_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
   if (!frames || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_batch(frames, count, device_id, iters, ms);
+  return time_frames<PngRoute>(frames, count, device_id, iters, ms);
 }

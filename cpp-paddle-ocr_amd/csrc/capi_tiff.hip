@@ -319,85 +319,32 @@ using namespace ocr;
 
 namespace {
 
-int time_batch(const ocr_tiff_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
-  for (int i = 0; i < count; ++i) {
-    if (!frames[i]) return fail(OCR_ERR_ARG, "null argument");
-    if (const char* fault = tiff_frame_fault(*frames[i])) return fail(OCR_ERR_ARG, fault);
-  }
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  std::vector<DevBuf<uint8_t>> out((size_t)count);
-  std::vector<uint8_t*> dst((size_t)count);
-  std::string err;
-  for (int i = 0; i < count; ++i) {
-    if (!out[i].ensure((size_t)frames[i]->width * frames[i]->height * 3, err)) return fail(OCR_ERR_DEVICE, err);
-    dst[i] = out[i].p;
-  }
-  TiffScratch sc;
-  TiffLaunch L;
-  rc = tiff_decode_async(frames, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
-  if (rc) return fail(rc, err);
-  return time_phases(iters, ms, [&] { return hipMemcpyAsync(sc.data.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
-                     [&] { tiff_relaunch(sc, L, nullptr); return hipSuccess; });
-}
+struct TiffRoute : PlainRoute<ocr_tiff_frame, TiffScratch, TiffLaunch, tiff_frame_fault, tiff_decode_async, tiff_relaunch> {};
 
 // the coded route: upload, expansion, pixel stage
-int time_coded_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
-  for (int i = 0; i < count; ++i) {
-    if (!coded[i]) return fail(OCR_ERR_ARG, "null argument");
-    if (const char* fault = tiff_coded_fault(*coded[i])) return fail(OCR_ERR_ARG, fault);
+struct TiffCodedRoute {
+  using Frame = ocr_tiff_coded;
+  using Scratch = TiffScratch;
+  using Launch = TiffLaunch;
+  static const char* fault(const Frame& c) { return tiff_coded_fault(c); }
+  static int rows(const Frame& c) { return c.frame.height; }
+  static int cols(const Frame& c) { return c.frame.width; }
+  static int decode(const Frame* const* coded, int count, uint8_t* const* dst, Scratch& sc, std::string& err, Launch* L) {
+    return tiff_coded_decode_async(coded, count, dst, sc, nullptr, err, L);
   }
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  std::vector<DevBuf<uint8_t>> out((size_t)count);
-  std::vector<uint8_t*> dst((size_t)count);
-  std::string err;
-  for (int i = 0; i < count; ++i) {
-    if (!out[i].ensure((size_t)coded[i]->frame.width * coded[i]->frame.height * 3, err)) return fail(OCR_ERR_DEVICE, err);
-    dst[i] = out[i].p;
-  }
-  TiffScratch sc;
-  TiffLaunch L;
-  rc = tiff_coded_decode_async(coded, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
-  if (rc) return fail(rc, err);
-  double t[2];
-  rc = time_phases(iters, t, [&] { return hipMemcpyAsync(sc.coded.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
-                   [&] { tiff_expand_relaunch(sc, L, nullptr); return hipGetLastError(); });
-  if (rc) return rc;
-  ms[0] = t[0]; ms[1] = t[1];
-  rc = time_phases(iters, t, [&] { tiff_relaunch(sc, L, nullptr); return hipGetLastError(); }, [] { return hipSuccess; });
-  ms[2] = t[0];
-  return rc;
-}
+  static uint8_t* uploaded(Scratch& sc, const Launch&) { return sc.coded.p; }
+  static hipError_t middle(Scratch& sc, const Launch& L) { tiff_expand_relaunch(sc, L, nullptr); return hipGetLastError(); }
+  static void pixels(Scratch& sc, const Launch& L) { tiff_relaunch(sc, L, nullptr); }
+};
 
 // the Deflate route: upload, the inflate launch with its read-back, pixel stage
-int time_deflate_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
-  for (int i = 0; i < count; ++i) {
-    if (!coded[i]) return fail(OCR_ERR_ARG, "null argument");
-    if (const char* fault = tiff_deflate_fault(*coded[i])) return fail(OCR_ERR_ARG, fault);
+struct TiffDeflateRoute : TiffCodedRoute {
+  static const char* fault(const Frame& c) { return tiff_deflate_fault(c); }
+  static int decode(const Frame* const* coded, int count, uint8_t* const* dst, Scratch& sc, std::string& err, Launch* L) {
+    return tiff_deflate_decode_async(coded, count, dst, sc, nullptr, err, L);
   }
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  std::vector<DevBuf<uint8_t>> out((size_t)count);
-  std::vector<uint8_t*> dst((size_t)count);
-  std::string err;
-  for (int i = 0; i < count; ++i) {
-    if (!out[i].ensure((size_t)coded[i]->frame.width * coded[i]->frame.height * 3, err)) return fail(OCR_ERR_DEVICE, err);
-    dst[i] = out[i].p;
-  }
-  TiffScratch sc;
-  TiffLaunch L;
-  rc = tiff_deflate_decode_async(coded, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
-  if (rc) return fail(rc, err);
-  double t[2];
-  rc = time_phases(iters, t, [&] { return hipMemcpyAsync(sc.coded.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
-                   [&] { return tiff_inflate_relaunch(sc, L, nullptr) == OCR_OK ? hipSuccess : hipErrorUnknown; });
-  if (rc) return rc;
-  ms[0] = t[0]; ms[1] = t[1];
-  rc = time_phases(iters, t, [&] { tiff_relaunch(sc, L, nullptr); return hipGetLastError(); }, [] { return hipSuccess; });
-  ms[2] = t[0];
-  return rc;
-}
+  static hipError_t middle(Scratch& sc, const Launch& L) { return tiff_inflate_relaunch(sc, L, nullptr) == OCR_OK ? hipSuccess : hipErrorUnknown; }
+};
 
 }  // namespace
 
@@ -417,24 +364,17 @@ extern "C" int ocr_tiff_inflate(const ocr_tiff_coded* coded, int device_id, uint
 }
 
 extern "C" int ocr_tiff_decode_deflate(const ocr_tiff_coded* coded, int device_id, uint8_t* bgr, size_t cap) {
-  if (!coded || !bgr) return fail(OCR_ERR_ARG, "null argument");
-  if (const char* fault = tiff_deflate_fault(*coded)) return fail(OCR_ERR_ARG, fault);
-  const size_t bytes = (size_t)coded->frame.width * coded->frame.height * 3;
-  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  TiffScratch sc;
-  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return tiff_deflate_decode_async(&coded, 1, dst, sc, nullptr, err); });
+  return decode_frame<TiffDeflateRoute>(coded, device_id, bgr, cap);
 }
 
 extern "C" int ocr_tiff_time_deflate(const ocr_tiff_coded* coded, int device_id, int iters, double ms[3]) {
   if (!coded || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_deflate_batch(&coded, 1, device_id, iters, ms);
+  return time_frames3<TiffDeflateRoute>(&coded, 1, device_id, iters, ms);
 }
 
 extern "C" int ocr_tiff_time_deflate_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
   if (!coded || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_deflate_batch(coded, count, device_id, iters, ms);
+  return time_frames3<TiffDeflateRoute>(coded, count, device_id, iters, ms);
 }
 
 extern "C" int ocr_tiff_expand(const ocr_tiff_coded* coded, int device_id, uint8_t* out, size_t cap) {
@@ -454,46 +394,29 @@ extern "C" int ocr_tiff_expand(const ocr_tiff_coded* coded, int device_id, uint8
 }
 
 extern "C" int ocr_tiff_decode_coded(const ocr_tiff_coded* coded, int device_id, uint8_t* bgr, size_t cap) {
-  if (!coded || !bgr) return fail(OCR_ERR_ARG, "null argument");
-  if (const char* fault = tiff_coded_fault(*coded)) return fail(OCR_ERR_ARG, fault);
-  const size_t bytes = (size_t)coded->frame.width * coded->frame.height * 3;
-  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  TiffScratch sc;
-  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return tiff_coded_decode_async(&coded, 1, dst, sc, nullptr, err); });
+  return decode_frame<TiffCodedRoute>(coded, device_id, bgr, cap);
 }
 
 extern "C" int ocr_tiff_time_coded(const ocr_tiff_coded* coded, int device_id, int iters, double ms[3]) {
   if (!coded || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_coded_batch(&coded, 1, device_id, iters, ms);
+  return time_frames3<TiffCodedRoute>(&coded, 1, device_id, iters, ms);
 }
 
 extern "C" int ocr_tiff_time_coded_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]) {
   if (!coded || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_coded_batch(coded, count, device_id, iters, ms);
+  return time_frames3<TiffCodedRoute>(coded, count, device_id, iters, ms);
 }
 
-extern "C" int ocr_tiff_decode(const ocr_tiff_frame* frame, int device_id, uint8_t* bgr, size_t cap) {
-  if (!frame || !bgr) return fail(OCR_ERR_ARG, "null argument");
-  // (the descriptor first: a bad one is an argument error wherever the call is made)
-  if (const char* fault = tiff_frame_fault(*frame)) return fail(OCR_ERR_ARG, fault);
-  const size_t bytes = (size_t)frame->width * frame->height * 3;
-  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  TiffScratch sc;
-  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return tiff_decode_async(&frame, 1, dst, sc, nullptr, err); });
-}
+extern "C" int ocr_tiff_decode(const ocr_tiff_frame* frame, int device_id, uint8_t* bgr, size_t cap) { return decode_frame<TiffRoute>(frame, device_id, bgr, cap); }
 
 extern "C" int ocr_tiff_time(const ocr_tiff_frame* frame, int device_id, int iters, double ms[2]) {
   if (!frame || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_batch(&frame, 1, device_id, iters, ms);
+  return time_frames<TiffRoute>(&frame, 1, device_id, iters, ms);
 }
 
 extern "C" int ocr_tiff_time_batch(const ocr_tiff_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
   if (!frames || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_batch(frames, count, device_id, iters, ms);
+  return time_frames<TiffRoute>(frames, count, device_id, iters, ms);
 }
 
 // measurement aid (decode_tool --time): the device time of one plain copy KERNEL over `bytes` (16 bytes a lane, grid stride:

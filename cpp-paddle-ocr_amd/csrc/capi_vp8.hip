@@ -89,49 +89,17 @@ int vp8_decode_async(const ocr_vp8_frame* const* imgs, int count, uint8_t* const
 using namespace ocr;
 
 namespace {
-
-int time_batch(const ocr_vp8_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
-  for (int i = 0; i < count; ++i) {
-    if (!frames[i]) return fail(OCR_ERR_ARG, "null argument");
-    if (const char* fault = vp8_frame_fault(*frames[i])) return fail(OCR_ERR_ARG, fault);
-  }
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  std::vector<DevBuf<uint8_t>> out((size_t)count);
-  std::vector<uint8_t*> dst((size_t)count);
-  std::string err;
-  for (int i = 0; i < count; ++i) {
-    if (!out[i].ensure((size_t)frames[i]->width * frames[i]->height * 3, err)) return fail(OCR_ERR_DEVICE, err);
-    dst[i] = out[i].p;
-  }
-  Vp8Scratch sc;
-  Vp8Launch L;
-  rc = vp8_decode_async(frames, count, dst.data(), sc, nullptr, err, &L);  // uploads, and the first (untimed) launches
-  if (rc) return fail(rc, err);
-  return time_phases(iters, ms, [&] { return hipMemcpyAsync(sc.data.p, sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); },
-                     [&] { vp8_relaunch(sc, L, nullptr); return hipSuccess; });
-}
-
+struct Vp8Route : PlainRoute<ocr_vp8_frame, Vp8Scratch, Vp8Launch, vp8_frame_fault, vp8_decode_async, vp8_relaunch> {};
 }  // namespace
 
-extern "C" int ocr_vp8_decode(const ocr_vp8_frame* frame, int device_id, uint8_t* bgr, size_t cap) {
-  if (!frame || !bgr) return fail(OCR_ERR_ARG, "null argument");
-  // (the descriptor first: a bad one is an argument error wherever the call is made)
-  if (const char* fault = vp8_frame_fault(*frame)) return fail(OCR_ERR_ARG, fault);
-  const size_t bytes = (size_t)frame->width * frame->height * 3;
-  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
-  int rc = ocr_rt_init(device_id);
-  if (rc) return rc;
-  Vp8Scratch sc;
-  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return vp8_decode_async(&frame, 1, dst, sc, nullptr, err); });
-}
+extern "C" int ocr_vp8_decode(const ocr_vp8_frame* frame, int device_id, uint8_t* bgr, size_t cap) { return decode_frame<Vp8Route>(frame, device_id, bgr, cap); }
 
 extern "C" int ocr_vp8_time(const ocr_vp8_frame* frame, int device_id, int iters, double ms[2]) {
   if (!frame || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_batch(&frame, 1, device_id, iters, ms);
+  return time_frames<Vp8Route>(&frame, 1, device_id, iters, ms);
 }
 
 extern "C" int ocr_vp8_time_batch(const ocr_vp8_frame* const* frames, int count, int device_id, int iters, double ms[2]) {
   if (!frames || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
-  return time_batch(frames, count, device_id, iters, ms);
+  return time_frames<Vp8Route>(frames, count, device_id, iters, ms);
 }

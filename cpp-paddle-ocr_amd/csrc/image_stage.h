@@ -1,5 +1,6 @@
-// What the image-format back-ends (JPEG, PNG, BMP / PNM) and the pipeline's staging slots share on the host side: the pinned
-// staging buffer, the threaded host copy into it, the two-phase timing loop and the single-frame decode.
+// What the image-format back-ends and the pipeline's staging slots share on the host side: the pinned staging buffer, the
+// threaded host copy into it, the two-phase timing loop, the single-frame decode, and the bodies of a format route's C entry
+// points (decode_frame, time_frames, time_frames3 over a Route).
 #pragma once
 #include <algorithm>
 #include <string>
@@ -87,6 +88,96 @@ int decode_one(size_t bytes, uint8_t* bgr, Decode&& decode) {
   if (rc) return fail(rc, err);
   CAPI_HIP(g_memcpy(bgr, out.p, bytes, hipMemcpyDeviceToHost));
   return OCR_OK;
+}
+
+// ---- The C entry points of a format route (ocr_X_decode, ocr_X_time, ocr_X_time_batch) are the bodies below over a Route,
+// which its capi_*.hip declares next to its *_decode_async:
+//   Frame, Scratch, Launch                          the descriptor and the route's *Scratch and *Launch
+//   const char* fault(const Frame&)                 why a frame is refused, nullptr when it is sound
+//   int rows(const Frame&), cols(const Frame&)      of the decoded image
+//   int decode(frames, count, dst, sc, err, &L)     the route's *_decode_async on the null stream
+//   uint8_t* uploaded(sc, L)                        where the upload went: L.bytes from sc.stage.p
+//   void pixels(sc, L)                              the pixel stage again
+//   hipError_t middle(sc, L)                        a three-phase route: what runs between upload and pixel stage, again
+
+// The routes whose frame says height and width, whose upload goes to sc.data and whose *_relaunch takes (sc, L, stream).
+template <class F, class S, class L, const char* (*Fault)(const F&), int (*Decode)(const F* const*, int, uint8_t* const*, S&, hipStream_t, std::string&, L*),
+          void (*Relaunch)(const S&, const L&, hipStream_t)>
+struct PlainRoute {
+  using Frame = F;
+  using Scratch = S;
+  using Launch = L;
+  static const char* fault(const F& f) { return Fault(f); }
+  static int rows(const F& f) { return f.height; }
+  static int cols(const F& f) { return f.width; }
+  static int decode(const F* const* frames, int count, uint8_t* const* dst, S& sc, std::string& err, L* launched) {
+    return Decode(frames, count, dst, sc, nullptr, err, launched);
+  }
+  static uint8_t* uploaded(S& sc, const L&) { return sc.data.p; }
+  static void pixels(S& sc, const L& launched) { Relaunch(sc, launched, nullptr); }
+};
+
+template <class Route>
+int decode_frame(const typename Route::Frame* frame, int device_id, uint8_t* bgr, size_t cap) {
+  if (!frame || !bgr) return fail(OCR_ERR_ARG, "null argument");
+  // (the descriptor first: a bad one is an argument error wherever the call is made)
+  if (const char* fault = Route::fault(*frame)) return fail(OCR_ERR_ARG, fault);
+  const size_t bytes = (size_t)Route::rows(*frame) * Route::cols(*frame) * 3;
+  if (bytes > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
+  const int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  typename Route::Scratch sc;
+  return decode_one(bytes, bgr, [&](uint8_t* const* dst, std::string& err) { return Route::decode(&frame, 1, dst, sc, err, nullptr); });
+}
+
+// A batch decoded once on the null stream into buffers of its own - the uploads, and the first (untimed) launches - and
+// what the timed repetitions need of it.
+template <class Route>
+struct TimedBatch {
+  std::vector<DevBuf<uint8_t>> out;
+  typename Route::Scratch sc;
+  typename Route::Launch L;
+  int start(const typename Route::Frame* const* frames, int count, int device_id) {
+    for (int i = 0; i < count; ++i) {
+      if (!frames[i]) return fail(OCR_ERR_ARG, "null argument");
+      if (const char* fault = Route::fault(*frames[i])) return fail(OCR_ERR_ARG, fault);
+    }
+    int rc = ocr_rt_init(device_id);
+    if (rc) return rc;
+    out.resize((size_t)count);
+    std::vector<uint8_t*> dst((size_t)count);
+    std::string err;
+    for (int i = 0; i < count; ++i) {
+      if (!out[i].ensure((size_t)Route::rows(*frames[i]) * Route::cols(*frames[i]) * 3, err)) return fail(OCR_ERR_DEVICE, err);
+      dst[i] = out[i].p;
+    }
+    rc = Route::decode(frames, count, dst.data(), sc, err, &L);
+    return rc ? fail(rc, err) : OCR_OK;
+  }
+  hipError_t upload() { return hipMemcpyAsync(Route::uploaded(sc, L), sc.stage.p, L.bytes, hipMemcpyHostToDevice, nullptr); }
+};
+
+// ms: upload, pixel stage
+template <class Route>
+int time_frames(const typename Route::Frame* const* frames, int count, int device_id, int iters, double ms[2]) {
+  TimedBatch<Route> B;
+  if (const int rc = B.start(frames, count, device_id)) return rc;
+  return time_phases(iters, ms, [&] { return B.upload(); }, [&] { Route::pixels(B.sc, B.L); return hipSuccess; });
+}
+
+// ms: upload, Route::middle, pixel stage
+template <class Route>
+int time_frames3(const typename Route::Frame* const* frames, int count, int device_id, int iters, double ms[3]) {
+  TimedBatch<Route> B;
+  int rc = B.start(frames, count, device_id);
+  if (rc) return rc;
+  double t[2];
+  rc = time_phases(iters, t, [&] { return B.upload(); }, [&] { return Route::middle(B.sc, B.L); });
+  if (rc) return rc;
+  ms[0] = t[0]; ms[1] = t[1];
+  rc = time_phases(iters, t, [&] { Route::pixels(B.sc, B.L); return hipGetLastError(); }, [] { return hipSuccess; });
+  ms[2] = t[0];
+  return rc;
 }
 
 }  // namespace ocr

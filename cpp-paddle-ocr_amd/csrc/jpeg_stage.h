@@ -20,7 +20,7 @@ struct JpegScratch {
 // colour conversion + EXIF orientation on `s`; image i is written as packed BGR to dst[i] (device), jpeg_out_rows x
 // jpeg_out_cols.  launched: the kernels' launch parameters, for a caller that repeats them (ocr_jpeg_time).
 // Returns an OCR_* code.
-int jpeg_decode_async(const ocr_jpeg_frame* imgs, int count, uint8_t* const* dst, JpegScratch& sc, hipStream_t s, std::string& err,
+int jpeg_decode_async(const ocr_jpeg_frame* const* imgs, int count, uint8_t* const* dst, JpegScratch& sc, hipStream_t s, std::string& err,
                       JpegLaunch* launched = nullptr);
 bool jpeg_img_valid(const ocr_jpeg_img& im);
 // why a frame is refused, nullptr when it is sound

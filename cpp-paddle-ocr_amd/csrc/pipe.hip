@@ -11,13 +11,7 @@
 
 #include "capi_common.h"
 #include "crop.h"
-#include "jpeg_stage.h"
-#include "png_stage.h"
-#include "raw_stage.h"
-#include "tiff_stage.h"
-#include "webp_stage.h"
-#include "vp8_stage.h"
-#include "j2k_stage.h"
+#include "frame_kinds.h"
 #include "stages.h"
 
 using namespace ocr;
@@ -430,13 +424,7 @@ struct ocr_pipe {
   int device = 0;
   StageSlot slots[2];
   hipStream_t copy_stream = nullptr;
-  JpegScratch jpeg;
-  PngScratch png;
-  RawScratch raw;
-  TiffScratch tiff, tiff_coded, tiff_deflate;  // expanded frames, coded ones and Deflate ones are three batches: their uploads differ
-  WebpScratch webp;
-  Vp8Scratch vp8;
-  J2kScratch j2k, j2k_coded;  // coefficient-form frames and coded ones are two batches: their uploads differ
+  FrameScratch frame_scratch;
   DevBuf<uint8_t> work;  // the requests' clones (OCRRequest copies the Mat, ocr_worker.h:28-29): cls rotates in place on them
   // Two batches in flight (round 5, ocr_pipe_run_device_on / ocr_pipe_run_staged_on): a call that names a chain runs its WHOLE
   // batch on that chain's worker, with a clone buffer of the chain's own; calls on different chains may run concurrently from
@@ -507,71 +495,30 @@ struct ocr_pipe {
     return OCR_OK;
   }
 
-  // ---- stage a batch of JPEG coefficients, inflated PNG streams, stored BMP / PNM rows, expanded TIFF chunks and entropy-decoded
-  // WebP images, VP8 and JPEG 2000 frame descriptors (coefficients or coded blocks) and coded TIFF chunks, in any mix: the seven pixel stages run on the copy stream, into the slot.  Image i is frames[i], a tagged descriptor (validated by the caller
-  // before the sizes are used - a refused batch leaves the slot as it was: a known kind, and a sound descriptor)
+  // ---- stage a batch of tagged frame descriptors, of any kinds in any mix: the frames of a kind are decoded by that kind's
+  // row of kFrameKinds, on the copy stream, into the slot.  The caller has validated every frame (a known kind, a sound
+  // descriptor) before the sizes are used: a batch refused there leaves the slot as it was.
   int stage_coded(int si, const ocr_coded_frame* frames, int count, std::string& err) {
     StageSlot& S = slots[si];
-    auto jp = [&](int i) { return (const ocr_jpeg_frame*)frames[i].frame; };
-    auto pn = [&](int i) { return (const ocr_png_frame*)frames[i].frame; };
-    auto rw = [&](int i) { return (const ocr_raw_frame*)frames[i].frame; };
-    auto tf = [&](int i) { return (const ocr_tiff_frame*)frames[i].frame; };
-    auto wf = [&](int i) { return (const ocr_webp_frame*)frames[i].frame; };
-    auto vf = [&](int i) { return (const ocr_vp8_frame*)frames[i].frame; };
-    auto kf = [&](int i) { return (const ocr_j2k_frame*)frames[i].frame; };
-    int rc = layout(S, count, [&](int i, int& r, int& c) {
-      // the oriented size: a 40 x 72 image and a 72 x 40 one that EXIF turns by 90 degrees share a size group and a det pass
-      switch (frames[i].kind) {
-        case OCR_FRAME_JPEG: r = jpeg_out_rows(*jp(i)); c = jpeg_out_cols(*jp(i)); break;
-        case OCR_FRAME_PNG: r = pn(i)->height; c = pn(i)->width; break;
-        case OCR_FRAME_RAW: r = rw(i)->height; c = rw(i)->width; break;
-        case OCR_FRAME_TIFF: case OCR_FRAME_TIFF_CODED: case OCR_FRAME_TIFF_DEFLATE: r = tf(i)->height; c = tf(i)->width; break;  // (an ocr_tiff_coded starts with its ocr_tiff_frame)
-        case OCR_FRAME_WEBP: r = wf(i)->height; c = wf(i)->width; break;
-        case OCR_FRAME_VP8: r = vf(i)->height; c = vf(i)->width; break;
-        default: r = kf(i)->height; c = kf(i)->width; break;  // (an ocr_j2k_coded starts with its ocr_j2k_frame)
-      }
-    }, err);
+    int rc = layout(S, count, [&](int i, int& r, int& c) { kFrameKinds[frames[i].kind].size(frames[i].frame, r, c); }, err);
     if (rc) return rc;
-    std::vector<ocr_jpeg_frame> jf;
-    std::vector<const ocr_png_frame*> pf;
-    std::vector<const ocr_raw_frame*> rf;
-    std::vector<const ocr_tiff_frame*> tff;
-    std::vector<const ocr_webp_frame*> wff;
-    std::vector<const ocr_vp8_frame*> vff;
-    std::vector<const ocr_j2k_frame*> kff;
-    std::vector<const ocr_j2k_coded*> kcf;
-    std::vector<const ocr_tiff_coded*> tcf, tdf;
-    std::vector<uint8_t*> tddst;
-    std::vector<int> tdid;  // a Deflate frame's place in the batch: what a refusal names
-    std::vector<uint8_t*> jdst, pdst, rdst, tdst, wdst, vdst, kdst, kcdst, tcdst;
-    for (int k = 0; k < count; ++k) {
-      const int i = S.imgs[k].orig;
-      uint8_t* d = S.dev.p + S.imgs[k].off;
-      switch (frames[i].kind) {
-        case OCR_FRAME_JPEG: jf.push_back(*jp(i)); jdst.push_back(d); break;
-        case OCR_FRAME_PNG: pf.push_back(pn(i)); pdst.push_back(d); break;
-        case OCR_FRAME_RAW: rf.push_back(rw(i)); rdst.push_back(d); break;
-        case OCR_FRAME_TIFF: tff.push_back(tf(i)); tdst.push_back(d); break;
-        case OCR_FRAME_WEBP: wff.push_back(wf(i)); wdst.push_back(d); break;
-        case OCR_FRAME_VP8: vff.push_back(vf(i)); vdst.push_back(d); break;
-        case OCR_FRAME_J2K_CODED: kcf.push_back((const ocr_j2k_coded*)frames[i].frame); kcdst.push_back(d); break;
-        case OCR_FRAME_TIFF_CODED: tcf.push_back((const ocr_tiff_coded*)frames[i].frame); tcdst.push_back(d); break;
-        case OCR_FRAME_TIFF_DEFLATE: tdf.push_back((const ocr_tiff_coded*)frames[i].frame); tddst.push_back(d); tdid.push_back(i); break;
-        default: kff.push_back(kf(i)); kdst.push_back(d); break;
-      }
+    struct Bucket {
+      std::vector<const void*> frames;
+      std::vector<uint8_t*> dst;
+      std::vector<int> ids;  // a frame's place in the batch: what a refusal names
+    } bucket[kFrameKindCount];
+    for (const StageSlot::Img& im : S.imgs) {
+      Bucket& b = bucket[frames[im.orig].kind];
+      b.frames.push_back(frames[im.orig].frame);
+      b.dst.push_back(S.dev.p + im.off);
+      b.ids.push_back(im.orig);
     }
-    // (Deflate frames first: theirs is the one route that can refuse a stream, and it does so before anything else is enqueued)
-    if (!tdf.empty()) rc = tiff_deflate_decode_async(tdf.data(), (int)tdf.size(), tddst.data(), tiff_deflate, copy_stream, err, nullptr, true, nullptr, tdid.data());
-    if (!rc && !jf.empty()) rc = jpeg_decode_async(jf.data(), (int)jf.size(), jdst.data(), jpeg, copy_stream, err);
-    if (!rc && !pf.empty()) rc = png_decode_async(pf.data(), (int)pf.size(), pdst.data(), png, copy_stream, err);
-    if (!rc && !rf.empty()) rc = raw_decode_async(rf.data(), (int)rf.size(), rdst.data(), raw, copy_stream, err);
-    if (!rc && !tff.empty()) rc = tiff_decode_async(tff.data(), (int)tff.size(), tdst.data(), tiff, copy_stream, err);
-    if (!rc && !wff.empty()) rc = webp_decode_async(wff.data(), (int)wff.size(), wdst.data(), webp, copy_stream, err);
-    if (!rc && !vff.empty()) rc = vp8_decode_async(vff.data(), (int)vff.size(), vdst.data(), vp8, copy_stream, err);
-    if (!rc && !kff.empty()) rc = j2k_decode_async(kff.data(), (int)kff.size(), kdst.data(), j2k, copy_stream, err);
-    if (!rc && !kcf.empty()) rc = j2k_coded_decode_async(kcf.data(), (int)kcf.size(), kcdst.data(), j2k_coded, copy_stream, err);
-    if (!rc && !tcf.empty()) rc = tiff_coded_decode_async(tcf.data(), (int)tcf.size(), tcdst.data(), tiff_coded, copy_stream, err);
-    if (rc) return rc;
+    for (int kind : kFrameLaunchOrder) {
+      const Bucket& b = bucket[kind];
+      if (b.frames.empty()) continue;
+      rc = kFrameKinds[kind].decode(b.frames.data(), (int)b.frames.size(), b.dst.data(), frame_scratch, copy_stream, err, b.ids.data());
+      if (rc) return rc;
+    }
     if (hipEventRecord(S.ready, copy_stream) != hipSuccess) { err = "hipEventRecord failed"; return OCR_ERR_DEVICE; }
     S.staged = true;
     return OCR_OK;
@@ -907,20 +854,8 @@ int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, i
   for (int i = 0; i < count; ++i) {
     const void* f = frames[i].frame;
     if (!f) return fail(OCR_ERR_ARG, "null frame in the batch");
-    const char* fault;
-    switch (frames[i].kind) {
-      case OCR_FRAME_JPEG: fault = jpeg_frame_fault(*(const ocr_jpeg_frame*)f); break;
-      case OCR_FRAME_PNG: fault = png_frame_fault(*(const ocr_png_frame*)f); break;
-      case OCR_FRAME_RAW: fault = raw_frame_fault(*(const ocr_raw_frame*)f); break;
-      case OCR_FRAME_TIFF: fault = tiff_frame_fault(*(const ocr_tiff_frame*)f); break;
-      case OCR_FRAME_WEBP: fault = webp_frame_fault(*(const ocr_webp_frame*)f); break;
-      case OCR_FRAME_VP8: fault = vp8_frame_fault(*(const ocr_vp8_frame*)f); break;
-      case OCR_FRAME_J2K: fault = j2k_frame_fault(*(const ocr_j2k_frame*)f); break;
-      case OCR_FRAME_J2K_CODED: fault = j2k_coded_fault(*(const ocr_j2k_coded*)f); break;
-      case OCR_FRAME_TIFF_CODED: fault = tiff_coded_fault(*(const ocr_tiff_coded*)f); break;
-      case OCR_FRAME_TIFF_DEFLATE: fault = tiff_deflate_fault(*(const ocr_tiff_coded*)f); break;
-      default: fault = "frame kind is not an ocr_frame_kind"; break;
-    }
+    const int kind = frames[i].kind;
+    const char* fault = kind >= 0 && kind < kFrameKindCount ? kFrameKinds[kind].fault(f) : "frame kind is not an ocr_frame_kind";
     if (fault) return fail(OCR_ERR_ARG, fault);
   }
   return stage_validated(h, slot, std::vector<ocr_coded_frame>(frames, frames + count));

@@ -12,6 +12,7 @@
 // decode_tool --stage <model dir> <image file> <out.ppm> [...]: all files (JPEG, PNG, BMP, PNM in any mix) as ONE batch
 // through ocr_pipe_stage_frames into a pipeline's staging slot, each staged image read back (ocr_pipe_slot_image) and written.
 // A "--" between pairs starts a further batch: the batches go through the same slot of the same pipeline, one after the other.
+// Per batch one JSON line on stdout, "kinds": the ocr_frame_kind each file is staged as.
 // decode_tool --stage-ways <model dir> <jpeg file> <out.ppm> <jpeg file> <out.ppm> [...]: one batch of JPEGs that ocr_jpeg_img
 // can hold through each of ocr_pipe_stage_jpeg, _jpeg_frames, _coded and _frames; after each, the same batch with an unsound
 // second image must be refused with OCR_ERR_ARG, and the slot is read back after that: <out.ppm>.jpeg, .jpeg_frames, .coded, .frames.
@@ -72,7 +73,24 @@ static ocr_jpeg_img jpeg_desc(const PaddleOCR::jpeg::Coefs& j) {
   return d;
 }
 
+// --time: `n` copies of the descriptor `d` as one batch through ocr_X_time_batch (n == 1: through ocr_X_time) into ms, then,
+// where host_ms is given, pixels() - the format's stage on one host thread - for as many frames, per repetition.  false
+// after reporting a failure.
+template <class D, class Pixels = void (*)()>
+static bool time_copies(const D& d, int n, int iters, int (*one)(const D*, int, int, double*), int (*many)(const D* const*, int, int, int, double*),
+                        double* ms, Pixels pixels = nullptr, double* host_ms = nullptr) {
+  const std::vector<const D*> all((size_t)n, &d);
+  if ((n > 1 ? many(all.data(), n, 0, iters, ms) : one(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return false; }
+  if (!host_ms) return true;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int i = 0; i < iters; ++i)
+    for (int k = 0; k < n; ++k) pixels();
+  *host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+  return true;
+}
+
 static int time_device(int iters, const char* in, int batch) {
+  const int n = batch > 1 ? batch : 1;
   std::vector<uint8_t> bytes;
   PaddleOCR::Image im;
   if (PaddleOCR::ipc::read_file(in, bytes) && bytes.size() > 8 && bytes[0] == 0x89 && bytes[1] == 'P') {
@@ -81,11 +99,10 @@ static int time_device(int iters, const char* in, int batch) {
     im.rows = f->height; im.cols = f->width;
     im.png = f;
     const ocr_png_frame d = im.png_frame();
-    std::vector<const ocr_png_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
     double ms[2];
-    if ((batch > 1 ? ocr_png_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_png_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    if (!time_copies(d, n, iters, ocr_png_time, ocr_png_time_batch, ms)) return 1;
     printf("{\"size\": [%d, %d], \"color_type\": %d, \"bit_depth\": %d, \"interlace\": %d, \"segments\": %d, \"batch\": %d, \"iters\": %d, "
-           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f}\n", d.height, d.width, d.color_type, d.bit_depth, d.interlace, d.nsegments, (int)all.size(), iters, ms[0], ms[1]);
+           "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f}\n", d.height, d.width, d.color_type, d.bit_depth, d.interlace, d.nsegments, n, iters, ms[0], ms[1]);
     return 0;
   }
   if (PaddleOCR::ipc::is_j2k(bytes.data(), bytes.size())) {
@@ -96,14 +113,9 @@ static int time_device(int iters, const char* in, int batch) {
     im.rows = v->height; im.cols = v->width;
     im.j2k = v;
     const ocr_j2k_frame d = im.j2k_frame();
-    std::vector<const ocr_j2k_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
-    double ms[2];
-    if ((batch > 1 ? ocr_j2k_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_j2k_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    double ms[2], host_ms;
     std::vector<uint8_t> px;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < iters; ++i)
-      for (size_t k = 0; k < all.size(); ++k) PaddleOCR::j2k::pixels(*v, px);
-    const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+    if (!time_copies(d, n, iters, ocr_j2k_time, ocr_j2k_time_batch, ms, [&] { PaddleOCR::j2k::pixels(*v, px); }, &host_ms)) return 1;
     // the coded route
     auto c = std::make_shared<PaddleOCR::j2k::Coded>();
     const auto c0 = std::chrono::steady_clock::now();
@@ -111,15 +123,14 @@ static int time_device(int iters, const char* in, int batch) {
     const double tier2_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
     im.j2k_coded = c;
     const ocr_j2k_coded cd = im.j2k_coded_frame();
-    std::vector<const ocr_j2k_coded*> call(all.size(), &cd);
     double cms[3];
-    if ((batch > 1 ? ocr_j2k_time_coded_batch(call.data(), (int)call.size(), 0, iters, cms) : ocr_j2k_time_coded(&cd, 0, iters, cms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    if (!time_copies(cd, n, iters, ocr_j2k_time_coded, ocr_j2k_time_coded_batch, cms)) return 1;
     printf("{\"size\": [%d, %d], \"j2k\": true, \"transform\": \"%s\", \"levels\": %d, \"batch\": %d, \"iters\": %d, "
            "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"host_tier1_ms_per_image\": %.5f, \"descriptor_bytes\": %zu, \"bytes_out\": %zu, "
            "\"coded_upload_ms\": %.5f, \"tier1_stage_ms\": %.5f, \"coded_pixel_stage_ms\": %.5f, \"coded_descriptor_bytes\": %zu, \"code_blocks\": %zu, "
            "\"host_tier2_ms_per_image\": %.5f}\n",
-           d.height, d.width, d.transform ? "9/7" : "5/3", v->tcs[0].levels, (int)all.size(), iters, ms[0], ms[1], host_ms, parse_ms,
-           v->coeffs.size() * 4 + v->steps.size() * 4 + v->tcs.size() * sizeof(PaddleOCR::j2k::TileComp), (size_t)d.width * d.height * 3 * all.size(),
+           d.height, d.width, d.transform ? "9/7" : "5/3", v->tcs[0].levels, n, iters, ms[0], ms[1], host_ms, parse_ms,
+           v->coeffs.size() * 4 + v->steps.size() * 4 + v->tcs.size() * sizeof(PaddleOCR::j2k::TileComp), (size_t)d.width * d.height * 3 * n,
            cms[0], cms[1], cms[2], c->bytes.size() + c->cblks.size() * sizeof(PaddleOCR::j2k::CodedBlock) + v->steps.size() * 4 + v->tcs.size() * sizeof(PaddleOCR::j2k::TileComp),
            c->cblks.size(), tier2_ms);
     return 0;
@@ -130,18 +141,13 @@ static int time_device(int iters, const char* in, int batch) {
       im.rows = v->height; im.cols = v->width;
       im.vp8 = v;
       const ocr_vp8_frame d = im.vp8_frame();
-      std::vector<const ocr_vp8_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
-      double ms[2];
-      if ((batch > 1 ? ocr_vp8_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_vp8_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+      double ms[2], host_ms;
       std::vector<uint8_t> px;
-      const auto t0 = std::chrono::steady_clock::now();
-      for (int i = 0; i < iters; ++i)
-        for (size_t k = 0; k < all.size(); ++k) PaddleOCR::vp8::pixels(*v, px);
-      const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+      if (!time_copies(d, n, iters, ocr_vp8_time, ocr_vp8_time_batch, ms, [&] { PaddleOCR::vp8::pixels(*v, px); }, &host_ms)) return 1;
       printf("{\"size\": [%d, %d], \"lossy\": true, \"filter_type\": %d, \"batch\": %d, \"iters\": %d, "
              "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"descriptor_bytes\": %zu, \"bytes_out\": %zu}\n",
-             d.height, d.width, d.filter_type, (int)all.size(), iters, ms[0], ms[1], host_ms, v->mbs.size() * sizeof(PaddleOCR::vp8::Mb) + v->coeffs.size() * 2,
-             (size_t)d.width * d.height * 3 * all.size());
+             d.height, d.width, d.filter_type, n, iters, ms[0], ms[1], host_ms, v->mbs.size() * sizeof(PaddleOCR::vp8::Mb) + v->coeffs.size() * 2,
+             (size_t)d.width * d.height * 3 * n);
       return 0;
     }
     auto f = std::make_shared<PaddleOCR::webp::Frame>();
@@ -149,21 +155,16 @@ static int time_device(int iters, const char* in, int batch) {
     im.rows = f->height; im.cols = f->width;
     im.webp = f;
     const ocr_webp_frame d = im.webp_frame();
-    std::vector<const ocr_webp_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
-    double ms[2];
-    if ((batch > 1 ? ocr_webp_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_webp_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    double ms[2], host_ms;
     std::vector<uint8_t> px;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < iters; ++i)
-      for (size_t k = 0; k < all.size(); ++k) PaddleOCR::webp::pixels(*f, px);
-    const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+    if (!time_copies(d, n, iters, ocr_webp_time, ocr_webp_time_batch, ms, [&] { PaddleOCR::webp::pixels(*f, px); }, &host_ms)) return 1;
     size_t in = f->argb.size() * 4;
     std::string kinds;
     for (const auto& t : f->transforms) { in += t.data.size() * 4; kinds += (kinds.empty() ? "" : ", ") + std::to_string(t.kind); }
     printf("{\"size\": [%d, %d], \"coded_width\": %d, \"transforms\": [%s], \"batch\": %d, \"iters\": %d, "
            "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"bytes_in\": %zu, \"bytes_out\": %zu}\n",
-           d.height, d.width, PaddleOCR::webp::coded_width(*f), kinds.c_str(), (int)all.size(), iters, ms[0], ms[1], host_ms, in * all.size(),
-           (size_t)d.width * d.height * 3 * all.size());
+           d.height, d.width, PaddleOCR::webp::coded_width(*f), kinds.c_str(), n, iters, ms[0], ms[1], host_ms, in * n,
+           (size_t)d.width * d.height * 3 * n);
     return 0;
   }
   if (PaddleOCR::ipc::is_tiff(bytes.data(), bytes.size())) {
@@ -172,16 +173,11 @@ static int time_device(int iters, const char* in, int batch) {
     im.rows = f->height; im.cols = f->width;
     im.tiff = f;
     const ocr_tiff_frame d = im.tiff_frame();
-    std::vector<const ocr_tiff_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
-    double ms[2];
-    if ((batch > 1 ? ocr_tiff_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_tiff_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    double ms[2], host_ms;
     std::vector<uint8_t> px;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < iters; ++i)
-      for (size_t k = 0; k < all.size(); ++k) PaddleOCR::tiff::pixels(*f, px);
-    const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+    if (!time_copies(d, n, iters, ocr_tiff_time, ocr_tiff_time_batch, ms, [&] { PaddleOCR::tiff::pixels(*f, px); }, &host_ms)) return 1;
     // the yardstick of the same run: a plain copy kernel that reads and writes as many bytes in all as the pixel stage (chunks in, BGR out)
-    const size_t in = f->data.size() * all.size(), out = (size_t)d.width * d.height * 3 * all.size(), half = (in + out) / 2;
+    const size_t in = f->data.size() * n, out = (size_t)d.width * d.height * 3 * n, half = (in + out) / 2;
     double copy_ms = -1;
     void *a = nullptr, *b = nullptr;
     if (ocr_dev_alloc(&a, half) == OCR_OK && ocr_dev_alloc(&b, half) == OCR_OK) {
@@ -194,7 +190,7 @@ static int time_device(int iters, const char* in, int batch) {
     if (b) ocr_dev_free(b);
     printf("{\"size\": [%d, %d], \"photometric\": %d, \"bits\": %d, \"samples\": %d, \"planar\": %d, \"predictor\": %d, \"tile\": [%d, %d], \"batch\": %d, \"iters\": %d, "
            "\"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, \"host_pixels_ms\": %.5f, \"bytes_in\": %zu, \"bytes_out\": %zu, \"copy_ms\": %.5f",
-           d.height, d.width, d.photometric, d.bits_per_sample, d.samples_per_pixel, d.planar, d.predictor, d.tile_width, d.tile_height, (int)all.size(), iters,
+           d.height, d.width, d.photometric, d.bits_per_sample, d.samples_per_pixel, d.planar, d.predictor, d.tile_width, d.tile_height, n, iters,
            ms[0], ms[1], host_ms, in, out, copy_ms);
     // the coded route (Compression 1, LZW, PackBits): upload of the coded chunks, expansion and pixel stage on the device, and
     // what the host pays either way, per image on one thread: the extent scan (both routes) and tiff::expand (the =1 route)
@@ -202,9 +198,8 @@ static int time_device(int iters, const char* in, int batch) {
     if (PaddleOCR::tiff::parse_coded(bytes.data(), bytes.size(), *c) == PaddleOCR::tiff::kCoded && c->frame.device_ok) {
       im.tiff_coded = c;
       const ocr_tiff_coded cd = im.tiff_coded_frame();
-      std::vector<const ocr_tiff_coded*> call(all.size(), &cd);
       double cms[3];
-      if ((batch > 1 ? ocr_tiff_time_coded_batch(call.data(), (int)call.size(), 0, iters, cms) : ocr_tiff_time_coded(&cd, 0, iters, cms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+      if (!time_copies(cd, n, iters, ocr_tiff_time_coded, ocr_tiff_time_coded_batch, cms)) return 1;
       PaddleOCR::tiff::Geometry g;
       const int reps = iters < 3 ? 3 : iters;
       auto t1 = std::chrono::steady_clock::now();
@@ -224,9 +219,8 @@ static int time_device(int iters, const char* in, int batch) {
       // against tiff::inflate_all - zlib on one thread - per image
       im.tiff_deflate = c;
       const ocr_tiff_coded cd = im.tiff_deflate_frame();
-      std::vector<const ocr_tiff_coded*> call(all.size(), &cd);
       double cms[3];
-      if ((batch > 1 ? ocr_tiff_time_deflate_batch(call.data(), (int)call.size(), 0, iters, cms) : ocr_tiff_time_deflate(&cd, 0, iters, cms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+      if (!time_copies(cd, n, iters, ocr_tiff_time_deflate, ocr_tiff_time_deflate_batch, cms)) return 1;
       const int reps = iters < 3 ? 3 : iters;
       PaddleOCR::tiff::Frame ef;
       bool sound = true;
@@ -247,16 +241,11 @@ static int time_device(int iters, const char* in, int batch) {
     im.rows = f->height; im.cols = f->width;
     im.raw = f;
     const ocr_raw_frame d = im.raw_frame();
-    std::vector<const ocr_raw_frame*> all((size_t)(batch > 1 ? batch : 1), &d);
-    double ms[2];
-    if ((batch > 1 ? ocr_raw_time_batch(all.data(), (int)all.size(), 0, iters, ms) : ocr_raw_time(&d, 0, iters, ms)) != OCR_OK) { fprintf(stderr, "device timing failed: %s\n", ocr_last_error()); return 1; }
+    double ms[2], host_ms;
     std::vector<uint8_t> px;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; i < iters; ++i)
-      for (size_t k = 0; k < all.size(); ++k) PaddleOCR::raw::pixels(*f, px);
-    const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / iters;
+    if (!time_copies(d, n, iters, ocr_raw_time, ocr_raw_time_batch, ms, [&] { PaddleOCR::raw::pixels(*f, px); }, &host_ms)) return 1;
     printf("{\"size\": [%d, %d], \"kind\": %d, \"bottom_up\": %d, \"batch\": %d, \"iters\": %d, \"upload_ms\": %.5f, \"pixel_stage_ms\": %.5f, "
-           "\"host_pixels_ms\": %.5f}\n", d.height, d.width, d.kind, d.bottom_up, (int)all.size(), iters, ms[0], ms[1], host_ms);
+           "\"host_pixels_ms\": %.5f}\n", d.height, d.width, d.kind, d.bottom_up, n, iters, ms[0], ms[1], host_ms);
     return 0;
   }
   if (bytes.empty() || !PaddleOCR::ipc::decode_jpeg(bytes, im, true) || !im.device_decodable()) { fprintf(stderr, "decode failed\n"); return 1; }
@@ -382,6 +371,9 @@ static int stage_batches(const std::string& model_dir, int nargs, char** args, b
       }
       b.frames.add(b.ims[i]);
     }
+    printf("{\"kinds\": [");  // the ocr_frame_kind each file of the batch is staged as
+    for (size_t i = 0; i < b.frames.list.size(); ++i) printf("%s%d", i ? ", " : "", b.frames.list[i].kind);
+    printf("]}\n");
   }
   const std::string det = model_dir + "/det", cls = model_dir + "/cls", rec = model_dir + "/rec", dict = rec + "/ppocr_keys_v1.txt";
   ocr_pipe_cfg c;

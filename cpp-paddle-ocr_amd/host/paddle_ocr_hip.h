@@ -269,17 +269,22 @@ struct DeviceFrames {
   std::deque<ocr_j2k_coded> kcf;
   std::deque<ocr_tiff_coded> tcf, tdf;
   std::vector<ocr_coded_frame> list;
-  void add(const Image& im) {  // only when im.device_decodable()
-    if (im.j2k_coded) { kcf.push_back(im.j2k_coded_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K_CODED, &kcf.back()}); }
-    else if (im.j2k) { kf.push_back(im.j2k_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_J2K, &kf.back()}); }
-    else if (im.vp8) { vf.push_back(im.vp8_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_VP8, &vf.back()}); }
-    else if (im.webp) { wf.push_back(im.webp_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_WEBP, &wf.back()}); }
-    else if (im.tiff_deflate) { tdf.push_back(im.tiff_deflate_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF_DEFLATE, &tdf.back()}); }
-    else if (im.tiff_coded) { tcf.push_back(im.tiff_coded_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF_CODED, &tcf.back()}); }
-    else if (im.tiff) { tf.push_back(im.tiff_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_TIFF, &tf.back()}); }
-    else if (im.raw) { rf.push_back(im.raw_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_RAW, &rf.back()}); }
-    else if (im.png) { pf.push_back(im.png_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_PNG, &pf.back()}); }
-    else { jf.push_back(im.jpeg_frame()); list.push_back(ocr_coded_frame{OCR_FRAME_JPEG, &jf.back()}); }
+  template <class D>
+  void push(std::deque<D>& q, int kind, const D& d) {
+    q.push_back(d);
+    list.push_back(ocr_coded_frame{kind, &q.back()});
+  }
+  void add(const Image& im) {  // only when im.device_decodable(); the first form in this order that the image holds
+    if (im.j2k_coded) push(kcf, OCR_FRAME_J2K_CODED, im.j2k_coded_frame());
+    else if (im.j2k) push(kf, OCR_FRAME_J2K, im.j2k_frame());
+    else if (im.vp8) push(vf, OCR_FRAME_VP8, im.vp8_frame());
+    else if (im.webp) push(wf, OCR_FRAME_WEBP, im.webp_frame());
+    else if (im.tiff_deflate) push(tdf, OCR_FRAME_TIFF_DEFLATE, im.tiff_deflate_frame());
+    else if (im.tiff_coded) push(tcf, OCR_FRAME_TIFF_CODED, im.tiff_coded_frame());
+    else if (im.tiff) push(tf, OCR_FRAME_TIFF, im.tiff_frame());
+    else if (im.raw) push(rf, OCR_FRAME_RAW, im.raw_frame());
+    else if (im.png) push(pf, OCR_FRAME_PNG, im.png_frame());
+    else push(jf, OCR_FRAME_JPEG, im.jpeg_frame());
   }
   int stage(ocr_pipe* pipe, int slot) const { return ocr_pipe_stage_batch(pipe, slot, list.data(), (int)list.size()); }
 };
