@@ -34,6 +34,16 @@ class ocr_det_cfg(C.Structure):
 CV_45, CV_410 = 45, 410  # ocr_det_cfg.cv_compat (0 = default = OCR_CV_COMPAT from the environment, else CV_410)
 
 
+POST_REC_FLOATS, POST_REC_FILL = 12, 0xFFFFFFFF  # OCR_POST_REC_FLOATS / OCR_POST_REC_FILL
+
+
+class ocr_post_stages(C.Structure):
+    _fields_ = [("cap_pixels", C.c_size_t), ("cap_borders", C.c_int), ("cap_verts", C.c_int), ("bitmap", C.c_void_p),
+                ("starts", C.c_void_p), ("npts", C.c_void_p), ("voff", C.c_void_p), ("verts", C.c_void_p),
+                ("cand_valid", C.c_void_p), ("cand_boxes", C.c_void_p), ("record", C.c_void_p),
+                ("rows", C.c_int), ("cols", C.c_int), ("ncont_all", C.c_int), ("ncont", C.c_int), ("nverts", C.c_int)]
+
+
 class ocr_cls_cfg(C.Structure):
     _fields_ = [("model_dir", C.c_char_p), ("device_id", C.c_int), ("cls_thresh", C.c_double),
                 ("cls_batch_num", C.c_int), ("precision", C.c_char_p)]
@@ -50,6 +60,7 @@ EXPORTS = [
     "ocr_last_error", "ocr_rt_init", "ocr_rt_device_count", "ocr_rt_set_wait_mode", "ocr_rt_get_wait_mode",
     "ocr_det_cfg_default", "ocr_det_create", "ocr_det_destroy", "ocr_det_run", "ocr_det_run_batch",
     "ocr_det_last_shape", "ocr_det_prob_map", "ocr_det_bitmap", "ocr_det_resized", "ocr_det_post",
+    "ocr_det_post_stages",
     "ocr_cls_cfg_default", "ocr_cls_create", "ocr_cls_destroy", "ocr_cls_run", "ocr_cls_probs",
     "ocr_rec_cfg_default", "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_run", "ocr_rec_label",
     "ocr_rec_num_classes", "ocr_rec_steps", "ocr_rec_run_chars", "ocr_rec_logits_row", "ocr_selftest_topk",
@@ -469,6 +480,7 @@ def _stage_protos(L):
     L.ocr_det_bitmap.argtypes = [vp, C.c_int, vp, C.c_size_t]
     L.ocr_det_resized.argtypes = [vp, C.c_int, vp, C.c_size_t]
     L.ocr_det_post.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, ip]
+    L.ocr_det_post_stages.argtypes = [vp, C.POINTER(ocr_post_stages)]
     L.ocr_cls_cfg_default.argtypes = [C.POINTER(ocr_cls_cfg)]
     L.ocr_cls_create.argtypes = [C.POINTER(ocr_cls_cfg), C.POINTER(vp)]
     L.ocr_cls_destroy.argtypes = [vp]
@@ -549,6 +561,35 @@ class Det:
         check(lib().ocr_det_post(self.h, prob.ctypes.data, prob.shape[0], prob.shape[1], src_h, src_w,
                                  boxes.ctypes.data, cap, C.byref(n)))
         return boxes[:n.value].reshape(-1, 4, 2).copy()
+
+    def post_stages_raw(self, cap_pixels, cap_borders, cap_verts, null=None):
+        """ocr_det_post_stages with the given capacities: (return code, the struct, the arrays it points to); `null` names a
+        pointer field to pass as NULL"""
+        a = dict(bitmap=np.zeros(max(cap_pixels, 1), np.uint8), starts=np.zeros(max(cap_borders, 1), np.int32),
+                 npts=np.zeros(max(cap_borders, 1), np.int32), voff=np.zeros(max(cap_borders, 1), np.int32),
+                 verts=np.zeros((max(cap_verts, 1), 2), np.int32), cand_valid=np.zeros(max(cap_borders, 1), np.int32),
+                 cand_boxes=np.zeros((max(cap_borders, 1), 8), np.int32),
+                 record=np.zeros((max(cap_borders, 1), POST_REC_FLOATS), np.float32))
+        s = ocr_post_stages()
+        s.cap_pixels, s.cap_borders, s.cap_verts = cap_pixels, cap_borders, cap_verts
+        for k, v in a.items():
+            setattr(s, k, None if k == null else v.ctypes.data)
+        return lib().ocr_det_post_stages(self.h, C.byref(s)), s, a
+
+    def post_stages(self):
+        """what the last post() on this handle left behind for its map (include/ocr_hip.h, ocr_det_post_stages): a dict of
+        arrays cut to their counts; `verts` a list with one (npts, 2) array per kept border (None: none stored)"""
+        rc, s, _ = self.post_stages_raw(0, 0, 0)
+        if rc != -4:  # OCR_ERR_CAPACITY carries the sizes; everything else (an empty map included: rc 0 is impossible at 0 pixels)
+            check(rc)
+        rc, s, a = self.post_stages_raw(s.rows * s.cols, s.ncont, s.nverts)
+        check(rc)
+        nc = s.ncont
+        voff, npts = a["voff"][:nc], a["npts"][:nc]
+        return dict(bitmap=a["bitmap"][:s.rows * s.cols].reshape(s.rows, s.cols), ncont_all=s.ncont_all, ncont=nc,
+                    starts=a["starts"][:nc], npts=npts, cand_valid=a["cand_valid"][:nc],
+                    cand_boxes=a["cand_boxes"][:nc].reshape(nc, 4, 2), record=a["record"][:nc],
+                    verts=[a["verts"][voff[c]:voff[c] + npts[c]].copy() if voff[c] >= 0 else None for c in range(nc)])
 
     def close(self):
         if self.h:

@@ -96,6 +96,13 @@ int ocr_det_post(ocr_det* h, const float* prob, int rows, int cols, int src_rows
   return rc ? fail(rc, err) : OCR_OK;
 }
 
+int ocr_det_post_stages(ocr_det* h, ocr_post_stages* out) {
+  if (!h || !out) return fail(OCR_ERR_ARG, "null argument");
+  std::string err;
+  const int rc = h->s.post_stages(out, err);
+  return rc ? fail(rc, err) : OCR_OK;
+}
+
 // ---- self-test taps: the device's ClipperOffset / UnClip in front of vectors the caller holds (tests/golden/unclip_ref*:
 // outputs of the reference's own compiled src/clipper.cpp).  The calling thread's current device (ocr_rt_init).
 int ocr_selftest_unclip(const int32_t* quads, const double* deltas, int n, int64_t* out, int cap, int* counts, double* trig) {

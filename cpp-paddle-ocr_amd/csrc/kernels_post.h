@@ -46,7 +46,13 @@ struct PostArgs {
   float box_thresh, unclip_ratio, ratio_h, ratio_w;
   int src_h, src_w;
   int probe_stop;         // development probe (OCR_POST_STOP): border_box_kernel returns after stage n (timing only)
+  // stage tap (ocr_det_post_stages, tests only; NULL in every production call): [N][max_cand][POST_REC_FLOATS], per
+  // candidate the four GetMiniBoxes corners of the contour's min-area rectangle, its ssid, the box score and the number of
+  // mask pixels the score averaged over.  Lane 0 of border_box_kernel stores what the candidate reached; the rest keeps
+  // whatever the host filled the buffer with.
+  float* stage_rec;
 };
+enum : int { POST_REC_SSID = 8, POST_REC_SCORE = 9, POST_REC_CNT = 10, POST_REC_FLOATS = 12 };
 
 void launch_bitmap(const float* prob, uint8_t* bm, long total, int ithresh, hipStream_t s);
 void launch_dilate2(const uint8_t* src, uint8_t* dst, int N, int H, int W, hipStream_t s);

@@ -890,8 +890,8 @@ __device__ EdgeRast make_edge(int mw, int mh, int ax, int ay, int bx, int by, bo
 }
 
 // BoxScoreFast: masked mean over the bbox with the mask of fillPoly(int-truncated corners).
-// All 64 lanes participate; returns the score in every lane.
-__device__ float box_score_fast_wave(const P2f arr[4], const float* __restrict__ pred, int H, int W, int lane, bool shifted) {
+// All 64 lanes participate; returns the score in every lane, and the mask's pixel count in npix.
+__device__ float box_score_fast_wave(const P2f arr[4], const float* __restrict__ pred, int H, int W, int lane, bool shifted, int& npix) {
   float fxmin = fminf(fminf(arr[0].x, arr[1].x), fminf(arr[2].x, arr[3].x));
   float fxmax = fmaxf(fmaxf(arr[0].x, arr[1].x), fmaxf(arr[2].x, arr[3].x));
   float fymin = fminf(fminf(arr[0].y, arr[1].y), fminf(arr[2].y, arr[3].y));
@@ -984,6 +984,7 @@ __device__ float box_score_fast_wave(const P2f arr[4], const float* __restrict__
     sum += __shfl_xor(sum, off);
     cnt += __shfl_xor(cnt, off);
   }
+  npix = cnt;
   return cnt ? (float)(sum / (double)cnt) : 0.f;
 }
 
@@ -995,10 +996,10 @@ __device__ float box_score_fast_wave(const P2f arr[4], const float* __restrict__
 //             per row sorts its few crossings and sets the spans [ceil(x_even), floor(x_odd)]
 //   mean    : lanes stride over the mask words.
 // pts: the border's vertices in contour order as (x, y) keys.  scratch: this border's slice of the
-// per-image word pool.  Returns the score in every lane, or -1 when the pool is exhausted.
+// per-image word pool.  Returns the score in every lane (the mask's pixel count in npix), or -1 when the pool is exhausted.
 __device__ float polygon_score_wave(const unsigned long long* __restrict__ pts, int npts, 
                                     const float* __restrict__ pred, int H, int W, unsigned* pool, unsigned pool_words,
-                                    unsigned* pool_top, int lane, int* s_tmp /* >= 4 ints of LDS */, bool shifted) {
+                                    unsigned* pool_top, int lane, int* s_tmp /* >= 4 ints of LDS */, bool shifted, int& npix) {
   // bounding box of the vertices (ints already; PolygonScoreAcc floors/ceils floats of ints)
   int bx0 = INT_MAX, bx1 = INT_MIN, by0 = INT_MAX, by1 = INT_MIN;
   for (int i = lane; i < npts; i += 64) {
@@ -1127,6 +1128,7 @@ __device__ float polygon_score_wave(const unsigned long long* __restrict__ pts, 
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) { sum += __shfl_xor(sum, off); n += __shfl_xor(n, off); }
+  npix = n;
   return n ? (float)(sum / (double)n) : 0.f;
 }
 
@@ -1402,6 +1404,11 @@ __global__ void __launch_bounds__(64) border_box_kernel(const PostArgs a) {
       float ssid;
       P2f arr[4];
       get_mini_boxes(box, ssid, arr);
+      if (a.stage_rec) {  // stage tap (tests): null in production
+        float* rec = a.stage_rec + ci * POST_REC_FLOATS;
+        for (int i = 0; i < 4; ++i) { rec[2 * i] = arr[i].x; rec[2 * i + 1] = arr[i].y; }
+        rec[POST_REC_SSID] = ssid;
+      }
       if (ssid >= 3.0f) {  // min_size = 3
         s_flag = 1;
         for (int i = 0; i < 4; ++i) { s_box[2 * i] = arr[i].x; s_box[2 * i + 1] = arr[i].y; }
@@ -1415,6 +1422,7 @@ __global__ void __launch_bounds__(64) border_box_kernel(const PostArgs a) {
   for (int i = 0; i < 4; ++i) { arr[i].x = s_box[2 * i]; arr[i].y = s_box[2 * i + 1]; }
   // ---- box score (whole wave)
   float score;
+  int npix = 0;
   if (a.slow) {
     // PolygonScoreAcc needs the vertices in contour order: the unsorted keys are still in the pool when
     // the sort ran in LDS; after an in-place (global) sort restore the order by sorting on the index
@@ -1428,10 +1436,15 @@ __global__ void __launch_bounds__(64) border_box_kernel(const PostArgs a) {
       __syncthreads();
     }
     score = polygon_score_wave(gkeys, total, g_pred, g_H, g_W, a.mask_pool + (size_t)n * a.mask_pool_words,
-                               a.mask_pool_words, a.mask_pool_top + n, lane, &s_flag, a.fill_shifted != 0);
+                               a.mask_pool_words, a.mask_pool_top + n, lane, &s_flag, a.fill_shifted != 0, npix);
     if (score < 0.f) { if (lane == 0) atomicOr(a.status, POST_ERR_POOL); return; }
   } else {
-    score = box_score_fast_wave(arr, g_pred, g_H, g_W, lane, a.fill_shifted != 0);
+    score = box_score_fast_wave(arr, g_pred, g_H, g_W, lane, a.fill_shifted != 0, npix);
+  }
+  if (a.stage_rec && lane == 0) {
+    float* rec = a.stage_rec + ci * POST_REC_FLOATS;
+    rec[POST_REC_SCORE] = score;
+    rec[POST_REC_CNT] = (float)npix;  // (exact: a map has fewer than 2^24 pixels wherever the tap is used)
   }
   if (score < a.box_thresh) return;
   if (lane != 0) return;

@@ -83,6 +83,10 @@ class DetStage {
   uint8_t* dev_images_mut() { return src_.p; }
   int post_only(const float* prob, int rows, int cols, int src_rows, int src_cols, int32_t* boxes, int cap, int* n,
                 std::string& err);
+  // Stage tap (ocr_det_post_stages, tests): what the launch sequence of the last post_only left in this stage's buffers for
+  // image 0 - nothing is launched.  The first call on a stage arms it (the per-candidate record of kernels_post.h is
+  // allocated and handed to the kernels from then on) and is refused like every call that has no recorded post_only before it.
+  int post_stages(ocr_post_stages* out, std::string& err);
   // device-resident copy of the last uploaded images (for the fused pipeline)
   const uint8_t* dev_images() const { return src_.p; }
   size_t dev_image_bytes() const { return (size_t)src_rows_ * src_cols_ * 3; }
@@ -119,6 +123,9 @@ class DetStage {
       out_n_;
   DevBuf<unsigned long long> pool_;
   DevBuf<unsigned> mask_pool_, mask_top_;
+  DevBuf<float> stage_rec_;  // [images][max_cand][POST_REC_FLOATS], only on a stage whose tap has been asked for
+  bool tap_armed_ = false, tap_valid_ = false;  // valid: the last post-processing pass was a post_only that recorded
+  int tap_h_ = 0, tap_w_ = 0;
   DevBuf<int> pool_need_;   // [images] keys the traced borders of an image would have needed (kernels_post.h)
   size_t mask_words_ = 0;   // words of polygon-score scratch per image in this call
   // words of polygon-score scratch per image: masks + crossing lists of all its borders (8 map areas of bits + slack)

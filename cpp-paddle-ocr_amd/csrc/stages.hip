@@ -156,6 +156,7 @@ bool DetStage::ensure_post(int count, size_t px, int H, int W, int cap, std::str
          cand_valid_.ensure((size_t)count * max_cand, err) && status_.ensure(1, err) && pool_need_.ensure(count, err) &&
          out_boxes_.ensure((size_t)count * cap * 8, err) && out_n_.ensure(count, err) &&
          (cfg_.use_dilation ? bitmap2_.ensure(px, err) : true) &&
+         (tap_armed_ ? stage_rec_.ensure((size_t)count * max_cand * POST_REC_FLOATS, err) : true) &&
          (cfg_.score_mode == "slow" ? (mask_pool_.ensure((size_t)count * mask_words_, err) && mask_top_.ensure(count, err)) : true);
 }
 
@@ -176,7 +177,13 @@ int DetStage::post_launch(PostArgs a, int count, int32_t* boxes, int cap, int* n
 #ifdef OCR_DEV_PROBES  // development probe (tools/post_kernel_times.sh builds with -DOCR_DEV_PROBES): timing only, results are wrong
   { static const char* stop = getenv("OCR_POST_STOP"); a.probe_stop = stop ? atoi(stop) : 0; }
 #endif
+  tap_valid_ = false;
   int status = 0;
+  // (stage tap, tests: what a candidate does not reach keeps this fill - every pass of the per-border stage starts from it)
+  auto fill_rec = [&]() -> int {
+    if (a.stage_rec) ST_HIP(hipMemsetAsync(a.stage_rec, 0xFF, (size_t)count * a.max_cand * POST_REC_FLOATS * sizeof(float), stream_));
+    return OCR_OK;
+  };
   auto fetch = [&]() -> int {
     ST_HIP(hipMemcpyAsync(n, out_n_.p, count * sizeof(int), hipMemcpyDeviceToHost, stream_));
     ST_HIP(hipMemcpyAsync(boxes, out_boxes_.p, (size_t)count * cap * 8 * sizeof(int), hipMemcpyDeviceToHost, stream_));
@@ -190,6 +197,7 @@ int DetStage::post_launch(PostArgs a, int count, int32_t* boxes, int cap, int* n
       ST_HIP(hipMemsetAsync(mask_top_.p, 0, count * sizeof(unsigned), stream_));
     }
     ST_HIP(hipMemsetAsync(status_.p, 0, sizeof(int), stream_));
+    if (int rc = fill_rec()) return rc;
     launch_post(a, count, out_boxes_.p, cap, out_n_.p, stream_);
     ST_HIP(hipGetLastError());  // a refused launch (e.g. LDS limit on this device) must not leave stale borders behind
     if (int rc = fetch()) return rc;
@@ -199,6 +207,7 @@ int DetStage::post_launch(PostArgs a, int count, int32_t* boxes, int cap, int* n
       // a border outgrew the small LDS working set of the per-border stage: run that stage again with the large one
       ST_HIP(hipMemsetAsync(status_.p, 0, sizeof(int), stream_));
       if (a.slow) ST_HIP(hipMemsetAsync(mask_top_.p, 0, count * sizeof(unsigned), stream_));
+      if (int rc = fill_rec()) return rc;
       launch_post_large(a, count, out_boxes_.p, cap, out_n_.p, stream_);
       ST_HIP(hipGetLastError());
       if (int rc = fetch()) return rc;
@@ -249,6 +258,7 @@ int DetStage::run_post(int count, int H, int W, const float* prob, float ratio_h
   a.bitmap = bm; a.pred = prob;
   a.H = H; a.W = W;
   a.ratio_h = ratio_h; a.ratio_w = ratio_w; a.src_h = src_h; a.src_w = src_w;
+  a.stage_rec = tap_armed_ ? stage_rec_.p : nullptr;
   return post_launch(a, count, boxes, cap, n, err);
 }
 
@@ -414,7 +424,65 @@ int DetStage::post_only(const float* prob, int rows, int cols, int src_rows, int
   launch_bitmap(prob_in_.p, bitmap_.p, (long)px, ithresh_, stream_);
   last_count = 1; last_h = rows; last_w = cols;
   const float ratio_h = float(rows) / float(src_rows), ratio_w = float(cols) / float(src_cols);
-  return run_post(1, rows, cols, prob_in_.p, ratio_h, ratio_w, src_rows, src_cols, boxes, cap, n, err);
+  const int rc = run_post(1, rows, cols, prob_in_.p, ratio_h, ratio_w, src_rows, src_cols, boxes, cap, n, err);
+  tap_valid_ = tap_armed_ && rc == OCR_OK;
+  tap_h_ = rows; tap_w_ = cols;
+  return rc;
+}
+
+static_assert(POST_REC_FLOATS == OCR_POST_REC_FLOATS, "the stage record of kernels_post.h is the one include/ocr_hip.h describes");
+int DetStage::post_stages(ocr_post_stages* o, std::string& err) {
+  if (!o || !o->bitmap || !o->starts || !o->npts || !o->voff || !o->verts || !o->cand_valid || !o->cand_boxes || !o->record) {
+    err = "post_stages: null pointer";
+    return OCR_ERR_ARG;
+  }
+  const bool was_valid = tap_valid_;
+  tap_armed_ = true;
+  if (!was_valid) { err = "post_stages: no recorded ocr_det_post on this handle (the tap is armed from now on)"; return OCR_ERR_ARG; }
+  ST_HIP(rt_set_device(cfg_.device));
+  const int max_cand = 1000;
+  const size_t px = (size_t)tap_h_ * tap_w_;
+  if (px >= (1ul << 24)) { err = "post_stages: the record counts mask pixels in a float, maps below 2^24 pixels only"; return OCR_ERR_ARG; }
+  int nall = 0, nc = 0;
+  ST_HIP(g_memcpy(&nall, ncont_all_.p, sizeof(int), hipMemcpyDeviceToHost));
+  ST_HIP(g_memcpy(&nc, ncont_.p, sizeof(int), hipMemcpyDeviceToHost));
+  if (nc < 0 || nc > max_cand) { err = "post_stages: border count out of range"; return OCR_ERR_DEVICE; }
+  std::vector<int> npts(nc), poff(nc);
+  if (nc) {
+    ST_HIP(g_memcpy(npts.data(), npts_.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
+    ST_HIP(g_memcpy(poff.data(), poff_.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  // the key pool holds the vertices of the borders the per-border stage looked at (more than 2 vertices, offset >= 0)
+  long nverts = 0, pool_end = 0;
+  for (int c = 0; c < nc; ++c) {
+    if (npts[c] <= 2 || poff[c] < 0) continue;
+    if ((long)poff[c] + npts[c] > pool_cap_) { err = "post_stages: border outside the key pool"; return OCR_ERR_DEVICE; }
+    nverts += npts[c];
+    pool_end = std::max(pool_end, (long)poff[c] + npts[c]);
+  }
+  o->rows = tap_h_; o->cols = tap_w_; o->ncont_all = nall; o->ncont = nc; o->nverts = (int)nverts;
+  if (px > o->cap_pixels || nc > o->cap_borders || nverts > o->cap_verts) { err = "post_stages: output capacity too small"; return OCR_ERR_CAPACITY; }
+  ST_HIP(g_memcpy(o->bitmap, bitmap_dev(), px, hipMemcpyDeviceToHost));
+  if (nc) {
+    ST_HIP(g_memcpy(o->starts, starts_.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
+    memcpy(o->npts, npts.data(), (size_t)nc * sizeof(int));
+    ST_HIP(g_memcpy(o->cand_valid, cand_valid_.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
+    ST_HIP(g_memcpy(o->cand_boxes, cand_boxes_.p, (size_t)nc * 8 * sizeof(int), hipMemcpyDeviceToHost));
+    ST_HIP(g_memcpy(o->record, stage_rec_.p, (size_t)nc * POST_REC_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  std::vector<unsigned long long> keys((size_t)pool_end);
+  if (pool_end) ST_HIP(g_memcpy(keys.data(), pool_.p, (size_t)pool_end * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  long k = 0;
+  for (int c = 0; c < nc; ++c) {
+    if (npts[c] <= 2 || poff[c] < 0) { o->voff[c] = -1; continue; }
+    o->voff[c] = (int)k;
+    for (int i = 0; i < npts[c]; ++i, ++k) {  // make_key of kernels_post.hip: x + 16384 in bits 48.., y + 16384 in bits 32..47
+      const unsigned long long key = keys[(size_t)poff[c] + i];
+      o->verts[2 * k] = (int)(key >> 48) - 16384;
+      o->verts[2 * k + 1] = (int)((key >> 32) & 0xffff) - 16384;
+    }
+  }
+  return OCR_OK;
 }
 
 // ================================================================= recognizer

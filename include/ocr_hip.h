@@ -726,6 +726,39 @@ int ocr_selftest_lds_memo(void);
 int ocr_selftest_unclip(const int32_t* quads, const double* deltas, int n, int64_t* out, int cap, int* counts, double* trig);
 int ocr_selftest_unclip_box(const float* boxes, float unclip_ratio, int n, float* out14, int* status);
 
+/* Stage tap of the detector's post-processing (tests/test_gpu_post_stages.py): what the launch sequence of the last
+ * ocr_det_post on this handle left in its device buffers - nothing is launched, nothing computed again on the device.
+ * The caller sets the three capacities and the pointers; the call sets rows .. nverts (also when it answers OCR_ERR_CAPACITY,
+ * so that the caller can size its buffers) and fills:
+ *   bitmap      rows*cols bytes {0,1}: the map the kernels read (after the 2x2 dilate with use_dilation)
+ *   ncont_all   borders discovered; ncont = min(ncont_all, 1000) borders kept, in cv::findContours' order
+ *   starts      per kept border the pixel (y*cols + x) its raster scan met first: the border's first pixel for an outer border,
+ *               the background pixel right of it for a hole border
+ *   npts        per kept border its CHAIN_APPROX_SIMPLE vertex count
+ *   voff, verts per kept border the first (x, y) pair of its npts vertices in verts, or -1: borders of one or two vertices are
+ *               dropped before anything is stored.  Vertices come in the order the key pool holds them after the call: contour
+ *               order with det_db_score_mode "slow", and with "fast" for borders of at most 512 vertices (sorted in LDS; a
+ *               longer border was sorted in place and comes back ordered by (x, y))
+ *   cand_valid, cand_boxes   per kept border whether it gave a box, and the box (8 int32) if so
+ *   record      per kept border OCR_POST_REC_FLOATS floats written by the per-border kernel itself: the four GetMiniBoxes
+ *               corners (x, y) of the contour's min-area rectangle, [8] its ssid, [9] the box score, [10] the number of mask
+ *               pixels the score averaged over; what a candidate did not reach holds OCR_POST_REC_FILL (as bits)
+ * The first call on a handle switches the record on for the ocr_det_post calls that follow and is refused (OCR_ERR_ARG), as
+ * is every call that has no recorded ocr_det_post before it; NULL pointers: OCR_ERR_ARG; a capacity too small:
+ * OCR_ERR_CAPACITY.  The handle stays usable after every refusal. */
+#define OCR_POST_REC_FLOATS 12
+#define OCR_POST_REC_FILL 0xFFFFFFFFu
+typedef struct ocr_post_stages {
+  size_t cap_pixels; /* in: bytes of bitmap */
+  int cap_borders;   /* in: entries of starts / npts / voff / cand_valid, cand_boxes / 8, record / OCR_POST_REC_FLOATS */
+  int cap_verts;     /* in: (x, y) pairs of verts */
+  uint8_t* bitmap;
+  int32_t *starts, *npts, *voff, *verts, *cand_valid, *cand_boxes;
+  float* record;
+  int rows, cols, ncont_all, ncont, nverts; /* out */
+} ocr_post_stages;
+int ocr_det_post_stages(ocr_det* h, ocr_post_stages* out);
+
 /* The resize-and-normalise launches of csrc/kernels_pre.hip alone (tests/test_gpu_pre_ops.py), each with the named stage's own
  * normalisation table.  Every output buffer is pre-filled on the device with the byte OCR_SELFTEST_FILL and comes back with
  * OCR_SELFTEST_GUARD more bytes than the launch may write, taken from device memory right behind its last element: what no

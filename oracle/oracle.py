@@ -173,6 +173,77 @@ def det_post(pred, thresh, box_thresh, unclip_ratio, src_h, src_w, use_dilation=
     return boxes[:n].reshape(n, 4, 2).copy()
 
 
+# ---- the post-processing stages one by one (oracle_post.cpp "pieces")
+def contours(bm):
+    """findContours(RETR_LIST, CHAIN_APPROX_SIMPLE): a list of (npts, 2) int32 arrays in the reference's order, and per contour
+    (x, y, hole) of the pixel the border following started on"""
+    bm = np.ascontiguousarray(bm, dtype=np.uint8)
+    H, W = bm.shape
+    cap_c, cap_p = H * W + 1, 4 * H * W + 16
+    pts = np.zeros((cap_p, 2), np.int32)
+    sizes = np.zeros(cap_c, np.int32)
+    xyh = np.zeros((cap_c, 3), np.int32)
+    L = lib()
+    n = L.oracle_find_contours(C.c_void_p(_p(bm)), H, W, C.c_void_p(_p(pts)), cap_p, C.c_void_p(_p(sizes)), cap_c)
+    assert n <= cap_c and int(sizes[:n].sum()) <= cap_p
+    assert L.oracle_contour_starts(C.c_void_p(_p(bm)), H, W, C.c_void_p(_p(xyh)), cap_c) == n
+    offs = np.concatenate([[0], np.cumsum(sizes[:n])])
+    return [pts[offs[i]:offs[i + 1]].copy() for i in range(n)], xyh[:n].copy()
+
+
+def mini_box(pts):
+    """minAreaRect(contour) -> GetMiniBoxes: corners (4, 2) f32 in GetMiniBoxes' order, ssid, corners in RotatedRect::points' order"""
+    pts = np.ascontiguousarray(pts, dtype=np.int32)
+    out = np.zeros(17, np.float32)
+    lib().oracle_mini_box_i(C.c_void_p(_p(pts)), len(pts), C.c_void_p(_p(out)))
+    return out[:8].reshape(4, 2).copy(), out[8], out[9:].reshape(4, 2).copy()
+
+
+def unclip_box(corners, unclip_ratio):
+    """UnClip -> minAreaRect -> GetMiniBoxes of one mini box: (RotatedRect cx cy w h angle, ssid, corners (4, 2))"""
+    box = np.ascontiguousarray(corners, dtype=np.float32).reshape(8)
+    out = np.zeros(14, np.float32)
+    lib().oracle_unclip_box(C.c_void_p(_p(box)), C.c_float(unclip_ratio), C.c_void_p(_p(out)))
+    return out[:5].copy(), out[5], out[6:].reshape(4, 2).copy()
+
+
+def polygon_score(pts, pred, cv_compat=0):
+    pts = np.ascontiguousarray(pts, dtype=np.int32)
+    pred = np.ascontiguousarray(pred, dtype=np.float32)
+    f = lib().oracle_polygon_score
+    f.restype = C.c_float
+    return np.float32(f(C.c_void_p(_p(pts)), len(pts), C.c_void_p(_p(pred)), pred.shape[0], pred.shape[1], int(cv_compat)))
+
+
+def box_score_fast(corners, pred, cv_compat=0):
+    box = np.ascontiguousarray(corners, dtype=np.float32).reshape(8)
+    pred = np.ascontiguousarray(pred, dtype=np.float32)
+    f = lib().oracle_box_score_fast
+    f.restype = C.c_float
+    return np.float32(f(C.c_void_p(_p(box)), C.c_void_p(_p(pred)), pred.shape[0], pred.shape[1], int(cv_compat)))
+
+
+def fill_poly(pts, w, h, cv_compat=0, outline=True):
+    """cv::fillPoly of one polygon into a zeroed h x w mask"""
+    pts = np.ascontiguousarray(pts, dtype=np.int32)
+    mask = np.zeros((h, w), np.uint8)
+    f = lib().oracle_fill_poly if outline else lib().oracle_fill_poly_no_outline
+    f(C.c_void_p(_p(mask)), w, h, C.c_void_p(_p(pts)), len(pts), int(cv_compat))
+    return mask
+
+
+def det_post_candidates(pred, thresh, box_thresh, unclip_ratio, src_h, src_w, use_dilation=False, slow=False, cap=2000, cv_compat=0):
+    """det_post with, per box, the index of the contour it came from"""
+    pred = np.ascontiguousarray(pred, dtype=np.float32)
+    boxes = np.zeros((cap, 8), np.int32)
+    cand = np.zeros(cap, np.int32)
+    n = lib().oracle_det_post_candidates(C.c_void_p(_p(pred)), pred.shape[0], pred.shape[1], C.c_double(thresh),
+                                         C.c_double(box_thresh), C.c_double(unclip_ratio), int(use_dilation), int(slow), src_h,
+                                         src_w, C.c_void_p(_p(boxes)), C.c_void_p(_p(cand)), cap, int(cv_compat))
+    assert n <= cap
+    return boxes[:n].reshape(n, 4, 2).copy(), cand[:n].copy()
+
+
 def crop_rect(box, rows, cols):
     b = np.ascontiguousarray(np.asarray(box, dtype=np.int32).reshape(8))
     x, y, w, h = C.c_int(), C.c_int(), C.c_int(), C.c_int()

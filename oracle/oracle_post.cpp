@@ -36,7 +36,11 @@ struct RRect { float cx = 0, cy = 0, w = 0, h = 0, angle = 0; };
 // Legacy implementation semantics: the image is padded by one zero pixel, binarised to {0,1},
 // scanned in raster order; every new border is traced with icvFetchContour; contours come back
 // in reverse discovery order.
-void find_contours(const uint8_t* bitmap, int H, int W, std::vector<std::vector<Pt>>& out) {
+// `starts` (optional): per contour, in the order of `out`, the pixel icvFetchContour was started on and whether the
+// border is a hole border - the scan's own knowledge, not the first stored vertex.
+struct ContourStart { int x, y, hole; };
+void find_contours(const uint8_t* bitmap, int H, int W, std::vector<std::vector<Pt>>& out,
+                   std::vector<ContourStart>* starts = nullptr) {
   const int step = W + 2, rows = H + 2;
   std::vector<signed char> img((size_t)step * rows, 0);
   for (int y = 0; y < H; ++y)
@@ -46,6 +50,7 @@ void find_contours(const uint8_t* bitmap, int H, int W, std::vector<std::vector<
   for (int i = 0; i < 16; ++i) deltas[i] = deltas8[i & 7];
   static const int cdx[8] = {1, 1, 0, -1, -1, -1, 0, 1}, cdy[8] = {0, -1, -1, -1, 0, 1, 1, 1};
   std::vector<std::vector<Pt>> found;
+  std::vector<ContourStart> origins;
   for (int y = 1; y < rows - 1; ++y) {
     signed char* row = img.data() + (size_t)y * step;
     int prev = 0;
@@ -61,6 +66,7 @@ void find_contours(const uint8_t* bitmap, int H, int W, std::vector<std::vector<
         std::vector<Pt> c;
         signed char* i0 = row + x - (is_hole ? 1 : 0);
         Pt pt{x - (is_hole ? 1 : 0) - 1, y - 1};  // offset (-1,-1) undoes the padding
+        origins.push_back({pt.x, pt.y, is_hole ? 1 : 0});
         const signed char nbd = 2;
         int s_end, s;
         s_end = s = is_hole ? 0 : 4;
@@ -103,6 +109,7 @@ void find_contours(const uint8_t* bitmap, int H, int W, std::vector<std::vector<
     }
   }
   out.assign(found.rbegin(), found.rend());
+  if (starts) starts->assign(origins.rbegin(), origins.rend());
 }
 
 // ------------------------------------------------------------------ cv::convexHull (returnPoints, clockwise=false)
@@ -451,7 +458,8 @@ void draw_line(uint8_t* mask, int W, int H, Pt p1, Pt p2) {
 // fills [xa >> 16, xb >> 16] (`delta = 0` for line_type < LINE_AA): both span ends are the crossing rounded half up.
 enum { CV_FILL_CLASSIC = 0, CV_FILL_SHIFTED = 1 };
 
-void fill_poly(uint8_t* mask, int W, int H, const std::vector<Pt>& v, int compat) {
+// (outline = false: the scan fill alone, without the Bresenham outline - a mutated rule for the tests' sensitivity checks)
+void fill_poly(uint8_t* mask, int W, int H, const std::vector<Pt>& v, int compat, bool outline = true) {
   const int count = (int)v.size();
   if (count == 0) return;
   const int XY_SHIFT = 16;
@@ -463,7 +471,7 @@ void fill_poly(uint8_t* mask, int W, int H, const std::vector<Pt>& v, int compat
     for (int i = 0; i < count; ++i) {
       int64_t p1x = (int64_t)v[i].x << XY_SHIFT, p1y = v[i].y;
       Pt t0{(int)((p0x + (XY_ONE >> 1)) >> XY_SHIFT), (int)p0y}, t1{(int)((p1x + (XY_ONE >> 1)) >> XY_SHIFT), (int)p1y};
-      draw_line(mask, W, H, t0, t1);
+      if (outline) draw_line(mask, W, H, t0, t1);
       int64_t c0x = p0x, c0y = p0y, c1x = p1x, c1y = p1y;  // pt0c, pt1c
       if (compat == CV_FILL_SHIFTED) {
         if ((unsigned)t0.x >= (unsigned)W || (unsigned)t1.x >= (unsigned)W || (unsigned)t0.y >= (unsigned)H || (unsigned)t1.y >= (unsigned)H) {
@@ -753,7 +761,7 @@ inline float clampf(float x, float lo, float hi) { return x > hi ? hi : (x < lo 
 struct Box { int p[4][2]; };
 
 void boxes_from_bitmap(const float* pred, const uint8_t* bitmap, int H, int W, float box_thresh, float unclip_ratio,
-                       bool slow, std::vector<Box>& boxes, int compat) {
+                       bool slow, std::vector<Box>& boxes, int compat, std::vector<int>* cand = nullptr) {
   const int min_size = 3, max_candidates = 1000;
   std::vector<std::vector<Pt>> contours;
   find_contours(bitmap, H, W, contours);
@@ -778,11 +786,14 @@ void boxes_from_bitmap(const float* pred, const uint8_t* bitmap, int H, int W, f
       b.p[k][1] = int(clampf(roundf(clip[k].y / float(H) * float(H)), 0, float(H)));
     }
     boxes.push_back(b);
+    if (cand) cand->push_back(ci);
   }
 }
 
-void filter_tag_det_res(std::vector<Box>& boxes, float ratio_h, float ratio_w, int src_h, int src_w) {
+// (cand, optional: the contour index of every box, filtered along with the boxes)
+void filter_tag_det_res(std::vector<Box>& boxes, float ratio_h, float ratio_w, int src_h, int src_w, std::vector<int>* cand = nullptr) {
   std::vector<Box> keep;
+  std::vector<int> keep_cand;
   for (auto& b : boxes) {
     // OrderPointsClockwise: std::sort by x (XsortInt) on 4 elements == insertion sort
     int a[4][2];
@@ -811,13 +822,16 @@ void filter_tag_det_res(std::vector<Box>& boxes, float ratio_h, float ratio_w, i
       b.p[m][0] = x; b.p[m][1] = y;
     }
   }
-  for (auto& b : boxes) {
+  for (size_t i = 0; i < boxes.size(); ++i) {
+    const Box& b = boxes[i];
     int rect_width = int(sqrt(pow(b.p[0][0] - b.p[1][0], 2) + pow(b.p[0][1] - b.p[1][1], 2)));
     int rect_height = int(sqrt(pow(b.p[0][0] - b.p[3][0], 2) + pow(b.p[0][1] - b.p[3][1], 2)));
     if (rect_width <= 4 || rect_height <= 4) continue;
     keep.push_back(b);
+    if (cand) keep_cand.push_back((*cand)[i]);
   }
   boxes = keep;
+  if (cand) *cand = keep_cand;
 }
 
 
@@ -884,6 +898,50 @@ int oracle_find_contours(const uint8_t* bitmap, int H, int W, int* pts_xy, int c
   return (int)c.size();
 }
 
+// the start pixel (x, y) and the hole flag of every contour, in oracle_find_contours' order; returns the contour count
+int oracle_contour_starts(const uint8_t* bitmap, int H, int W, int* xyh, int cap_contours) {
+  std::vector<std::vector<Pt>> c;
+  std::vector<ContourStart> st;
+  find_contours(bitmap, H, W, c, &st);
+  for (size_t i = 0; i < st.size() && (int)i < cap_contours; ++i) { xyh[3 * i] = st[i].x; xyh[3 * i + 1] = st[i].y; xyh[3 * i + 2] = st[i].hole; }
+  return (int)c.size();
+}
+
+// cv::minAreaRect(contour) -> GetMiniBoxes (postprocess_op.cpp:134-168, 277-283): out17 = the four corners in GetMiniBoxes'
+// order, ssid, the four corners in RotatedRect::points' order
+void oracle_mini_box_i(const int* pts_xy, int n, float* out17) {
+  std::vector<Pt> p(n);
+  for (int i = 0; i < n; ++i) p[i] = {pts_xy[2 * i], pts_xy[2 * i + 1]};
+  const RRect r = min_area_rect_i(p);
+  float ssid;
+  Pt2f c[4], raw[4];
+  get_mini_boxes(r, ssid, c);
+  box_points(r, raw);
+  for (int i = 0; i < 4; ++i) { out17[2 * i] = c[i].x; out17[2 * i + 1] = c[i].y; out17[9 + 2 * i] = raw[i].x; out17[10 + 2 * i] = raw[i].y; }
+  out17[8] = ssid;
+}
+
+// PolygonScoreAcc (postprocess_op.cpp:170-214) of one contour
+float oracle_polygon_score(const int* pts_xy, int n, const float* pred, int H, int W, int cv_compat) {
+  std::vector<Pt> p(n);
+  for (int i = 0; i < n; ++i) p[i] = {pts_xy[2 * i], pts_xy[2 * i + 1]};
+  return polygon_score_acc(p, pred, H, W, fill_rule(cv_compat));
+}
+
+// oracle_det_post per candidate: cand[i] = the contour (index into oracle_find_contours' list) box i came from
+int oracle_det_post_candidates(const float* pred, int H, int W, double det_db_thresh, double box_thresh, double unclip_ratio,
+                               int use_dilation, int slow, int src_h, int src_w, int* boxes, int* cand, int cap, int cv_compat) {
+  std::vector<uint8_t> bitmap((size_t)H * W);
+  oracle_bitmap(pred, H, W, det_db_thresh, use_dilation, bitmap.data());
+  std::vector<Box> bx;
+  std::vector<int> ci;
+  boxes_from_bitmap(pred, bitmap.data(), H, W, (float)box_thresh, (float)unclip_ratio, slow != 0, bx, fill_rule(cv_compat), &ci);
+  filter_tag_det_res(bx, float(H) / float(src_h), float(W) / float(src_w), src_h, src_w, &ci);
+  const int n = std::min((int)bx.size(), cap);
+  for (int i = 0; i < n; ++i) { memcpy(boxes + i * 8, bx[i].p, 8 * sizeof(int)); cand[i] = ci[i]; }
+  return (int)bx.size();
+}
+
 void oracle_min_area_rect_i(const int* pts_xy, int n, float* out5) {
   std::vector<Pt> p(n);
   for (int i = 0; i < n; ++i) p[i] = {pts_xy[2 * i], pts_xy[2 * i + 1]};
@@ -936,6 +994,12 @@ void oracle_fill_poly(uint8_t* mask, int W, int H, const int* pts_xy, int n, int
   std::vector<Pt> p(n);
   for (int i = 0; i < n; ++i) p[i] = {pts_xy[2 * i], pts_xy[2 * i + 1]};
   fill_poly(mask, W, H, p, fill_rule(cv_compat));
+}
+// the same without the Bresenham outline (scan fill only): a deliberately wrong rule for the tests' sensitivity checks
+void oracle_fill_poly_no_outline(uint8_t* mask, int W, int H, const int* pts_xy, int n, int cv_compat) {
+  std::vector<Pt> p(n);
+  for (int i = 0; i < n; ++i) p[i] = {pts_xy[2 * i], pts_xy[2 * i + 1]};
+  fill_poly(mask, W, H, p, fill_rule(cv_compat), false);
 }
 
 // crop rectangle of ocr_worker.cpp:245-258: boundingRect(Point2f of int coords) & image rect.  returns 0 if empty
