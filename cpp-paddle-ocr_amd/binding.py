@@ -68,9 +68,11 @@ EXPORTS = [
     "ocr_net_timing", "ocr_net_timing_report", "ocr_probe", "ocr_selftest_refuse_launch", "ocr_selftest_lds_memo",
     "ocr_selftest_unclip", "ocr_selftest_unclip_box",
     "ocr_selftest_det_pre", "ocr_selftest_line_pre", "ocr_selftest_line_pre_ragged",
+    "ocr_selftest_softmax_argmax", "ocr_selftest_head_combine", "ocr_selftest_srv_argmax", "ocr_selftest_ctc_reduce",
+    "ocr_selftest_ctc", "ocr_selftest_topk_lines", "ocr_selftest_rec_head",
     "ocr_srv_net_create", "ocr_srv_net_destroy", "ocr_srv_net_forward", "ocr_srv_net_rerun", "ocr_srv_net_num_tensors", "ocr_srv_net_fetch",
     "ocr_srv_net_timing", "ocr_srv_net_timing_report", "ocr_srv_net_num_launches", "ocr_srv_net_launch_info", "ocr_srv_net_run_launches",
-    "ocr_srv_net_upload",
+    "ocr_srv_net_upload", "ocr_srv_net_set_ctc", "ocr_srv_net_ctc_tail",
 ]
 
 
@@ -217,6 +219,23 @@ class SrvNet:
         x = np.ascontiguousarray(x, dtype=np.float32)
         check(lib().ocr_srv_net_upload(self.h, tid, x.ctypes.data, x.size))
 
+    def set_ctc(self, on=True):
+        """test hook: the CTC head's partial mode (f16 build), as the recognizer stage switches it; the next forward re-binds"""
+        L = lib()
+        L.ocr_srv_net_set_ctc.argtypes = [C.c_void_p, C.c_int]
+        check(L.ocr_srv_net_set_ctc(self.h, 1 if on else 0))
+
+    def ctc_tail(self):
+        """test hook: the stage's tail launch on the output of the current binding -> (amax int32 [rows], pmax f32 [rows], slots, step)"""
+        L = lib()
+        L.ocr_srv_net_ctc_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int)]
+        cap = 1 << 16
+        a, p = np.zeros(cap, np.int32), np.zeros(cap, np.float32)
+        rows, slots, step = C.c_long(), C.c_int(), C.c_int()
+        check(L.ocr_srv_net_ctc_tail(self.h, a.ctypes.data, p.ctypes.data, cap, C.byref(rows), C.byref(slots), C.byref(step)))
+        return a[:rows.value].copy(), p[:rows.value].copy(), slots.value, step.value
+
     def timing(self, on=True):
         check(lib().ocr_srv_net_timing(self.h, 1 if on else 0))
 
@@ -359,6 +378,143 @@ def selftest_line_pre_ragged(parent, cols, lines, imgH, stage=STAGE_REC):
         outs.append(x[at:at + imgH * w * 3].reshape(imgH, w, 3))
         at += imgH * w * 3
     return outs, g
+
+
+# ---- the recognizer's tail launches alone (include/ocr_hip.h): every output comes back as (values, guard bytes)
+def _tail_buf(count):
+    return np.zeros(max(0, int(count)) * 4 + SELFTEST_GUARD, np.uint8)
+
+
+def _tail_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _tail_call(name, argtypes, *args):
+    L = lib()
+    fn = getattr(L, name)
+    fn.argtypes = argtypes
+    rc = fn(*args)
+    if rc != 0:
+        _raise(L, rc, None)
+
+
+def selftest_softmax_argmax(logits, probs=False):
+    """launch_softmax_argmax on f32 [rows, C] -> {"amax": (int32 [rows], guard), "pmax": (f32 [rows], guard), "probs": (f32 [rows, C],
+    guard) when asked for}"""
+    x = np.ascontiguousarray(logits, dtype=np.float32)
+    rows, C_ = x.shape
+    ok = 0 < rows * C_ <= 1 << 26
+    q = _tail_buf(rows * C_ if ok else 0) if probs else None
+    a, p = _tail_buf(rows), _tail_buf(rows)
+    _tail_call("ocr_selftest_softmax_argmax", [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+               x.ctypes.data, rows, C_, _tail_ptr(q), a.ctypes.data, p.ctypes.data)
+    out = {"amax": _split_guard(a, rows, np.int32), "pmax": _split_guard(p, rows, np.float32)}
+    if probs:
+        v, g = _split_guard(q, rows * C_, np.float32)
+        out["probs"] = (v.reshape(rows, C_), g)
+    return out
+
+
+def selftest_head_combine(hmax, hsum, hidx):
+    """launch_head_combine on [rows, groups] partials -> ((amax, guard), (pmax, guard))"""
+    m = np.ascontiguousarray(hmax, dtype=np.float32)
+    s = np.ascontiguousarray(hsum, dtype=np.float32)
+    i = np.ascontiguousarray(hidx, dtype=np.int32)
+    assert m.ndim == 2 and m.shape == s.shape == i.shape
+    rows, G = m.shape
+    a, p = _tail_buf(rows), _tail_buf(rows)
+    _tail_call("ocr_selftest_head_combine", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p],
+               m.ctypes.data, s.ctypes.data, i.ctypes.data, rows, G, a.ctypes.data, p.ctypes.data)
+    return _split_guard(a, rows, np.int32), _split_guard(p, rows, np.float32)
+
+
+def selftest_srv_argmax(logits, ncols=None, one_pass=False):
+    """srv::launch_argmax_softmax on f32 [rows, ld] of which the first ncols columns are the logits -> ((amax, guard), (pmax, guard))"""
+    x = np.ascontiguousarray(logits, dtype=np.float32)
+    rows, ld = x.shape
+    a, p = _tail_buf(rows), _tail_buf(rows)
+    _tail_call("ocr_selftest_srv_argmax", [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+               x.ctypes.data, rows, ld if ncols is None else int(ncols), ld, 1 if one_pass else 0, a.ctypes.data, p.ctypes.data)
+    return _split_guard(a, rows, np.int32), _split_guard(p, rows, np.float32)
+
+
+def selftest_ctc_reduce(part, step=1):
+    """srv::launch_ctc_reduce on f32 [rows, slots, 4] partials (the index as int bits) -> ((amax, guard), (pmax, guard))"""
+    x = np.ascontiguousarray(part, dtype=np.float32)
+    rows, slots, four = x.shape
+    assert four == 4
+    a, p = _tail_buf(rows), _tail_buf(rows)
+    _tail_call("ocr_selftest_ctc_reduce", [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+               x.ctypes.data, rows, slots, int(step), a.ctypes.data, p.ctypes.data)
+    return _split_guard(a, rows, np.int32), _split_guard(p, rows, np.float32)
+
+
+def selftest_ctc(amax, pmax, max_len, T=None, lines=None, chars=False):
+    """launch_ctc (T given) / launch_ctc_ragged (lines: rows of (first step, steps)) / launch_ctc_chars (chars) on flat step arrays
+    -> dict of (values, guard): ids [n, max_len], lens [n], scores [n] and, with chars, steps / nsteps / probs [n, max_len]"""
+    am = np.ascontiguousarray(amax, dtype=np.int32).reshape(-1)
+    pm = np.ascontiguousarray(pmax, dtype=np.float32).reshape(-1)
+    assert am.size == pm.size
+    if lines is not None:
+        lines = np.ascontiguousarray(lines, dtype=np.int32).reshape(-1, 2)
+        n = len(lines)
+    else:
+        n = am.size // T if T and T > 0 else 0
+    nch = n * max_len if 0 < n and 0 < max_len <= 4096 and n <= 1 << 18 else 0
+    nl = n if nch else 0
+    bufs = {"ids": _tail_buf(nch), "lens": _tail_buf(nl), "scores": _tail_buf(nl)}
+    if chars:
+        bufs.update(steps=_tail_buf(nch), nsteps=_tail_buf(nch), probs=_tail_buf(nch))
+    _tail_call("ocr_selftest_ctc", [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6,
+               am.ctypes.data, pm.ctypes.data, am.size, n, int(T or 0), _tail_ptr(lines), int(max_len), 1 if chars else 0,
+               bufs["ids"].ctypes.data, bufs["lens"].ctypes.data, bufs["scores"].ctypes.data, _tail_ptr(bufs.get("steps")),
+               _tail_ptr(bufs.get("nsteps")), _tail_ptr(bufs.get("probs")))
+    out = {}
+    for k, b in bufs.items():
+        per_char = k in ("ids", "steps", "nsteps", "probs")
+        v, g = _split_guard(b, nch if per_char else nl, np.float32 if k in ("scores", "probs") else np.int32)
+        out[k] = (v.reshape(n, max_len) if per_char else v, g)
+    return out
+
+
+def selftest_topk_lines(rows, T, lens, steps, p0, k, ncols=None):
+    """launch_ctc_topk on nlines lines of T rows: rows f32 [nlines * T, pitch]; lens [nlines]; steps, p0 [nlines, max_len] ->
+    ((ids [nlines, max_len, k], guard), (probs likewise, guard))"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    nrows, pitch = rows.shape
+    lens = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+    n = lens.size
+    steps = np.ascontiguousarray(steps, dtype=np.int32).reshape(n, -1)
+    max_len = steps.shape[1]
+    p0 = np.ascontiguousarray(p0, dtype=np.float32).reshape(n, max_len)
+    assert nrows == n * T
+    cnt = n * max_len * k if 1 <= k <= 8 else 0
+    ids, probs = _tail_buf(cnt), _tail_buf(cnt)
+    _tail_call("ocr_selftest_topk_lines", [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_int, C.c_void_p, C.c_void_p],
+               rows.ctypes.data, n, int(T), pitch if ncols is None else int(ncols), pitch, lens.ctypes.data, steps.ctypes.data,
+               p0.ctypes.data, max_len, int(k), ids.ctypes.data, probs.ctypes.data)
+    (i, gi), (p, gp) = _split_guard(ids, cnt, np.int32), _split_guard(probs, cnt, np.float32)
+    return (i.reshape(n, max_len, k), gi), (p.reshape(n, max_len, k), gp)
+
+
+def selftest_rec_head(weights, precision, rows, lines, imgH, imgW, mode=0, ncols=6625, model_dir=None):
+    """ocr_selftest_rec_head: the mobile recognizer's head through its binder on rows f32 [nrows, K] -> dict(amax=(int32 [nrows],
+    guard), pmax=(f32 [nrows], guard), logits=f32 [nrows, C] or None, names=[the two launches' names])"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    n, K = rows.shape
+    if model_dir is None:
+        model_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "models", "rec")
+    a, p = _tail_buf(n), _tail_buf(n)
+    lg = np.zeros((n, ncols), np.float32) if mode else None
+    nc = C.c_int()
+    names = C.create_string_buffer(512)
+    _tail_call("ocr_selftest_rec_head", [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t],
+               model_dir.encode(), None if weights is None else weights.encode(), precision.encode(), rows.ctypes.data, n, K, int(lines),
+               int(imgH), int(imgW), int(mode), a.ctypes.data, p.ctypes.data, _tail_ptr(lg), C.byref(nc), names, len(names))
+    assert nc.value == ncols
+    return dict(amax=_split_guard(a, n, np.int32), pmax=_split_guard(p, n, np.float32), logits=lg, names=names.value.decode().split())
 
 
 def probe(a, b):

@@ -250,6 +250,84 @@ int ocr_net_create_precision(const char* kind, const char* model_dir, const char
   return OCR_OK;
 }
 
+// self-test: the mobile recognizer's head alone, through the binder (tests/test_gpu_rec_tail.py).  The embedded rec plan is loaded
+// with the weights of `weights` (the caller's: its last linear's may be anything), bound on `lines` blank lines of imgH x imgW
+// with the head's sinks set as RecStage sets them, the caller's rows uploaded as the head linear's input, and the binding's last
+// two launches - the linear and the softmax behind it, fused into conv_finish<OUT_HEAD> + head_combine or not, by the binder's own
+// rules - run alone.  mode 0: sinks (null, amax, pmax); 1: the same with the logits kept (Net::set_keep_logits); 2: probabilities
+// requested as well.  amax / pmax: nrows values + OCR_SELFTEST_GUARD bytes, pre-filled; logits (modes 1, 2): nrows * C.
+namespace {
+struct HeadScratch {
+  float *x = nullptr, *q = nullptr;
+  unsigned char *a = nullptr, *p = nullptr;
+  hipStream_t s = nullptr;
+  ~HeadScratch() {
+    if (x) (void)g_free(x);
+    if (q) (void)g_free(q);
+    if (a) (void)g_free(a);
+    if (p) (void)g_free(p);
+    if (s) (void)hipStreamDestroy(s);
+  }
+};
+}  // namespace
+int ocr_selftest_rec_head(const char* model_dir, const char* weights, const char* precision, const float* rows, long nrows, int K,
+                          int lines, int imgH, int imgW, int mode, int32_t* amax, float* pmax, float* logits, int* ncols, char* names,
+                          size_t names_cap) {
+  if (!model_dir || !precision || !rows || !amax || !pmax || !ncols || !names || names_cap == 0) return fail(OCR_ERR_ARG, "null argument");
+  if (mode < 0 || mode > 2 || (mode != 0 && !logits)) return fail(OCR_ERR_ARG, "mode is 0, 1 or 2; modes 1 and 2 return the logits");
+  if (nrows < 1 || nrows > (1 << 16) || lines < 1 || lines > nrows || nrows % lines != 0) return fail(OCR_ERR_ARG, "rows or lines out of range");
+  if (imgH < 8 || imgH > 256 || imgW < 8 || imgW > 4096) return fail(OCR_ERR_ARG, "line size out of range");
+  const bool half = !strcmp(precision, "fp16");
+  if (!half && strcmp(precision, "fp32")) return fail(OCR_ERR_ARG, "precision must be fp32 or fp16");
+  int rc = ocr_rt_init(0);
+  if (rc) return rc;
+  WeightMap w;
+  std::string err;
+  if (!load_model_dir(model_dir, weights, "rec", w, err)) return fail(OCR_ERR_MODEL, err);
+  Net net;
+  if (!net.load(embedded_plan("rec"), w, err, half)) return fail(OCR_ERR_MODEL, err);
+  const PlanOp* lin = nullptr;
+  for (size_t i = 0; i + 1 < net.plan().ops.size(); ++i) {
+    const PlanOp &a = net.plan().ops[i], &b = net.plan().ops[i + 1];
+    if (a.kind == PlanOp::LINEAR && b.kind == PlanOp::SOFTMAX && b.in == a.out) lin = &a;
+  }
+  if (!lin) return fail(OCR_ERR_MODEL, "the plan has no linear -> softmax head");
+  if (K != lin->cin) return fail(OCR_ERR_ARG, "K is not the head linear's input width");
+  const int C = lin->cout;
+  *ncols = C;
+  HeadScratch d;
+  const size_t nx = (size_t)lines * imgH * imgW * 3, out_bytes = (size_t)nrows * 4 + OCR_SELFTEST_GUARD;
+  CAPI_HIP(g_malloc(&d.x, nx * sizeof(float)));
+  CAPI_HIP(g_malloc(&d.a, out_bytes));
+  CAPI_HIP(g_malloc(&d.p, out_bytes));
+  if (mode == 2) CAPI_HIP(g_malloc(&d.q, (size_t)nrows * C * sizeof(float)));
+  CAPI_HIP(hipMemset(d.x, 0, nx * sizeof(float)));
+  CAPI_HIP(g_stream_create(&d.s));
+  net.set_keep_logits(mode == 1);
+  net.set_head_outputs(d.q, (int*)d.a, (float*)d.p);
+  if (!net.run(d.x, lines, imgH, imgW, d.s, err)) return fail(OCR_ERR_DEVICE, err);
+  CAPI_HIP(g_stream_sync(d.s));
+  if (net.tensor(lin->in).pixels() != nrows) return fail(OCR_ERR_ARG, "nrows is not lines * the CTC steps of a line this wide");
+  CAPI_HIP(hipMemset(d.a, OCR_SELFTEST_FILL, out_bytes));
+  CAPI_HIP(hipMemset(d.p, OCR_SELFTEST_FILL, out_bytes));
+  if (!net.upload_logical(lin->in, rows, (size_t)nrows * K, d.s, err)) return fail(OCR_ERR_ARG, err);
+  if (!net.run_tail_launches(2, d.s, err)) return fail(OCR_ERR_DEVICE, err);
+  CAPI_HIP(g_stream_sync(d.s));
+  const std::string nm = net.tail_launch_names(2) + (net.head_fused() ? "logits_fused" : "logits_stored");
+  if (nm.size() >= names_cap) return fail(OCR_ERR_CAPACITY, "name buffer too small");
+  memcpy(names, nm.c_str(), nm.size() + 1);
+  CAPI_HIP(g_memcpy(amax, d.a, out_bytes, hipMemcpyDeviceToHost));
+  CAPI_HIP(g_memcpy(pmax, d.p, out_bytes, hipMemcpyDeviceToHost));
+  if (mode != 0) {
+    std::vector<float> host;
+    int dims[4];
+    if (!net.fetch_logical(lin->out, host, dims, d.s, err)) return fail(OCR_ERR_DEVICE, err);
+    if (host.size() != (size_t)nrows * C) return fail(OCR_ERR_DEVICE, "logits tensor has another size");
+    memcpy(logits, host.data(), host.size() * sizeof(float));
+  }
+  return OCR_OK;
+}
+
 void ocr_net_destroy(ocr_net* h) {
   if (!h) return;
   (void)rt_set_device(h->device);

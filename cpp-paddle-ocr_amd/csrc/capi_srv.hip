@@ -160,6 +160,42 @@ int ocr_srv_net_upload(ocr_srv_net* h, int tid, const float* data, size_t count)
   return OCR_OK;
 }
 
+// test hooks for the CTC head (tests/test_gpu_rec_tail.py): the head's partial mode as RecStage switches it, and the tail launch
+// RecStage issues behind the network - launch_ctc_reduce on the head's partials with the handle's own ctc_slots() / ctc_step(),
+// or launch_argmax_softmax on its logits - for the rows of the current binding
+int ocr_srv_net_set_ctc(ocr_srv_net* h, int on) {
+  if (!h) return fail(OCR_ERR_ARG, "null handle");
+  h->net.set_ctc_partials(on != 0);
+  return OCR_OK;
+}
+int ocr_srv_net_ctc_tail(ocr_srv_net* h, int32_t* amax, float* pmax, long cap_rows, long* rows, int* slots, int* step) {
+  if (!h || !amax || !pmax || !rows || !slots || !step) return fail(OCR_ERR_ARG, "null argument");
+  if (h->net.num_launches() == 0) return fail(OCR_ERR_ARG, "no binding yet: run ocr_srv_net_forward first");
+  CAPI_HIP(rt_set_device(h->device));
+  const auto& ot = h->net.tensor(h->net.output_tid());
+  const long n = (long)ot.n * ot.h * ot.w;
+  *rows = n;
+  *slots = h->net.ctc_partials() ? h->net.ctc_slots() : 0;
+  *step = h->net.ctc_partials() ? h->net.ctc_step() : 0;
+  if (n < 1 || n > cap_rows) return fail(OCR_ERR_CAPACITY, "output buffers too small");
+  int* da = nullptr;
+  float* dp = nullptr;
+  CAPI_HIP(g_malloc(&da, (size_t)n * sizeof(int)));
+  if (g_malloc(&dp, (size_t)n * sizeof(float)) != hipSuccess) { (void)g_free(da); return fail(OCR_ERR_DEVICE, "hipMalloc failed"); }
+  const float* out = (const float*)h->net.tensor_ptr(h->net.output_tid());
+  if (h->net.ctc_partials())
+    srv::launch_ctc_reduce(out, n, h->net.ctc_slots(), h->net.ctc_step(), da, dp, h->stream);
+  else
+    srv::launch_argmax_softmax(out, n, ot.c, ot.cs, da, dp, h->net.half(), h->stream);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = g_stream_sync(h->stream);
+  if (e == hipSuccess) e = g_memcpy(amax, da, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = g_memcpy(pmax, dp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
+  (void)g_free(da); (void)g_free(dp);
+  CAPI_HIP(e);
+  return OCR_OK;
+}
+
 int ocr_srv_net_timing(ocr_srv_net* h, int enable) {
   if (!h) return fail(OCR_ERR_ARG, "null handle");
   h->net.enable_timing(enable != 0);

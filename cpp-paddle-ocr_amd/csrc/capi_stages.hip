@@ -391,6 +391,185 @@ int ocr_selftest_topk(const float* rows, int n, int C, int pitch, const float* p
   CAPI_HIP(g_memcpy(out_probs, dprobs.p, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost));
   return OCR_OK;
 }
+// ---- self-test taps: the recognizer's tail launches alone (tests/test_gpu_rec_tail.py).  Outputs pre-filled with
+// OCR_SELFTEST_FILL, each handed back with OCR_SELFTEST_GUARD bytes from behind its last element.
+extern "C++" {
+namespace {
+const long kTailMaxRows = 1 << 20, kTailMaxLines = 1 << 18;
+const int kTailMaxSteps = 4096, kTailMaxLen = 4096;
+const size_t kTailMaxBytes = (size_t)1 << 28;
+
+// a pre-filled device array of n elements + guard
+template <typename T>
+bool tail_out(DevBuf<uint8_t>& d, size_t n, std::string& err) {
+  const size_t bytes = n * sizeof(T) + OCR_SELFTEST_GUARD;
+  if (!d.ensure(bytes, err)) return false;
+  if (hipMemset(d.p, OCR_SELFTEST_FILL, bytes) != hipSuccess) { err = "hipMemset failed"; return false; }
+  return true;
+}
+template <typename T>
+hipError_t tail_back(void* host, const DevBuf<uint8_t>& d, size_t n) {
+  return g_memcpy(host, d.p, n * sizeof(T) + OCR_SELFTEST_GUARD, hipMemcpyDeviceToHost);
+}
+template <typename T>
+bool tail_in(DevBuf<T>& d, const T* host, size_t n, std::string& err) {
+  if (!d.ensure(n, err)) return false;
+  if (g_memcpy(d.p, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { err = "upload failed"; return false; }
+  return true;
+}
+}  // namespace
+}  // extern "C++"
+
+int ocr_selftest_topk_lines(const float* rows, int nlines, int T, int C, int pitch, const int32_t* lens, const int32_t* steps,
+                            const float* p0, int max_len, int k, int32_t* out_ids, float* out_probs) {
+  if (!rows || !lens || !steps || !p0 || !out_ids || !out_probs) return fail(OCR_ERR_ARG, "null argument");
+  if (nlines < 1 || nlines > kTailMaxLines || T < 1 || T > kTailMaxSteps || C < 1 || pitch < C || k < 1 || k > 8 || max_len < 1 ||
+      max_len > kTailMaxLen)
+    return fail(OCR_ERR_ARG, "size out of range");
+  const size_t nrows = (size_t)nlines * T, nfl = (nrows - 1) * pitch + C, nch = (size_t)nlines * max_len;
+  if (nfl * sizeof(float) > kTailMaxBytes || nch * k * sizeof(float) > kTailMaxBytes) return fail(OCR_ERR_ARG, "buffers too large");
+  for (int i = 0; i < nlines; ++i) {
+    if (lens[i] < 0) return fail(OCR_ERR_ARG, "negative line length");
+    for (int j = 0; j < std::min(lens[i], max_len); ++j)
+      if (steps[(size_t)i * max_len + j] < 0 || steps[(size_t)i * max_len + j] >= T) return fail(OCR_ERR_ARG, "step outside the line");
+  }
+  std::string err;
+  DevBuf<float> drows, dp0;
+  DevBuf<int> dlens, dsteps;
+  DevBuf<uint8_t> dids, dprobs;
+  if (!tail_in(drows, rows, nfl, err) || !tail_in(dp0, p0, nch, err) || !tail_in(dlens, (const int*)lens, (size_t)nlines, err) ||
+      !tail_in(dsteps, (const int*)steps, nch, err) || !tail_out<int>(dids, nch * k, err) || !tail_out<float>(dprobs, nch * k, err))
+    return fail(OCR_ERR_DEVICE, err);
+  launch_ctc_topk(drows.p, pitch, C, k, nullptr, nlines, T, max_len, dlens.p, dsteps.p, dp0.p, (int*)dids.p, (float*)dprobs.p, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(tail_back<int>(out_ids, dids, nch * k));
+  CAPI_HIP(tail_back<float>(out_probs, dprobs, nch * k));
+  return OCR_OK;
+}
+
+int ocr_selftest_softmax_argmax(const float* logits, long rows, int C, float* probs, int32_t* amax, float* pmax) {
+  if (!logits || !amax || !pmax) return fail(OCR_ERR_ARG, "null argument");
+  if (rows < 1 || rows > kTailMaxRows || C < 1) return fail(OCR_ERR_ARG, "rows or columns out of range");
+  if (C > kSoftmaxMaxCols) return fail(OCR_ERR_ARG, "more columns than softmax_argmax_kernel takes (8192)");
+  const size_t nel = (size_t)rows * C;
+  if (nel * sizeof(float) > kTailMaxBytes) return fail(OCR_ERR_ARG, "logits too large");
+  std::string err;
+  DevBuf<float> dx;
+  DevBuf<uint8_t> dq, da, dp;
+  if (!tail_in(dx, logits, nel, err) || (probs && !tail_out<float>(dq, nel, err)) || !tail_out<int>(da, (size_t)rows, err) ||
+      !tail_out<float>(dp, (size_t)rows, err))
+    return fail(OCR_ERR_DEVICE, err);
+  launch_softmax_argmax(dx.p, probs ? (float*)dq.p : nullptr, (int*)da.p, (float*)dp.p, rows, C, nullptr);
+  CAPI_HIP(hipGetLastError());
+  if (probs) CAPI_HIP(tail_back<float>(probs, dq, nel));
+  CAPI_HIP(tail_back<int>(amax, da, (size_t)rows));
+  CAPI_HIP(tail_back<float>(pmax, dp, (size_t)rows));
+  return OCR_OK;
+}
+
+int ocr_selftest_head_combine(const float* hmax, const float* hsum, const int32_t* hidx, long rows, int groups, int32_t* amax,
+                              float* pmax) {
+  if (!hmax || !hsum || !hidx || !amax || !pmax) return fail(OCR_ERR_ARG, "null argument");
+  if (rows < 1 || rows > kTailMaxRows || groups < 1 || groups > 1 << 16) return fail(OCR_ERR_ARG, "rows or groups out of range");
+  const size_t nel = (size_t)rows * groups;
+  if (nel * sizeof(float) > kTailMaxBytes) return fail(OCR_ERR_ARG, "partials too large");
+  std::string err;
+  DevBuf<float> dm, ds;
+  DevBuf<int> di;
+  DevBuf<uint8_t> da, dp;
+  if (!tail_in(dm, hmax, nel, err) || !tail_in(ds, hsum, nel, err) || !tail_in(di, (const int*)hidx, nel, err) ||
+      !tail_out<int>(da, (size_t)rows, err) || !tail_out<float>(dp, (size_t)rows, err))
+    return fail(OCR_ERR_DEVICE, err);
+  launch_head_combine(dm.p, ds.p, di.p, rows, groups, (int*)da.p, (float*)dp.p, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(tail_back<int>(amax, da, (size_t)rows));
+  CAPI_HIP(tail_back<float>(pmax, dp, (size_t)rows));
+  return OCR_OK;
+}
+
+int ocr_selftest_ctc(const int32_t* amax, const float* pmax, long nsteps_total, int nlines, int T, const int32_t* lines, int max_len,
+                     int chars, int32_t* ids, int32_t* lens, float* scores, int32_t* steps, int32_t* nsteps, float* probs) {
+  if (!amax || !pmax || !ids || !lens || !scores) return fail(OCR_ERR_ARG, "null argument");
+  if (chars && (!steps || !nsteps || !probs)) return fail(OCR_ERR_ARG, "null argument (per-character outputs)");
+  if (nlines < 1 || nlines > kTailMaxLines || max_len < 1 || max_len > kTailMaxLen) return fail(OCR_ERR_ARG, "line count or max_len out of range");
+  if (nsteps_total < 1 || nsteps_total > kTailMaxRows) return fail(OCR_ERR_ARG, "step count out of range");
+  if (lines) {
+    for (int i = 0; i < nlines; ++i) {
+      const int32_t s0 = lines[2 * i], n = lines[2 * i + 1];
+      if (n < 0 || n > kTailMaxSteps || s0 < 0 || s0 > nsteps_total - n) return fail(OCR_ERR_ARG, "a line's steps lie outside the step arrays");
+    }
+  } else if (T < 1 || T > kTailMaxSteps || (long)nlines * T != nsteps_total) {
+    return fail(OCR_ERR_ARG, "T out of range or nlines * T is not the step count");
+  }
+  const size_t nch = (size_t)nlines * max_len;
+  std::string err;
+  DevBuf<int> dam;
+  DevBuf<float> dpm;
+  DevBuf<LineDesc> ddesc;
+  DevBuf<uint8_t> dids, dlens, dsc, dst, dns, dpr;
+  if (!tail_in(dam, (const int*)amax, (size_t)nsteps_total, err) || !tail_in(dpm, pmax, (size_t)nsteps_total, err) ||
+      !tail_out<int>(dids, nch, err) || !tail_out<int>(dlens, (size_t)nlines, err) || !tail_out<float>(dsc, (size_t)nlines, err))
+    return fail(OCR_ERR_DEVICE, err);
+  if (chars && (!tail_out<int>(dst, nch, err) || !tail_out<int>(dns, nch, err) || !tail_out<float>(dpr, nch, err))) return fail(OCR_ERR_DEVICE, err);
+  if (lines) {
+    std::vector<LineDesc> d((size_t)nlines, LineDesc::make(nullptr, 0, 0, 0, 1, 1, 1, 0, 1));
+    for (int i = 0; i < nlines; ++i) { d[i].slot = i; d[i].step0 = lines[2 * i]; d[i].steps = lines[2 * i + 1]; }
+    if (!tail_in(ddesc, (const LineDesc*)d.data(), (size_t)nlines, err)) return fail(OCR_ERR_DEVICE, err);
+  }
+  if (chars)
+    launch_ctc_chars(dam.p, dpm.p, lines ? ddesc.p : nullptr, nlines, T, max_len, (int*)dids.p, (int*)dlens.p, (float*)dsc.p, (int*)dst.p,
+                     (int*)dns.p, (float*)dpr.p, nullptr);
+  else if (lines)
+    launch_ctc_ragged(dam.p, dpm.p, ddesc.p, nlines, max_len, (int*)dids.p, (int*)dlens.p, (float*)dsc.p, nullptr);
+  else
+    launch_ctc(dam.p, dpm.p, nlines, T, max_len, (int*)dids.p, (int*)dlens.p, (float*)dsc.p, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(tail_back<int>(ids, dids, nch));
+  CAPI_HIP(tail_back<int>(lens, dlens, (size_t)nlines));
+  CAPI_HIP(tail_back<float>(scores, dsc, (size_t)nlines));
+  if (chars) {
+    CAPI_HIP(tail_back<int>(steps, dst, nch));
+    CAPI_HIP(tail_back<int>(nsteps, dns, nch));
+    CAPI_HIP(tail_back<float>(probs, dpr, nch));
+  }
+  return OCR_OK;
+}
+
+int ocr_selftest_srv_argmax(const float* logits, long rows, int C, int ld, int one_pass, int32_t* amax, float* pmax) {
+  if (!logits || !amax || !pmax) return fail(OCR_ERR_ARG, "null argument");
+  if (rows < 1 || rows > kTailMaxRows || C < 1 || ld < C) return fail(OCR_ERR_ARG, "rows, columns or row pitch out of range");
+  if (one_pass && (ld % 4 != 0 || ld < ((C + 3) & ~3))) return fail(OCR_ERR_ARG, "the one-pass form reads 16 bytes at a time: ld % 4 == 0 and ld >= C rounded up to 4");
+  const size_t nel = (size_t)rows * ld;  // (whole rows: the one-pass form reads up to the row's pitch)
+  if (nel * sizeof(float) > kTailMaxBytes) return fail(OCR_ERR_ARG, "logits too large");
+  std::string err;
+  DevBuf<float> dx;
+  DevBuf<uint8_t> da, dp;
+  if (!tail_in(dx, logits, nel, err) || !tail_out<int>(da, (size_t)rows, err) || !tail_out<float>(dp, (size_t)rows, err))
+    return fail(OCR_ERR_DEVICE, err);
+  srv::launch_argmax_softmax(dx.p, rows, C, ld, (int*)da.p, (float*)dp.p, one_pass != 0, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(tail_back<int>(amax, da, (size_t)rows));
+  CAPI_HIP(tail_back<float>(pmax, dp, (size_t)rows));
+  return OCR_OK;
+}
+
+int ocr_selftest_ctc_reduce(const float* part, long rows, int slots, int step, int32_t* amax, float* pmax) {
+  if (!part || !amax || !pmax) return fail(OCR_ERR_ARG, "null argument");
+  if (rows < 1 || rows > kTailMaxRows || slots < 1 || slots > 1 << 16 || step < 1 || step > slots) return fail(OCR_ERR_ARG, "rows, slots or step out of range");
+  const size_t nel = (size_t)rows * slots * 4;
+  if (nel * sizeof(float) > kTailMaxBytes) return fail(OCR_ERR_ARG, "partials too large");
+  std::string err;
+  DevBuf<float> dx;
+  DevBuf<uint8_t> da, dp;
+  if (!tail_in(dx, part, nel, err) || !tail_out<int>(da, (size_t)rows, err) || !tail_out<float>(dp, (size_t)rows, err))
+    return fail(OCR_ERR_DEVICE, err);
+  srv::launch_ctc_reduce(dx.p, rows, slots, step, (int*)da.p, (float*)dp.p, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(tail_back<int>(amax, da, (size_t)rows));
+  CAPI_HIP(tail_back<float>(pmax, dp, (size_t)rows));
+  return OCR_OK;
+}
+
 const char* ocr_rec_label(ocr_rec* h, int id) {
   if (!h || id < 0 || id >= (int)h->s.labels().size()) return nullptr;
   return h->s.labels()[id].c_str();

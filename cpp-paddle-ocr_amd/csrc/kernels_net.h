@@ -247,6 +247,9 @@ bool attn_ragged_fits(int T);
 // second half of the fused head: rows x groups partials -> arg max / max probability per row
 void launch_head_combine(const float* hmax, const float* hsum, const int* hidx, long rows, int groups, int* amax, float* pmax,
                          hipStream_t s);
+// C <= kSoftmaxMaxCols: the kernel keeps a wave's group maxima and chain sums in LDS tables of 64 groups of 128 columns
+// (Net::bind refuses a wider softmax)
+constexpr int kSoftmaxMaxCols = 8192;
 void launch_softmax_argmax(const float* logits, float* probs, int* amax, float* pmax, long rows, int C, hipStream_t s);
 
 struct DetTailArgs {

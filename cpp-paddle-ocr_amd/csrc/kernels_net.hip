@@ -2157,8 +2157,10 @@ __global__ void __launch_bounds__(256) softmax_argmax_kernel(const float* __rest
     if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
   }
   if (lane == 0) {
+    float p = ocr_expf(best - M) / S;
+    head_result(bi, p);
     if (amax) amax[r] = bi;
-    if (pmax) pmax[r] = ocr_expf(best - M) / S;
+    if (pmax) pmax[r] = p;
   }
 }
 void launch_softmax_argmax(const float* logits, float* probs, int* amax, float* pmax, long rows, int C, hipStream_t s) {
@@ -2184,8 +2186,10 @@ __global__ void __launch_bounds__(256) head_combine_kernel(const float* __restri
     const float t = sg[g] * ocr_expf(m[g] - M);
     S = S + t;
   }
+  float p = ocr_expf(M - M) / S;
+  head_result(bi, p);
   if (amax) amax[r] = bi;
-  if (pmax) pmax[r] = ocr_expf(M - M) / S;
+  if (pmax) pmax[r] = p;
 }
 void launch_head_combine(const float* hmax, const float* hsum, const int* hidx, long rows, int groups, int* amax, float* pmax,
                          hipStream_t s) {

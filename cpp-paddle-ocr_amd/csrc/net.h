@@ -102,6 +102,14 @@ class Net {
   // Copies tensor `tid` to host in logical NHWC order (parity taps).
   bool fetch_logical(int tid, std::vector<float>& host, int dims[4], hipStream_t s, std::string& err);
 
+  // --- test hooks (ocr_selftest_rec_head): logical NHWC values into a C8I tensor of the current uniform binding (rounded to its
+  // element type, pad channels zero); the last `count` launches of that binding alone, issued plainly; their names, '\n'-separated
+  bool upload_logical(int tid, const float* host, size_t count, hipStream_t s, std::string& err);
+  bool run_tail_launches(int count, hipStream_t s, std::string& err);
+  std::string tail_launch_names(int count) const;
+  const Plan& plan() const { return plan_; }
+  bool head_fused() const { return cur_ && fused_head_rows_ >= 0; }  // the current binding folds the softmax into its linear (OUT_HEAD)
+
   // --- det tail options: fused u8 threshold bitmap (null = none) ---
   void set_det_bitmap(uint8_t* bitmap, int ithresh) { det_bitmap_ = bitmap; det_ithresh_ = ithresh; invalidate(); }
   // --- rec/cls head options: where the row softmax leaves its results ---

@@ -1656,6 +1656,7 @@ struct Net::BindCtx {
       L.bytes = 12.0 * rows * G;
       L.fn = [net = &net, hm, hs, hi, rows, G](hipStream_t s) { launch_head_combine(hm, hs, hi, rows, G, net->head_amax_, net->head_pmax_, s); };
     } else {
+      if (C > kSoftmaxMaxCols) { err = fmt("softmax over %d columns: softmax_argmax_kernel takes at most %d", C, kSoftmaxMaxCols); return false; }
       L.fn = [net = &net, ip, optr, rows, C](hipStream_t s) {
         float* probs = (net->head_amax_ || net->head_pmax_) ? net->head_probs_ : optr;
         launch_softmax_argmax(ip, probs, net->head_amax_, net->head_pmax_, rows, C, s);
@@ -1927,6 +1928,42 @@ bool Net::head_logits(HeadLogits& out, std::string& err) const {
   }
   err = "the plan has no linear -> softmax head";
   return false;
+}
+
+bool Net::upload_logical(int tid, const float* host, size_t count, hipStream_t s, std::string& err) {
+  if (tid <= 0 || tid >= plan_.ntensors || !cur_ || !cur_->exists[tid]) { err = "upload: no such tensor under this binding"; return false; }
+  const TensorDesc& t = tensors_[tid];
+  if (t.plain || t.lvl >= 0) { err = "upload: a C8I tensor of a uniform binding"; return false; }
+  const size_t px = (size_t)t.pixels();
+  if (count != px * t.c) { err = "upload: element count is not the tensor's"; return false; }
+  std::vector<unsigned char> img(px * t.cs * (t.f16 ? 2 : 4), 0);
+  for (size_t p = 0; p < px; ++p)
+    for (int c = 0; c < t.c; ++c) {
+      const float v = host[p * t.c + c];
+      const size_t k = p * t.cs + c8i_phys(c);
+      if (t.f16) ((_Float16*)img.data())[k] = (_Float16)v;
+      else ((float*)img.data())[k] = v;
+    }
+  HIP_OK(g_stream_sync(s));
+  HIP_OK(g_memcpy(arena_ + t.offset, img.data(), img.size(), hipMemcpyHostToDevice));
+  return true;
+}
+
+bool Net::run_tail_launches(int count, hipStream_t s, std::string& err) {
+  if (!cur_ || count < 1 || count > (int)cur_->launches.size()) { err = "no such launch range"; return false; }
+  launch_error_.clear();
+  for (size_t i = cur_->launches.size() - count; i < cur_->launches.size(); ++i) cur_->launches[i].fn(s);
+  if (!launch_error_.empty()) { err = launch_error_; return false; }
+  HIP_OK(hipGetLastError());
+  return true;
+}
+
+std::string Net::tail_launch_names(int count) const {
+  std::string out;
+  if (!cur_) return out;
+  const size_t n = cur_->launches.size();
+  for (size_t i = n - std::min<size_t>(n, (size_t)std::max(0, count)); i < n; ++i) out += cur_->launches[i].name + "\n";
+  return out;
 }
 
 bool Net::fetch_logical(int tid, std::vector<float>& host, int dims[4], hipStream_t s, std::string& err) {

@@ -21,6 +21,16 @@ OCR_HD int c8i_phys(int c) { return (c & ~7) | ((c & 1) << 2) | ((c & 7) >> 1); 
 OCR_HD int c8i_logical(int p) { return (p & ~7) | (((p & 3) << 1) | ((p >> 2) & 1)); }
 OCR_HD int c8i_stride(int c) { return (c + 7) & ~7; }
 
+// A row's (arg max, probability) as the head kernels store it (DESIGN.md section 4, rows without a finite maximum).  Every
+// arg-max site starts from (-inf, kNoMax) and takes `x > best`: a row in which no column exceeds -inf (all -inf and / or NaN)
+// still carries kNoMax here and is stored as (0, 0) - column 0, the blank; a probability whose divisor underflowed to 0
+// (+inf in the row) is stored as 0, never as inf.
+constexpr int kNoMax = 0x7fffffff;
+OCR_HD void head_result(int& idx, float& p) {
+  if (idx == kNoMax) { idx = 0; p = 0.f; }
+  else if (p == INFINITY || p == -INFINITY) p = 0.f;
+}
+
 // exp with a fixed sequence of f32 roundings (same sequence as the CPU oracle; never libm).
 OCR_HD float ocr_expf(float x) {
   x = fminf(fmaxf(x, -87.0f), 88.0f);

@@ -1461,8 +1461,10 @@ __global__ void __launch_bounds__(256) ctc_reduce_kernel(const float* __restrict
     mx = M2;
     sum = sa + sb;
   }
+  float p = 1.0f / sum;
+  head_result(mi, p);
   amax[row] = mi;
-  pmax[row] = 1.0f / sum;
+  pmax[row] = p;
 }
 void launch_ctc_reduce(const float* part, long rows, int slots, int step, int* amax, float* pmax, hipStream_t s) {
   hipLaunchKernelGGL(ctc_reduce_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, part, rows, slots, step, amax, pmax);
@@ -1491,7 +1493,12 @@ __global__ void __launch_bounds__(256) argmax_softmax_kernel(const float* __rest
   for (int c = lane; c < C; c += 64) s += ocr_expf(x[c] - m);
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-  if (lane == 0) { amax[row] = mi; pmax[row] = 1.0f / s; }
+  if (lane == 0) {
+    float p = 1.0f / s;
+    head_result(mi, p);
+    amax[row] = mi;
+    pmax[row] = p;
+  }
 }
 // f16 build: ONE pass over the row (the form above reads it twice, four bytes per lane: 1.17 ms for the 2.17 GB of a step's logits,
 // more than the head's matrix product), 16 bytes per lane, each lane an online softmax of its own - running maximum m, sum of
@@ -1530,7 +1537,12 @@ __global__ void __launch_bounds__(256) argmax_softmax_fast_kernel(const float* _
     m = M;
     sum = sa + sb;
   }
-  if (lane == 0) { amax[row] = mi; pmax[row] = 1.0f / sum; }
+  if (lane == 0) {
+    float p = 1.0f / sum;
+    head_result(mi, p);
+    amax[row] = mi;
+    pmax[row] = p;
+  }
 }
 void launch_argmax_softmax(const float* logits, long rows, int C, int ld, int* amax, float* pmax, bool half, hipStream_t s) {
   if (half && ld % 4 == 0 && ld >= ((C + 3) & ~3)) {

@@ -692,6 +692,12 @@ int ocr_srv_net_forward(ocr_srv_net* h, const float* x, int N, int H, int W, int
 int ocr_srv_net_rerun(ocr_srv_net* h, int N, int H, int W, int iters);
 int ocr_srv_net_num_tensors(ocr_srv_net* h);
 int ocr_srv_net_fetch(ocr_srv_net* h, int tid, float* out, size_t cap_floats, int dims[4]);
+/* test hooks for the CTC head: ocr_srv_net_set_ctc switches the head's partial mode as the recognizer stage does (the next forward
+ * re-binds); ocr_srv_net_ctc_tail issues the tail launch the stage issues behind the network - launch_ctc_reduce on the head's
+ * partials with the handle's own slot count and step (returned; 0 outside partial mode), else launch_argmax_softmax on its logits -
+ * for the rows of the current binding (returned in *rows; OCR_ERR_CAPACITY when cap_rows is below it). */
+int ocr_srv_net_set_ctc(ocr_srv_net* h, int on);
+int ocr_srv_net_ctc_tail(ocr_srv_net* h, int32_t* amax, float* pmax, long cap_rows, long* rows, int* slots, int* step);
 int ocr_srv_net_timing(ocr_srv_net* h, int enable);
 int ocr_srv_net_timing_report(ocr_srv_net* h, char* buf, size_t cap);
 /* test hooks on the binding the last forward made (tests/test_gpu_srv_ops.py checks every launch alone against a float64
@@ -784,6 +790,45 @@ int ocr_selftest_line_pre(const uint8_t* img, int rows, int cols, size_t stride,
                           int nslots, int pad_mode, int stage, float* out);
 int ocr_selftest_line_pre_ragged(const uint8_t* img, int rows, int cols, size_t stride, const int32_t* lines, int n, int imgH,
                                  int stage, float* out);
+
+/* The recognizer's tail launches alone, on caller-held data (tests/test_gpu_rec_tail.py): what turns logits into (arg max,
+ * probability) per CTC step and steps into characters.  Each calls the launch function production binds.  Every output is
+ * pre-filled with OCR_SELFTEST_FILL and comes back with OCR_SELFTEST_GUARD more bytes, taken from behind its last element
+ * (so every output buffer holds count * 4 + OCR_SELFTEST_GUARD bytes); what a launcher does not define is refused with
+ * OCR_ERR_ARG before anything reaches the device.
+ * ocr_selftest_softmax_argmax: launch_softmax_argmax (the mobile heads' unfused form) on rows x C logits, C <= 8192; probs
+ * (rows * C, may be NULL), amax, pmax (rows each).
+ * ocr_selftest_head_combine: launch_head_combine (second half of the mobile fused head) on rows x groups partials (group
+ * maximum, group sum, index of the group's first maximum).
+ * ocr_selftest_srv_argmax: srv::launch_argmax_softmax on rows of C logits ld floats apart (rows * ld floats are uploaded);
+ * one_pass: the f16 build's form (ld % 4 == 0 and ld >= C rounded up to 4), else the two-pass form.
+ * ocr_selftest_ctc_reduce: srv::launch_ctc_reduce on rows x slots partials of 4 floats (maximum, sum of exp(x - maximum), the
+ * first maximum's column as int bits, unused); slots 0, step, 2 step, .. are folded.
+ * ocr_selftest_ctc: the greedy collapse of nsteps_total (amax, pmax) pairs.  lines NULL: launch_ctc on nlines lines of T steps
+ * (nlines * T == nsteps_total); lines: nlines x 2 int32 (first step, step count) - launch_ctc_ragged; chars != 0:
+ * launch_ctc_chars in either form, which also fills steps / nsteps / probs.  ids, steps, nsteps, probs: nlines * max_len; lens,
+ * scores: nlines.
+ * ocr_selftest_topk_lines: launch_ctc_topk on nlines lines of T rows (C f32 at `pitch` floats) each; lens[nlines], steps and p0
+ * [nlines * max_len] as launch_ctc_chars leaves them; out_ids / out_probs: nlines * max_len * k. */
+int ocr_selftest_softmax_argmax(const float* logits, long rows, int C, float* probs, int32_t* amax, float* pmax);
+int ocr_selftest_head_combine(const float* hmax, const float* hsum, const int32_t* hidx, long rows, int groups, int32_t* amax,
+                              float* pmax);
+int ocr_selftest_srv_argmax(const float* logits, long rows, int C, int ld, int one_pass, int32_t* amax, float* pmax);
+int ocr_selftest_ctc_reduce(const float* part, long rows, int slots, int step, int32_t* amax, float* pmax);
+int ocr_selftest_ctc(const int32_t* amax, const float* pmax, long nsteps_total, int nlines, int T, const int32_t* lines, int max_len,
+                     int chars, int32_t* ids, int32_t* lens, float* scores, int32_t* steps, int32_t* nsteps, float* probs);
+int ocr_selftest_topk_lines(const float* rows, int nlines, int T, int C, int pitch, const int32_t* lens, const int32_t* steps,
+                            const float* p0, int max_len, int k, int32_t* out_ids, float* out_probs);
+
+/* The mobile recognizer's head alone, through the network's own binder: the embedded rec plan with the weights file `weights`
+ * (NULL: model_dir's), bound on `lines` blank lines of imgH x imgW with the head's sinks set as the recognizer stage sets them;
+ * rows (nrows x K f32, nrows = lines * the CTC steps of such a line) replace the head linear's input and the binding's last two
+ * launches run alone - the fused head (mode 0), the unfused one with the logits kept (1) or with probabilities requested (2).
+ * amax / pmax: nrows values + OCR_SELFTEST_GUARD bytes; logits (modes 1, 2): nrows * *ncols; names: the two launches' names and `logits_stored` or
+ * `logits_fused` (whether the binder folded the softmax into the linear), separated by newlines. */
+int ocr_selftest_rec_head(const char* model_dir, const char* weights, const char* precision, const float* rows, long nrows, int K,
+                          int lines, int imgH, int imgW, int mode, int32_t* amax, float* pmax, float* logits, int* ncols, char* names,
+                          size_t names_cap);
 
 /* numerics probe (tests): out[8*n] = a/b, sqrt|a|, ocr_expf(a), fma(a,b,a), a*b+a, rint(a*log2e), hswish(a), hswish(b) */
 int ocr_probe(const float* a, const float* b, float* out, int n);

@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from tail_ref import collapse as _collapse  # (tools/ is on the path: conftest.py)
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,19 +111,6 @@ def _crops():
             x, y, w, h = r
             crops.append(img[y:y + h, x:x + w])
     return crops
-
-
-def _collapse(amax, pmax):
-    """greedy CTC collapse that keeps where every character came from"""
-    ids, steps, nsteps, probs = [], [], [], []
-    last = 0
-    for n, a in enumerate(amax):
-        if a > 0 and not (n > 0 and a == last):
-            ids.append(int(a)); steps.append(n); nsteps.append(1); probs.append(pmax[n])
-        elif a > 0:
-            nsteps[-1] += 1
-        last = a
-    return np.array(ids, np.int32), np.array(steps, np.int32), np.array(nsteps, np.int32), np.array(probs, np.float32)
 
 
 def _mobile_T(w):

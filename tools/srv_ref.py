@@ -36,6 +36,20 @@ one rounding to f16 near zero).  Rounding points, per op kind:
   the larger term, so such rows do not separate the two forms.  The residual LN(u) is formed in f32, not rounded.
   head tail: the mid map relu(x W1 + b1) rounded to f16, the second product on f16 weights, sigmoid: 0.25 (sum |w4| bound_mid +
   64 u32 S2 + u32 |b2|) + 2^-21.
+  CTC tail (`ctc_tail`: arg max = first maximum, p = 1 / sum_c exp(x_c - M), relative bounds on p).  A term's exponent is formed as
+  (x - m) log2(e): the difference rounds (u32 |x - m|), the constant and the product round (2 u32 |x - m|), and the hardware exp2
+  is good to 2^-22 = 4 u32 (CDNA ISA: v_exp_f32, 1 ulp): relative 3 u32 |x - m| + 4 u32.  A running sum that is rescaled when its
+  maximum moves from m to m' takes the same again with |m - m'|, plus one product and one addition (2 u32); maxima only grow, so the
+  differences along a term's path add up to |x - M| and only the count of rescales n matters.  A sum of positive terms keeps the
+  largest relative error of its terms plus u32 per addition on a term's path.  1 / sum: 2 u32 (the IEEE quotient has 1, v_rcp_f32 2).
+      two-pass (argmax_softmax_kernel, ocr_expf = EXP_REL 4 u32 on the f32 difference): u32 D + 4 u32 + (ceil(C / 64) + 6) u32 + 2 u32
+      one-pass (argmax_softmax_fast_kernel): per step of 256 columns a lane rescales once (exp2 4 + product 1) and adds 4 terms (4);
+          each of the 6 butterfly folds is one rescale, one product, one addition (6): 3 u32 D + 9 u32 ceil(C / 256) + 36 u32 + 2 u32
+      fused head (the matrix kernel's ctc_part epilogue, then ctc_reduce_kernel; `ctc_head`): inside a tile of W columns a term takes
+          one exp2 (4), at most W additions and at most 6 cross-lane rescales (6 each); then the fold over n tiles:
+          3 u32 D + 4 u32 + W u32 + 36 u32 + 6 u32 n + 2 u32
+      fold of partials (ctc_reduce_kernel on given (m_s, sum_s)): 3 u32 max_s |m_s - M| + (4 + 2) u32 n_slots + 2 u32
+  with D = max_c |x_c - M| over the finite columns, all times SECOND = 1 + 2^-10 for the second-order terms.
 """
 import math
 
@@ -574,3 +588,46 @@ def check_tensors(ref, t):
         y, bound = ref.op(op, t)
         res[k] = (kind_of(op), ratio(t[gi(op, "o")], y, bound))
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------- CTC tail
+def ctc_tail(x, kind):
+    """x f64 [rows, C] logits (finite maximum per row) -> (first maximum, p = 1 / sum exp(x - M), its bound); kind "two_pass" |
+    "one_pass" (module docstring)"""
+    x = np.asarray(x, dtype=np.float64)
+    C = x.shape[-1]
+    M = x.max(-1, keepdims=True)
+    d = np.where(np.isfinite(x), np.abs(x - M), 0.0).max(-1)
+    p = 1.0 / np.exp(x - M).sum(-1)
+    if kind == "two_pass":
+        rel = U32 * d + 4 * U32 + (-(-C // 64) + 6) * U32 + 2 * U32
+    else:
+        assert kind == "one_pass"
+        rel = 3 * U32 * d + 9 * U32 * -(-C // 256) + 36 * U32 + 2 * U32
+    return x.argmax(-1), p, p * rel * (1.0 + 2.0 ** -10)
+
+
+def ctc_fold(m, s):
+    """per-slot partials m, s f64 [rows, slots] (maximum, sum of exp(x - maximum)) of the slots that are folded -> (p, its bound)"""
+    m, s = np.asarray(m, dtype=np.float64), np.asarray(s, dtype=np.float64)
+    M = m.max(-1, keepdims=True)
+    live = np.isfinite(m)
+    p = 1.0 / np.where(live, s * np.exp(np.where(live, m - M, 0.0)), 0.0).sum(-1)
+    d = np.where(live, np.abs(m - M), 0.0).max(-1)
+    rel = 3 * U32 * d + 6 * U32 * m.shape[-1] + 2 * U32
+    return p, p * rel * (1.0 + 2.0 ** -10)
+
+
+def ctc_head(y, slots, step):
+    """y f64 [rows, C] exact logits of a head run in partial mode, its slot count and step -> (first maximum, p, its bound)"""
+    y = np.asarray(y, dtype=np.float64)
+    M = y.max(-1, keepdims=True)
+    d = np.abs(y - M).max(-1)
+    p = 1.0 / np.exp(y - M).sum(-1)
+    rel = 3 * U32 * d + 4 * U32 + 64 * step * U32 + 36 * U32 + 6 * U32 * -(-slots // step) + 2 * U32
+    return y.argmax(-1), p, p * rel * (1.0 + 2.0 ** -10)
+
+
+def linear_f32_bound(A, W, b, y):
+    """the GEMM bound of the module docstring for an f32-output linear without activation: K u32 S + 2 u32 |b| + u32 |y|"""
+    return A.shape[1] * U32 * (np.abs(A) @ np.abs(W)) + 2 * U32 * np.abs(b) + U32 * np.abs(y)
