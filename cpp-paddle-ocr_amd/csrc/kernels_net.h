@@ -8,6 +8,7 @@
 #include "hip_guard.h"
 #include "lds_attr.h"
 #include "ocr_common.h"
+#include "rec_plan.h"  // attn_ragged_fits
 #include "rt_options.h"
 
 namespace ocr {
@@ -242,8 +243,7 @@ void launch_ln(const float* in, float* out, long rows, int C, int Cs, float eps,
 // rag (ragged batch): line n is a sequence of rag.w[n] tokens starting at row rag.cw[n]; T = the longest line
 void launch_attn(const float* qkv, float* out, int N, int T, int heads, int hd, int Cs_in, int Cs_out, float scale,
                  hipStream_t s, RagLevel rag = RagLevel(), bool h16 = false);
-// does the ragged form of the attention kernel take sequences of this length? (its working set must fit LDS)
-bool attn_ragged_fits(int T);
+// (attn_ragged_fits - does the ragged form take sequences of this length? - is host arithmetic: rec_plan.h)
 // second half of the fused head: rows x groups partials -> arg max / max probability per row
 void launch_head_combine(const float* hmax, const float* hsum, const int* hidx, long rows, int groups, int* amax, float* pmax,
                          hipStream_t s);

@@ -2071,9 +2071,6 @@ __global__ void __launch_bounds__(HEADS * 64) attn_line_kernel(const float* __re
   for (int d = 0; d < HD; ++d) st1<kH16>(out, dst + c8i_phys(hh * HD + d), o[d]);
 }
 
-#ifndef OCR_TU_H16
-bool attn_ragged_fits(int T) { return ((size_t)T * 96 + 64 * 17) * sizeof(float) <= 150 * 1024; }
-#endif
 void OCR_L(launch_attn)(const float* qkv, float* out, int N, int T, int heads, int hd, int Cs_in, int Cs_out, float scale,
                         hipStream_t s, RagLevel rag, bool h16) {
   OCR_H16_TWIN(h16, launch_attn_h16(qkv, out, N, T, heads, hd, Cs_in, Cs_out, scale, s, rag, h16))
@@ -2087,8 +2084,8 @@ void OCR_L(launch_attn)(const float* qkv, float* out, int N, int T, int heads, i
       return;
     }
   }
-  const size_t lds = ((size_t)T * 96 + 64 * 17) * sizeof(float);
-  if (lds <= 150 * 1024) {
+  const size_t lds = attn_lds_bytes(T);
+  if (attn_ragged_fits(T)) {
     static LdsAttrMemo attr_state;  // per device: the pool drives several from one process
     if (lds <= 64 * 1024 || raise_dynamic_lds((const void*)attn_lds_kernel<15>, 150 * 1024, attr_state)) {
       hipLaunchKernelGGL(attn_lds_kernel<15>, dim3((unsigned)(N * heads)), dim3(64), lds, s, qkv, out, N, T, heads, Cs_in,

@@ -191,6 +191,7 @@ class RecStage {
   std::vector<float> tap_pmax;
 
  private:
+  struct LinesCtx;  // stages.hip: what the phases of run_lines share
   RecConfig cfg_;
   // One network instance, one stream: the lines of a call run as ONE ragged launch list whatever their tensor widths
   // (run_lines); rounds 1-2 launched once per distinct width on up to six streams ("lanes").

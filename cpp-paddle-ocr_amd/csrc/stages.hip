@@ -585,258 +585,224 @@ int RecStage::logits_row(int index, int step, float* out, size_t cap_floats, std
   return OCR_OK;
 }
 
-int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int>& seg, int32_t* ids, int max_len,
-                        int* lens, float* scores, std::string& err, const CharOut* co) {
-  const int n = (int)lines.size();
-  const int topk = co ? co->topk : 0;
-  // top-k needs the logits in HBM: the mobile head unfused (Net::set_keep_logits), the server head without CTC partials.
-  // Both switches re-bind only when they change; every other call keeps its launch lists.
-  if (srv_) srv_->set_ctc_partials(topk > 0 ? false : srv_ctc_);
-  else net_.set_keep_logits(topk > 0);
-  tap_row0_.assign(n, -1);
-  const int imgH = cfg_.img_h, imgW = cfg_.img_w;
-  struct Item { int line, resize_w, tensor_w; };
-  std::vector<Item> items;
-  items.reserve(n);
-  for (size_t sg = 0; sg + 1 < seg.size(); ++sg) {
-    // CRNNRecognizer::Run batching, /root/reference/src/ocr_rec.cpp:34-57, on one image's lines
-    const int s0 = seg[sg], sn = seg[sg + 1] - seg[sg];
-    std::vector<float> width_list(sn);
-    for (int i = 0; i < sn; ++i) width_list[i] = float(lines[s0 + i].w) / lines[s0 + i].h;
-    std::vector<size_t> indices(sn);
-    for (int i = 0; i < sn; ++i) indices[i] = i;
-    // Utility::argsort is std::sort: the order of equal ratios is the host library's
-    if (cfg_.sort_mode == OCR_SORT_MSVC_STRICT && sn > 32) {
-      // MSVC's std::sort is an insertion sort (ties in input order) only up to _ISORT_MAX = 32 elements; its quicksort's order
-      // of ties beyond that is not restated here - refuse rather than answer in an order the reference's build may not produce
-      std::vector<float> sorted_w(width_list);
-      std::sort(sorted_w.begin(), sorted_w.end());
-      if (std::adjacent_find(sorted_w.begin(), sorted_w.end()) != sorted_w.end()) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "sort_mode OCR_SORT_MSVC_STRICT: image %d has %d crops (> 32) with tied w/h ratios - MSVC's std::sort order of ties beyond 32 elements is not restated (use OCR_SORT_STABLE or OCR_SORT_STD)", (int)sg, sn);
-        err = msg;
-        return OCR_ERR_ARG;
-      }
-    }
-    if (cfg_.sort_mode != OCR_SORT_STD) std::stable_sort(indices.begin(), indices.end(), [&](size_t a, size_t b) { return width_list[a] < width_list[b]; });
-    else std::sort(indices.begin(), indices.end(), [&](size_t a, size_t b) { return width_list[a] < width_list[b]; });
-    for (int beg = 0; beg < sn; beg += cfg_.batch_num) {
-      const int end = std::min(sn, beg + cfg_.batch_num);
-      float max_wh_ratio = imgW * 1.0 / imgH;
-      for (int ino = beg; ino < end; ++ino) {
-        const int h = lines[s0 + indices[ino]].h, w = lines[s0 + indices[ino]].w;
-        const float wh_ratio = w * 1.0 / h;
-        max_wh_ratio = std::max(max_wh_ratio, wh_ratio);
-      }
-      if (srv_) max_wh_ratio = imgW * 1.0 / imgH;  // (the server recognizer's fixed token grid: create())
-      const int bw = int(imgH * max_wh_ratio);  // CrnnResizeImg: imgW = int(imgH * wh_ratio)
-      const int tensor_w = std::max(bw, imgW);
-      for (int ino = beg; ino < end; ++ino) {
-        const LineSrc& L = lines[s0 + indices[ino]];
-        const float ratio = float(L.w) / float(L.h);
-        const int resize_w = ceilf(imgH * ratio) > bw ? bw : int(ceilf(imgH * ratio));
-        items.push_back({s0 + (int)indices[ino], resize_w, tensor_w});
-      }
-    }
-  }
-  tap_T.assign(n, 0);
-  tap_off.assign(n, 0);
-  tap_amax.clear();
-  tap_pmax.clear();
-  for (int i = 0; i < n; ++i) { lens[i] = 0; scores[i] = 0.f; }
-  if (items.empty()) return OCR_OK;
-  // One launch list for every tensor width of the call (a ragged batch: kernels_net.h, RagLevel).  In the reference each
-  // batch of rec_batch_num lines is a predictor run of its own width (ocr_rec.cpp:47-81); a line's results depend on
-  // its own tensor width only (padding, attention length), never on the other lines of a launch, so the lines of all
-  // batches - and of all images of a request batch - share the launches.  Lines in ascending tensor width (equal
-  // widths stay neighbours: a workgroup's tiles then belong to lines of one shape); a launch is cut where its
-  // activation arena would pass the pixel budget; a line too wide for the ragged attention kernel's LDS working set
-  // (> ~3000 px) runs as a uniform launch of its own width.
-  std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.tensor_w < b.tensor_w; });
-  struct Slot { int first, count; bool ragged; int T; size_t step_off; };
+// What the phases of one run_lines call share: the plan (rec_plan.h), the line table and the host copies of the results.
+struct RecStage::LinesCtx {
+  struct Slot : rec_plan::Slot {  // a launch of the plan, and where its steps sit in amax_ / pmax_
+    Slot(const rec_plan::Slot& s) : rec_plan::Slot(s) {}
+    int T = 0;  // steps per line of a uniform launch, known once it has run
+    size_t step_off = 0;
+  };
+  // What a launch left for the decode: T steps per line (0: ragged, the steps are in the table), the launch's line table on
+  // the device (null: uniform), and with top-k its logits, still in place (the next launch overwrites them)
+  struct View { int T = 0; const LineDesc* lines_dev = nullptr; const float* logits = nullptr; long pitch = 0; };
+  RecStage& st;
+  const std::vector<LineSrc>& lines;
+  const CharOut* const co;
+  const int max_len, topk, imgH, imgW, C;
+  std::string& err;
+  std::vector<rec_plan::Item> items;
   std::vector<Slot> slots;
-  const long budget = (long)max_lines_per_launch * imgH * std::max(imgW, 320);
-  {
-    int i = 0;
-    const int ni = (int)items.size();
-    while (i < ni) {
-      if (srv_ || !attn_ragged_fits(items[i].tensor_w / 8 + 2)) {  // uniform launch: the lines of exactly this width
-        int j = i;
-        while (j < ni && items[j].tensor_w == items[i].tensor_w && j - i < max_lines_per_launch) ++j;
-        slots.push_back({i, j - i, false, 0, 0});
-        i = j;
-        continue;
-      }
-      long pix = 0;
-      int j = i;
-      while (j < ni && attn_ragged_fits(items[j].tensor_w / 8 + 2) && (j == i || pix + (long)imgH * items[j].tensor_w <= budget)) {
-        pix += (long)imgH * items[j].tensor_w;
-        ++j;
-      }
-      slots.push_back({i, j - i, true, 0, 0});
-      i = j;
-    }
-  }
-  // per launch: bind (host only), so that the step counts are known before the line descriptors travel
-  const int ni = (int)items.size();
-  std::vector<LineDesc> d(ni);
+  std::vector<LineDesc> d;
   std::vector<int> widths;
-  size_t step_total = 0, xneed = 0;
+  size_t step_total = 0, nchar = 0;
+  bool tap_logits = false;  // (tap) a copy of every logits row of the call
+  std::vector<int> h_ids, h_lens, h_amax, h_steps, h_nsteps, h_alt_ids;
+  std::vector<float> h_scores, h_pmax, h_cprobs, h_alt_probs;
+
+  LinesCtx(RecStage& s, const std::vector<LineSrc>& l, const CharOut* c, int ml, std::string& e)
+      : st(s), lines(l), co(c), max_len(ml), topk(c ? c->topk : 0), imgH(s.cfg_.img_h), imgW(s.cfg_.img_w), C((int)s.labels_.size()), err(e) {}
+
+  int plan(const std::vector<int>& seg);
+  int describe();
+  int check_output(int oh, int oc, int T, int tensor_w);
+  int mobile_logits(const Slot& sl, View& v);
+  int run_srv(Slot& sl, View& v);
+  int run_ragged(Slot& sl, View& v);
+  int run_uniform(Slot& sl, View& v);
+  int decode(const Slot& sl, const View& v);
+  template <class T>
+  bool fetch(std::vector<T>& host, const T* dev, size_t count) {  // a result array of the call, queued behind its launches
+    host.resize(count);
+    const hipError_t e = hipMemcpyAsync(host.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost, st.stream_);
+    if (e != hipSuccess) err = std::string("rec read-back: ") + hipGetErrorString(e);
+    return e == hipSuccess;
+  }
+  int read_back();
+  int scatter(int32_t* ids, int* lens, float* scores);
+  // first step of line j of a launch in amax_ / pmax_ (and its first row in the logits tap)
+  size_t step_of(const Slot& sl, int j) const { return sl.step_off + (sl.ragged ? (size_t)d[sl.first + j].step0 : (size_t)j * sl.T); }
+};
+
+int RecStage::LinesCtx::plan(const std::vector<int>& seg) {
+  const int rc = rec_plan::plan_items(lines, seg, imgH, imgW, st.cfg_.batch_num, st.cfg_.sort_mode, st.srv_ != nullptr, items, err);
+  if (rc) return rc;
+  const std::vector<rec_plan::Slot> cut = rec_plan::plan_slots(items, imgH, imgW, st.max_lines_per_launch, st.srv_ != nullptr);
+  slots.assign(cut.begin(), cut.end());
+  return OCR_OK;
+}
+
+// per launch: bind (host only), so that the step counts are known before the line descriptors travel; then the buffers
+int RecStage::LinesCtx::describe() {
+  const int ni = (int)items.size();
+  d.resize(ni);
+  size_t xneed = 0;
   for (Slot& sl : slots) {
     sl.step_off = step_total;
+    const std::vector<int>* T = nullptr;  // ragged: the steps of every line under the launch's binding
     if (sl.ragged) {
       widths.resize(sl.count);
       for (int j = 0; j < sl.count; ++j) widths[j] = items[sl.first + j].tensor_w;
-      if (!net_.bind_ragged(imgH, widths.data(), sl.count, err)) return OCR_ERR_DEVICE;
-      const TensorDesc& ot = net_.tensor(net_.output_tid());
-      if (ot.h != 1) { err = "rec_img_h does not reduce to a single row"; return OCR_ERR_ARG; }
-      if (ot.c != (int)labels_.size()) { err = "dictionary size does not match the CTC head"; return OCR_ERR_MODEL; }
-      const std::vector<int>& T = net_.ragged_widths(net_.output_tid());
-      long pix = 0;
-      for (int j = 0; j < sl.count; ++j) {
-        const Item& it = items[sl.first + j];
-        const LineSrc& L = lines[it.line];
-        LineDesc& q = d[sl.first + j];
-        q = LineDesc::make(L.img, L.stride, L.x, L.y, L.w, L.h, it.resize_w, j, imgH);
+      if (!st.net_.bind_ragged(imgH, widths.data(), sl.count, err)) return OCR_ERR_DEVICE;
+      const TensorDesc& ot = st.net_.tensor(st.net_.output_tid());
+      if (const int rc = check_output(ot.h, ot.c, 0, 0)) return rc;
+      T = &st.net_.ragged_widths(st.net_.output_tid());
+    }
+    long pix = 0;
+    for (int j = 0; j < sl.count; ++j) {
+      const rec_plan::Item& it = items[sl.first + j];
+      const LineSrc& L = lines[it.line];
+      LineDesc& q = d[sl.first + j];
+      q = LineDesc::make(L.img, L.stride, L.x, L.y, L.w, L.h, it.resize_w, j, imgH);
+      if (T) {
         q.tensor_w = it.tensor_w;
         q.pix0 = (int)pix;
         q.step0 = (int)(step_total - sl.step_off);
-        q.steps = T[j];
-        pix += (long)imgH * it.tensor_w;
-        step_total += T[j];
+        q.steps = (*T)[j];
+        step_total += (*T)[j];
       }
-      xneed = std::max(xneed, (size_t)pix * 3);
-    } else {
-      for (int j = 0; j < sl.count; ++j) {
-        const Item& it = items[sl.first + j];
-        const LineSrc& L = lines[it.line];
-        d[sl.first + j] = LineDesc::make(L.img, L.stride, L.x, L.y, L.w, L.h, it.resize_w, j, imgH);
-      }
-      step_total += (size_t)sl.count * (items[sl.first].tensor_w / 4 + 8);  // >= count * T
-      xneed = std::max(xneed, (size_t)sl.count * imgH * items[sl.first].tensor_w * 3);
+      pix += (long)imgH * it.tensor_w;
     }
+    if (!T) step_total += (size_t)sl.count * rec_plan::uniform_step_cap(items[sl.first].tensor_w);  // >= count * T
+    xneed = std::max(xneed, (size_t)pix * 3);
   }
-  if (!amax_.ensure(step_total, err) || !pmax_.ensure(step_total, err) || !ids_.ensure((size_t)ni * max_len, err) ||
-      !lens_.ensure(ni, err) || !scores_.ensure(ni, err) || !descs_.ensure(ni, err) || !x_.ensure(xneed, err))
+  if (!st.amax_.ensure(step_total, err) || !st.pmax_.ensure(step_total, err) || !st.ids_.ensure((size_t)ni * max_len, err) ||
+      !st.lens_.ensure(ni, err) || !st.scores_.ensure(ni, err) || !st.descs_.ensure(ni, err) || !st.x_.ensure(xneed, err))
     return OCR_ERR_DEVICE;
-  const size_t nchar = (size_t)ni * max_len;
-  if (co && (!csteps_.ensure(nchar, err) || !cnsteps_.ensure(nchar, err) || !cprobs_.ensure(nchar, err))) return OCR_ERR_DEVICE;
-  if (topk > 0 && (!alt_ids_.ensure(nchar * topk, err) || !alt_probs_.ensure(nchar * topk, err))) return OCR_ERR_DEVICE;
-  const int C = (int)labels_.size();
+  nchar = (size_t)ni * max_len;
+  if (co && (!st.csteps_.ensure(nchar, err) || !st.cnsteps_.ensure(nchar, err) || !st.cprobs_.ensure(nchar, err))) return OCR_ERR_DEVICE;
+  if (topk > 0 && (!st.alt_ids_.ensure(nchar * topk, err) || !st.alt_probs_.ensure(nchar * topk, err))) return OCR_ERR_DEVICE;
   // (tap) a copy of every logits row of the call, while that stays a test-sized buffer
-  const bool tap_logits = topk > 0 && want_taps && step_total * (size_t)C * sizeof(float) <= ((size_t)1 << 30);
-  if (tap_logits && !logit_tap_.ensure(step_total * (size_t)C, err)) return OCR_ERR_DEVICE;
-  tap_C_ = C;
-  // the collapse of one launch's lines (lines_dev: the ragged table, or null with uniform T) and, behind it, the top-k
-  // classes of its kept characters from the launch's logits (still in place: the next launch overwrites them)
-  auto collapse = [&](const Slot& sl, const LineDesc* lines_dev, int T, const float* logits, long pitch) -> int {
-    const size_t o = (size_t)sl.first * max_len;
-    launch_ctc_chars(amax_.p + sl.step_off, pmax_.p + sl.step_off, lines_dev, sl.count, T, max_len, ids_.p + o, lens_.p + sl.first,
-                     scores_.p + sl.first, csteps_.p + o, cnsteps_.p + o, cprobs_.p + o, stream_);
-    if (topk <= 0) return OCR_OK;
-    launch_ctc_topk(logits, pitch, C, topk, lines_dev, sl.count, T, max_len, lens_.p + sl.first, csteps_.p + o, cprobs_.p + o,
-                    alt_ids_.p + o * topk, alt_probs_.p + o * topk, stream_);
-    if (tap_logits) {
-      const size_t rows = lines_dev ? (size_t)(d[sl.first + sl.count - 1].step0 + d[sl.first + sl.count - 1].steps) : (size_t)sl.count * T;
-      ST_HIP(hipMemcpy2DAsync(logit_tap_.p + sl.step_off * (size_t)C, (size_t)C * sizeof(float), logits, (size_t)pitch * sizeof(float),
-                              (size_t)C * sizeof(float), rows, hipMemcpyDeviceToDevice, stream_));
-    }
+  tap_logits = topk > 0 && st.want_taps && step_total * (size_t)C * sizeof(float) <= ((size_t)1 << 30);
+  if (tap_logits && !st.logit_tap_.ensure(step_total * (size_t)C, err)) return OCR_ERR_DEVICE;
+  st.tap_C_ = C;
+  ST_HIP(hipMemcpyAsync(st.descs_.p, d.data(), (size_t)ni * sizeof(LineDesc), hipMemcpyHostToDevice, st.stream_));
+  return OCR_OK;
+}
+
+// the network's output under the binding at hand: one row of C classes per step, and (uniform launches: T > 0) no more steps
+// per line than the step buffers were sized for
+int RecStage::LinesCtx::check_output(int oh, int oc, int T, int tensor_w) {
+  if (oh != 1) { err = "rec_img_h does not reduce to a single row"; return OCR_ERR_ARG; }
+  if (oc != C) { err = "dictionary size does not match the CTC head"; return OCR_ERR_MODEL; }
+  if (T > 0 && T > rec_plan::uniform_step_cap(tensor_w)) { err = "rec step buffer too small"; return OCR_ERR_CAPACITY; }
+  return OCR_OK;
+}
+
+// with top-k: the mobile network's logits under the binding that just ran
+int RecStage::LinesCtx::mobile_logits(const Slot& sl, View& v) {
+  if (topk <= 0) return OCR_OK;
+  Net::HeadLogits hl;
+  if (!st.net_.head_logits(hl, err)) return OCR_ERR_DEVICE;
+  if (hl.C != C) { err = "dictionary size does not match the CTC head"; return OCR_ERR_MODEL; }
+  if (sl.ragged)
+    for (int j = 0; j < sl.count; ++j)
+      if ((int)hl.row0.size() != sl.count + 1 || hl.row0[j] != d[sl.first + j].step0) { err = "ragged logits rows do not match the step table"; return OCR_ERR_DEVICE; }
+  v.logits = hl.ptr;
+  v.pitch = hl.pitch;
+  return OCR_OK;
+}
+
+int RecStage::LinesCtx::run_srv(Slot& sl, View& v) {
+  SrvNet& srv = *st.srv_;
+  const int Wt = items[sl.first].tensor_w;
+  launch_line_pre(st.descs_.p + sl.first, sl.count, imgH, Wt, st.lut_.p, false, st.x_.p, st.stream_);
+  if (!srv.run(st.x_.p, sl.count, imgH, Wt, st.stream_, err)) return OCR_ERR_DEVICE;
+  const SrvTensor& ot = srv.tensor(srv.output_tid());
+  if (const int rc = check_output(ot.h, ot.c, ot.w, Wt)) return rc;
+  sl.T = ot.w;
+  const float* out = (const float*)srv.tensor_ptr(srv.output_tid());
+  if (srv.ctc_partials())  // the head left per-row partials instead of logits (srv_net.h): fold them
+    srv::launch_ctc_reduce(out, (long)sl.count * sl.T, srv.ctc_slots(), srv.ctc_step(), st.amax_.p + sl.step_off, st.pmax_.p + sl.step_off,
+                           st.stream_);
+  else
+    srv::launch_argmax_softmax(out, (long)sl.count * sl.T, ot.c, ot.cs, st.amax_.p + sl.step_off, st.pmax_.p + sl.step_off, srv.half(),
+                               st.stream_);
+  v.T = sl.T;
+  v.logits = out;
+  v.pitch = ot.cs;
+  return OCR_OK;
+}
+
+int RecStage::LinesCtx::run_ragged(Slot& sl, View& v) {
+  st.net_.set_head_outputs(nullptr, st.amax_.p + sl.step_off, st.pmax_.p + sl.step_off);
+  widths.resize(sl.count);
+  long pix = 0;
+  for (int j = 0; j < sl.count; ++j) { widths[j] = items[sl.first + j].tensor_w; pix += (long)imgH * widths[j]; }
+  launch_line_pre_ragged(st.descs_.p + sl.first, sl.count, pix, imgH, st.lut_.p, st.x_.p, st.stream_);
+  if (!st.net_.run_ragged(st.x_.p, imgH, widths.data(), sl.count, st.stream_, err)) return OCR_ERR_DEVICE;
+  v.lines_dev = st.descs_.p + sl.first;
+  return mobile_logits(sl, v);
+}
+
+int RecStage::LinesCtx::run_uniform(Slot& sl, View& v) {
+  st.net_.set_head_outputs(nullptr, st.amax_.p + sl.step_off, st.pmax_.p + sl.step_off);
+  const int Wt = items[sl.first].tensor_w;
+  launch_line_pre(st.descs_.p + sl.first, sl.count, imgH, Wt, st.lut_.p, false, st.x_.p, st.stream_);
+  if (!st.net_.run(st.x_.p, sl.count, imgH, Wt, st.stream_, err)) return OCR_ERR_DEVICE;
+  const TensorDesc& ot = st.net_.tensor(st.net_.output_tid());
+  if (const int rc = check_output(ot.h, ot.c, ot.w, Wt)) return rc;
+  v.T = sl.T = ot.w;
+  return mobile_logits(sl, v);
+}
+
+// The collapse of one launch's lines.  Plain calls: ids, lengths and scores.  run_chars: also the step, run length and
+// probability of every kept character and, behind it, the top-k classes of those steps from the launch's logits.
+int RecStage::LinesCtx::decode(const Slot& sl, const View& v) {
+  const int* amax = st.amax_.p + sl.step_off;
+  const float* pmax = st.pmax_.p + sl.step_off;
+  const size_t o = (size_t)sl.first * max_len;
+  if (!co) {
+    if (v.lines_dev) launch_ctc_ragged(amax, pmax, v.lines_dev, sl.count, max_len, st.ids_.p + o, st.lens_.p + sl.first, st.scores_.p + sl.first, st.stream_);
+    else launch_ctc(amax, pmax, sl.count, v.T, max_len, st.ids_.p + o, st.lens_.p + sl.first, st.scores_.p + sl.first, st.stream_);
     return OCR_OK;
-  };
-  // the mobile network's logits under the binding that just ran
-  auto mobile_logits = [&](Net::HeadLogits& hl, const Slot& sl, bool ragged) -> int {
-    if (topk <= 0) return OCR_OK;
-    if (!net_.head_logits(hl, err)) return OCR_ERR_DEVICE;
-    if (hl.C != C) { err = "dictionary size does not match the CTC head"; return OCR_ERR_MODEL; }
-    if (ragged)
-      for (int j = 0; j < sl.count; ++j)
-        if ((int)hl.row0.size() != sl.count + 1 || hl.row0[j] != d[sl.first + j].step0) { err = "ragged logits rows do not match the step table"; return OCR_ERR_DEVICE; }
-    return OCR_OK;
-  };
-  ST_HIP(hipMemcpyAsync(descs_.p, d.data(), (size_t)ni * sizeof(LineDesc), hipMemcpyHostToDevice, stream_));
-  for (Slot& sl : slots) {
-    if (!srv_) net_.set_head_outputs(nullptr, amax_.p + sl.step_off, pmax_.p + sl.step_off);
-    if (srv_) {
-      const int Wt = items[sl.first].tensor_w;
-      launch_line_pre(descs_.p + sl.first, sl.count, imgH, Wt, lut_.p, false, x_.p, stream_);
-      if (!srv_->run(x_.p, sl.count, imgH, Wt, stream_, err)) return OCR_ERR_DEVICE;
-      const SrvTensor& ot = srv_->tensor(srv_->output_tid());
-      if (ot.h != 1) { err = "rec_img_h does not reduce to a single row"; return OCR_ERR_ARG; }
-      if (ot.c != (int)labels_.size()) { err = "dictionary size does not match the CTC head"; return OCR_ERR_MODEL; }
-      sl.T = ot.w;
-      if (sl.T > Wt / 4 + 8) { err = "rec step buffer too small"; return OCR_ERR_CAPACITY; }
-      if (srv_->ctc_partials())  // the head left per-row partials instead of logits (srv_net.h): fold them
-        srv::launch_ctc_reduce((const float*)srv_->tensor_ptr(srv_->output_tid()), (long)sl.count * sl.T, srv_->ctc_slots(), srv_->ctc_step(),
-                               amax_.p + sl.step_off, pmax_.p + sl.step_off, stream_);
-      else
-        srv::launch_argmax_softmax((const float*)srv_->tensor_ptr(srv_->output_tid()), (long)sl.count * sl.T, ot.c, ot.cs, amax_.p + sl.step_off,
-                                   pmax_.p + sl.step_off, srv_->half(), stream_);
-      if (co) {
-        const int rc = collapse(sl, nullptr, sl.T, (const float*)srv_->tensor_ptr(srv_->output_tid()), ot.cs);
-        if (rc) return rc;
-      } else
-      launch_ctc(amax_.p + sl.step_off, pmax_.p + sl.step_off, sl.count, sl.T, max_len, ids_.p + (size_t)sl.first * max_len,
-                 lens_.p + sl.first, scores_.p + sl.first, stream_);
-    } else if (sl.ragged) {
-      widths.resize(sl.count);
-      long pix = 0;
-      for (int j = 0; j < sl.count; ++j) { widths[j] = items[sl.first + j].tensor_w; pix += (long)imgH * widths[j]; }
-      launch_line_pre_ragged(descs_.p + sl.first, sl.count, pix, imgH, lut_.p, x_.p, stream_);
-      if (!net_.run_ragged(x_.p, imgH, widths.data(), sl.count, stream_, err)) return OCR_ERR_DEVICE;
-      if (co) {
-        Net::HeadLogits hl;
-        int rc = mobile_logits(hl, sl, true);
-        if (!rc) rc = collapse(sl, descs_.p + sl.first, 0, hl.ptr, hl.pitch);
-        if (rc) return rc;
-      } else
-      launch_ctc_ragged(amax_.p + sl.step_off, pmax_.p + sl.step_off, descs_.p + sl.first, sl.count, max_len,
-                        ids_.p + (size_t)sl.first * max_len, lens_.p + sl.first, scores_.p + sl.first, stream_);
-    } else {
-      const int Wt = items[sl.first].tensor_w;
-      launch_line_pre(descs_.p + sl.first, sl.count, imgH, Wt, lut_.p, false, x_.p, stream_);
-      if (!net_.run(x_.p, sl.count, imgH, Wt, stream_, err)) return OCR_ERR_DEVICE;
-      const TensorDesc& ot = net_.tensor(net_.output_tid());
-      if (ot.h != 1) { err = "rec_img_h does not reduce to a single row"; return OCR_ERR_ARG; }
-      if (ot.c != (int)labels_.size()) { err = "dictionary size does not match the CTC head"; return OCR_ERR_MODEL; }
-      sl.T = ot.w;
-      if (sl.T > Wt / 4 + 8) { err = "rec step buffer too small"; return OCR_ERR_CAPACITY; }
-      if (co) {
-        Net::HeadLogits hl;
-        int rc = mobile_logits(hl, sl, false);
-        if (!rc) rc = collapse(sl, nullptr, sl.T, hl.ptr, hl.pitch);
-        if (rc) return rc;
-      } else
-      launch_ctc(amax_.p + sl.step_off, pmax_.p + sl.step_off, sl.count, sl.T, max_len, ids_.p + (size_t)sl.first * max_len,
-                 lens_.p + sl.first, scores_.p + sl.first, stream_);
-    }
   }
-  std::vector<int> h_ids((size_t)ni * max_len), h_lens(ni), h_amax;
-  std::vector<float> h_scores(ni), h_pmax;
-  ST_HIP(hipMemcpyAsync(h_ids.data(), ids_.p, h_ids.size() * sizeof(int), hipMemcpyDeviceToHost, stream_));
-  ST_HIP(hipMemcpyAsync(h_lens.data(), lens_.p, (size_t)ni * sizeof(int), hipMemcpyDeviceToHost, stream_));
-  ST_HIP(hipMemcpyAsync(h_scores.data(), scores_.p, (size_t)ni * sizeof(float), hipMemcpyDeviceToHost, stream_));
-  if (want_taps) {
-    h_amax.resize(step_total);
-    h_pmax.resize(step_total);
-    ST_HIP(hipMemcpyAsync(h_amax.data(), amax_.p, step_total * sizeof(int), hipMemcpyDeviceToHost, stream_));
-    ST_HIP(hipMemcpyAsync(h_pmax.data(), pmax_.p, step_total * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  launch_ctc_chars(amax, pmax, v.lines_dev, sl.count, v.T, max_len, st.ids_.p + o, st.lens_.p + sl.first, st.scores_.p + sl.first,
+                   st.csteps_.p + o, st.cnsteps_.p + o, st.cprobs_.p + o, st.stream_);
+  if (topk <= 0) return OCR_OK;
+  launch_ctc_topk(v.logits, v.pitch, C, topk, v.lines_dev, sl.count, v.T, max_len, st.lens_.p + sl.first, st.csteps_.p + o, st.cprobs_.p + o,
+                  st.alt_ids_.p + o * topk, st.alt_probs_.p + o * topk, st.stream_);
+  if (tap_logits) {
+    const LineDesc& last = d[sl.first + sl.count - 1];
+    const size_t rows = v.lines_dev ? (size_t)(last.step0 + last.steps) : (size_t)sl.count * v.T;
+    ST_HIP(hipMemcpy2DAsync(st.logit_tap_.p + sl.step_off * (size_t)C, (size_t)C * sizeof(float), v.logits, (size_t)v.pitch * sizeof(float),
+                            (size_t)C * sizeof(float), rows, hipMemcpyDeviceToDevice, st.stream_));
   }
-  std::vector<int> h_steps, h_nsteps, h_alt_ids;
-  std::vector<float> h_cprobs, h_alt_probs;
+  return OCR_OK;
+}
+
+int RecStage::LinesCtx::read_back() {
+  const size_t ni = items.size();
+  bool ok = fetch(h_ids, st.ids_.p, ni * max_len);
+  ok = ok && fetch(h_lens, st.lens_.p, ni);
+  ok = ok && fetch(h_scores, st.scores_.p, ni);
+  if (st.want_taps) {
+    ok = ok && fetch(h_amax, st.amax_.p, step_total);
+    ok = ok && fetch(h_pmax, st.pmax_.p, step_total);
+  }
   if (co) {
-    h_steps.resize(nchar); h_nsteps.resize(nchar); h_cprobs.resize(nchar);
-    ST_HIP(hipMemcpyAsync(h_steps.data(), csteps_.p, nchar * sizeof(int), hipMemcpyDeviceToHost, stream_));
-    ST_HIP(hipMemcpyAsync(h_nsteps.data(), cnsteps_.p, nchar * sizeof(int), hipMemcpyDeviceToHost, stream_));
-    ST_HIP(hipMemcpyAsync(h_cprobs.data(), cprobs_.p, nchar * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    ok = ok && fetch(h_steps, st.csteps_.p, nchar);
+    ok = ok && fetch(h_nsteps, st.cnsteps_.p, nchar);
+    ok = ok && fetch(h_cprobs, st.cprobs_.p, nchar);
   }
   if (topk > 0) {
-    h_alt_ids.resize(nchar * topk); h_alt_probs.resize(nchar * topk);
-    ST_HIP(hipMemcpyAsync(h_alt_ids.data(), alt_ids_.p, nchar * topk * sizeof(int), hipMemcpyDeviceToHost, stream_));
-    ST_HIP(hipMemcpyAsync(h_alt_probs.data(), alt_probs_.p, nchar * topk * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    ok = ok && fetch(h_alt_ids, st.alt_ids_.p, nchar * topk);
+    ok = ok && fetch(h_alt_probs, st.alt_probs_.p, nchar * topk);
   }
-  ST_HIP(g_stream_sync(stream_));
-  net_.collect_timings();
-  if (srv_) srv_->collect_timings();
+  return ok ? OCR_OK : OCR_ERR_DEVICE;
+}
+
+// results back in input order (after the stream has been synchronised)
+int RecStage::LinesCtx::scatter(int32_t* ids, int* lens, float* scores) {
   for (const Slot& sl : slots)
     for (int j = 0; j < sl.count; ++j) {
       const int q = sl.first + j, li = items[q].line;
@@ -845,6 +811,7 @@ int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int
       scores[li] = h_scores[q];
       memcpy(ids + (size_t)li * max_len, h_ids.data() + (size_t)q * max_len, (size_t)h_lens[q] * sizeof(int));
       const int T = sl.ragged ? d[q].steps : sl.T;
+      const size_t step = step_of(sl, j);
       if (co) {
         const size_t from = (size_t)q * max_len, to = (size_t)li * max_len, len = (size_t)h_lens[q];
         if (co->steps) memcpy(co->steps + to, h_steps.data() + from, len * sizeof(int));
@@ -855,17 +822,48 @@ int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int
           memcpy(co->alt_ids + to * topk, h_alt_ids.data() + from * topk, len * topk * sizeof(int));
           memcpy(co->alt_probs + to * topk, h_alt_probs.data() + from * topk, len * topk * sizeof(float));
         }
-        if (tap_logits) tap_row0_[li] = (long)(sl.step_off + (sl.ragged ? (size_t)d[q].step0 : (size_t)j * sl.T));
+        if (tap_logits) st.tap_row0_[li] = (long)step;
       }
-      tap_T[li] = T;
-      if (want_taps) {
-        tap_off[li] = (int)tap_amax.size();
-        const size_t o = sl.step_off + (sl.ragged ? (size_t)d[q].step0 : (size_t)j * sl.T);
-        tap_amax.insert(tap_amax.end(), h_amax.begin() + o, h_amax.begin() + o + T);
-        tap_pmax.insert(tap_pmax.end(), h_pmax.begin() + o, h_pmax.begin() + o + T);
+      st.tap_T[li] = T;
+      if (st.want_taps) {
+        st.tap_off[li] = (int)st.tap_amax.size();
+        st.tap_amax.insert(st.tap_amax.end(), h_amax.begin() + step, h_amax.begin() + step + T);
+        st.tap_pmax.insert(st.tap_pmax.end(), h_pmax.begin() + step, h_pmax.begin() + step + T);
       }
     }
   return OCR_OK;
+}
+
+int RecStage::run_lines(const std::vector<LineSrc>& lines, const std::vector<int>& seg, int32_t* ids, int max_len,
+                        int* lens, float* scores, std::string& err, const CharOut* co) {
+  const int n = (int)lines.size();
+  const int topk = co ? co->topk : 0;
+  // top-k needs the logits in HBM: the mobile head unfused (Net::set_keep_logits), the server head without CTC partials.
+  // Both switches re-bind only when they change; every other call keeps its launch lists.
+  if (srv_) srv_->set_ctc_partials(topk > 0 ? false : srv_ctc_);
+  else net_.set_keep_logits(topk > 0);
+  tap_row0_.assign(n, -1);
+  LinesCtx c(*this, lines, co, max_len, err);
+  int rc = c.plan(seg);
+  if (rc) return rc;
+  tap_T.assign(n, 0);
+  tap_off.assign(n, 0);
+  tap_amax.clear();
+  tap_pmax.clear();
+  for (int i = 0; i < n; ++i) { lens[i] = 0; scores[i] = 0.f; }
+  if (c.items.empty()) return OCR_OK;
+  if ((rc = c.describe())) return rc;
+  for (LinesCtx::Slot& sl : c.slots) {  // every launch and copy on stream_, in this order
+    LinesCtx::View v;
+    rc = srv_ ? c.run_srv(sl, v) : sl.ragged ? c.run_ragged(sl, v) : c.run_uniform(sl, v);
+    if (!rc) rc = c.decode(sl, v);
+    if (rc) return rc;
+  }
+  if ((rc = c.read_back())) return rc;
+  ST_HIP(g_stream_sync(stream_));
+  net_.collect_timings();
+  if (srv_) srv_->collect_timings();
+  return c.scatter(ids, lens, scores);
 }
 
 // ================================================================= classifier
@@ -921,9 +919,7 @@ int ClsStage::run_lines(const std::vector<LineSrc>& lines, int* labels, float* s
   std::vector<LineDesc> d(n);
   for (int i = 0; i < n; ++i) {
     const LineSrc& L = lines[i];
-    const float ratio = float(L.w) / float(L.h);
-    const int resize_w = ceilf(imgH * ratio) > imgW ? imgW : int(ceilf(imgH * ratio));
-    d[i] = LineDesc::make(L.img, L.stride, L.x, L.y, L.w, L.h, resize_w, i, imgH);
+    d[i] = LineDesc::make(L.img, L.stride, L.x, L.y, L.w, L.h, rec_plan::rec_resize_w(L.w, L.h, imgH, imgW), i, imgH);
   }
   if (!descs_.ensure(n, err) || !x_.ensure((size_t)n * imgH * imgW * 3, err)) return OCR_ERR_DEVICE;
   ST_HIP(hipMemcpyAsync(descs_.p, d.data(), n * sizeof(LineDesc), hipMemcpyHostToDevice, stream_));

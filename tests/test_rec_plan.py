@@ -1,0 +1,325 @@
+"""The recognizer's batching plan (csrc/rec_plan.h), on the CPU: which lines share a batch of the reference and what widths
+they get (CRNNRecognizer::Run, ocr_rec.cpp:34-57), and how the lines of a call are cut into launches.  The header runs in
+host/rec_plan_check.cpp, a plain host program, built twice: as it is and with -fsanitize=address,undefined; every case goes
+through both and nothing of either is loaded into Python.
+
+Items are compared exactly with a restatement of ocr_rec.cpp:34-57 composed of the oracle's exports (its argsort in the mode
+asked for, oracle_rec_width, oracle_rec_resize_w).  The cut into launches is held to its rules: the slots partition the
+items in order; a ragged slot holds only lines the ragged attention kernel takes and, beyond one line, stays within the pixel
+budget of max_lines_per_launch lines of imgH x max(imgW, 320); a uniform slot holds one width and at most max_lines_per_launch
+lines, and is there only for the server net or a line the ragged kernel does not take; and the cut is greedy - no slot could
+have taken the next line too."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = os.path.join(ROOT, "cpp-paddle-ocr_amd", "host")
+STD, STABLE, STRICT = 0, 1, 2  # include/ocr_hip.h: OCR_SORT_STD, OCR_SORT_STABLE, OCR_SORT_MSVC_STRICT
+OCR_ERR_ARG = -1
+
+
+class Case:
+    def __init__(self, sizes, seg=None, shape=(48, 320), batch_num=16, mode=STD, server=False, cap=4096):
+        self.sizes = [(int(w), int(h)) for w, h in sizes]
+        self.seg = list(seg) if seg is not None else [0, len(self.sizes)]
+        self.imgH, self.imgW = shape
+        self.batch_num, self.mode, self.server, self.cap = batch_num, mode, server, cap
+
+    def text(self):
+        head = [self.imgH, self.imgW, self.batch_num, self.mode, int(self.server), self.cap, len(self.seg) - 1] + self.seg
+        return " ".join(map(str, head + [v for wh in self.sizes for v in wh]))
+
+
+def _mixed(n, seed, lo=20, hi=60):
+    """n lines of distinct-looking shapes, heights lo..hi, ratios from below the floor to several times above it"""
+    rs = np.random.RandomState(seed)
+    h = rs.randint(lo, hi + 1, n)
+    return [(max(1, int(hh * r)), int(hh)) for hh, r in zip(h, rs.uniform(0.4, 24.0, n))]
+
+
+def _tied(n, ties, seed):
+    """n lines of which `ties` have w/h == 4 exactly (in three shapes), the others distinct ratios, in a shuffled order"""
+    rs = np.random.RandomState(seed)
+    sizes = [[(96, 24), (48, 12), (200, 50)][i % 3] for i in range(ties)]
+    sizes += [(41 + 13 * i, 37) for i in range(n - ties)]  # distinct ratios, none of them 4 (148 / 37 is not in the list)
+    return [sizes[i] for i in rs.permutation(n)]
+
+
+def _std_differs_from_stable(O, sizes):
+    r = np.array([np.float32(w) / np.float32(h) for w, h in sizes], np.float32)
+    return not np.array_equal(O.argsort(r), O.argsort(r, stable=True))
+
+
+FLOOR = [(30, 20), (100, 40), (64, 32), (55, 55), (20, 60), (120, 48), (90, 30)]  # every w/h below 192/28 and 320/48
+ABOVE = FLOOR[:3] + [(700, 35)] + FLOOR[3:]                                       # one of ratio 20 in the middle
+BUDGET_LINES = [(100, 48), (200, 48), (320, 48), (400, 48), (480, 48), (2000, 48)]  # tensor widths 320 x 3, 400, 480, 2000
+CASES = {
+    "empty": Case([], seg=[0]),
+    "empty_segment": Case([], seg=[0, 0]),
+    "empty_between": Case(_mixed(9, 1), seg=[0, 5, 5, 9]),
+    "one": Case([(131, 33)]),
+    "sixteen": Case(_mixed(16, 2)),
+    "seventeen": Case(_mixed(17, 3)),
+    "two_segments": Case(_mixed(40, 4), seg=[0, 19, 40]),
+    "three_segments": Case(_mixed(60, 5), seg=[0, 17, 35, 60]),
+    "floor_48": Case(FLOOR), "floor_28": Case(FLOOR, shape=(28, 192)),
+    "above_48": Case(ABOVE), "above_28": Case(ABOVE, shape=(28, 192)),
+    "above_48_b4": Case(ABOVE, batch_num=4), "above_28_b4": Case(ABOVE, shape=(28, 192), batch_num=4),
+    "strict_33_tied": Case(_tied(33, 2, 6), mode=STRICT),
+    "strict_32_tied": Case(_tied(32, 5, 7), mode=STRICT), "stable_32_tied": Case(_tied(32, 5, 7), mode=STABLE),
+    "strict_33_untied": Case(_tied(33, 1, 8), mode=STRICT), "stable_33_untied": Case(_tied(33, 1, 8), mode=STABLE),
+    "strict_second_image": Case(_mixed(5, 9) + _tied(33, 2, 6), seg=[0, 5, 38], mode=STRICT),
+    "server": Case(_mixed(20, 10), server=True),
+    "server_cap": Case([(100, 48), (2000, 40), (320, 48), (50, 50), (900, 30)], server=True, cap=2),
+    "budget_1": Case(BUDGET_LINES, batch_num=1, cap=1),
+    "budget_2": Case(BUDGET_LINES, batch_num=1, cap=2),
+    "budget_3": Case(BUDGET_LINES, batch_num=1, cap=3),
+}
+
+
+@pytest.fixture(scope="module")
+def checkers(tmp_path_factory):
+    """host/rec_plan_check.cpp as it is and with AddressSanitizer and UBSan: stand-alone host programs"""
+    d = str(tmp_path_factory.mktemp("recplan"))
+    exes = []
+    for name, flags in (("rec_plan_check", ["-O2"]), ("rec_plan_check_san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
+        exes.append(os.path.join(d, name))
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", *flags, "-o", exes[-1], os.path.join(HOST, "rec_plan_check.cpp")])
+    return exes
+
+
+def _parse(out, n):
+    """what rec_plan_check printed for n cases: per case ("refused", code, message) or ("plan", items, slots)"""
+    lines = out.splitlines()
+    res, p = [], 0
+    for k in range(n):
+        assert lines[p] == "case %d" % k
+        if lines[p + 1].startswith("refused "):
+            _, code, msg = lines[p + 1].split(" ", 2)
+            res.append(("refused", int(code), msg))
+            p += 2
+            continue
+        ni = int(lines[p + 1].split()[1])
+        assert lines[p + 1] == "items %d" % ni
+        items = [tuple(map(int, l.split())) for l in lines[p + 2:p + 2 + ni]]
+        p += 2 + ni
+        ns = int(lines[p].split()[1])
+        assert lines[p] == "slots %d" % ns
+        slots = [tuple(map(int, l.split())) for l in lines[p + 1:p + 1 + ns]]
+        p += 1 + ns
+        assert all(len(i) == 3 for i in items) and all(len(s) == 3 for s in slots)
+        res.append(("plan", items, slots))
+    assert p == len(lines)
+    return res
+
+
+def run_cases(checkers, cases, directory):
+    """every case through ONE process of each build; both must print the same"""
+    path = os.path.join(str(directory), "cases.txt")
+    with open(path, "w") as f:
+        f.write("\n".join(c.text() for c in cases) + "\n")
+    outs = []
+    for exe in checkers:
+        r = subprocess.run([exe, path], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, (exe, r.returncode, r.stderr[-2000:])
+        outs.append(r.stdout)
+    assert outs[0] == outs[1]
+    return _parse(outs[0], len(cases))
+
+
+@pytest.fixture(scope="module")
+def ragged_bound(checkers):
+    """the smallest tensor width whose line the ragged attention kernel does not take, by the predicate the plan uses"""
+    outs = [subprocess.run([exe, "--ragged-bound"], capture_output=True, text=True, check=True).stdout for exe in checkers]
+    assert outs[0] == outs[1]
+    return int(outs[0])
+
+
+@pytest.fixture(scope="module")
+def oracle_fns(built):
+    import oracle as O
+    L = O.lib()
+    L.oracle_rec_width.restype = ctypes.c_int
+    L.oracle_rec_width.argtypes = [ctypes.c_int, ctypes.c_float]
+    L.oracle_rec_resize_w.restype = ctypes.c_int
+    L.oracle_rec_resize_w.argtypes = [ctypes.c_int] * 4
+    return O, L
+
+
+@pytest.fixture(scope="module")
+def tie_case(oracle_fns):
+    """20 lines, 5 of them tied, in an order on which the oracle's std::sort and its stable sort disagree"""
+    O, _ = oracle_fns
+    for seed in range(400):
+        sizes = _tied(20, 5, seed)
+        if _std_differs_from_stable(O, sizes):
+            return sizes
+    raise AssertionError("no order of 5 tied ratios among 20 on which the oracle's two argsorts differ")
+
+
+@pytest.fixture(scope="module")
+def plans(checkers, ragged_bound, tie_case, tmp_path_factory):
+    B = ragged_bound
+    cases = dict(CASES)
+    cases["tied_std"] = Case(tie_case, mode=STD)
+    cases["tied_stable"] = Case(tie_case, mode=STABLE)
+    # tensor widths 320, B - 8, B, B, B + 104 at imgH 32 (w / 32 is exact in a float for these w)
+    cases["over_wide"] = Case([(B, 32), (200, 32), (B + 104, 32), (B - 8, 32), (B, 32)], shape=(32, 320), batch_num=1)
+    cases["over_wide_cap"] = Case([(B, 32)] * 3 + [(B - 8, 32)] * 3, shape=(32, 320), batch_num=1, cap=2)
+    names = list(cases)
+    got = run_cases(checkers, [cases[k] for k in names], tmp_path_factory.mktemp("recplan_cases"))
+    return {k: (cases[k], g) for k, g in zip(names, got)}
+
+
+# ------------------------------------------------------------------------------------------ the restatement
+def restate(fns, c, force_stable=False, batch_num=None, cap_resize=True):
+    """ocr_rec.cpp:34-57 per segment, from the oracle's parts; None where OCR_SORT_MSVC_STRICT refuses.  The three keyword
+    arguments are the mistakes the comparison must notice (test_the_comparison_has_teeth)."""
+    O, L = fns
+    f32 = np.float32
+    batch_num = batch_num or c.batch_num
+    items = []
+    for s0, s1 in zip(c.seg[:-1], c.seg[1:]):
+        sizes = c.sizes[s0:s1]
+        ratios = np.array([f32(w) / f32(h) for w, h in sizes], f32)                  # :38 float(cols) / rows
+        if c.mode == STRICT and len(sizes) > 32 and len(set(ratios.tolist())) < len(sizes):
+            return None
+        order = O.argsort(ratios, stable=force_stable or c.mode != STD).tolist()    # :40
+        for beg in range(0, len(sizes), batch_num):                                  # :42-46
+            batch = order[beg:beg + batch_num]
+            max_wh_ratio = f32(c.imgW * 1.0 / c.imgH)                                # :49
+            for i in batch:
+                w, h = sizes[i]
+                max_wh_ratio = max(max_wh_ratio, f32(w * 1.0 / h))                   # :53-54
+            if c.server:
+                max_wh_ratio = f32(c.imgW * 1.0 / c.imgH)                            # one token grid: every tensor imgW wide
+            bw = L.oracle_rec_width(c.imgH, max_wh_ratio)                            # CrnnResizeImg: int(imgH * max_wh_ratio)
+            for i in batch:
+                w, h = sizes[i]
+                resize_w = L.oracle_rec_resize_w(h, w, c.imgH, bw if cap_resize else 1 << 30)
+                items.append((s0 + i, resize_w, max(bw, c.imgW)))                    # :57, :67 batch_width
+    return sorted(items, key=lambda it: it[2])  # (stable) ascending tensor width, as the launches take them
+
+
+def check_invariants(c, items, slots, bound):
+    assert sorted(it[0] for it in items) == list(range(len(c.sizes)))
+    tw = [it[2] for it in items]
+    assert tw == sorted(tw)
+    budget = c.cap * c.imgH * max(c.imgW, 320)
+    pix = lambda a, b: sum(c.imgH * w for w in tw[a:b])
+    at = 0
+    for k, (first, count, ragged) in enumerate(slots):
+        assert first == at and count >= 1 and ragged in (0, 1)
+        at += count
+        nxt = slots[k + 1] if k + 1 < len(slots) else None
+        if ragged:
+            assert not c.server and all(w < bound for w in tw[first:at])
+            assert count == 1 or pix(first, at) <= budget
+            if nxt and nxt[2]:  # greedy: the next ragged slot's first line did not fit
+                assert pix(first, at + 1) > budget
+        else:
+            assert c.server or tw[first] >= bound
+            assert len(set(tw[first:at])) == 1 and count <= c.cap
+            if nxt and tw[at] == tw[first]:  # greedy: a width is split only where the slot is full
+                assert count == c.cap
+    assert at == len(items)
+
+
+# ------------------------------------------------------------------------------------------ the tests
+@pytest.mark.parametrize("name", list(CASES) + ["tied_std", "tied_stable", "over_wide", "over_wide_cap"])
+def test_items_equal_the_restatement_and_slots_keep_their_rules(plans, oracle_fns, ragged_bound, name):
+    c, got = plans[name]
+    want = restate(oracle_fns, c)
+    if want is None:
+        assert got[0] == "refused" and got[1] == OCR_ERR_ARG and "MSVC" in got[2]
+        return
+    assert got[0] == "plan"
+    assert got[1] == want
+    check_invariants(c, got[1], got[2], ragged_bound)
+
+
+def test_empty_calls_and_the_batch_boundary(plans):
+    for name in ("empty", "empty_segment"):
+        assert plans[name][1] == ("plan", [], [])
+    assert len(plans["empty_between"][1][1]) == 9
+    # 16 lines are one batch of one width; the 17th (the widest ratio) is a batch of its own
+    assert len({it[2] for it in plans["sixteen"][1][1]}) == 1
+    items = plans["seventeen"][1][1]
+    c = plans["seventeen"][0]
+    widest = max(range(17), key=lambda i: c.sizes[i][0] / c.sizes[i][1])
+    assert [it[0] for it in items if it[2] == items[-1][2]] == [widest] and len({it[2] for it in items}) == 2
+
+
+def test_segments_interleave_in_tensor_width(plans):
+    for name in ("two_segments", "three_segments"):
+        c, (_, items, _) = plans[name]
+        seg_of = [sum(it[0] >= s for s in c.seg[1:]) for it in items]
+        assert len(set(seg_of)) == len(c.seg) - 1
+        # not segment after segment (that would change segment len(seg) - 2 times): the launches mix the images' lines
+        assert sum(a != b for a, b in zip(seg_of, seg_of[1:])) > len(c.seg) - 2
+
+
+def test_floor_and_one_ratio_above_it(plans):
+    for name, w in (("floor_48", 320), ("floor_28", 192)):
+        assert {it[2] for it in plans[name][1][1]} == {w}
+    for name, w, h in (("above_48", 320, 48), ("above_28", 192, 28)):
+        assert {it[2] for it in plans[name][1][1]} == {20 * h}  # one batch: all as wide as its widest line
+        got = {it[2] for it in plans[name + "_b4"][1][1]}
+        assert got == {w, 20 * h}                               # batches of 4: only the last one holds it
+
+
+def test_tied_ratios_follow_the_sort_mode(plans, oracle_fns):
+    (c_std, std), (c_stable, stable) = plans["tied_std"], plans["tied_stable"]
+    assert _std_differs_from_stable(oracle_fns[0], c_std.sizes)
+    assert std[1] != stable[1]  # each equals the oracle's argsort of its mode (the parametrised test); the two differ
+    assert plans["strict_33_tied"][1][0] == "refused" and "MSVC" in plans["strict_33_tied"][1][2]
+    assert "image 1 " in plans["strict_second_image"][1][2]
+    for n in ("32_tied", "33_untied"):
+        assert plans["strict_" + n][1][0] == "plan" and plans["strict_" + n][1] == plans["stable_" + n][1]
+
+
+def test_server_lines_share_one_width(plans):
+    c, (_, items, slots) = plans["server"]
+    assert max(w / h for w, h in c.sizes) > 320 / 48
+    assert {it[2] for it in items} == {320} and slots == [(0, 20, 0)]
+    assert plans["server_cap"][1][2] == [(0, 2, 0), (2, 2, 0), (4, 1, 0)]
+
+
+def test_over_wide_lines_are_uniform_slots_of_their_own(plans, ragged_bound):
+    B = ragged_bound
+    assert B % 8 == 0
+    _, (_, items, slots) = plans["over_wide"]
+    assert [it[2] for it in items] == [320, B - 8, B, B, B + 104]
+    assert slots == [(0, 2, 1), (2, 2, 0), (4, 1, 0)]
+    _, (_, items, slots) = plans["over_wide_cap"]
+    assert [it[2] for it in items] == [B - 8] * 3 + [B] * 3
+    # max_lines_per_launch 2: each ragged line alone is past the budget of 2 x 32 x 320 pixels; the uniform width goes 2 + 1
+    assert slots == [(0, 1, 1), (1, 1, 1), (2, 1, 1), (3, 2, 0), (5, 1, 0)]
+
+
+def test_budget_cuts(plans):
+    want = {
+        1: [(i, 1, 1) for i in range(6)],                                     # 48 x 320 pixels: every line alone, 400 and up exceed it
+        2: [(0, 2, 1), (2, 1, 1), (3, 1, 1), (4, 1, 1), (5, 1, 1)],            # 640 columns: 320 + 320 | 320 (+ 400 > 640) | 400 | 480 | 2000
+        3: [(0, 3, 1), (3, 2, 1), (5, 1, 1)],                                  # 960 columns: 3 x 320 | 400 + 480 | 2000
+    }
+    for cap, slots in want.items():
+        _, (_, items, got) = plans["budget_%d" % cap]
+        assert [it[2] for it in items] == [320, 320, 320, 400, 480, 2000]
+        assert got == slots
+
+
+def test_the_comparison_has_teeth(plans, oracle_fns):
+    """three mistakes, made in the restatement: each must break the comparison on a case of the suite"""
+    c, got = plans["tied_std"]
+    assert restate(oracle_fns, c) == got[1] != restate(oracle_fns, c, force_stable=True)
+    c, got = plans["seventeen"]
+    assert restate(oracle_fns, c) == got[1]
+    assert restate(oracle_fns, c, batch_num=17) != got[1] and restate(oracle_fns, c, batch_num=15) != got[1]
+    c, got = plans["server"]  # lines wider than the tensor: only the cap keeps resize_w inside it
+    assert restate(oracle_fns, c) == got[1] != restate(oracle_fns, c, cap_resize=False)
+    assert max(it[1] for it in got[1]) == 320 < max(it[1] for it in restate(oracle_fns, c, cap_resize=False))
