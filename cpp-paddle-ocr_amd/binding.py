@@ -68,6 +68,7 @@ EXPORTS = [
     "ocr_net_timing", "ocr_net_timing_report", "ocr_probe", "ocr_selftest_refuse_launch", "ocr_selftest_lds_memo",
     "ocr_selftest_unclip", "ocr_selftest_unclip_box",
     "ocr_selftest_det_pre", "ocr_selftest_line_pre", "ocr_selftest_line_pre_ragged",
+    "ocr_selftest_warp_crops", "ocr_selftest_rotate180_groups", "ocr_selftest_crop_plan", "ocr_selftest_rotation_groups",
     "ocr_selftest_softmax_argmax", "ocr_selftest_head_combine", "ocr_selftest_srv_argmax", "ocr_selftest_ctc_reduce",
     "ocr_selftest_ctc", "ocr_selftest_topk_lines", "ocr_selftest_rec_head",
     "ocr_srv_net_create", "ocr_srv_net_destroy", "ocr_srv_net_forward", "ocr_srv_net_rerun", "ocr_srv_net_num_tensors", "ocr_srv_net_fetch",
@@ -378,6 +379,74 @@ def selftest_line_pre_ragged(parent, cols, lines, imgH, stage=STAGE_REC):
         outs.append(x[at:at + imgH * w * 3].reshape(imgH, w, 3))
         at += imgH * w * 3
     return outs, g
+
+
+# ---- the crop geometry between detector and recognizer alone (include/ocr_hip.h)
+class ocr_warp_case(C.Structure):
+    _fields_ = [("src_off", C.c_uint64), ("sstride", C.c_uint64), ("sw", C.c_int32), ("sh", C.c_int32), ("dw", C.c_int32), ("dh", C.c_int32),
+                ("rot", C.c_int32), ("bw0", C.c_int32), ("m", C.c_double * 9)]
+
+
+def selftest_warp_crops(src, crops, max_pixels, out_off, out_bytes):
+    """ONE launch_warp_crops (ocr_selftest_warp_crops): src a flat uint8 buffer; crops: dicts with src_off, sstride, sw, sh, dw, dh, rot,
+    bw0 and m (9 doubles, destination -> source); crop k writes dw * dh * 3 bytes at out_off[k] of an output of out_bytes bytes ->
+    (uint8 [out_bytes] with the fill wherever nothing was written, guard bytes behind it)"""
+    src = np.ascontiguousarray(src, dtype=np.uint8).reshape(-1)
+    n = len(crops)
+    arr = (ocr_warp_case * max(1, n))()
+    for k, c in enumerate(crops):
+        arr[k] = ocr_warp_case(int(c["src_off"]), int(c["sstride"]), int(c["sw"]), int(c["sh"]), int(c["dw"]), int(c["dh"]), int(c["rot"]),
+                               int(c["bw0"]), (C.c_double * 9)(*[float(v) for v in c["m"]]))
+    off = np.ascontiguousarray(out_off, dtype=np.uint64).reshape(-1)
+    assert off.size == n
+    if n == 0:
+        off = np.zeros(1, np.uint64)
+    cnt = int(out_bytes) if 0 < out_bytes <= 1 << 28 else 0
+    out = np.zeros(cnt + SELFTEST_GUARD, np.uint8)
+    _tail_call("ocr_selftest_warp_crops", [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
+               src.ctypes.data, src.size, C.addressof(arr), n, int(max_pixels), off.ctypes.data, int(out_bytes), out.ctypes.data)
+    return out[:cnt], out[cnt:]
+
+
+def selftest_rotate180_groups(buf, rois, seg):
+    """ONE launch_rotate180_groups (ocr_selftest_rotate180_groups) on a copy of the flat uint8 buffer `buf`; rois: rows of (byte offset of
+    the view, stride, x, y, w, h) in launch order; seg: the ngroups + 1 offsets into rois -> the whole buffer afterwards"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1).copy()
+    rois = np.ascontiguousarray(rois, dtype=np.int64).reshape(-1, 6)
+    seg = np.ascontiguousarray(seg, dtype=np.int32).reshape(-1)
+    assert seg.size >= 1
+    _tail_call("ocr_selftest_rotate180_groups", [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_int],
+               buf.ctypes.data, buf.size, rois.ctypes.data, len(rois), seg.ctypes.data, seg.size - 1)
+    return buf
+
+
+CROP_PLAN_FIELDS = ("left", "top", "sw", "sh", "dw", "dh", "rot", "orows", "ocols", "bw0")
+
+
+def selftest_crop_plan(rows, cols, box):
+    """plan_rotate_crop of csrc/crop.h for one box (ocr_selftest_crop_plan, host only) -> dict of CROP_PLAN_FIELDS and minv (float64 [9])"""
+    b = np.ascontiguousarray(np.asarray(box, np.int32).reshape(8))
+    f = np.zeros(len(CROP_PLAN_FIELDS), np.int32)
+    minv = np.zeros(9, np.float64)
+    _tail_call("ocr_selftest_crop_plan", [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p], int(rows), int(cols), b.ctypes.data,
+               f.ctypes.data, minv.ctypes.data)
+    p = {k: int(v) for k, v in zip(CROP_PLAN_FIELDS, f)}
+    p["minv"] = minv
+    return p
+
+
+def selftest_rotation_groups(rects, views):
+    """the grouping the 180-degree rotations are launched with (ocr_selftest_rotation_groups, host only): rects rows of (x, y, w, h),
+    views[i] the view rectangle i lies in -> (order: request indices group after group, seg: ngroups + 1 offsets into order)"""
+    r = np.ascontiguousarray(rects, dtype=np.int32).reshape(-1, 4)
+    v = np.ascontiguousarray(views, dtype=np.int32).reshape(-1)
+    assert v.size == len(r)
+    order = np.zeros(max(1, len(r)), np.int32)
+    seg = np.zeros(len(r) + 1, np.int32)
+    ng = C.c_int(0)
+    _tail_call("ocr_selftest_rotation_groups", [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)],
+               r.ctypes.data, v.ctypes.data, len(r), order.ctypes.data, seg.ctypes.data, C.byref(ng))
+    return [int(k) for k in order[:len(r)]], [int(s) for s in seg[:ng.value + 1]]
 
 
 # ---- the recognizer's tail launches alone (include/ocr_hip.h): every output comes back as (values, guard bytes)

@@ -4,6 +4,8 @@
 #include <vector>
 
 #include "capi_common.h"
+#include "crop.h"
+#include "rot_groups.h"
 #include "stages.h"
 
 using namespace ocr;
@@ -281,6 +283,129 @@ int ocr_selftest_line_pre_ragged(const uint8_t* img, int rows, int cols, size_t 
   launch_line_pre_ragged(ddesc.p, n, pix, imgH, lut.p, dout.p, nullptr);
   CAPI_HIP(hipGetLastError());
   CAPI_HIP(g_memcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
+// ---- self-test taps: the crop geometry between detector and recognizer alone (launch_warp_crops, launch_rotate180_groups,
+// plan_rotate_crop, rot_groups::group).  The warp's matrix, column block and grid size and the rotation's segments are the
+// caller's: the launches are checked where no box of the product leads.
+int ocr_selftest_warp_crops(const uint8_t* src, size_t src_bytes, const ocr_warp_case* cases, int n, int max_pixels,
+                            const uint64_t* out_off, size_t out_bytes, uint8_t* out) {
+  if (!src || !cases || !out_off || !out) return fail(OCR_ERR_ARG, "null argument");
+  if (n < 1 || n > kPreMaxCount) return fail(OCR_ERR_ARG, "crop count out of range");
+  if (max_pixels < 1 || max_pixels > kPreMaxSide * kPreMaxSide) return fail(OCR_ERR_ARG, "max_pixels out of range");
+  if (src_bytes < 1 || src_bytes > kPreMaxBytes || out_bytes < 1 || out_bytes > kPreMaxBytes) return fail(OCR_ERR_ARG, "buffer size out of range");
+  for (int k = 0; k < n; ++k) {
+    const ocr_warp_case& c = cases[k];
+    if (c.sw < 1 || c.sh < 1 || c.dw < 1 || c.dh < 1 || c.sw > kPreMaxSide || c.sh > kPreMaxSide || c.dw > kPreMaxSide || c.dh > kPreMaxSide)
+      return fail(OCR_ERR_ARG, "crop size out of range");
+    if (c.bw0 < 1) return fail(OCR_ERR_ARG, "bw0 < 1");
+    if (c.rot != 0 && c.rot != 1) return fail(OCR_ERR_ARG, "rot is neither 0 nor 1");
+    if (c.sstride < (uint64_t)c.sw * 3 || c.sstride > src_bytes) return fail(OCR_ERR_ARG, "sstride below 3 * sw");
+    const size_t one = (size_t)(c.sh - 1) * c.sstride + (size_t)c.sw * 3;
+    if (c.src_off > src_bytes || one > src_bytes - c.src_off) return fail(OCR_ERR_ARG, "the source crop does not lie inside the buffer");
+    const size_t bytes = (size_t)c.dw * c.dh * 3;
+    if (out_off[k] > out_bytes || bytes > out_bytes - out_off[k]) return fail(OCR_ERR_ARG, "the crop does not lie inside the output");
+  }
+  std::string err;
+  DevBuf<uint8_t> dsrc, dout;
+  DevBuf<WarpDesc> ddesc;
+  const size_t all = out_bytes + OCR_SELFTEST_GUARD;
+  if (!dsrc.ensure(src_bytes, err) || !dout.ensure(all, err) || !ddesc.ensure(n, err)) return fail(OCR_ERR_DEVICE, err);
+  std::vector<WarpDesc> wd(n);
+  for (int k = 0; k < n; ++k) {
+    const ocr_warp_case& c = cases[k];
+    WarpDesc& d = wd[k];
+    d.src = dsrc.p + c.src_off; d.sstride = c.sstride; d.sw = c.sw; d.sh = c.sh; d.dst = dout.p + out_off[k];
+    d.dw = c.dw; d.dh = c.dh; d.rot = c.rot; d.bw0 = c.bw0;
+    memcpy(d.m, c.m, sizeof(d.m));
+  }
+  CAPI_HIP(g_memcpy(dsrc.p, src, src_bytes, hipMemcpyHostToDevice));
+  CAPI_HIP(g_memcpy(ddesc.p, wd.data(), (size_t)n * sizeof(WarpDesc), hipMemcpyHostToDevice));
+  CAPI_HIP(hipMemset(dout.p, OCR_SELFTEST_FILL, all));
+  launch_warp_crops(ddesc.p, n, max_pixels, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(g_memcpy(out, dout.p, all, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
+int ocr_selftest_rotate180_groups(uint8_t* buf, size_t buf_bytes, const int64_t* rois, int n, const int32_t* seg, int ngroups) {
+  if (!buf || !rois || !seg) return fail(OCR_ERR_ARG, "null argument");
+  if (n < 1 || n > kPreMaxCount) return fail(OCR_ERR_ARG, "ROI count out of range");
+  if (ngroups < 0 || ngroups > n) return fail(OCR_ERR_ARG, "group count out of range");
+  if (buf_bytes < 1 || buf_bytes > kPreMaxBytes) return fail(OCR_ERR_ARG, "buffer size out of range");
+  if (seg[0] != 0) return fail(OCR_ERR_ARG, "seg[0] is not 0");
+  for (int g = 0; g < ngroups; ++g)
+    if (seg[g + 1] < seg[g] || seg[g + 1] > n) return fail(OCR_ERR_ARG, "seg is not ascending inside the ROI list");
+  std::vector<size_t> first(n), last(n);  // the bytes an ROI's rotation may touch: [first, last)
+  for (int k = 0; k < n; ++k) {
+    const int64_t* q = rois + (size_t)k * 6;
+    if (q[4] < 1 || q[5] < 1 || q[4] > kPreMaxSide || q[5] > kPreMaxSide) return fail(OCR_ERR_ARG, "empty ROI");
+    if (q[2] < 0 || q[3] < 0 || q[2] > kPreMaxSide || q[3] > kPreMaxSide) return fail(OCR_ERR_ARG, "ROI origin out of range");
+    if (q[0] < 0 || (uint64_t)q[0] > buf_bytes) return fail(OCR_ERR_ARG, "view outside the buffer");
+    if (q[1] < (q[2] + q[4]) * 3 || (uint64_t)q[1] > buf_bytes) return fail(OCR_ERR_ARG, "stride below the ROI's right edge");
+    first[k] = (size_t)q[0] + (size_t)q[3] * q[1] + (size_t)q[2] * 3;
+    last[k] = (size_t)q[0] + (size_t)(q[3] + q[5] - 1) * q[1] + (size_t)(q[2] + q[4]) * 3;
+    if (last[k] > buf_bytes) return fail(OCR_ERR_ARG, "ROI outside the buffer");
+  }
+  const int used = seg[ngroups];
+  std::vector<int> group_of(used, 0);
+  for (int g = 0; g < ngroups; ++g)
+    for (int k = seg[g]; k < seg[g + 1]; ++k) group_of[k] = g;
+  for (int a = 0; a < used; ++a)
+    for (int b = a + 1; b < used; ++b) {
+      if (group_of[a] == group_of[b]) continue;
+      const int64_t *p = rois + (size_t)a * 6, *q = rois + (size_t)b * 6;
+      const bool same_view = p[0] == q[0] && p[1] == q[1];
+      const bool touch = same_view ? rot_groups::intersects(rot_groups::Rect{(int)p[2], (int)p[3], (int)p[4], (int)p[5]},
+                                                            rot_groups::Rect{(int)q[2], (int)q[3], (int)q[4], (int)q[5]})
+                                   : first[a] < last[b] && first[b] < last[a];
+      if (touch) return fail(OCR_ERR_ARG, "ROIs of two groups may touch the same bytes");
+    }
+  std::string err;
+  DevBuf<uint8_t> dimg;
+  DevBuf<RotDesc> ddesc;
+  DevBuf<int> dseg;
+  if (!dimg.ensure(buf_bytes, err) || !ddesc.ensure(n, err) || !dseg.ensure((size_t)ngroups + 1, err)) return fail(OCR_ERR_DEVICE, err);
+  std::vector<RotDesc> rd(n);
+  for (int k = 0; k < n; ++k) {
+    const int64_t* q = rois + (size_t)k * 6;
+    rd[k] = RotDesc{dimg.p + q[0], (size_t)q[1], (int)q[2], (int)q[3], (int)q[4], (int)q[5]};
+  }
+  CAPI_HIP(g_memcpy(dimg.p, buf, buf_bytes, hipMemcpyHostToDevice));
+  CAPI_HIP(g_memcpy(ddesc.p, rd.data(), (size_t)n * sizeof(RotDesc), hipMemcpyHostToDevice));
+  CAPI_HIP(g_memcpy(dseg.p, seg, ((size_t)ngroups + 1) * sizeof(int), hipMemcpyHostToDevice));
+  launch_rotate180_groups(ddesc.p, dseg.p, ngroups, nullptr);
+  CAPI_HIP(hipGetLastError());
+  CAPI_HIP(g_memcpy(buf, dimg.p, buf_bytes, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
+int ocr_selftest_crop_plan(int rows, int cols, const int32_t* box8, int32_t* fields, double* minv) {
+  if (!box8 || !fields || !minv) return fail(OCR_ERR_ARG, "null argument");
+  CropPlan p;
+  if (!plan_rotate_crop(rows, cols, box8, p)) return fail(OCR_ERR_ARG, "box has no crop inside the image");
+  const int32_t f[10] = {p.left, p.top, p.sw, p.sh, p.dw, p.dh, p.rot, p.orows, p.ocols, p.bw0};
+  memcpy(fields, f, sizeof(f));
+  memcpy(minv, p.minv, sizeof(p.minv));
+  return OCR_OK;
+}
+
+int ocr_selftest_rotation_groups(const int32_t* rects, const int32_t* views, int n, int32_t* order, int32_t* seg, int* ngroups) {
+  if (!rects || !views || !order || !seg || !ngroups) return fail(OCR_ERR_ARG, "null argument");
+  if (n < 1 || n > (1 << 20)) return fail(OCR_ERR_ARG, "rectangle count out of range");
+  std::vector<rot_groups::Rect> r(n);
+  std::vector<int32_t> v(views, views + n);
+  for (int k = 0; k < n; ++k) {
+    const int32_t* q = rects + (size_t)k * 4;
+    if (q[2] < 1 || q[3] < 1 || q[0] > INT32_MAX - q[2] || q[1] > INT32_MAX - q[3]) return fail(OCR_ERR_ARG, "empty rectangle");
+    r[k] = rot_groups::Rect{q[0], q[1], q[2], q[3]};
+  }
+  std::vector<int> ord, sg;
+  rot_groups::group(r, v, ord, sg);
+  for (int k = 0; k < n; ++k) order[k] = ord[k];
+  for (size_t g = 0; g < sg.size(); ++g) seg[g] = sg[g];
+  *ngroups = (int)sg.size() - 1;
   return OCR_OK;
 }
 

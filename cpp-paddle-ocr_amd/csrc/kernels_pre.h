@@ -39,7 +39,6 @@ struct LineDesc {
 };
 void launch_line_pre(const LineDesc* lines, int nlines, int imgH, int imgW, const float* lut, bool pad_after_norm,
                      float* out, hipStream_t s);
-void launch_rotate180(uint8_t* img, size_t stride, int x0, int y0, int w, int h, hipStream_t s);
 struct RotDesc {
   uint8_t* img;
   size_t stride;

@@ -262,27 +262,11 @@ void launch_line_pre_ragged(const LineDesc* lines, int nlines, long total_pixels
                      imgH, lut, out);
 }
 
-// cv::rotate(roi, roi, ROTATE_180) in place: pixel i <-> total-1-i
-__global__ void __launch_bounds__(256) rotate180_kernel(uint8_t* img, size_t stride, int x0, int y0, int w, int h) {
-  const long total = (long)w * h;
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total / 2) return;
-  const long j = total - 1 - i;
-  uint8_t* a = img + (size_t)(y0 + i / w) * stride + (size_t)(x0 + i % w) * 3;
-  uint8_t* b = img + (size_t)(y0 + j / w) * stride + (size_t)(x0 + j % w) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { const uint8_t t = a[c]; a[c] = b[c]; b[c] = t; }
-}
-void launch_rotate180(uint8_t* img, size_t stride, int x0, int y0, int w, int h, hipStream_t s) {
-  const long half = ((long)w * h) / 2;
-  if (half <= 0) return;
-  hipLaunchKernelGGL(rotate180_kernel, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, s, img, stride, x0, y0, w, h);
-}
-
-// The same for a whole batch.  ROIs of one image may overlap, so their order matters - but only between ROIs that do
-// overlap: the host groups the batch into the connected components of the "intersects" relation (pipe.hip), one
-// workgroup applies the rotations of ONE component in request order, components run concurrently.  Pixel (y, x)
-// swaps with (h-1-y, w-1-x) for the first total/2 pixels in raster order (cv::rotate's flip).
+// cv::rotate(roi, roi, ROTATE_180) in place for a whole batch: pixel i <-> total-1-i of each ROI.  ROIs of one image may
+// overlap, so their order matters - but only between ROIs that do overlap: the host groups the batch into the connected
+// components of the "intersects" relation (rot_groups.h), one workgroup applies the rotations of ONE component in request
+// order, components run concurrently.  Pixel (y, x) swaps with (h-1-y, w-1-x) for the first total/2 pixels in raster order
+// (cv::rotate's flip).
 // one BGR pixel as the low 24 bits of a word.  A pixel that is not the last of its ROI row is fetched with ONE unaligned
 // 4-byte load (the fourth byte is the next pixel's first, inside the ROI); the TA processes a wave's byte loads no
 // faster than its dword loads, and the kernel is bound by their number.

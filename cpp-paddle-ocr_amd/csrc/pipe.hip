@@ -12,6 +12,7 @@
 #include "capi_common.h"
 #include "crop.h"
 #include "frame_kinds.h"
+#include "rot_groups.h"
 #include "stages.h"
 
 using namespace ocr;
@@ -53,33 +54,18 @@ static int rotate180_in_order(const std::vector<RotDesc>& rd, DevBuf<RotDesc>& s
                               std::string& err) {
   if (rd.empty()) return OCR_OK;
   const int n = (int)rd.size();
-  std::vector<int> parent(n);
-  for (int i = 0; i < n; ++i) parent[i] = i;
-  auto find = [&](int a) { while (parent[a] != a) { parent[a] = parent[parent[a]]; a = parent[a]; } return a; };
-  std::map<std::pair<const uint8_t*, size_t>, std::vector<int>> views;  // per view the list is short (the lines of one image)
+  std::vector<rot_groups::Rect> rects(n);
+  std::vector<std::pair<const uint8_t*, size_t>> view(n);
   for (int k = 0; k < n; ++k) {
-    const RotDesc& q = rd[k];
-    std::vector<int>& mine = views[{q.img, q.stride}];
-    for (int j : mine) {
-      const RotDesc& e = rd[j];
-      if (e.x < q.x + q.w && q.x < e.x + e.w && e.y < q.y + q.h && q.y < e.y + e.h) {
-        const int a = find(j), b = find(k);
-        if (a != b) parent[std::max(a, b)] = std::min(a, b);  // the root is the component's first ROI
-      }
-    }
-    mine.push_back(k);
+    rects[k] = rot_groups::Rect{rd[k].x, rd[k].y, rd[k].w, rd[k].h};
+    view[k] = {rd[k].img, rd[k].stride};
   }
   // components in order of their first ROI, members in request order
-  std::vector<std::vector<int>> members(n);
-  for (int k = 0; k < n; ++k) members[find(k)].push_back(k);
+  std::vector<int> order, seg;
+  rot_groups::group(rects, view, order, seg);
   std::vector<RotDesc> sorted;
-  std::vector<int> seg(1, 0);
   sorted.reserve(n);
-  for (int r = 0; r < n; ++r) {
-    if (members[r].empty()) continue;
-    for (int k : members[r]) sorted.push_back(rd[k]);
-    seg.push_back((int)sorted.size());
-  }
+  for (int k : order) sorted.push_back(rd[k]);
   if (!scratch.ensure(sorted.size(), err) || !seg_scratch.ensure(seg.size(), err)) return OCR_ERR_DEVICE;
   if (hipMemcpyAsync(scratch.p, sorted.data(), sorted.size() * sizeof(RotDesc), hipMemcpyHostToDevice, stream) != hipSuccess ||
       hipMemcpyAsync(seg_scratch.p, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) {

@@ -791,6 +791,34 @@ int ocr_selftest_line_pre(const uint8_t* img, int rows, int cols, size_t stride,
 int ocr_selftest_line_pre_ragged(const uint8_t* img, int rows, int cols, size_t stride, const int32_t* lines, int n, int imgH,
                                  int stage, float* out);
 
+/* The crop geometry between detector and recognizer alone (tests/test_gpu_crop_ops.py, tests/test_crop_ref.py).  Arguments
+ * the launchers do not define are refused with OCR_ERR_ARG before anything reaches the device.
+ * ocr_selftest_warp_crops: ONE launch_warp_crops over n descriptors on the device copy of src[src_bytes].  The CALLER gives the
+ * matrix (destination -> source, as the kernel reads it), the column block bw0 and max_pixels (what sizes the grid; at least
+ * one); crop k reads the sw x sh pixels that start at byte src_off of the copy, rows sstride apart (they must lie inside it),
+ * and writes dw * dh * 3 bytes at out_off[k] of an output of out_bytes bytes.  The device output is pre-filled with
+ * OCR_SELFTEST_FILL; out receives all of it and OCR_SELFTEST_GUARD more bytes from behind its last.
+ * ocr_selftest_rotate180_groups: ONE launch_rotate180_groups on the device copy of buf[buf_bytes], which comes back whole.
+ * rois: n x 6 int64 (byte offset of the view's first pixel, row stride, x, y, w, h; every ROI inside the buffer), already in
+ * launch order; seg: ngroups + 1 ascending offsets into rois, seg[0] = 0, as the caller chooses them (ngroups = 0: nothing
+ * is launched).  ROIs of DIFFERENT groups that could touch one byte are refused: the launch leaves their order open.
+ * ocr_selftest_crop_plan (host only): every field of the plan of Utility::GetRotateCropImage for one box of a rows x cols
+ * image - fields = {left, top, sw, sh, dw, dh, rot, orows, ocols, bw0}, minv = the 9 doubles of the inverse homography;
+ * OCR_ERR_ARG where ocr_rotate_crop refuses the box.
+ * ocr_selftest_rotation_groups (host only): the grouping ocr_rotate180_rois and the pipeline launch with, for n rectangles
+ * (n x 4 int32: x, y, w, h) of which rectangle i lies in view views[i]: order[n] = request indices group after group,
+ * seg[*ngroups + 1] = the groups' offsets into order (seg has room for n + 1). */
+typedef struct ocr_warp_case {
+  uint64_t src_off, sstride;
+  int32_t sw, sh, dw, dh, rot, bw0;
+  double m[9];
+} ocr_warp_case;
+int ocr_selftest_warp_crops(const uint8_t* src, size_t src_bytes, const ocr_warp_case* cases, int n, int max_pixels,
+                            const uint64_t* out_off, size_t out_bytes, uint8_t* out);
+int ocr_selftest_rotate180_groups(uint8_t* buf, size_t buf_bytes, const int64_t* rois, int n, const int32_t* seg, int ngroups);
+int ocr_selftest_crop_plan(int rows, int cols, const int32_t* box8, int32_t* fields, double* minv);
+int ocr_selftest_rotation_groups(const int32_t* rects, const int32_t* views, int n, int32_t* order, int32_t* seg, int* ngroups);
+
 /* The recognizer's tail launches alone, on caller-held data (tests/test_gpu_rec_tail.py): what turns logits into (arg max,
  * probability) per CTC step and steps into characters.  Each calls the launch function production binds.  Every output is
  * pre-filled with OCR_SELFTEST_FILL and comes back with OCR_SELFTEST_GUARD more bytes, taken from behind its last element
