@@ -116,14 +116,15 @@ def _raise(L, rc, out):
     raise err
 
 
-def _decode_frame(name, c, h, w, device_id, fill=0):
+def _decode_frame(name, c, h, w, device_id, fill=0, cap=None):
     """L.<name>(&c, device_id, bgr, cap) - the ocr_X_decode of a format route - into an (h, w, 3) buffer pre-filled with `fill`;
-    (1, 1, 3) where h x w is no image size: the library refuses the descriptor before it looks at the capacity"""
+    (1, 1, 3) where h x w is no image size: the library refuses the descriptor before it looks at the capacity.  cap: the
+    capacity the call is told, when it is not the buffer's size"""
     L = lib()
     fn = getattr(L, name)
     fn.argtypes = [C.POINTER(type(c)), C.c_int, C.c_void_p, C.c_size_t]
     out = np.full((h, w, 3) if 0 < h and 0 < w and h * w <= (64 << 20) else (1, 1, 3), fill, np.uint8)
-    rc = fn(C.byref(c), device_id, out.ctypes.data, out.size)
+    rc = fn(C.byref(c), device_id, out.ctypes.data, out.size if cap is None else cap)
     if rc != 0:
         _raise(L, rc, out)
     return out
@@ -1005,6 +1006,74 @@ def _pipe_protos(L):
 CROP_BOUNDING_RECT, CROP_ROTATE = 0, 1
 
 
+class ocr_jpeg_comp(C.Structure):
+    _fields_ = [("coef", C.c_void_p), ("quant", C.c_uint16 * 64), ("bw", C.c_int), ("bh", C.c_int), ("dw", C.c_int), ("dh", C.c_int)]
+
+
+class ocr_jpeg_img(C.Structure):
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("ncomp", C.c_int), ("hmax", C.c_int), ("vmax", C.c_int), ("orientation", C.c_int),
+                ("comp", ocr_jpeg_comp * 3)]
+
+
+class ocr_jpeg_fcomp(C.Structure):
+    _fields_ = [("coef", C.c_void_p), ("quant", C.c_uint16 * 64), ("bw", C.c_int), ("bh", C.c_int), ("dw", C.c_int), ("dh", C.c_int),
+                ("h", C.c_int), ("v", C.c_int)]
+
+
+class ocr_jpeg_frame(C.Structure):
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("ncomp", C.c_int), ("orientation", C.c_int), ("color", C.c_int), ("reserved", C.c_int),
+                ("comp", ocr_jpeg_fcomp * 4)]
+
+
+JPEG_COLORS = ["GREY", "YCBCR", "RGB", "CMYK", "YCCK"]
+
+
+class JpegFrame:
+    """an ocr_jpeg_frame over Python-owned memory.  rows, cols: the stored size; color: index into JPEG_COLORS; comps: per
+    component a mapping with h, v, bw, bh, dw, dh, quant (64 values, natural order) and coef (bw * bh * 64 int16, blocks row-major).
+    .coefs and the fields of .c may be changed before a call (the tests' tampering)."""
+
+    def __init__(self, rows, cols, color, orientation, comps):
+        self.coefs = [np.ascontiguousarray(k["coef"], np.int16).reshape(-1).copy() for k in comps]
+        c = ocr_jpeg_frame()
+        c.rows, c.cols, c.ncomp, c.orientation, c.color = rows, cols, len(comps), orientation, color
+        for o, k, coef in zip(c.comp, comps, self.coefs):
+            o.coef = coef.ctypes.data
+            o.quant[:] = [int(q) for q in np.asarray(k["quant"]).reshape(64)]
+            o.bw, o.bh, o.dw, o.dh, o.h, o.v = (int(k[f]) for f in ("bw", "bh", "dw", "dh", "h", "v"))
+        self.c = c
+
+    def out_shape(self):
+        return (self.c.cols, self.c.rows) if 5 <= self.c.orientation <= 8 else (self.c.rows, self.c.cols)
+
+    def decode(self, device_id=0, fill=0, cap=None):
+        """ocr_jpeg_decode_frame: the oriented BGR image; OcrError where the call refuses (err.out: the buffer as the call left
+        it, pre-filled with `fill`).  cap: the capacity in bytes the call is told instead of the buffer's"""
+        return _decode_frame("ocr_jpeg_decode_frame", self.c, *self.out_shape(), device_id, fill, cap)
+
+    def classic(self):
+        """the ocr_jpeg_img that says the same, None where that descriptor cannot hold the frame (it holds grey, and YCbCr with
+        luma at 1x1, 2x1 or 2x2 over 1x1 chroma)"""
+        c = self.c
+        f = [(c.comp[i].h, c.comp[i].v) for i in range(c.ncomp)]
+        if c.ncomp == 3 and (c.color != 1 or f[0] not in ((1, 1), (2, 1), (2, 2)) or f[1:] != [(1, 1), (1, 1)]):
+            return None
+        if c.ncomp not in (1, 3):
+            return None
+        im = ocr_jpeg_img()
+        im.rows, im.cols, im.ncomp, im.orientation = c.rows, c.cols, c.ncomp, c.orientation
+        im.hmax, im.vmax = f[0]
+        for o, k in zip(im.comp, c.comp[:c.ncomp]):
+            o.coef, o.bw, o.bh, o.dw, o.dh = k.coef, k.bw, k.bh, k.dw, k.dh
+            C.memmove(o.quant, k.quant, 128)
+        return im
+
+    def decode_classic(self, device_id=0, fill=0):
+        """ocr_jpeg_decode of classic(): the oriented BGR image, None where ocr_jpeg_img cannot hold the frame"""
+        im = self.classic()
+        return None if im is None else _decode_frame("ocr_jpeg_decode", im, *self.out_shape(), device_id, fill)
+
+
 class ocr_png_segment(C.Structure):
     _fields_ = [("pass_", C.c_int32), ("first_row", C.c_int32), ("rows", C.c_int32)]
 
@@ -1536,6 +1605,26 @@ class Pipe:
         for i, d in enumerate(dev_probs):
             arr[i] = d.ptr.value
         check(lib().ocr_pipe_slot_probs(self.h, slot, arr, n))
+
+    def stage_jpeg_frames(self, slot, frames):
+        """ocr_pipe_stage_jpeg_frames: a list of JpegFrame as one batch into the slot (one IDCT launch over all their planes)"""
+        L = lib()
+        L.ocr_pipe_stage_jpeg_frames.argtypes = [C.c_void_p, C.c_int, C.POINTER(ocr_jpeg_frame), C.c_int]
+        arr = (ocr_jpeg_frame * len(frames))(*[f.c for f in frames])  # (copies of the structs: the coefficient arrays stay the frames')
+        check(L.ocr_pipe_stage_jpeg_frames(self.h, slot, arr, len(frames)))
+        self._staged_n = getattr(self, "_staged_n", {})
+        self._staged_n[slot] = len(frames)
+
+    def slot_image(self, slot, index, rows, cols):
+        """ocr_pipe_slot_image: the staged image that was number `index` of the slot's last stage call, (rows, cols, 3) BGR;
+        rows, cols: the size the caller expects (the buffer's capacity) - the call's own answer is asserted against it"""
+        L = lib()
+        L.ocr_pipe_slot_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        out = np.zeros((rows, cols, 3), np.uint8)
+        r, c = C.c_int(), C.c_int()
+        check(L.ocr_pipe_slot_image(self.h, slot, index, out.ctypes.data, out.size, C.byref(r), C.byref(c)))
+        assert (r.value, c.value) == (rows, cols), (r.value, c.value, rows, cols)
+        return out
 
     def stats(self):
         """{'runs', 'binds', 'graph_replays'} summed over the pipeline's networks (Net::stats)"""

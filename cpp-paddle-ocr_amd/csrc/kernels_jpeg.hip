@@ -13,7 +13,8 @@
 //   * the EXIF orientation (cv::imdecode turns the decoded image; the table in host/jpeg_decode.h): the finished pixel
 //     of stored position (y, x) goes to its place in the oriented image, upsampling stays in the stored frame
 // Integer arithmetic throughout: results equal host/jpeg_decode.h (itself pinned to libjpeg-turbo through PIL) bit for
-// bit - tests/test_ipc_service.py::test_device_jpeg_decode_equals_host.
+// bit - tests/test_ipc_service.py::test_device_jpeg_decode_equals_host over files, and per descriptor, every kernel and branch of
+// this file against tools/jpeg_ref.py (libjpeg-turbo's arithmetic in exact integers): tests/test_gpu_jpeg_ops.py.
 #include <hip/hip_runtime.h>
 
 #include "kernels_jpeg.h"
