@@ -64,6 +64,7 @@ EXPORTS = [
     "ocr_cls_cfg_default", "ocr_cls_create", "ocr_cls_destroy", "ocr_cls_run", "ocr_cls_probs",
     "ocr_rec_cfg_default", "ocr_rec_create", "ocr_rec_destroy", "ocr_rec_run", "ocr_rec_label",
     "ocr_rec_num_classes", "ocr_rec_steps", "ocr_rec_run_chars", "ocr_rec_logits_row", "ocr_selftest_topk",
+    "ocr_rec_set_launch_lines", "ocr_rec_timing", "ocr_rec_timing_report",
     "ocr_net_create", "ocr_net_create_precision", "ocr_net_destroy", "ocr_net_forward", "ocr_net_forward_ragged", "ocr_net_forward_ragged_images", "ocr_net_num_tensors", "ocr_net_tensor_exists", "ocr_net_fetch",
     "ocr_net_timing", "ocr_net_timing_report", "ocr_probe", "ocr_selftest_refuse_launch", "ocr_selftest_lds_memo",
     "ocr_selftest_unclip", "ocr_selftest_unclip_box",
@@ -723,6 +724,9 @@ def _stage_protos(L):
     L.ocr_rec_run_chars.argtypes = [vp, C.POINTER(ocr_img), C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp,
                                     C.POINTER(C.c_double)]
     L.ocr_rec_logits_row.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
+    L.ocr_rec_set_launch_lines.argtypes = [vp, C.c_int]
+    L.ocr_rec_timing.argtypes = [vp, C.c_int]
+    L.ocr_rec_timing_report.argtypes = [vp, C.c_char_p, C.c_size_t]
     L._stage_protos_done = True
 
 
@@ -921,6 +925,23 @@ class Rec:
         T = C.c_int()
         check(lib().ocr_rec_steps(self.h, index, amax.ctypes.data, pmax.ctypes.data, cap, C.byref(T)))
         return amax[:T.value].copy(), pmax[:T.value].copy()
+
+    def set_launch_lines(self, n):
+        """self-test: at most n lines per network launch from the next run on (n < 1: OcrError, the handle keeps its value)"""
+        check(lib().ocr_rec_set_launch_lines(self.h, int(n)))
+
+    def timing(self, on=True):
+        check(lib().ocr_rec_timing(self.h, int(on)))
+
+    def timing_report(self):
+        """{launch name: dict(ms, count, flops, bytes)} since timing(True); a name carries the shape the launch was bound to"""
+        buf = C.create_string_buffer(1 << 20)
+        check(lib().ocr_rec_timing_report(self.h, buf, len(buf)))
+        out = {}
+        for line in buf.value.decode().splitlines():
+            name, ms, cnt, fl, by = line.split()
+            out[name] = dict(ms=float(ms), count=int(cnt), flops=float(fl), bytes=float(by))
+        return out
 
     def label(self, i):
         s = lib().ocr_rec_label(self.h, int(i))

@@ -710,5 +710,33 @@ int ocr_rec_steps(ocr_rec* h, int index, int32_t* amax, float* pmax, int cap, in
   if (pmax) memcpy(pmax, h->s.tap_pmax.data() + h->s.tap_off[index], t * sizeof(float));
   return OCR_OK;
 }
+int ocr_rec_set_launch_lines(ocr_rec* h, int n) {
+  if (!h) return fail(OCR_ERR_ARG, "null handle");
+  if (n < 1) return fail(OCR_ERR_ARG, "lines per launch must be >= 1");
+  h->s.max_lines_per_launch = n;
+  return OCR_OK;
+}
+int ocr_rec_timing(ocr_rec* h, int enable) {
+  if (!h) return fail(OCR_ERR_ARG, "null handle");
+  SrvNet* srv = h->s.srv();
+  if (!srv) return fail(OCR_ERR_ARG, "launch timing of a recognizer handle: the server recognizer only");
+  srv->enable_timing(enable != 0);
+  srv->reset_timings();
+  return OCR_OK;
+}
+int ocr_rec_timing_report(ocr_rec* h, char* buf, size_t cap) {
+  if (!h || !buf) return fail(OCR_ERR_ARG, "null argument");
+  SrvNet* srv = h->s.srv();
+  if (!srv) return fail(OCR_ERR_ARG, "launch timing of a recognizer handle: the server recognizer only");
+  size_t off = 0;
+  for (auto& kv : srv->timings()) {
+    int n = snprintf(buf + off, cap > off ? cap - off : 0, "%s %.6f %ld %.0f %.0f\n", kv.first.c_str(), kv.second.ms, kv.second.count,
+                     kv.second.flops, kv.second.bytes);
+    if (n < 0 || off + n >= cap) return fail(OCR_ERR_CAPACITY, "report buffer too small");
+    off += n;
+  }
+  if (off < cap) buf[off] = 0;
+  return OCR_OK;
+}
 
 }  // extern "C"

@@ -145,8 +145,12 @@ struct PipeWorker {
       return d.run_device(base + g.off, img_bytes, row, g.rows, g.cols, g.count, boxes.data() + (size_t)g.first * kCap * 8, kCap,
                           nbox.data() + g.first, nullptr, e, probs ? probs + g.prob_off : nullptr);
     };
-    const int lanes = (int)std::min<size_t>((size_t)det_lanes, groups.size());
-    if (groups.size() > 1 && det_ragged) {
+    // A server detector (arch.txt: srv_det) has no ragged launch list (DetStage::mixed_net refuses it) and never gets a
+    // further instance: each one would load, bind and tune another ResNet50.  Its size groups run one after another on
+    // the chain's one detector, whatever OCR_DET_RAGGED and OCR_DET_LANES say.
+    const bool srv_det = det.srv() != nullptr;
+    const int lanes = srv_det ? 1 : (int)std::min<size_t>((size_t)det_lanes, groups.size());
+    if (groups.size() > 1 && det_ragged && !srv_det) {
       // MIXED sizes (round 3): ONE detector network pass over all size groups (every image keeps its own size inside a
       // ragged launch: Net::run_ragged_images) instead of a latency-bound pass per distinct size; only BoxesFromBitmap
       // still runs per group, dealt over the detector lanes.  Chunks bound the activation arena (~64 Mpixel of

@@ -52,8 +52,9 @@ struct GemmArgs {
   int res_up = 0;
   int act = SACT_NONE;
   int out_f32 = 0;
-  // CTC head (f32-output launches): instead of writing the logits, every workgroup leaves per output row ONE partial of its column
-  // tile - (max logit, sum of exp(logit - max), index of the first maximum) as 4 floats at ctc_part[(row * ctc_slots + n0 / 64) * 4] -
+  // CTC head (f32-output launches): instead of writing the logits, every workgroup leaves per output row one partial per 64 columns
+  // of its tile - (max logit, sum of exp(logit - max), index of the first maximum) as 4 floats at ctc_part[(row * ctc_slots + n / 64) * 4],
+  // formed in one order whatever the tile shape (so a row's result does not depend on the tile configuration) -
   // which launch_ctc_reduce folds into the row's arg max and its softmax probability: the logits (2.2 GB per 1024 lines) never exist
   // halo form only: the input is the CONCATENATION of cat_n 64-channel tensors, source j nearest-upsampled by 2^cat_sh[j] (the DB
   // neck's `concat up=8,4,2,1` in front of the head conv): channel tile j of the K order (channel tile, tap) IS source j, so the

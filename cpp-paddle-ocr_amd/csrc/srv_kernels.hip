@@ -452,13 +452,16 @@ __global__ void __launch_bounds__(64 * WM * WN) srv_gemm_kernel(const GemmArgs a
   // executes a wave's instructions in order, no barrier inside.
   if constexpr (HALF) {
     if (ctc_regs) {
-      // ---- CTC head (GemmArgs::ctc_part): no logits leave the workgroup.  A lane folds the 16 TN logits it holds of its row (bias added;
-      // columns past Ncols do not exist) into (max, first arg max, sum of exp(x - max)), its half-wave partner adds the other half, the
-      // WN waves of a pixel row meet in LDS, and one lane per row writes the column tile's partial.  Big tiles (256 x 256) may run this:
-      // nothing is staged
+      // ---- CTC head (GemmArgs::ctc_part): no logits leave the workgroup.  The partial of a row over 64 columns is formed in ONE order,
+      // whatever the tile: a lane folds the 16 logits it holds of a 32-column block (bias added; columns past Ncols do not exist;
+      // ascending registers) into (max, first arg max, sum of exp(x - max)), its half-wave partner adds the block's other 16 columns
+      // (lower half first), the blocks meet in LDS and a thread per (row, 64 columns) folds the even block with the odd one.  The tile
+      // shape - columns per wave, waves per row, BN - decides only who does it: a line's probability does not depend on the tile that
+      // tune() picked for the launch's batch size.  Big tiles (256 x 256) may run this: nothing is staged
       constexpr float L2E = 1.44269504088896341f;
       __syncthreads();
-      float* const part = (float*)smem;  // [wave][j][row r] x (max, sum, arg max, -)
+      float* const part = (float*)smem;  // [32-column block of the tile][pixel row of the tile] x (max, sum, arg max, -): BM * BN / 2 bytes <= a stage
+      static_assert((unsigned)(BM * (BN / 32) * 16) <= STG && BN % 64 == 0, "the blocks' partials fit the ring's first stage; whole 64-column slots");
       auto fold = [&](float& mx, float& sum, int& mi, float om, float os, int oi) __attribute__((always_inline)) {
         const float M2 = fmaxf(mx, om);
         const float sa = mx == -INFINITY ? 0.f : sum * __builtin_amdgcn_exp2f((mx - M2) * L2E);
@@ -469,12 +472,12 @@ __global__ void __launch_bounds__(64 * WM * WN) srv_gemm_kernel(const GemmArgs a
       };
 #pragma unroll
       for (int j = 0; j < TM; ++j) {
-        float mx = -INFINITY, sum = 0.f;
-        int mi = 0x7fffffff;
         // (the eight swaps of the storing epilogue first: the prefetched bias vectors are laid out for its chunks - registers 8 c + e of
         // block i = columns 32 i + 16 c + 8 h + e, ascending in (i, c, e))
 #pragma unroll
         for (int i = 0; i < TN; ++i) {
+          float mx = -INFINITY, sum = 0.f;
+          int mi = 0x7fffffff;
           f16x& A = acc[i][j];
           float a0 = A[0], a1 = A[1], a2 = A[2], a3 = A[3], a4 = A[4], a5 = A[5], a6 = A[6], a7 = A[7];
           float b0 = A[8], b1 = A[9], b2 = A[10], b3 = A[11], b4 = A[12], b5 = A[13], b6 = A[14], b7 = A[15];
@@ -495,40 +498,34 @@ __global__ void __launch_bounds__(64 * WM * WN) srv_gemm_kernel(const GemmArgs a
               if (v > mx) { mx = v; mi = n + e; }  // (ascending columns within the lane: the first maximum stays)
             }
           }
-        }
-        if (mx != -INFINITY) {
+          if (mx != -INFINITY) {
 #pragma unroll
-          for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) sum += __builtin_amdgcn_exp2f((acc[i][j][q] - mx) * L2E);
+            for (int q = 0; q < 16; ++q) sum += __builtin_amdgcn_exp2f((A[q] - mx) * L2E);
+          }
+          {
+            float am = mx, bm = mx, as = sum, bs = sum;
+            float ai = __int_as_float(mi), bi = ai;  // the other half-wave's lanes hold the same rows' other columns of the block
+            asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3\n\tv_permlane32_swap_b32 %4, %5\n\ts_nop 1"
+                         : "+v"(am), "+v"(bm), "+v"(as), "+v"(bs), "+v"(ai), "+v"(bi));
+            // after the swap a lane of half 0 holds (its own, the partner's) in (a, b), a lane of half 1 (the partner's, its own)
+            const float om = h ? am : bm, os = h ? as : bs;
+            const int oi = __float_as_int(h ? ai : bi);
+            fold(mx, sum, mi, om, os, oi);
+          }
+          if (h == 0) *(f4v*)(part + ((wn * TN + i) * BM + wm * TM * 32 + j * 32 + r) * 4) = f4v{mx, sum, __int_as_float(mi), 0.f};
         }
-        {
-          float am = mx, bm = mx, as = sum, bs = sum;
-          float ai = __int_as_float(mi), bi = ai;  // the other half-wave's lanes hold the same rows' other columns
-          asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3\n\tv_permlane32_swap_b32 %4, %5\n\ts_nop 1"
-                       : "+v"(am), "+v"(bm), "+v"(as), "+v"(bs), "+v"(ai), "+v"(bi));
-          // after the swap a lane of half 0 holds (its own, the partner's) in (a, b), a lane of half 1 (the partner's, its own)
-          const float om = h ? am : bm, os = h ? as : bs;
-          const int oi = __float_as_int(h ? ai : bi);
-          fold(mx, sum, mi, om, os, oi);
-        }
-        if (h == 0) *(f4v*)(part + ((wave * TM + j) * 32 + r) * 4) = f4v{mx, sum, __int_as_float(mi), 0.f};
       }
       __syncthreads();
-      if (wn == 0 && h == 0) {
-#pragma unroll
-        for (int j = 0; j < TM; ++j) {
-          const long m = m0 + wm * TM * 32 + j * 32 + r;
-          f4v p4 = *(const f4v*)(part + (((wm * WN) * TM + j) * 32 + r) * 4);
-          float mx = p4[0], sum = p4[1];
-          int mi = __float_as_int(p4[2]);
-#pragma unroll
-          for (int w2 = 1; w2 < WN; ++w2) {
-            p4 = *(const f4v*)(part + (((wm * WN + w2) * TM + j) * 32 + r) * 4);
-            fold(mx, sum, mi, p4[0], p4[1], __float_as_int(p4[2]));
-          }
-          if (m < a.M) *(f4v*)(a.ctc_part + ((size_t)m * (size_t)a.ctc_slots + (size_t)(n0 >> 6)) * 4) = f4v{mx, sum, __int_as_float(mi), 0.f};
-        }
+      for (int idx = tid; idx < BM * (BN / 64); idx += NT) {
+        const int row = idx % BM, sl = idx / BM;  // (a row's two blocks of slot sl: columns n0 + 64 sl .. + 63)
+        f4v p4 = *(const f4v*)(part + ((2 * sl) * BM + row) * 4);
+        float mx = p4[0], sum = p4[1];
+        int mi = __float_as_int(p4[2]);
+        p4 = *(const f4v*)(part + ((2 * sl + 1) * BM + row) * 4);
+        fold(mx, sum, mi, p4[0], p4[1], __float_as_int(p4[2]));
+        const long m = m0 + row;
+        const int n = n0 + 64 * sl;
+        if (m < a.M && n < a.Ncols) *(f4v*)(a.ctc_part + ((size_t)m * (size_t)a.ctc_slots + (size_t)(n >> 6)) * 4) = f4v{mx, sum, __int_as_float(mi), 0.f};
       }
       return;
     }

@@ -49,7 +49,7 @@ class SrvNet {
   bool launch_info(int i, std::string& name, int& out, std::vector<int>& ins) const;
   bool run_launches(int first, int count, hipStream_t s, std::string& err);
   bool upload_logical(int tid, const float* host, size_t count, hipStream_t s, std::string& err);
-  // CTC mode of the LAST linear (f32 logits), f16 build: it leaves per-row partials in the output tensor's slot instead of the logits
+  // CTC mode of the LAST linear (f32 logits), f16 build: it leaves per-row partials (one per 64 columns, in one order for every tile) in the output tensor's slot instead of the logits
   // (GemmArgs::ctc_part); the caller folds them with srv::launch_ctc_reduce(tensor_ptr(output_tid()), rows, ctc_slots(), ctc_step(), ..)
   void set_ctc_partials(bool on) { if (on != ctc_) { ctc_ = on; bound_n_ = -1; } }
   bool ctc_partials() const { return ctc_ && half_ && ctc_slots_ > 0; }

@@ -769,7 +769,7 @@ bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
       const int cfg = tune(a, lname, s);
       if (cfg < 0) { err = std::string("no tile configuration runs ") + lname; return false; }
       L.name = lname + "[" + srv::gemm_config_name(cfg) + "]";
-      if (ctc_here) { ctc_slots_ = a.ctc_slots; ctc_step_ = std::max(1, srv::gemm_config_bn(cfg) / 64); }
+      if (ctc_here) { ctc_slots_ = a.ctc_slots; ctc_step_ = 1; }  // (a partial per 64 columns, whatever the tile: the fold does not depend on cfg)
       const double klog = (double)a.KH * a.KW * in.c;
       L.flops = 2.0 * (double)a.M * klog * (double)op.ncols;
       double in_bytes = (double)in.bytes(half_);

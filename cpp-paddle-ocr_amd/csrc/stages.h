@@ -180,7 +180,20 @@ class RecStage {
   // tap: the logits row behind step `step` of line `index` of the last run_chars(topk > 0) with want_taps (C floats)
   int logits_row(int index, int step, float* out, size_t cap_floats, std::string& err);
   bool want_taps = true;
-  int max_lines_per_launch = 4096;  // bounds the activation arena of one launch: this many 48x320 lines' pixels (~1.2 MB each)
+  // Lines per network launch; a longer call is cut into several (rec_plan::plan_slots; ocr_rec_set_launch_lines for tests).
+  // Mobile recognizer: bounds the activation arena of one launch - this many 48x320 lines' pixels (~1.2 MB each).
+  // Server recognizer (create() sets kSrvLinesPerLaunch): every tensor of a launch is read through one buffer descriptor, which
+  // spans less than 0xfffffff0 bytes (srv_kernels.hip, launch_gemm / launch_mlp: "tensor beyond the 4 GB ...").  The largest
+  // tensor of srv_rec.plan per 48 x 320 line is an MLP's hidden one in the first stage, [12][80][768] = 737 280 elements
+  // (tensors 8, 15, 22; next: qkv [12][80][576], the f32 logits [80][6632]) - 2 949 120 bytes in the f32 twin, 1 474 560 in the
+  // f16 build with every tensor materialised (keep_all, OCR_SRV_MLP=0; with the fused MLP it never exists and qkv's
+  // 1 105 920 bytes lead).  0xfffffff0 / 2 949 120 = 1456.3 lines: 1024 keeps every build and mode below the guard (3.02 GB),
+  // where 4096 lines passed it even in the f16 build (4096 x 1 105 920 = 4.5 GB).  This is arithmetic on the plan: no launch of more
+  // than a few lines has run in a test.  A call of more than 1024 lines binds a second batch size (the remainder), which is timed
+  // for its tiles like every new one (srv_net.hip, tune).
+  static constexpr int kSrvLinesPerLaunch = 1024;
+  static_assert((unsigned long long)kSrvLinesPerLaunch * (12 * 80 * 768) * sizeof(float) < 0xfffffff0ull, "a server launch passes the buffer-descriptor guard");
+  int max_lines_per_launch = 4096;
   const std::vector<std::string>& labels() const { return labels_; }
   hipStream_t stream() const { return stream_; }
   Net& net() { return net_; }

@@ -517,6 +517,7 @@ bool RecStage::create(const RecConfig& cfg, std::string& err, int& code) {
     if (!load_server_model_dir(cfg.model_dir, "srv_rec", w, err)) return false;
     srv_.reset(new SrvNet());
     if (!srv_->load(embedded_plan("srv_rec"), w, cfg.precision == "fp16", err)) return false;
+    max_lines_per_launch = kSrvLinesPerLaunch;  // (stages.h: no tensor of a launch reaches the 4 GB a buffer descriptor spans)
     {  // the pipeline needs arg max and its probability, never the logits: the CTC head in partial mode (f16 build; OCR_SRV_CTC=0: logits + one pass over them)
       static const bool ctc_on = [] { const char* e = getenv("OCR_SRV_CTC"); return !(e && e[0] == '0'); }();
       srv_ctc_ = ctc_on;

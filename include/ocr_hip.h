@@ -170,6 +170,15 @@ const char* ocr_rec_label(ocr_rec* h, int id);
 int ocr_rec_num_classes(ocr_rec* h);
 /* tap: per-step arg max / max prob of line `index` of the last run (T entries), and T */
 int ocr_rec_steps(ocr_rec* h, int index, int32_t* amax, float* pmax, int cap, int* T);
+/* self-test: at most n lines per recognizer launch from the next run on (a mobile recognizer: a launch's pixel budget is that of
+ * n lines of rec_img_h x max(rec_img_w, 320)).  A call is cut into as many launches as that takes; its results do not depend on
+ * the cut.  n < 1 is OCR_ERR_ARG and leaves the handle as it was.  No environment switch sets it; the default stays. */
+int ocr_rec_set_launch_lines(ocr_rec* h, int n);
+/* self-test, server recognizer only (OCR_ERR_ARG otherwise): HIP events around the network's launches (enable resets the rows), and one row per launch name,
+ * "name ms count flops bytes" - the format of ocr_net_timing_report.  A launch's name carries the shape it was bound to, and
+ * its count is the number of times it ran: what tells how many launches a call was cut into. */
+int ocr_rec_timing(ocr_rec* h, int enable);
+int ocr_rec_timing_report(ocr_rec* h, char* buf, size_t cap);
 
 
 /* ---------------------------------------------------------------- pipeline */

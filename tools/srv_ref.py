@@ -45,7 +45,7 @@ one rounding to f16 near zero).  Rounding points, per op kind:
       two-pass (argmax_softmax_kernel, ocr_expf = EXP_REL 4 u32 on the f32 difference): u32 D + 4 u32 + (ceil(C / 64) + 6) u32 + 2 u32
       one-pass (argmax_softmax_fast_kernel): per step of 256 columns a lane rescales once (exp2 4 + product 1) and adds 4 terms (4);
           each of the 6 butterfly folds is one rescale, one product, one addition (6): 3 u32 D + 9 u32 ceil(C / 256) + 36 u32 + 2 u32
-      fused head (the matrix kernel's ctc_part epilogue, then ctc_reduce_kernel; `ctc_head`): inside a tile of W columns a term takes
+      fused head (the matrix kernel's ctc_part epilogue, then ctc_reduce_kernel; `ctc_head`): inside a partial of W columns (64, whatever the tile) a term takes
           one exp2 (4), at most W additions and at most 6 cross-lane rescales (6 each); then the fold over n tiles:
           3 u32 D + 4 u32 + W u32 + 36 u32 + 6 u32 n + 2 u32
       fold of partials (ctc_reduce_kernel on given (m_s, sum_s)): 3 u32 max_s |m_s - M| + (4 + 2) u32 n_slots + 2 u32
