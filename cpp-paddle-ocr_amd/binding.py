@@ -75,6 +75,7 @@ EXPORTS = [
     "ocr_srv_net_create", "ocr_srv_net_destroy", "ocr_srv_net_forward", "ocr_srv_net_rerun", "ocr_srv_net_num_tensors", "ocr_srv_net_fetch",
     "ocr_srv_net_timing", "ocr_srv_net_timing_report", "ocr_srv_net_num_launches", "ocr_srv_net_launch_info", "ocr_srv_net_run_launches",
     "ocr_srv_net_upload", "ocr_srv_net_set_ctc", "ocr_srv_net_ctc_tail",
+    "ocr_srv_net_create_plan", "ocr_srv_net_set_config", "ocr_srv_gemm_num_configs", "ocr_srv_gemm_config_name", "ocr_srv_gemm_config_bn",
 ]
 
 
@@ -154,8 +155,20 @@ class SrvNet:
     """raw taps of a server network (BASELINE configs[4]; hand-written plans, seeded weights): kind "det" | "rec" """
 
     def __init__(self, kind, precision="fp16", model_dir=None, device=0):
+        L = self._lib()
+        if model_dir is None:
+            root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+            model_dir = os.path.join(root, "models_server", kind)
+        self.h = C.c_void_p()
+        check(L.ocr_srv_net_create(kind.encode(), model_dir.encode(), device, precision.encode(), C.byref(self.h)))
+        self.shape = None
+
+    @staticmethod
+    def _lib():
         L = lib()
         L.ocr_srv_net_create.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
+        L.ocr_srv_net_create_plan.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
+        L.ocr_srv_net_set_config.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ocr_srv_net_destroy.argtypes = [C.c_void_p]
         L.ocr_srv_net_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.ocr_srv_net_rerun.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -167,19 +180,49 @@ class SrvNet:
         L.ocr_srv_net_launch_info.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
         L.ocr_srv_net_run_launches.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.ocr_srv_net_upload.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-        if model_dir is None:
-            root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-            model_dir = os.path.join(root, "models_server", kind)
+        return L
+
+    @classmethod
+    def from_plan(cls, plan, params_path, precision="fp16", device=0):
+        """test hook: a network on the caller's plan text and parameter file (tools/synth_weights.py's .pdiparams format, records =
+        the plan's `# param` names in sorted order).  OcrError.code tells a bad plan (-1) from a missing parameter (-2)"""
+        L = cls._lib()
+        self = cls.__new__(cls)
         self.h = C.c_void_p()
-        check(L.ocr_srv_net_create(kind.encode(), model_dir.encode(), device, precision.encode(), C.byref(self.h)))
         self.shape = None
+        rc = L.ocr_srv_net_create_plan(None if plan is None else plan.encode(), None if params_path is None else os.fsencode(params_path),
+                                       device, precision.encode(), C.byref(self.h))
+        if rc != 0:
+            self.h = None
+            _raise(L, rc, None)
+        return self
+
+    @staticmethod
+    def configs():
+        """the GEMM family's tile configurations, from the library: [(id, name, column-tile width)]"""
+        L = lib()
+        L.ocr_srv_gemm_config_name.restype = C.c_char_p
+        L.ocr_srv_gemm_config_name.argtypes = [C.c_int]
+        L.ocr_srv_gemm_config_bn.argtypes = [C.c_int]
+        return [(i, L.ocr_srv_gemm_config_name(i).decode(), L.ocr_srv_gemm_config_bn(i)) for i in range(L.ocr_srv_gemm_num_configs())
+                if L.ocr_srv_gemm_config_name(i)]
+
+    def set_config(self, cfg, strict=True):
+        """test hook: every GEMM launch of this net on tile configuration `cfg` (-1: the default choice); the next forward re-binds.
+        strict: a launch the configuration cannot run makes that forward raise (OcrError.code -1) instead of falling back"""
+        L = lib()
+        rc = L.ocr_srv_net_set_config(self.h, cfg, 1 if strict else 0)
+        if rc != 0:
+            _raise(L, rc, None)
 
     def forward(self, x, keep_all=False):
         x = np.ascontiguousarray(x, dtype=np.float32)
         n, h, w, c = x.shape
         assert c == 3
         self.shape = (n, h, w)
-        check(lib().ocr_srv_net_forward(self.h, x.ctypes.data, n, h, w, 1 if keep_all else 0))
+        rc = lib().ocr_srv_net_forward(self.h, x.ctypes.data, n, h, w, 1 if keep_all else 0)
+        if rc != 0:
+            _raise(lib(), rc, None)
         return self.fetch(-1)
 
     def rerun(self, iters=1):

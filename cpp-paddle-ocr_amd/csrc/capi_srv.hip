@@ -77,6 +77,37 @@ int ocr_srv_net_create(const char* kind, const char* model_dir, int device_id, c
   return OCR_OK;
 }
 
+// test tap (tests/test_gpu_srv_gemm.py): ocr_srv_net_create on the CALLER's plan text and parameter file - the plan's `# param` lines
+// name the records of the .pdiparams file (tools/synth_weights.py writes that format), in sorted order
+int ocr_srv_net_create_plan(const char* plan_text, const char* params_path, int device_id, const char* precision, ocr_srv_net** out) {
+  if (!plan_text || !params_path || !out || !precision) return fail(OCR_ERR_ARG, "null argument");
+  const bool half = !strcmp(precision, "fp16");
+  if (!half && strcmp(precision, "fp32")) return fail(OCR_ERR_ARG, "precision must be fp16 or fp32 (the parity twin)");
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  WeightMap w;
+  std::string err;
+  if (!file_exists(params_path)) return fail(OCR_ERR_MODEL, std::string("No parameter file ") + params_path);
+  if (!pdiparams_read(params_path, srv_param_names(plan_text), w, err)) return fail(OCR_ERR_MODEL, err);
+  std::unique_ptr<ocr_srv_net> h(new ocr_srv_net());
+  h->device = device_id;
+  if (!h->net.load(plan_text, w, half, err)) return fail(err.rfind("server plan:", 0) == 0 ? OCR_ERR_ARG : OCR_ERR_MODEL, err);
+  CAPI_HIP(g_stream_create(&h->stream));
+  *out = h.release();
+  return OCR_OK;
+}
+
+// test tap: SrvNet::set_config - every GEMM launch of this handle on tile configuration `cfg` (-1: the default choice again)
+int ocr_srv_net_set_config(ocr_srv_net* h, int cfg, int strict) {
+  if (!h) return fail(OCR_ERR_ARG, "null handle");
+  if (cfg < -1 || cfg >= srv::gemm_num_configs() || (cfg >= 0 && srv::gemm_config_bn(cfg) == 0)) return fail(OCR_ERR_ARG, "no such tile configuration: " + std::to_string(cfg));
+  h->net.set_config(cfg, strict != 0);
+  return OCR_OK;
+}
+int ocr_srv_gemm_num_configs(void) { return srv::gemm_num_configs(); }
+const char* ocr_srv_gemm_config_name(int cfg) { return cfg >= 0 && cfg < srv::gemm_num_configs() && srv::gemm_config_bn(cfg) ? srv::gemm_config_name(cfg) : nullptr; }
+int ocr_srv_gemm_config_bn(int cfg) { return cfg >= 0 && cfg < srv::gemm_num_configs() ? srv::gemm_config_bn(cfg) : 0; }
+
 void ocr_srv_net_destroy(ocr_srv_net* h) {
   if (!h) return;
   (void)rt_set_device(h->device);
@@ -99,7 +130,7 @@ int ocr_srv_net_forward(ocr_srv_net* h, const float* x, int N, int H, int W, int
   CAPI_HIP(hipMemcpyAsync(h->x_dev, x, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   h->net.set_keep_all(keep_all != 0);
   std::string err;
-  if (!h->net.run(h->x_dev, N, H, W, h->stream, err)) return fail(OCR_ERR_DEVICE, err);
+  if (!h->net.run(h->x_dev, N, H, W, h->stream, err)) return fail(h->net.refused() ? OCR_ERR_ARG : OCR_ERR_DEVICE, err);  // (a strict set_config's refusal)
   CAPI_HIP(g_stream_sync(h->stream));
   h->net.collect_timings();
   return OCR_OK;

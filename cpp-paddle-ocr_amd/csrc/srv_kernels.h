@@ -75,8 +75,9 @@ struct GemmArgs {
 int gemm_num_configs();       // configuration ids run 0 .. gemm_num_configs() - 1; gemm_config_ok refuses an unused one
 int gemm_config_bn(int cfg);  // column-tile width of a configuration (the CTC partials' slot step is bn / 64)
 const char* gemm_config_name(int cfg);
-// can tile configuration `cfg` run this problem? (shape divisibility, LDS attribute) - asked at bind time
-bool gemm_config_ok(const GemmArgs& a, bool half, int cfg);
+// can tile configuration `cfg` run this problem? (shape divisibility, LDS attribute) - asked at bind time; why: the dispatch's own
+// reason when it cannot
+bool gemm_config_ok(const GemmArgs& a, bool half, int cfg, std::string* why = nullptr);
 bool launch_gemm(const GemmArgs& a, bool half, int cfg, hipStream_t s, std::string& err);
 
 // SVTR's MLP in one launch (f16 build): y = x + fc2(gelu(fc1(x) + b1)) + b2, x / y [M][C] f16, the weight images of the two linears

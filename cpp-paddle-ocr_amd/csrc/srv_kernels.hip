@@ -1028,9 +1028,11 @@ static bool gemm_dispatch(const GemmArgs& a, bool half, int cfg, hipStream_t s, 
   err = "no such tile configuration";
   return false;
 }
-bool gemm_config_ok(const GemmArgs& a, bool half, int cfg) {
+bool gemm_config_ok(const GemmArgs& a, bool half, int cfg, std::string* why) {
   std::string e;
-  return gemm_dispatch(a, half, cfg, nullptr, true, e);
+  const bool ok = gemm_dispatch(a, half, cfg, nullptr, true, e);
+  if (!ok && why) *why = e;
+  return ok;
 }
 bool launch_gemm(const GemmArgs& a, bool half, int cfg, hipStream_t s, std::string& err) { return gemm_dispatch(a, half, cfg, s, false, err); }
 

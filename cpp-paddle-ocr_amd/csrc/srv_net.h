@@ -55,6 +55,11 @@ class SrvNet {
   bool ctc_partials() const { return ctc_ && half_ && ctc_slots_ > 0; }
   int ctc_slots() const { return ctc_slots_; }
   int ctc_step() const { return ctc_step_; }
+  // test tap: the tile configuration of every GEMM launch of this net (cfg < 0: the default choice - OCR_SRV_CFG, the tune file, the
+  // heuristic or the timing loop).  The next run re-binds and no earlier choice is kept.  strict: a launch that gemm_config_ok refuses
+  // under `cfg` fails the bind (refused() then tells it from a device failure) instead of falling back to the default choice
+  void set_config(int cfg, bool strict) { cfg_ = cfg; strict_ = strict; bound_n_ = -1; tuned_.clear(); }
+  bool refused() const { return refused_; }
   void enable_timing(bool on) { timing_ = on; }
   const std::map<std::string, KernelTiming>& timings() const { return timings_; }
   void reset_timings() { timings_.clear(); }
@@ -97,7 +102,7 @@ class SrvNet {
   bool prepare_op(Op& op, const WeightMap& w, std::string& err);
   bool prepare_ln_fold(Op& fc1, const Op& ln, const WeightMap& w, std::string& err);
   bool bind(int N, int H, int W, hipStream_t s, std::string& err);
-  int tune(const srv::GemmArgs& a, const std::string& key, hipStream_t s);
+  int tune(const srv::GemmArgs& a, const std::string& key, hipStream_t s, std::string& refusal);
   void* upload_bytes(const void* p, size_t n);
   const float* upload_f32(const std::vector<float>& v);
 
@@ -105,6 +110,8 @@ class SrvNet {
   int ntensors_ = 0, out_tid_ = -1;
   bool half_ = true, keep_all_ = false, timing_ = false, ctc_ = false;
   int ctc_slots_ = 0, ctc_step_ = 0;
+  int cfg_ = -1;                           // set_config
+  bool strict_ = false, refused_ = false;
   std::vector<void*> dev_allocs_;
   std::vector<SrvTensor> tensors_;
   std::vector<Launch> launches_;

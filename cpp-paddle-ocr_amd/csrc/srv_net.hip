@@ -301,6 +301,28 @@ bool SrvNet::prepare_ln_fold(Op& fc1, const Op& ln, const WeightMap& W, std::str
 bool SrvNet::load(const char* plan_text, const WeightMap& weights, bool half, std::string& err) {
   half_ = half;
   if (!parse(plan_text, err)) return false;
+  {  // every tensor an op reads is the input or written by an op before it
+    std::vector<char> written(ntensors_ + 1, 0);
+    written[0] = 1;
+    auto reads = [&](int t) {
+      if (t >= 0 && t <= ntensors_ && written[t]) return true;
+      err = "server plan: tensor " + std::to_string(t) + " is read before it is written";
+      return false;
+    };
+    for (const Op& op : ops_) {
+      if (op.kind == "concat") {
+        if (op.ins.empty() || op.ins.size() != op.ups.size()) { err = "server plan: concat needs one up factor per source"; return false; }
+        for (int t : op.ins)
+          if (!reads(t)) return false;
+      } else if (!reads(op.geti("i", -1))) return false;
+      for (const Stage& st : op.ep)
+        if ((st.kind == "addt" || st.kind == "addup") && !reads(st.tid)) return false;
+      if (op.kind == "output") continue;
+      const int o = op.geti("o", -1);
+      if (o <= 0 || o >= ntensors_) { err = "server plan: op writes tensor " + std::to_string(o) + " of " + std::to_string(ntensors_); return false; }
+      written[o] = 1;
+    }
+  }
   for (Op& op : ops_)
     if (!prepare_op(op, weights, err)) return false;
   for (size_t oi = 0; half_ && oi + 1 < ops_.size(); ++oi) {
@@ -335,7 +357,12 @@ std::map<std::string, int>& tune_file_cache() {
 }
 }  // namespace
 
-int SrvNet::tune(const srv::GemmArgs& a, const std::string& key, hipStream_t s) {
+int SrvNet::tune(const srv::GemmArgs& a, const std::string& key, hipStream_t s, std::string& refusal) {
+  if (cfg_ >= 0) {  // set_config: before the environment's, never written to the tune file
+    std::string why;
+    if (srv::gemm_config_ok(a, half_, cfg_, &why)) return cfg_;
+    if (strict_) { refusal = why.empty() ? "refused" : why; return -1; }
+  }
   auto it = tuned_.find(key);
   if (it != tuned_.end()) return it->second;
   const std::string fkey = std::string(half_ ? "fp16 " : "fp32 ") + key;
@@ -403,6 +430,7 @@ int SrvNet::tune(const srv::GemmArgs& a, const std::string& key, hipStream_t s) 
 }
 
 bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
+  refused_ = false;
   launches_.clear();
   flops_ = bytes_ = 0;
   ctc_slots_ = ctc_step_ = 0;
@@ -766,7 +794,13 @@ bool SrvNet::bind(int N, int H, int W, hipStream_t s, std::string& err) {
       snprintf(nm, sizeof nm, "%zu.%s%dx%d_%d_%d_s%d%s@%dx%dx%d", oi, op.kind.c_str(), a.KH, a.KW, in.c, op.geti("cout"), a.SH * 10 + a.SW,
                op.res_tid >= 0 ? "_res" : "", ot.n, ot.h, ot.w);
       const std::string lname = std::string(nm) + (ctc_here ? "_ctc" : "") + (cat_in ? "_cat" : "");  // (also the tuning key: these forms have their own candidates)
-      const int cfg = tune(a, lname, s);
+      std::string why;
+      const int cfg = tune(a, lname, s, why);
+      if (cfg < 0 && !why.empty()) {
+        refused_ = true;
+        err = "op " + std::to_string(oi) + " (" + lname + "): tile configuration " + srv::gemm_config_name(cfg_) + " refused: " + why;
+        return false;
+      }
       if (cfg < 0) { err = std::string("no tile configuration runs ") + lname; return false; }
       L.name = lname + "[" + srv::gemm_config_name(cfg) + "]";
       if (ctc_here) { ctc_slots_ = a.ctc_slots; ctc_step_ = 1; }  // (a partial per 64 columns, whatever the tile: the fold does not depend on cfg)

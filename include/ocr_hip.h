@@ -719,6 +719,19 @@ int ocr_srv_net_num_launches(ocr_srv_net* h);
 int ocr_srv_net_launch_info(ocr_srv_net* h, int i, char* name, size_t name_cap, int* out_tid, int* in_tids, int in_cap, int* n_in);
 int ocr_srv_net_run_launches(ocr_srv_net* h, int first, int count);
 int ocr_srv_net_upload(ocr_srv_net* h, int tid, const float* data, size_t count);
+/* test taps for the GEMM family alone (tests/test_gpu_srv_gemm.py).  ocr_srv_net_create_plan: as ocr_srv_net_create on the CALLER's
+ * plan text and .pdiparams file (records = the plan's `# param` names in sorted order); a plan that does not parse or reads a
+ * tensor before it is written is OCR_ERR_ARG, a missing parameter OCR_ERR_MODEL.  ocr_srv_net_set_config: every GEMM launch of the
+ * handle on tile configuration `cfg` (-1: the default choice - OCR_SRV_CFG, the tune file, the heuristic or the timing loop - which
+ * also holds while nothing is set); the next forward re-binds.  strict != 0: a launch the configuration cannot run fails that
+ * forward with OCR_ERR_ARG and a message (op index, configuration name, the dispatch's reason) instead of falling back; the handle
+ * stays usable.  An id that names no configuration is OCR_ERR_ARG.  ocr_srv_gemm_*: the configuration table, read-only - ids run
+ * 0 .. num_configs - 1, an unused id has name NULL and column width 0. */
+int ocr_srv_net_create_plan(const char* plan_text, const char* params_path, int device_id, const char* precision, ocr_srv_net** out);
+int ocr_srv_net_set_config(ocr_srv_net* h, int cfg, int strict);
+int ocr_srv_gemm_num_configs(void);
+const char* ocr_srv_gemm_config_name(int cfg);
+int ocr_srv_gemm_config_bn(int cfg);
 
 /* self-tests / fault injection (tests): ocr_selftest_refuse_launch - a network launch whose name contains `substr` is
  * refused as if its launcher had rejected the shape (NULL or "" switches it off): the run must fail with OCR_ERR_DEVICE

@@ -210,6 +210,11 @@ class Ref:
         if k == "pool":
             return self.pool(op, t[gi(op, "i")], mut)
         if k == "concat":
+            if (mut or {}).get("concat_next_shift"):  # source j read at (y >> s, x >> s) with source j + 1's shift (clamped to its own extent)
+                oh, ow = t[op["ins"][-1]].shape[1] * op["ups"][-1], t[op["ins"][-1]].shape[2] * op["ups"][-1]
+                ups = op["ups"][1:] + op["ups"][-1:]
+                return np.concatenate([t[i][:, np.minimum(np.arange(oh) // u, t[i].shape[1] - 1)][:, :, np.minimum(np.arange(ow) // u, t[i].shape[2] - 1)]
+                                       for i, u in zip(op["ins"], ups)], -1), None
             return np.concatenate([np.repeat(np.repeat(t[i], u, 1), u, 2) for i, u in zip(op["ins"], op["ups"])], -1), None
         if k == "ew":
             return self.addpos(op, t[gi(op, "i")])
@@ -224,8 +229,10 @@ class Ref:
             return U16 * np.abs(y) + SUB
         return U32 * np.abs(y)
 
-    def _product(self, op, x, W=None):
-        """(acc, S = sum |a w|, K) of a conv / linear / deconv on NHWC x; deconv: [N, H, W, 4, cout] by tap (dy, dx)"""
+    def _product(self, op, x, W=None, wrap_pad=False):
+        """(acc, S = sum |a w|, K) of a conv / linear / deconv on NHWC x; deconv: [N, H, W, 4, cout] by tap (dy, dx).  wrap_pad (a
+        mutation): a padding tap at the right or bottom border reads what lies at its address - pixel (iy W + ix) of the flattened
+        image, the neighbouring row or the next image - instead of zero"""
         W = op["W"] if W is None else W
         k = op["kind"]
         cin_s = (gi(op, "cin") + 7) // 8 * 8
@@ -242,6 +249,12 @@ class Ref:
         kh, kw, sh, sw, ph, pw = (gi(op, q) for q in ("kh", "kw", "sh", "sw", "ph", "pw"))
         n, h, w, c = x.shape
         xp = np.pad(x, ((0, 0), (ph, ph), (pw, pw), (0, 0)))
+        if wrap_pad:
+            flat = np.concatenate([x.reshape(-1, c), np.zeros(((ph + 1) * w + pw + 1, c))])
+            iy, ix = np.arange(-ph, h + ph)[:, None], np.arange(-pw, w + pw)[None, :]
+            past = ((ix >= w) & (iy >= 0) & (iy < h)) | ((iy >= h) & (ix >= 0) & (ix < w))
+            for k in range(n):
+                xp[k][past] = flat[(k * h * w + iy * w + ix)[past]]
         oh, ow = (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
         cols = np.empty((n, oh, ow, kh, kw, c))
         for y in range(kh):
@@ -257,11 +270,15 @@ class Ref:
         if mut.get("drop_granule_last_tap"):  # one 8-channel granule of the last tap of a k x k conv left out
             W = W.copy()
             W[:, 0:8, -1, -1] = 0.0
-        acc, S, K = self._product(op, t[gi(op, "i")], W)
+        if mut.get("drop_last_k_tile"):  # a linear's last K tile (64 stored channels, f16 build) left out
+            W = W.copy()
+            W[(-(-W.shape[0] // 64) - 1) * 64:] = 0.0
+        acc, S, K = self._product(op, t[gi(op, "i")], W, wrap_pad=bool(mut.get("pad_tap_from_neighbour")))
         b = op["b"]
         if op["kind"] == "deconv":  # taps (dy, dx) to pixels (2y + dy, 2x + dx)
             n, h, w, _, co = acc.shape
-            unt = lambda a: a.reshape(n, h, w, 2, 2, co).transpose(0, 1, 3, 2, 4, 5).reshape(n, 2 * h, 2 * w, co)
+            tp = (0, 1, 4, 2, 3, 5) if mut.get("deconv_swap_taps") else (0, 1, 3, 2, 4, 5)
+            unt = lambda a: a.reshape(n, h, w, 2, 2, co).transpose(*tp).reshape(n, 2 * h, 2 * w, co)
             acc, S = unt(acc), unt(S)
         s_, t_ = op["s"], op["t"]
         if s_ is not None:  # (f32 twin: the oracle's bias | scale | shift, here folded in f64)
@@ -276,6 +293,8 @@ class Ref:
             rt, up = op["res"]
             r = t[rt]
             if up > 1:
+                if mut.get("addup_shift_x"):  # the residual taken at (y / 2, x / 2 + 1) (the last column: its own)
+                    r = r[:, :, np.minimum(np.arange(r.shape[2]) + 1, r.shape[2] - 1)]
                 r = np.repeat(np.repeat(r, up, 1), up, 2)
             if mut.get("drop_res_last_row"):
                 r = r.copy()
@@ -283,6 +302,12 @@ class Ref:
             pre = pre + r
             ra = np.abs(r)
         y, aerr = _act(op["act"], pre, self.half)
+        if mut.get("last_row_from_previous") and y.reshape(-1, y.shape[-1]).shape[0] > 1:  # the last row of the last (partial) M tile
+            y = y.copy()
+            y.reshape(-1, y.shape[-1])[-1] = y.reshape(-1, y.shape[-1])[-2]
+        if mut.get("drop_last_column"):  # the last existing column written as a pad channel
+            y = y.copy()
+            y[..., -1] = 0.0
         f32_out = gi(op, "o") == self.out_tid
         ep = 2 * U32 * (np.abs(bb) + ra) if self.half else 4 * U32 * (np.abs(acc) + np.abs(bb) + ra)
         bound = ACT_L[op["act"]] * (K * U32 * S + ep) + aerr + self._out_round(y, f32_out)
@@ -478,6 +503,28 @@ def kind_of(op, launch_name=""):
 
 # the six errors the checker must reject (each local or small: what whole-network tolerances do not see)
 MUTATIONS = ("drop_res_last_row", "drop_last_bias", "window_shift_right_border", "drop_granule_last_tap", "ln_unbiased", "avg_include_pad")
+
+
+# seven errors of a tile edge or an index of the GEMM family (tests/srv_gemm_cases.py has an op for each; MUTATIONS above stays as it is)
+GEMM_MUTATIONS = ("last_row_from_previous", "drop_last_column", "drop_last_k_tile", "pad_tap_from_neighbour", "deconv_swap_taps", "addup_shift_x",
+                  "concat_next_shift")
+
+
+def gemm_mutation_sites(ref, mut):
+    """the ops of the plan a GEMM mutation changes (concat_next_shift: the concat ops - the conv behind one is then checked on the
+    mutated concatenation)"""
+    out = []
+    for op in ref.ops:
+        k = op["kind"]
+        gemm = k in ("conv", "linear") or (k == "deconv" and gi(op, "cout") > 1)
+        if ((mut in ("last_row_from_previous", "drop_last_column") and gemm and k != "deconv")
+                or (mut == "drop_last_k_tile" and k == "linear" and op["W"].shape[0] > 64)
+                or (mut == "pad_tap_from_neighbour" and k == "conv" and (gi(op, "ph") or gi(op, "pw")))
+                or (mut == "deconv_swap_taps" and k == "deconv" and gi(op, "cout") > 1)
+                or (mut == "addup_shift_x" and gemm and op["res"] is not None and op["res"][1] == 2)
+                or (mut == "concat_next_shift" and k == "concat" and len(op["ins"]) > 1)):
+            out.append(op)
+    return out
 
 
 # --------------------------------------------------------------------------------------------------------------- whole plan, torch
