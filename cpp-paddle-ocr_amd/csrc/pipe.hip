@@ -12,28 +12,42 @@
 #include "capi_common.h"
 #include "crop.h"
 #include "frame_kinds.h"
+#include "pipe_plan.h"
 #include "rot_groups.h"
 #include "stages.h"
 
 using namespace ocr;
+using pipe_plan::CharLists;
+using WordLists = std::vector<std::vector<ocr_word>>;  // per image, as IdLists: what a run hands to pipe_plan::emit
+using IdLists = std::vector<std::vector<int32_t>>;
 
 namespace {
 double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+
+// fn(i, message) for i = 0 .. n-1 side by side: 0 on the calling thread, every other on a thread of its own that lives for
+// this call; the code and the message of the first i that failed
+template <class F>
+int run_side_by_side(int n, std::string& err, F fn) {
+  std::vector<int> rcs(n, OCR_OK);
+  std::vector<std::string> errs(n);
+  std::vector<std::thread> th;
+  for (int i = 1; i < n; ++i) th.emplace_back([&, i] { rcs[i] = fn(i, errs[i]); });
+  rcs[0] = fn(0, errs[0]);
+  for (auto& t : th) t.join();
+  for (int i = 0; i < n; ++i)
+    if (rcs[i]) { err = errs[i]; return rcs[i]; }
+  return OCR_OK;
+}
 }  // namespace
 
-using CharLists = std::vector<std::vector<ocr_char>>;  // per image: one ocr_char per class id (ocr_pipe_run_chars)
-static int emit(const std::vector<std::vector<ocr_word>>& W, const std::vector<std::vector<int32_t>>& I, const std::vector<int>& order,
-                ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids, const CharLists* C = nullptr,
-                ocr_char* chars = nullptr);
-
-// One staged batch: host images copied into pinned memory and sent to the device on the copy stream, laid out size
-// group by size group (images of one size are contiguous: one det pass each).  Two slots = double buffering: batch
-// k+1 is staged (by another host thread) while batch k runs - SURVEY.md section 8e's "double-buffered pinned staging".
+// One staged batch: host images copied into pinned memory and sent to the device on the copy stream, laid out size group by
+// size group (pipe_plan::layout).  Two slots = double buffering: batch k+1 is staged (by another host thread) while batch k
+// runs - SURVEY.md section 8e's "double-buffered pinned staging".
 struct StageSlot {
-  struct Img { int rows, cols, orig; size_t off, prob_off; };
-  struct Group { int rows, cols, first, count; size_t off, prob_off; };
+  using Img = pipe_plan::Img;
+  using Group = pipe_plan::Group;
   PinnedStage pinned;  // free again once `ready` has passed (layout() waits for it: pinned.copied is never recorded)
   DevBuf<uint8_t> dev;
   DevBuf<float> probs;
@@ -131,231 +145,212 @@ struct PipeWorker {
     return OCR_OK;
   }
 
+  // What the phases of one run_images call share: the batch (or a chain's part of it), its text lines and what was read in them
+  struct Run {
+    uint8_t* base;
+    const std::vector<StageSlot::Img>& imgs;
+    const std::vector<StageSlot::Group>& groups;
+    const float* probs;
+    double* times;  // det | crops + cls | rec
+    std::string& err;
+    double t_last = now_ms();
+    void lap(int k) { const double t = now_ms(); times[k] += t - t_last; t_last = t; }
+    std::vector<LineSrc> lines;
+    std::vector<int> seg{0};    // lines seg[i] .. seg[i + 1] are image i's
+    std::vector<int> line_box;  // box index (within its image) of every line
+    std::vector<int> labels;    // per line: 1 = the classifier turned the crop by 180 degrees
+    static constexpr int max_len = 256;
+    std::vector<int32_t> ids, lens, csteps, cnsteps, geom;  // the recognizer's answers per line (ids, csteps, cnsteps, cprobs: x max_len)
+    std::vector<float> scores, cprobs;
+  };
+  int32_t* boxes_of(size_t img) { return boxes.data() + img * kCap * 8; }
+
   // ---- run: det per size group, then ONE cls pass and ONE rec pass over the crops of every image of the batch
   // (results are batch-invariant, so pooling lines across sizes changes nothing but the launch count)
   int run_images(uint8_t* base, const std::vector<StageSlot::Img>& imgs, const std::vector<StageSlot::Group>& groups, const float* probs,
-                 std::vector<std::vector<ocr_word>>& out_words, std::vector<std::vector<int32_t>>& out_ids, double times[3], std::string& err,
-                 CharLists* out_chars = nullptr) {
-    const int count = (int)imgs.size();
-    boxes.resize((size_t)count * kCap * 8);
+                 WordLists& out_words, IdLists& out_ids, double times[3], std::string& err, CharLists* out_chars = nullptr) {
+    const size_t count = imgs.size();
+    boxes.resize(count * kCap * 8);
     nbox.assign(count, 0);
-    double t0 = now_ms();
-    auto run_group = [&](DetStage& d, const StageSlot::Group& g, std::string& e) {
-      const size_t row = (size_t)g.cols * 3, img_bytes = row * g.rows;
-      return d.run_device(base + g.off, img_bytes, row, g.rows, g.cols, g.count, boxes.data() + (size_t)g.first * kCap * 8, kCap,
-                          nbox.data() + g.first, nullptr, e, probs ? probs + g.prob_off : nullptr);
-    };
+    Run r{base, imgs, groups, probs, times, err};
+    if (int rc = detect(r)) return rc;
+    r.lap(0);
+    if (int rc = crop_lines(r)) return rc;
+    out_words.assign(count, {}); out_ids.assign(count, {});
+    if (out_chars) out_chars->assign(count, {});
+    if (r.lines.empty()) return OCR_OK;
+    if (int rc = classify_and_turn(r)) return rc;
+    r.lap(1);
+    if (int rc = recognize(r, out_chars != nullptr)) return rc;
+    r.lap(2);
+    collect(r, out_words, out_ids, out_chars);
+    return OCR_OK;
+  }
+
+  int detect(Run& r) {
     // A server detector (arch.txt: srv_det) has no ragged launch list (DetStage::mixed_net refuses it) and never gets a
     // further instance: each one would load, bind and tune another ResNet50.  Its size groups run one after another on
     // the chain's one detector, whatever OCR_DET_RAGGED and OCR_DET_LANES say.
     const bool srv_det = det.srv() != nullptr;
-    const int lanes = srv_det ? 1 : (int)std::min<size_t>((size_t)det_lanes, groups.size());
-    if (groups.size() > 1 && det_ragged && !srv_det) {
-      // MIXED sizes (round 3): ONE detector network pass over all size groups (every image keeps its own size inside a
-      // ragged launch: Net::run_ragged_images) instead of a latency-bound pass per distinct size; only BoxesFromBitmap
-      // still runs per group, dealt over the detector lanes.  Chunks bound the activation arena (~64 Mpixel of
-      // detector input per launch, what a uniform batch of 64 x 960 x 960 needs).
-      std::vector<DetStage::MixedGroup> mg(groups.size());
-      std::vector<size_t> gpx(groups.size());
-      for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const auto& g = groups[gi];
-        mg[gi] = DetStage::MixedGroup{g.rows, g.cols, g.count, g.off, g.prob_off};
-        int rh = 0, rw = 0;
-        { float a, b; DetStage::resize_shape(g.rows, g.cols, det.cfg().limit_type, det.cfg().limit_side_len, rh, rw, a, b); }
-        gpx[gi] = (size_t)g.count * rh * rw;
-      }
-      static const size_t budget = [] { const char* e = getenv("OCR_DET_CHUNK_MP"); return (size_t)(e && atoi(e) > 0 ? atoi(e) : 64) << 20; }();
-      // chunk k+1's network pass is enqueued (on the other of two detector instances: own arena, own maps) BEFORE the
-      // host threads go through chunk k's per-group post-processing, so that the latency-bound post of one chunk runs
-      // under the dense kernels of the next
-      std::vector<std::pair<size_t, size_t>> chunks;
-      for (size_t g0 = 0; g0 < groups.size();) {
-        size_t g1 = g0, px = 0;
-        while (g1 < groups.size() && (g1 == g0 || px + gpx[g1] <= budget)) px += gpx[g1++];
-        chunks.emplace_back(g0, g1);
-        g0 = g1;
-      }
-      // Two network instances whenever there is more than one chunk - whatever OCR_DET_LANES says (the lanes only deal
-      // the per-group post-processing of the OCR_DET_RAGGED=net / dilation branch): chunk k+1's network is enqueued
-      // before chunk k's maps are post-processed, so it must not run on the instance that holds them.
-      const int want_extra = std::max(lanes - 1, chunks.size() > 1 ? 1 : 0);
-      while ((int)det_extra.size() < want_extra) {
-        int rc = add_det_extra(err);
-        if (rc) return rc;
-      }
-      const int ninst = 1 + (int)det_extra.size();
-      auto net_stage = [&](size_t k) -> DetStage& { return (k & 1) && ninst > 1 ? *det_extra[0] : det; };
-      auto start = [&](size_t k) {
-        return net_stage(k).mixed_net(base, mg.data() + chunks[k].first, (int)(chunks[k].second - chunks[k].first), probs, err);
-      };
-      int rc = start(0);
-      if (rc) return rc;
-      for (size_t k = 0; k < chunks.size(); ++k) {
-        const size_t g0 = chunks[k].first, g1 = chunks[k].second;
-        DetStage& src = net_stage(k);
-        const bool more = k + 1 < chunks.size();
-        if (more) {
-          // the next chunk's stage must have finished ITS previous chunk's post work (it was a lane two chunks ago: joined)
-          rc = start(k + 1);
-          if (rc) return rc;
-        }
-        if (!det.cfg().use_dilation && det_post_ragged) {
-          // every image of the chunk through ONE pass of the post-processing kernels (each takes its image's own map
-          // size), on the stage that ran the chunk's network; it ends with a stream synchronisation
-          const auto& gf = groups[g0];
-          rc = src.post_mixed(mg.data() + g0, (int)(g1 - g0), boxes.data() + (size_t)gf.first * kCap * 8, kCap, nbox.data() + gf.first, err);
-          if (rc) return rc;
-          src.collect_timings();
-          continue;
-        }
-        DetStage* busy = more ? &net_stage(k + 1) : nullptr;   // its stream is taken by the next chunk's network
-        std::vector<DetStage*> post;
-        for (int l = 0; l < ninst; ++l) {
-          DetStage* d = l == 0 ? &det : det_extra[l - 1].get();
-          if (d != busy) post.push_back(d);
-        }
-        const int np = (int)post.size();
-        std::vector<int> rcs(np, OCR_OK);
-        std::vector<std::string> errs(np);
-        auto lane_fn = [&](int l) {
-          DetStage& d = *post[l];
-          for (size_t gi = g0 + l; gi < g1; gi += np) {
-            const auto& g = groups[gi];
-            rcs[l] = d.post_group(src.mixed_prob((int)(gi - g0)), src.mixed_bitmap((int)(gi - g0)), mg[gi], &d == &src ? nullptr : src.done(),
-                                  boxes.data() + (size_t)g.first * kCap * 8, kCap, nbox.data() + g.first, errs[l]);
-            if (rcs[l]) return;
-          }
-        };
-        std::vector<std::thread> th;
-        for (int l = 1; l < np; ++l) th.emplace_back(lane_fn, l);
-        lane_fn(0);
-        for (auto& t : th) t.join();
-        for (int l = 0; l < np; ++l)
-          if (rcs[l]) { err = errs[l]; return rcs[l]; }
+    const int lanes = srv_det ? 1 : (int)std::min<size_t>((size_t)det_lanes, r.groups.size());
+    if (r.groups.size() > 1 && det_ragged && !srv_det) return detect_ragged(r, lanes);
+    return lanes <= 1 ? detect_serial(r) : detect_lanes(r, lanes);
+  }
+  int det_group(Run& r, DetStage& d, const StageSlot::Group& g, std::string& e) {  // one size group: one detector pass
+    const size_t row = (size_t)g.cols * 3, img_bytes = row * g.rows;
+    return d.run_device(r.base + g.off, img_bytes, row, g.rows, g.cols, g.count, boxes_of(g.first), kCap, nbox.data() + g.first, nullptr, e,
+                        r.probs ? r.probs + g.prob_off : nullptr);
+  }
+  int detect_serial(Run& r) {
+    for (const auto& g : r.groups)
+      if (int rc = det_group(r, det, g, r.err)) return rc;
+    return OCR_OK;
+  }
+  int detect_lanes(Run& r, int lanes) {  // OCR_DET_RAGGED=0: size group gi on detector instance gi % lanes, a host thread per instance
+    while ((int)det_extra.size() < lanes - 1)   // created on first use: single-size callers never pay for them
+      if (int rc = add_det_extra(r.err)) return rc;
+    // the clone was enqueued on lane 0's stream: the other lanes' streams must not read it earlier
+    if (g_stream_sync(det.stream()) != hipSuccess) { r.err = "det stream sync failed"; return OCR_ERR_DEVICE; }
+    return run_side_by_side(lanes, r.err, [&](int l, std::string& e) -> int {
+      DetStage& d = l == 0 ? det : *det_extra[l - 1];
+      for (size_t gi = l; gi < r.groups.size(); gi += lanes)
+        if (int rc = det_group(r, d, r.groups[gi], e)) return rc;
+      return OCR_OK;
+    });
+  }
+  // MIXED sizes (round 3): ONE detector network pass over all size groups (every image keeps its own size inside a
+  // ragged launch: Net::run_ragged_images) instead of a latency-bound pass per distinct size.  Chunks bound the activation
+  // arena (~64 Mpixel of detector input per launch, what a uniform batch of 64 x 960 x 960 needs).
+  int detect_ragged(Run& r, int lanes) {
+    const auto& groups = r.groups;
+    std::vector<DetStage::MixedGroup> mg(groups.size());
+    std::vector<size_t> gpx(groups.size());
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+      const auto& g = groups[gi];
+      mg[gi] = DetStage::MixedGroup{g.rows, g.cols, g.count, g.off, g.prob_off};
+      gpx[gi] = (size_t)g.count * pipe_plan::det_pixels(g.rows, g.cols, det.cfg().limit_type, det.cfg().limit_side_len);
+    }
+    static const size_t budget = [] { const char* e = getenv("OCR_DET_CHUNK_MP"); return (size_t)(e && atoi(e) > 0 ? atoi(e) : 64) << 20; }();
+    const std::vector<std::pair<size_t, size_t>> chunks = pipe_plan::det_chunks(gpx, budget);
+    // Two network instances whenever there is more than one chunk - whatever OCR_DET_LANES says (the lanes only deal
+    // the per-group post-processing of the OCR_DET_RAGGED=net / dilation branch): chunk k+1's network is enqueued (own
+    // arena, own maps) BEFORE chunk k's maps are post-processed, so that the latency-bound post of one chunk runs under the
+    // dense kernels of the next - and so it must not run on the instance that holds them.
+    const int want_extra = std::max(lanes - 1, chunks.size() > 1 ? 1 : 0);
+    while ((int)det_extra.size() < want_extra)
+      if (int rc = add_det_extra(r.err)) return rc;
+    auto net_stage = [&](size_t k) -> DetStage& { return (k & 1) && !det_extra.empty() ? *det_extra[0] : det; };
+    auto start = [&](size_t k) {
+      return net_stage(k).mixed_net(r.base, mg.data() + chunks[k].first, (int)(chunks[k].second - chunks[k].first), r.probs, r.err);
+    };
+    if (int rc = start(0)) return rc;
+    for (size_t k = 0; k < chunks.size(); ++k) {
+      const size_t g0 = chunks[k].first, g1 = chunks[k].second;
+      DetStage& src = net_stage(k);
+      const bool more = k + 1 < chunks.size();
+      // the next chunk's stage has finished ITS previous chunk's post work (it was a lane two chunks ago: joined)
+      if (more)
+        if (int rc = start(k + 1)) return rc;
+      if (!det.cfg().use_dilation && det_post_ragged) {
+        // every image of the chunk through ONE pass of the post-processing kernels (each takes its image's own map
+        // size), on the stage that ran the chunk's network; it ends with a stream synchronisation
+        const int first = groups[g0].first;
+        if (int rc = src.post_mixed(mg.data() + g0, (int)(g1 - g0), boxes_of(first), kCap, nbox.data() + first, r.err)) return rc;
+      } else {
+        if (int rc = post_on_lanes(r, mg, g0, g1, src, more ? &net_stage(k + 1) : nullptr)) return rc;
         // this chunk's maps are free again once its network stage is idle (its own post lane, if any, has synchronised;
         // when it was not a post lane the network pass itself must be over before the stage takes chunk k+2)
-        if (g_stream_sync(src.stream()) != hipSuccess) { err = "det stream sync failed"; return OCR_ERR_DEVICE; }
-        src.collect_timings();
+        if (g_stream_sync(src.stream()) != hipSuccess) { r.err = "det stream sync failed"; return OCR_ERR_DEVICE; }
       }
-    } else if (lanes <= 1) {
-      for (const auto& g : groups) {
-        int rc = run_group(det, g, err);
-        if (rc) return rc;
-      }
-    } else {
-      while ((int)det_extra.size() < lanes - 1) {   // created on first use: single-size callers never pay for them
-        int rc = add_det_extra(err);
-        if (rc) return rc;
-      }
-      // the clone above was enqueued on lane 0's stream: the other lanes' streams must not read it earlier
-      if (g_stream_sync(det.stream()) != hipSuccess) { err = "det stream sync failed"; return OCR_ERR_DEVICE; }
-      std::vector<int> rcs(lanes, OCR_OK);
-      std::vector<std::string> errs(lanes);
-      auto lane_fn = [&](int l) {
-        DetStage& d = l == 0 ? det : *det_extra[l - 1];
-        for (size_t gi = l; gi < groups.size(); gi += lanes) {
-          rcs[l] = run_group(d, groups[gi], errs[l]);
-          if (rcs[l]) return;
-        }
-      };
-      std::vector<std::thread> th;
-      for (int l = 1; l < lanes; ++l) th.emplace_back(lane_fn, l);
-      lane_fn(0);
-      for (auto& t : th) t.join();
-      for (int l = 0; l < lanes; ++l)
-        if (rcs[l]) { err = errs[l]; return rcs[l]; }
-    }
-    double t1 = now_ms();
-    times[0] += t1 - t0;
-    // crop rectangles: cv::boundingRect(points) & image rect (ocr_worker.cpp:245-258)
-    std::vector<LineSrc> lines;
-    std::vector<int> seg(1, 0);
-    std::vector<int> line_box;  // box index (within its image) of every line
-    line_plan.clear();
-    if (crop_mode == OCR_CROP_ROTATE) {
-      int rc = rotate_crops(base, imgs, lines, seg, line_box, err);
-      if (rc) return rc;
-    } else
-    for (int i = 0; i < count; ++i) {
-      const int rows = imgs[i].rows, cols = imgs[i].cols;
-      const size_t row = (size_t)cols * 3;
-      for (int j = 0; j < nbox[i]; ++j) {
-        const int32_t* b = &boxes[((size_t)i * kCap + j) * 8];
-        int x0 = b[0], x1 = b[0], y0 = b[1], y1 = b[1];
-        for (int k = 1; k < 4; ++k) {
-          x0 = std::min(x0, b[2 * k]); x1 = std::max(x1, b[2 * k]);
-          y0 = std::min(y0, b[2 * k + 1]); y1 = std::max(y1, b[2 * k + 1]);
-        }
-        const int ix0 = std::max(x0, 0), iy0 = std::max(y0, 0);
-        const int ix1 = std::min(x1 + 1, cols), iy1 = std::min(y1 + 1, rows);
-        if (ix1 - ix0 > 0 && iy1 - iy0 > 0) {
-          // `word.box = det_boxes[i]` pairs text k with box k of the image, even when an empty crop was
-          // skipped before it (reference quirk, ocr_worker.cpp:293-299) — kept.
-          line_box.push_back((int)lines.size() - seg.back());
-          lines.push_back(LineSrc{base + imgs[i].off, row, ix0, iy0, ix1 - ix0, iy1 - iy0});
-        }
-      }
-      seg.push_back((int)lines.size());
-    }
-    out_words.assign(count, {});
-    out_ids.assign(count, {});
-    if (out_chars) out_chars->assign(count, {});
-    if (lines.empty()) return OCR_OK;
-    std::vector<int> labels;  // per line: 1 = the classifier turned the crop by 180 degrees
-    if (cls) {
-      labels.resize(lines.size());
-      std::vector<float> scores(lines.size());
-      int rc = cls->run_lines(lines, labels.data(), scores.data(), err);
-      if (rc) return rc;
-      // rotate in request order, in place on the device copy (cv::rotate on ROI views aliasing the image)
-      std::vector<RotDesc> rd;
-      for (size_t k = 0; k < lines.size(); ++k)
-        if (labels[k] == 1) rd.push_back(RotDesc{const_cast<uint8_t*>(lines[k].img), lines[k].stride, lines[k].x, lines[k].y, lines[k].w, lines[k].h});
-      int rrc = rotate180_in_order(rd, rot_desc, rot_seg, cls->stream(), err);
-      if (rrc) return rrc;
-      if (g_stream_sync(cls->stream()) != hipSuccess) { err = "cls stream sync failed"; return OCR_ERR_DEVICE; }
-    }
-    double t2 = now_ms();
-    times[1] += t2 - t1;
-    const int max_len = 256;
-    std::vector<int32_t> ids(lines.size() * max_len);
-    std::vector<int> lens(lines.size());
-    std::vector<float> scores(lines.size());
-    std::vector<int32_t> csteps, cnsteps, geom;
-    std::vector<float> cprobs;
-    int rc;
-    if (out_chars) {
-      csteps.resize(ids.size()); cnsteps.resize(ids.size()); cprobs.resize(ids.size()); geom.resize(lines.size() * 3);
-      RecStage::CharOut co;
-      co.steps = csteps.data(); co.nsteps = cnsteps.data(); co.probs = cprobs.data(); co.geom = geom.data();
-      rc = rec.run_lines_chars(lines, seg, ids.data(), max_len, lens.data(), scores.data(), co, err);
-    } else {
-      rc = rec.run_lines(lines, seg, ids.data(), max_len, lens.data(), scores.data(), err);
-    }
-    if (rc) return rc;
-    times[2] += now_ms() - t2;
-    for (int i = 0; i < count; ++i) {
-      for (int k = seg[i]; k < seg[i + 1]; ++k) {
-        ocr_word w;
-        memcpy(w.box, &boxes[((size_t)i * kCap + line_box[k]) * 8], sizeof(w.box));
-        w.ids_off = (int32_t)out_ids[i].size();
-        w.ids_len = lens[k];
-        w.confidence = scores[k];
-        out_ids[i].insert(out_ids[i].end(), ids.begin() + (size_t)k * max_len, ids.begin() + (size_t)k * max_len + lens[k]);
-        out_words[i].push_back(w);
-        if (out_chars)
-          for (int j = 0; j < lens[k]; ++j) {  // the character's quad from the line's own geometry (crop.h, char_quad)
-            const size_t q = (size_t)k * max_len + j;
-            ocr_char ch;
-            ch.step = csteps[q]; ch.nsteps = cnsteps[q]; ch.prob = cprobs[q];
-            const LineSrc& L = lines[k];
-            char_quad(ch.step, ch.nsteps, geom[3 * k], geom[3 * k + 1], geom[3 * k + 2], L.w, L.h, !labels.empty() && labels[k] == 1,
-                      crop_mode == OCR_CROP_ROTATE ? &line_plan[k] : nullptr, L.x, L.y, imgs[i].rows, imgs[i].cols, ch.quad);
-            (*out_chars)[i].push_back(ch);
-          }
-      }
+      src.collect_timings();
     }
     return OCR_OK;
+  }
+  // BoxesFromBitmap of the groups [g0, g1) of a chunk whose network ran on `src`, group by group, dealt over every detector
+  // instance but `busy` (its stream is taken by the next chunk's network), a host thread per instance
+  int post_on_lanes(Run& r, const std::vector<DetStage::MixedGroup>& mg, size_t g0, size_t g1, DetStage& src, DetStage* busy) {
+    std::vector<DetStage*> post;
+    if (&det != busy) post.push_back(&det);
+    for (auto& d : det_extra)
+      if (d.get() != busy) post.push_back(d.get());
+    const int np = (int)post.size();
+    return run_side_by_side(np, r.err, [&](int l, std::string& e) -> int {
+      DetStage& d = *post[l];
+      for (size_t gi = g0 + l; gi < g1; gi += np) {
+        const auto& g = r.groups[gi];
+        if (int rc = d.post_group(src.mixed_prob((int)(gi - g0)), src.mixed_bitmap((int)(gi - g0)), mg[gi], &d == &src ? nullptr : src.done(),
+                                  boxes_of(g.first), kCap, nbox.data() + g.first, e))
+          return rc;
+      }
+      return OCR_OK;
+    });
+  }
+
+  // the text lines of every image: cv::boundingRect(points) & image rect (ocr_worker.cpp:245-258), or rotate_crops
+  int crop_lines(Run& r) {
+    line_plan.clear();
+    if (crop_mode == OCR_CROP_ROTATE) return rotate_crops(r.base, r.imgs, r.lines, r.seg, r.line_box, r.err);
+    std::vector<pipe_plan::RectLine> rl;
+    for (size_t i = 0; i < r.imgs.size(); ++i) {
+      const StageSlot::Img& im = r.imgs[i];
+      pipe_plan::rect_lines(boxes_of(i), nbox[i], im.rows, im.cols, rl);
+      for (const auto& l : rl) {
+        r.line_box.push_back(l.box);
+        r.lines.push_back(LineSrc{r.base + im.off, (size_t)im.cols * 3, l.x, l.y, l.w, l.h});
+      }
+      r.seg.push_back((int)r.lines.size());
+    }
+    return OCR_OK;
+  }
+
+  int classify_and_turn(Run& r) {
+    if (!cls) return OCR_OK;
+    r.labels.resize(r.lines.size());
+    std::vector<float> scores(r.lines.size());
+    if (int rc = cls->run_lines(r.lines, r.labels.data(), scores.data(), r.err)) return rc;
+    // rotate in request order, in place on the device copy (cv::rotate on ROI views aliasing the image)
+    std::vector<RotDesc> rd;
+    for (size_t k = 0; k < r.lines.size(); ++k) {
+      const LineSrc& L = r.lines[k];
+      if (r.labels[k] == 1) rd.push_back(RotDesc{const_cast<uint8_t*>(L.img), L.stride, L.x, L.y, L.w, L.h});
+    }
+    if (int rc = rotate180_in_order(rd, rot_desc, rot_seg, cls->stream(), r.err)) return rc;
+    if (g_stream_sync(cls->stream()) != hipSuccess) { r.err = "cls stream sync failed"; return OCR_ERR_DEVICE; }
+    return OCR_OK;
+  }
+
+  int recognize(Run& r, bool chars) {
+    const size_t n = r.lines.size();
+    r.ids.resize(n * Run::max_len); r.lens.resize(n); r.scores.resize(n);
+    if (!chars) return rec.run_lines(r.lines, r.seg, r.ids.data(), Run::max_len, r.lens.data(), r.scores.data(), r.err);
+    r.csteps.resize(r.ids.size()); r.cnsteps.resize(r.ids.size()); r.cprobs.resize(r.ids.size()); r.geom.resize(n * 3);
+    RecStage::CharOut co;
+    co.steps = r.csteps.data(); co.nsteps = r.cnsteps.data(); co.probs = r.cprobs.data(); co.geom = r.geom.data();
+    return rec.run_lines_chars(r.lines, r.seg, r.ids.data(), Run::max_len, r.lens.data(), r.scores.data(), co, r.err);
+  }
+
+  // words, class ids and (out_chars) character quads per image
+  void collect(const Run& r, WordLists& out_words, IdLists& out_ids, CharLists* out_chars) {
+    for (size_t i = 0; i < r.imgs.size(); ++i) {
+      for (int k = r.seg[i]; k < r.seg[i + 1]; ++k) {
+        const size_t at = (size_t)k * Run::max_len;
+        ocr_word w;
+        memcpy(w.box, boxes_of(i) + (size_t)r.line_box[k] * 8, sizeof(w.box));
+        w.ids_off = (int32_t)out_ids[i].size();
+        w.ids_len = r.lens[k];
+        w.confidence = r.scores[k];
+        out_ids[i].insert(out_ids[i].end(), r.ids.begin() + at, r.ids.begin() + at + r.lens[k]);
+        out_words[i].push_back(w);
+        for (int j = 0; out_chars && j < r.lens[k]; ++j) {  // the character's quad from the line's own geometry (crop.h, char_quad)
+          ocr_char ch;
+          ch.step = r.csteps[at + j]; ch.nsteps = r.cnsteps[at + j]; ch.prob = r.cprobs[at + j];
+          const LineSrc& L = r.lines[k];
+          char_quad(ch.step, ch.nsteps, r.geom[3 * k], r.geom[3 * k + 1], r.geom[3 * k + 2], L.w, L.h, !r.labels.empty() && r.labels[k] == 1,
+                    crop_mode == OCR_CROP_ROTATE ? &line_plan[k] : nullptr, L.x, L.y, r.imgs[i].rows, r.imgs[i].cols, ch.quad);
+          (*out_chars)[i].push_back(ch);
+        }
+      }
+    }
   }
 
   // crop_mode OCR_CROP_ROTATE: every box becomes its own perspective-rectified image
@@ -410,7 +405,6 @@ struct ocr_pipe {
   // owns the chip: what the per-kernel roofline figures of bench.py are measured with).
   std::vector<std::unique_ptr<PipeWorker>> extra;  // chains 2 .. phases
   int phases = 2;
-  int parts_per_chain = 1;
   int device = 0;
   StageSlot slots[2];
   hipStream_t copy_stream = nullptr;
@@ -422,11 +416,15 @@ struct ocr_pipe {
   // the two halves of one (no join per batch: what two free-running handles gained over one, without the second handle)
   DevBuf<uint8_t> work_chain[4];
   PipeWorker* worker(int c) { return c == 0 ? &w0 : (c >= 1 && c <= (int)extra.size() ? extra[c - 1].get() : nullptr); }
+  std::vector<PipeWorker*> workers() {  // every chain's
+    std::vector<PipeWorker*> ws{&w0};
+    for (auto& w : extra) ws.push_back(w.get());
+    return ws;
+  }
 
   ~ocr_pipe() { if (copy_stream) (void)hipStreamDestroy(copy_stream); }
 
-  // ---- stage: host images -> pinned -> device (asynchronous after the host copies)
-  // layout of a batch in a slot: stable order by (rows, cols), images of one size contiguous
+  // ---- stage: a slot takes the layout of a new batch (pipe_plan::layout) once its last upload has left the pinned buffer
   int layout(StageSlot& S, int count, const std::function<void(int, int&, int&)>& size_of, std::string& err) {
     if (!copy_stream && hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) != hipSuccess) { err = "hipStreamCreate failed"; return OCR_ERR_DEVICE; }
     if (!S.ready && hipEventCreateWithFlags(&S.ready, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return OCR_ERR_DEVICE; }
@@ -434,34 +432,14 @@ struct ocr_pipe {
     // from here to the end of stage() / stage_coded() the slot holds a half-written batch: a failure on the way must not
     // leave it runnable (a later ocr_pipe_run_staged would run the new layout over stale pixels)
     S.staged = false;
-    std::vector<int> order(count), rows(count), cols(count);
-    for (int i = 0; i < count; ++i) { order[i] = i; size_of(i, rows[i], cols[i]); }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return rows[a] != rows[b] ? rows[a] < rows[b] : cols[a] < cols[b]; });
-    const std::vector<StageSlot::Img> before = S.imgs;
-    S.imgs.clear();
-    S.groups.clear();
-    size_t off = 0, poff = 0;
-    for (int k = 0; k < count; ++k) {
-      const int r = rows[order[k]], c = cols[order[k]];
-      if (S.groups.empty() || S.groups.back().rows != r || S.groups.back().cols != c) {
-        off = (off + 255) & ~(size_t)255;
-        S.groups.push_back({r, c, k, 0, off, poff});
-      }
-      S.groups.back().count++;
-      int rh = 0, rw = 0;
-      { float a, b; DetStage::resize_shape(r, c, w0.det.cfg().limit_type, w0.det.cfg().limit_side_len, rh, rw, a, b); }
-      S.imgs.push_back({r, c, order[k], off, poff});
-      off += (size_t)r * c * 3;
-      poff += (size_t)rh * rw;
-    }
-    S.bytes = off;
-    S.prob_floats = poff;
+    std::vector<std::pair<int, int>> sizes(count);
+    for (int i = 0; i < count; ++i) size_of(i, sizes[i].first, sizes[i].second);
+    pipe_plan::Layout L = pipe_plan::layout(sizes, w0.det.cfg().limit_type, w0.det.cfg().limit_side_len);
     // probability maps attached to the slot (benchmark protocol) stay valid only while the layout is the same
-    bool same = before.size() == S.imgs.size();
-    for (size_t k = 0; same && k < before.size(); ++k)
-      same = before[k].rows == S.imgs[k].rows && before[k].cols == S.imgs[k].cols && before[k].orig == S.imgs[k].orig;
-    if (!same) S.has_probs = false;
-    if (!S.dev.ensure(off + 256, err)) return OCR_ERR_DEVICE;
+    if (!pipe_plan::same_layout(S.imgs, L.imgs)) S.has_probs = false;
+    S.imgs = std::move(L.imgs); S.groups = std::move(L.groups);
+    S.bytes = L.bytes; S.prob_floats = L.prob_floats;
+    if (!S.dev.ensure(S.bytes + 256, err)) return OCR_ERR_DEVICE;
     return OCR_OK;
   }
 
@@ -533,144 +511,78 @@ struct ocr_pipe {
     return OCR_OK;
   }
 
-  // ---- run: one chain, or several chains on as many parts of the batch
+  // ---- run: one chain, or several chains on as many parts of the batch (pipe_plan::split), each on its own host thread
   int run_images(uint8_t* base, const std::vector<StageSlot::Img>& imgs, const std::vector<StageSlot::Group>& groups, const float* probs,
-                 std::vector<std::vector<ocr_word>>& out_words, std::vector<std::vector<int32_t>>& out_ids, double times[3], std::string& err,
-                 CharLists* out_chars = nullptr) {
-    const int count = (int)imgs.size();
-    const int nchains = (int)std::min<size_t>(1 + extra.size(), (size_t)count);
-    if (nchains < 2) return w0.run_images(base, imgs, groups, probs, out_words, out_ids, times, err, out_chars);
-    // K parts, dealt round-robin to the chains (parts_per_chain > 1: a chain runs several smaller parts one after the
-    // other, so that the chains drift out of phase and the tail of the call is a part, not half a batch)
-    const int K = (int)std::min<size_t>((size_t)nchains * parts_per_chain, (size_t)count);
-    // parts: size groups dealt to the lightest part (pixels), a group cut where that part reaches its share of the batch
-    std::vector<std::vector<StageSlot::Img>> pi(K);
-    std::vector<std::vector<StageSlot::Group>> pg(K);
-    std::vector<std::vector<int>> gidx(K);  // layout index of a part's images
-    std::vector<size_t> load(K, 0);
-    auto give = [&](int p, const StageSlot::Group& g, int first, int n) {  // images first .. first+n-1 of group g
-      int rh = 0, rw = 0;
-      { float a, b; DetStage::resize_shape(g.rows, g.cols, w0.det.cfg().limit_type, w0.det.cfg().limit_side_len, rh, rw, a, b); }
-      StageSlot::Group ng = g;
-      ng.first = (int)pi[p].size();
-      ng.count = n;
-      ng.off = g.off + (size_t)first * g.rows * g.cols * 3;
-      ng.prob_off = g.prob_off + (size_t)first * rh * rw;
-      pg[p].push_back(ng);
-      for (int k = 0; k < n; ++k) { pi[p].push_back(imgs[g.first + first + k]); gidx[p].push_back(g.first + first + k); }
-      load[p] += (size_t)n * g.rows * g.cols;
-    };
-    size_t total = 0;
-    for (const auto& g : groups) total += (size_t)g.count * g.rows * g.cols;
-    const size_t share = (total + K - 1) / K;
-    for (const auto& g : groups) {
-      const size_t px = (size_t)g.rows * g.cols;
-      int first = 0;
-      while (first < g.count) {
-        const int p = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        const int left = g.count - first;
-        const size_t room = share > load[p] ? share - load[p] : 0;
-        int n = left;
-        if ((size_t)left * px > room + px / 2) n = (int)std::min<size_t>(left, std::max<size_t>(1, (room + px / 2) / px));
-        give(p, g, first, n);
-        first += n;
-      }
-    }
+                 WordLists& out_words, IdLists& out_ids, double times[3], std::string& err, CharLists* out_chars = nullptr) {
+    const size_t count = imgs.size();
+    const int K = (int)std::min(1 + extra.size(), count);
+    if (K < 2) return w0.run_images(base, imgs, groups, probs, out_words, out_ids, times, err, out_chars);
+    const std::vector<pipe_plan::Part> parts = pipe_plan::split(imgs, groups, K, w0.det.cfg().limit_type, w0.det.cfg().limit_side_len);
     // the clone was enqueued on worker 0's detector stream: the other workers' streams must not read it earlier
     if (g_stream_sync(w0.det.stream()) != hipSuccess) { err = "det stream sync failed"; return OCR_ERR_DEVICE; }
-    std::vector<std::vector<std::vector<ocr_word>>> W(K);
-    std::vector<std::vector<std::vector<int32_t>>> I(K);
-    std::vector<CharLists> Ch(K);
+    std::vector<WordLists> W(K); std::vector<IdLists> I(K); std::vector<CharLists> Ch(K);
     std::vector<std::array<double, 3>> t(K, std::array<double, 3>{0, 0, 0});
-    std::vector<int> rc(K, OCR_OK);
-    std::vector<std::string> errs(K);
-    auto chain = [&](int c) {  // parts c, c + nchains, ... on worker c
-      PipeWorker& w = c == 0 ? w0 : *extra[c - 1];
-      for (int p = c; p < K; p += nchains) {
-        if (pi[p].empty()) continue;
-        rc[p] = w.run_images(base, pi[p], pg[p], probs, W[p], I[p], t[p].data(), errs[p], out_chars ? &Ch[p] : nullptr);
-        if (rc[p]) return;
-      }
-    };
-    std::vector<std::thread> th;
     // (round 5: starting chain c a few milliseconds late - 3 .. 24 ms - so that one chain's matrix-bound kernels meet the other's
     // HBM-bound ones costs 2-11 %: 1282 -> 1257 / 1218 / 1177 / 1155 / 1140 img/s; what two free-running handles gain comes from
     // batches overlapping batches, not from a phase offset inside one)
-    for (int c = 1; c < nchains; ++c) th.emplace_back([&, c]() { (void)rt_set_device(device); chain(c); });
-    chain(0);
-    for (auto& x : th) x.join();
-    for (int p = 0; p < K; ++p)
-      if (rc[p]) { err = errs[p]; return rc[p]; }
-    out_words.assign(count, {});
-    out_ids.assign(count, {});
+    const int rc = run_side_by_side(K, err, [&](int c, std::string& e) -> int {  // part c on worker c
+      if (c) (void)rt_set_device(device);
+      if (parts[c].imgs.empty()) return OCR_OK;
+      return worker(c)->run_images(base, parts[c].imgs, parts[c].groups, probs, W[c], I[c], t[c].data(), e, out_chars ? &Ch[c] : nullptr);
+    });
+    if (rc) return rc;
+    out_words.assign(count, {}); out_ids.assign(count, {});
     if (out_chars) out_chars->assign(count, {});
     for (int p = 0; p < K; ++p)
-      for (size_t k = 0; k < gidx[p].size(); ++k) {
-        out_words[gidx[p][k]] = std::move(W[p][k]);
-        out_ids[gidx[p][k]] = std::move(I[p][k]);
-        if (out_chars) (*out_chars)[gidx[p][k]] = std::move(Ch[p][k]);
+      for (size_t k = 0; k < parts[p].index.size(); ++k) {
+        out_words[parts[p].index[k]] = std::move(W[p][k]);
+        out_ids[parts[p].index[k]] = std::move(I[p][k]);
+        if (out_chars) (*out_chars)[parts[p].index[k]] = std::move(Ch[p][k]);
       }
     for (int k = 0; k < 3; ++k) {  // the chains ran side by side: per stage, the busiest chain's time
       double m = 0;
-      for (int c = 0; c < nchains; ++c) {
-        double sum = 0;
-        for (int p = c; p < K; p += nchains) sum += t[p][k];
-        m = std::max(m, sum);
-      }
+      for (int c = 0; c < K; ++c) m = std::max(m, t[c][k]);
       times[k] += m;
     }
     return OCR_OK;
   }
 
-  // run a staged slot: wait for its upload, clone, run, hand the results back in the caller's order
-  int run_slot(int si, ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids, double times[3], int chain = -1,
-               ocr_char* chars = nullptr) {
-    StageSlot& S = slots[si];
-    if (!S.staged || S.imgs.empty()) return fail(OCR_ERR_ARG, "nothing staged in this slot");
-    std::string err;
-    PipeWorker* one = chain >= 0 ? worker(chain) : nullptr;  // the whole batch on one chain (two batches in flight), or split over all
+  struct Out {  // the caller's result arrays (ocr_pipe_run*); times and chars may be null
+    ocr_word* words; int cap_words; int* word_off; int* nwords; int32_t* ids; int cap_ids; double* times; ocr_char* chars;
+  };
+  // The tail of every run entry point.  The batch's clone (OCRRequest copies the Mat, ocr_worker.h:28-29: cls rotates in place
+  // on it) is enqueued, behind `after` if there is one, on the detector stream of the chain that runs it; the batch runs whole
+  // on one chain (chain >= 0: two batches in flight) or split over all; image i of the caller is imgs[order[i]].
+  int clone_run_emit(int chain, const void* src, size_t bytes, hipEvent_t after, const std::vector<StageSlot::Img>& imgs,
+                     const std::vector<StageSlot::Group>& groups, const float* probs, const std::vector<int>& order, const Out& o) {
+    PipeWorker* one = chain >= 0 ? worker(chain) : nullptr;
     if (chain >= 0 && !one) return fail(OCR_ERR_ARG, "no such chain (0 <= chain < phases)");
     PipeWorker& first = one ? *one : w0;
     DevBuf<uint8_t>& clone = one ? work_chain[chain] : work;
-    if (hipStreamWaitEvent(first.det.stream(), S.ready, 0) != hipSuccess) return fail(OCR_ERR_DEVICE, "hipStreamWaitEvent failed");
-    if (!clone.ensure(S.bytes + 256, err)) return fail(OCR_ERR_DEVICE, err);
-    if (hipMemcpyAsync(clone.p, S.dev.p, S.bytes, hipMemcpyDeviceToDevice, first.det.stream()) != hipSuccess) return fail(OCR_ERR_DEVICE, "clone failed");
+    std::string err;
+    if (after && hipStreamWaitEvent(first.det.stream(), after, 0) != hipSuccess) return fail(OCR_ERR_DEVICE, "hipStreamWaitEvent failed");
+    if (!clone.ensure(bytes + 256, err)) return fail(OCR_ERR_DEVICE, err);
+    CAPI_HIP(hipMemcpyAsync(clone.p, src, bytes, hipMemcpyDeviceToDevice, first.det.stream()));
     double t[3] = {0, 0, 0};
-    std::vector<std::vector<ocr_word>> W;
-    std::vector<std::vector<int32_t>> I;
-    CharLists C;
-    CharLists* pc = chars ? &C : nullptr;
-    const int rc = one ? one->run_images(clone.p, S.imgs, S.groups, S.has_probs ? S.probs.p : nullptr, W, I, t, err, pc)
-                       : run_images(clone.p, S.imgs, S.groups, S.has_probs ? S.probs.p : nullptr, W, I, t, err, pc);
+    WordLists W; IdLists I; CharLists C;
+    CharLists* pc = o.chars ? &C : nullptr;
+    const int rc = one ? one->run_images(clone.p, imgs, groups, probs, W, I, t, err, pc) : run_images(clone.p, imgs, groups, probs, W, I, t, err, pc);
     if (rc) return fail(rc, err);
-    if (times) { times[0] = t[0]; times[1] = t[1]; times[2] = t[2]; }
-    const int count = (int)S.imgs.size();
-    std::vector<int> order(count);  // order[original index] = layout index
-    for (int k = 0; k < count; ++k) order[S.imgs[k].orig] = k;
-    return emit(W, I, order, words, cap_words, word_off, nwords, ids, cap_ids, pc, chars);
+    if (o.times) { o.times[0] = t[0]; o.times[1] = t[1]; o.times[2] = t[2]; }
+    if (!pipe_plan::emit(W, I, order, o.words, o.cap_words, o.word_off, o.nwords, o.ids, o.cap_ids, pc, o.chars))
+      return fail(OCR_ERR_CAPACITY, "result buffers too small");
+    return OCR_OK;
+  }
+
+  // run a staged slot: wait for its upload, clone, run, hand the results back in the caller's order
+  int run_slot(int si, const Out& o, int chain = -1) {
+    StageSlot& S = slots[si];
+    if (!S.staged || S.imgs.empty()) return fail(OCR_ERR_ARG, "nothing staged in this slot");
+    std::vector<int> order(S.imgs.size());  // order[original index] = layout index
+    for (size_t k = 0; k < S.imgs.size(); ++k) order[S.imgs[k].orig] = (int)k;
+    return clone_run_emit(chain, S.dev.p, S.bytes, S.ready, S.imgs, S.groups, S.has_probs ? S.probs.p : nullptr, order, o);
   }
 };
-
-static int emit(const std::vector<std::vector<ocr_word>>& W, const std::vector<std::vector<int32_t>>& I, const std::vector<int>& order,
-                ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids, const CharLists* C, ocr_char* chars) {
-  int wo = 0, io = 0;
-  for (size_t i = 0; i < order.size(); ++i) {
-    const auto& w = W[order[i]];
-    const auto& d = I[order[i]];
-    word_off[i] = wo;
-    nwords[i] = (int)w.size();
-    if (wo + (int)w.size() > cap_words || io + (int)d.size() > cap_ids) return fail(OCR_ERR_CAPACITY, "result buffers too small");
-    for (size_t k = 0; k < w.size(); ++k) {
-      words[wo + k] = w[k];
-      words[wo + k].ids_off += io;
-    }
-    if (!d.empty()) memcpy(ids + io, d.data(), d.size() * sizeof(int32_t));
-    if (C && chars && !d.empty()) memcpy(chars + io, (*C)[order[i]].data(), d.size() * sizeof(ocr_char));
-    wo += (int)w.size();
-    io += (int)d.size();
-  }
-  return OCR_OK;
-}
 
 extern "C" {
 
@@ -718,19 +630,16 @@ int ocr_pipe_create(const ocr_pipe_cfg* c, ocr_pipe** out) {
   if (const char* e = getenv("OCR_DET_LANES")) lanes = std::min(32, std::max(1, atoi(e)));
   int rc = h->w0.create(d, r, c->enable_cls ? &k : nullptr, c->crop_mode, err);
   if (rc) return fail(rc, err);
-  h->w0.det_lanes = lanes;
   for (int p = 1; p < h->phases; ++p) {
     h->extra.emplace_back(new PipeWorker());
     rc = h->extra.back()->create(d, r, c->enable_cls ? &k : nullptr, c->crop_mode, err);
     if (rc) return fail(rc, err);
   }
   // the detector lanes (mixed-size batches) are dealt over the chains
-  h->w0.det_lanes = std::max(1, (lanes + h->phases - 1) / h->phases);
-  for (auto& w : h->extra) w->det_lanes = h->w0.det_lanes;
-  if (const char* e = getenv("OCR_DET_RAGGED")) {
-    h->w0.det_ragged = e[0] != '0';
-    h->w0.det_post_ragged = e[0] != 'n';
-    for (auto& w : h->extra) { w->det_ragged = h->w0.det_ragged; w->det_post_ragged = h->w0.det_post_ragged; }
+  const char* ragged = getenv("OCR_DET_RAGGED");
+  for (PipeWorker* w : h->workers()) {
+    w->det_lanes = std::max(1, (lanes + h->phases - 1) / h->phases);
+    if (ragged) { w->det_ragged = ragged[0] != '0'; w->det_post_ragged = ragged[0] != 'n'; }
   }
   // two idle high-priority streams per device (once per process), created after the first pipeline's stage streams and
   // before the detector lanes' (which come into being at the first mixed-size batch): the configuration in which the
@@ -746,27 +655,12 @@ static int pipe_run_device(ocr_pipe* h, int chain, const void* dev_bgr, int rows
   if (!h || !dev_bgr || rows <= 0 || cols <= 0 || count < 1 || !words || !word_off || !nwords || !ids)
     return fail(OCR_ERR_ARG, "bad argument");
   CAPI_HIP(rt_set_device(h->device));
-  PipeWorker* one = chain >= 0 ? h->worker(chain) : nullptr;
-  if (chain >= 0 && !one) return fail(OCR_ERR_ARG, "no such chain (0 <= chain < phases)");
-  PipeWorker& first = one ? *one : h->w0;
-  DevBuf<uint8_t>& clone = one ? h->work_chain[chain] : h->work;
-  double t[3] = {0, 0, 0};
-  std::vector<std::vector<ocr_word>> W;
-  std::vector<std::vector<int32_t>> I;
-  std::string err;
-  // the request's clone (OCRRequest copies the Mat, ocr_worker.h:28-29): cls rotation is in place on it
-  const size_t img_bytes = (size_t)rows * cols * 3, bytes = img_bytes * count;
-  if (!clone.ensure(bytes + 256, err)) return fail(OCR_ERR_DEVICE, err);
-  CAPI_HIP(hipMemcpyAsync(clone.p, dev_bgr, bytes, hipMemcpyDeviceToDevice, first.det.stream()));
+  const size_t img_bytes = (size_t)rows * cols * 3;
   std::vector<StageSlot::Img> imgs(count);
-  for (int i = 0; i < count; ++i) imgs[i] = {rows, cols, i, img_bytes * i, 0};
-  const std::vector<StageSlot::Group> groups = {{rows, cols, 0, count, 0, 0}};
-  const int rc = one ? one->run_images(clone.p, imgs, groups, dev_prob, W, I, t, err) : h->run_images(clone.p, imgs, groups, dev_prob, W, I, t, err);
-  if (rc) return fail(rc, err);
-  if (times) { times[0] = t[0]; times[1] = t[1]; times[2] = t[2]; }
   std::vector<int> order(count);
-  for (int i = 0; i < count; ++i) order[i] = i;
-  return emit(W, I, order, words, cap_words, word_off, nwords, ids, cap_ids);
+  for (int i = 0; i < count; ++i) { imgs[i] = {rows, cols, i, img_bytes * i, 0}; order[i] = i; }
+  return h->clone_run_emit(chain, dev_bgr, img_bytes * count, nullptr, imgs, {{rows, cols, 0, count, 0, 0}}, dev_prob, order,
+                           {words, cap_words, word_off, nwords, ids, cap_ids, times, nullptr});
 }
 int ocr_pipe_run_device(ocr_pipe* h, const void* dev_bgr, int rows, int cols, int count, const float* dev_prob, ocr_word* words,
                         int cap_words, int* word_off, int* nwords, int32_t* ids, int cap_ids, double times[3]) {
@@ -885,14 +779,14 @@ int ocr_pipe_run_staged(ocr_pipe* h, int slot, ocr_word* words, int cap_words, i
                         int cap_ids, double times[3]) {
   if (!h || slot < 0 || slot > 1 || !words || !word_off || !nwords || !ids) return fail(OCR_ERR_ARG, "bad argument");
   CAPI_HIP(rt_set_device(h->device));
-  return h->run_slot(slot, words, cap_words, word_off, nwords, ids, cap_ids, times);
+  return h->run_slot(slot, {words, cap_words, word_off, nwords, ids, cap_ids, times, nullptr});
 }
 
 int ocr_pipe_run_staged_on(ocr_pipe* h, int chain, int slot, ocr_word* words, int cap_words, int* word_off, int* nwords, int32_t* ids,
                            int cap_ids, double times[3]) {
   if (!h || chain < 0 || slot < 0 || slot > 1 || !words || !word_off || !nwords || !ids) return fail(OCR_ERR_ARG, "bad argument");
   CAPI_HIP(rt_set_device(h->device));
-  return h->run_slot(slot, words, cap_words, word_off, nwords, ids, cap_ids, times, chain);
+  return h->run_slot(slot, {words, cap_words, word_off, nwords, ids, cap_ids, times, nullptr}, chain);
 }
 
 int ocr_pipe_run(ocr_pipe* h, const ocr_img* imgs, int count, ocr_word* words, int cap_words, int* word_off, int* nwords,
@@ -900,7 +794,7 @@ int ocr_pipe_run(ocr_pipe* h, const ocr_img* imgs, int count, ocr_word* words, i
   if (!h || !imgs || count < 1 || !words || !word_off || !nwords || !ids) return fail(OCR_ERR_ARG, "bad argument");
   const int rc = ocr_pipe_stage(h, 0, imgs, count);
   if (rc) return rc;
-  return h->run_slot(0, words, cap_words, word_off, nwords, ids, cap_ids, times);
+  return h->run_slot(0, {words, cap_words, word_off, nwords, ids, cap_ids, times, nullptr});
 }
 
 int ocr_pipe_run_chars(ocr_pipe* h, const ocr_img* imgs, int count, ocr_word* words, int cap_words, int* word_off, int* nwords,
@@ -908,7 +802,7 @@ int ocr_pipe_run_chars(ocr_pipe* h, const ocr_img* imgs, int count, ocr_word* wo
   if (!h || !imgs || count < 1 || !words || !word_off || !nwords || !ids || !chars) return fail(OCR_ERR_ARG, "bad argument");
   const int rc = ocr_pipe_stage(h, 0, imgs, count);
   if (rc) return rc;
-  return h->run_slot(0, words, cap_words, word_off, nwords, ids, cap_ids, times, -1, chars);
+  return h->run_slot(0, {words, cap_words, word_off, nwords, ids, cap_ids, times, chars});
 }
 
 const char* ocr_pipe_label(ocr_pipe* h, int id) {
@@ -925,9 +819,7 @@ int ocr_pipe_det_shape(ocr_pipe* h, int rows, int cols, int* net_rows, int* net_
 
 static std::vector<Net*> pipe_nets(ocr_pipe* h) {
   std::vector<Net*> v;
-  std::vector<PipeWorker*> ws{&h->w0};
-  for (auto& w : h->extra) ws.push_back(w.get());
-  for (PipeWorker* w : ws) {
+  for (PipeWorker* w : h->workers()) {
     v.push_back(&w->det.net());
     for (auto& d : w->det_extra) v.push_back(&d->net());  // odd chunks of a mixed-size batch run here
     if (w->cls) v.push_back(&w->cls->net());
@@ -935,13 +827,11 @@ static std::vector<Net*> pipe_nets(ocr_pipe* h) {
   }
   return v;
 }
-static std::vector<SrvNet*> pipe_srv_nets(ocr_pipe* h) {  // the server networks of a configs[4] pipeline
-  std::vector<SrvNet*> v;
-  std::vector<PipeWorker*> ws{&h->w0};
-  for (auto& w : h->extra) ws.push_back(w.get());
-  for (PipeWorker* w : ws) {
-    if (w->det.srv()) v.push_back(w->det.srv());
-    if (w->rec.srv()) v.push_back(w->rec.srv());
+static std::vector<std::pair<const char*, SrvNet*>> pipe_srv_nets(ocr_pipe* h) {  // the server networks of a configs[4] pipeline
+  std::vector<std::pair<const char*, SrvNet*>> v;
+  for (PipeWorker* w : h->workers()) {
+    if (w->det.srv()) v.push_back({"det.", w->det.srv()});
+    if (w->rec.srv()) v.push_back({"rec.", w->rec.srv()});
   }
   return v;
 }
@@ -951,34 +841,24 @@ int ocr_pipe_timing(ocr_pipe* h, int enable) {
     net->enable_timing(enable != 0);
     net->reset_timings();
   }
-  for (SrvNet* net : pipe_srv_nets(h)) {
-    net->enable_timing(enable != 0);
-    net->reset_timings();
+  for (auto& net : pipe_srv_nets(h)) {
+    net.second->enable_timing(enable != 0);
+    net.second->reset_timings();
   }
-  h->w0.timing_on = enable != 0;
-  for (auto& w : h->extra) w->timing_on = enable != 0;
+  for (PipeWorker* w : h->workers()) w->timing_on = enable != 0;
   return OCR_OK;
 }
 int ocr_pipe_stats(ocr_pipe* h, long long out[3]) {
   if (!h || !out) return fail(OCR_ERR_ARG, "null argument");
   out[0] = out[1] = out[2] = 0;
-  auto add = [&](Net& n) { out[0] += n.stats().runs; out[1] += n.stats().binds; out[2] += n.stats().graph_replays; };
-  std::vector<PipeWorker*> ws{&h->w0};
-  for (auto& w : h->extra) ws.push_back(w.get());
-  for (PipeWorker* w : ws) {
-    add(w->det.net());
-    for (auto& d : w->det_extra) add(d->net());
-    if (w->cls) add(w->cls->net());
-    add(w->rec.net());
-  }
+  for (Net* n : pipe_nets(h)) { out[0] += n->stats().runs; out[1] += n->stats().binds; out[2] += n->stats().graph_replays; }
   return OCR_OK;
 }
 int ocr_pipe_timing_filter(ocr_pipe* h, const char* substr) {
   if (!h) return fail(OCR_ERR_ARG, "null handle");
   const std::string f = substr ? substr : "";
   for (Net* net : pipe_nets(h)) net->set_timing_filter(f);
-  h->w0.timing_filter = f;
-  for (auto& w : h->extra) w->timing_filter = f;
+  for (PipeWorker* w : h->workers()) w->timing_filter = f;
   return OCR_OK;
 }
 int ocr_pipe_timing_report(ocr_pipe* h, char* buf, size_t cap) {
@@ -986,24 +866,14 @@ int ocr_pipe_timing_report(ocr_pipe* h, char* buf, size_t cap) {
   size_t off = 0;
   // the halves of a split rec launch (and equal shapes on different lanes) have the same instance names: one row per name
   std::map<std::string, KernelTiming> all;
+  auto add = [&](const std::string& name, const auto& k) {
+    KernelTiming& t = all[name];
+    t.ms += k.ms; t.count += k.count; t.flops += k.flops; t.bytes += k.bytes;
+  };
   for (Net* net : pipe_nets(h))
-    for (auto& kv : net->timings()) {
-      KernelTiming& t = all[kv.first];
-      t.ms += kv.second.ms; t.count += kv.second.count; t.flops += kv.second.flops; t.bytes += kv.second.bytes;
-    }
-  {
-    std::vector<PipeWorker*> ws{&h->w0};
-    for (auto& w : h->extra) ws.push_back(w.get());
-    for (PipeWorker* w : ws)
-      for (int k = 0; k < 2; ++k) {
-        SrvNet* net = k ? w->rec.srv() : w->det.srv();
-        if (!net) continue;
-        for (auto& kv : net->timings()) {  // (the mobile networks' names start with "det." / "rec.": the same convention)
-          KernelTiming& t = all[std::string(k ? "rec." : "det.") + kv.first];
-          t.ms += kv.second.ms; t.count += kv.second.count; t.flops += kv.second.flops; t.bytes += kv.second.bytes;
-        }
-      }
-  }
+    for (auto& kv : net->timings()) add(kv.first, kv.second);
+  for (auto& net : pipe_srv_nets(h))  // (the mobile networks' names start with "det." / "rec.": the same convention)
+    for (auto& kv : net.second->timings()) add(net.first + kv.first, kv.second);
   for (auto& kv : all) {
     int n = snprintf(buf + off, cap > off ? cap - off : 0, "%s %.6f %ld %.0f %.0f\n", kv.first.c_str(), kv.second.ms,
                      kv.second.count, kv.second.flops, kv.second.bytes);

@@ -8,6 +8,7 @@
 #include <map>
 
 #include "capi_common.h"
+#include "pipe_plan.h"
 
 namespace ocr {
 
@@ -89,23 +90,7 @@ DetStage::~DetStage() {
 
 void DetStage::resize_shape(int h, int w, const std::string& limit_type, int limit_side_len, int& rh, int& rw,
                             float& ratio_h, float& ratio_w) {
-  // ResizeImgType0::Run, /root/reference/src/preprocess_op.cpp:57-93
-  float ratio = 1.f;
-  if (limit_type == "min") {
-    const int min_wh = std::min(h, w);
-    if (min_wh < limit_side_len) ratio = h < w ? float(limit_side_len) / float(h) : float(limit_side_len) / float(w);
-  } else {
-    const int max_wh = std::max(h, w);
-    if (max_wh > limit_side_len) ratio = h > w ? float(limit_side_len) / float(h) : float(limit_side_len) / float(w);
-  }
-  int resize_h = int(float(h) * ratio);
-  int resize_w = int(float(w) * ratio);
-  resize_h = std::max(int(round(float(resize_h) / 32) * 32), 32);
-  resize_w = std::max(int(round(float(resize_w) / 32) * 32), 32);
-  rh = resize_h;
-  rw = resize_w;
-  ratio_h = float(resize_h) / float(h);
-  ratio_w = float(resize_w) / float(w);
+  pipe_plan::det_resize_shape(h, w, limit_type, limit_side_len, rh, rw, ratio_h, ratio_w);  // ResizeImgType0::Run
 }
 
 bool DetStage::create(const DetConfig& cfg, std::string& err, int& code) {
