@@ -1028,6 +1028,7 @@ EXPORTS += ["ocr_pipe_cfg_default", "ocr_pipe_create", "ocr_pipe_destroy", "ocr_
             "ocr_j2k_tier1", "ocr_j2k_decode_coded", "ocr_j2k_time_coded", "ocr_j2k_time_coded_batch",
             "ocr_tiff_expand", "ocr_tiff_decode_coded", "ocr_tiff_time_coded", "ocr_tiff_time_coded_batch",
             "ocr_tiff_inflate", "ocr_tiff_decode_deflate", "ocr_tiff_time_deflate", "ocr_tiff_time_deflate_batch",
+            "ocr_tiff_unfax", "ocr_tiff_decode_fax", "ocr_tiff_time_fax", "ocr_tiff_time_fax_batch",
             "ocr_pipe_label", "ocr_pipe_det_shape", "ocr_pipe_stats", "ocr_pipe_timing", "ocr_pipe_timing_filter", "ocr_pipe_timing_report", "ocr_dev_alloc",
             "ocr_dev_free", "ocr_dev_upload", "ocr_dev_download", "ocr_dev_sync", "ocr_dev_copy_time", "ocr_rotate_crop", "ocr_rotate_crop_shape", "ocr_rotate180_rois"]
 
@@ -1208,6 +1209,7 @@ class ocr_coded_frame(C.Structure):
 
 FRAME_JPEG, FRAME_PNG, FRAME_RAW, FRAME_TIFF, FRAME_WEBP, FRAME_VP8, FRAME_J2K, FRAME_J2K_CODED, FRAME_TIFF_CODED = 0, 1, 2, 3, 4, 5, 6, 7, 8
 FRAME_TIFF_DEFLATE = 9
+FRAME_TIFF_FAX = 10
 
 
 class TiffFrame:
@@ -1342,6 +1344,63 @@ def time_tiff_deflate(coded, iters=3, device_id=0, single=False):
     """ocr_tiff_time_deflate_batch over TiffCoded objects as one batch (single: ocr_tiff_time_deflate of the first):
     [upload, inflate with its read-back, pixel stage] in ms"""
     return _time_coded("ocr_tiff_time_deflate", coded, iters, device_id, single)
+
+
+class ocr_tiff_fax(C.Structure):
+    _fields_ = [("coded", ocr_tiff_coded), ("t4_options", C.c_uint32)]
+
+
+class TiffFax:
+    """an ocr_tiff_fax over Python-owned memory: a CCITT frame before its chunks are expanded.  compression: 2, 3, 4 or 32771;
+    t4_options: T4Options of Compression 3; chunks and data as for TiffCoded.  The frame is 1 bit, 1 sample; the fields of
+    .c.coded and .c.t4_options may be changed before a call (the tests' tampering)."""
+
+    def __init__(self, width, height, photometric, compression, chunks, data, tile=None, t4_options=0):
+        self.inner = TiffCoded(width, height, photometric, 1, 1, compression, chunks, data, tile=tile)
+        self.chunks, self.data = self.inner.chunks, self.inner.data
+        self.c = ocr_tiff_fax()
+        C.memmove(C.byref(self.c.coded), C.byref(self.inner.c), C.sizeof(ocr_tiff_coded))
+        self.c.t4_options = t4_options
+
+    def nominal(self):
+        C.memmove(C.byref(self.inner.c), C.byref(self.c.coded), C.sizeof(ocr_tiff_coded))
+        return self.inner.nominal()
+
+    def unfax(self, device_id=0, fill=0):
+        """ocr_tiff_unfax: the chunks as tiff::parse fills Frame::data (uint8 array, pre-filled with `fill`); OcrError where the
+        call refuses (err.out: the buffer as the call left it)"""
+        L = lib()
+        L.ocr_tiff_unfax.argtypes = [C.POINTER(ocr_tiff_fax), C.c_int, C.c_void_p, C.c_size_t]
+        n = self.nominal()
+        out = np.full(n if 0 < n <= 1 << 30 else 1, fill, np.uint8)
+        rc = L.ocr_tiff_unfax(C.byref(self.c), device_id, out.ctypes.data, out.size)
+        if rc != 0:
+            _raise(L, rc, out)
+        return out
+
+    def decode(self, device_id=0, fill=0):
+        """ocr_tiff_decode_fax: the (height, width, 3) BGR image; OcrError where the call refuses (err.out as for unfax)"""
+        return _decode_frame("ocr_tiff_decode_fax", self.c, self.c.coded.frame.height, self.c.coded.frame.width, device_id, fill)
+
+    def time(self, iters=3, device_id=0):
+        """ocr_tiff_time_fax: [upload, expansion, pixel stage] in ms"""
+        return time_tiff_fax([self], iters, device_id, single=True)
+
+
+def tiff_unfax(fax, device_id=0):
+    """ocr_tiff_unfax of a TiffFax"""
+    return fax.unfax(device_id)
+
+
+def tiff_decode_fax(fax, device_id=0):
+    """ocr_tiff_decode_fax of a TiffFax"""
+    return fax.decode(device_id)
+
+
+def time_tiff_fax(fax, iters=3, device_id=0, single=False):
+    """ocr_tiff_time_fax_batch over TiffFax objects as one batch (single: ocr_tiff_time_fax of the first):
+    [upload, expansion, pixel stage] in ms"""
+    return _time_coded("ocr_tiff_time_fax", fax, iters, device_id, single)
 
 
 class ocr_webp_transform(C.Structure):

@@ -86,6 +86,25 @@ const char* tiff_deflate_fault_of(const ocr_tiff_coded& c, TiffGeometry& g) {
   return nullptr;
 }
 
+// host/tiff_decode.h fax_fault_of(): fault(), the coding's rules, the records and the walk of every chunk; the device bounds
+const char* tiff_fax_fault_of(const ocr_tiff_fax& x, TiffGeometry& g) {
+  const ocr_tiff_coded& c = x.coded;
+  const ocr_tiff_frame& f = c.frame;
+  if (f.data) return "tiff coded: a coded frame carries no expanded chunks";
+  if (const char* why = tiff_fault(f, g, false)) return why;
+  tiff::Frame h;
+  h.width = f.width; h.height = f.height; h.photometric = f.photometric; h.bits = f.bits_per_sample; h.samples = f.samples_per_pixel;
+  h.planar = f.planar; h.predictor = f.predictor; h.big_endian = f.big_endian; h.premultiply = f.premultiply;
+  h.tile_width = f.tile_width; h.tile_height = f.tile_height;
+  tiff::Geometry hg;
+  // the rules that need no stream first, the device bounds among them; then the walk of every chunk
+  if (const char* why = tiff::fax_structure_fault(h, c.compression, x.t4_options, (const tiff::Chunk*)c.chunks, c.chunks_len, c.bytes_len, hg)) return why;
+  if (c.chunks_len > tiff::kMaxDeviceChunks || g.total > tiff::kMaxDeviceBytes) return "tiff coded: beyond the device bounds (2^20 chunks, 512 MiB at their nominal size)";
+  static_assert(tiff::kMaxFaxDeviceWidth == kTiffFaxMaxWidth, "the host sends what the lists of the kernel have room for");
+  if (f.tile_width > kTiffFaxMaxWidth) return "tiff fax: a chunk wider than the device expansion takes (8192 pixels)";
+  return tiff::fax_fault_of(h, c.compression, x.t4_options, (const tiff::Chunk*)c.chunks, c.chunks_len, c.bytes, c.bytes_len, hg);
+}
+
 int kind_of(const ocr_tiff_frame& f) { return f.bits_per_sample < 8 ? 0 : f.bits_per_sample == 8 ? 1 : 2; }
 
 // The descriptors of validated frames ordered by the kernel that takes them, the units of a kind numbered through its
@@ -228,6 +247,66 @@ int tiff_coded_decode_async(const ocr_tiff_coded* const* imgs, int count, uint8_
   return OCR_OK;
 }
 
+const char* tiff_fax_fault(const ocr_tiff_fax& c) {
+  TiffGeometry g;
+  return tiff_fax_fault_of(c, g);
+}
+
+void tiff_fax_relaunch(const TiffScratch& sc, const TiffLaunch& L, hipStream_t s) { launch_tiff_fax(L.fax, L.nfax, L.pool, sc.data.p, s); }
+
+int tiff_fax_decode_async(const ocr_tiff_fax* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
+                          TiffLaunch* launched, bool pixels) {
+  std::vector<size_t> off((size_t)count), pool_at((size_t)count);
+  std::vector<TiffGeometry> geo((size_t)count);
+  std::vector<const ocr_tiff_frame*> frames((size_t)count);
+  size_t bytes = 0, nchunks = 0, pool = 0;
+  TiffLaunch L;
+  for (int i = 0; i < count; ++i) {
+    if (!imgs[i]) { err = "null tiff frame"; return OCR_ERR_ARG; }
+    if (const char* fault = tiff_fax_fault_of(*imgs[i], geo[i])) { err = fault; return OCR_ERR_ARG; }
+    frames[i] = &imgs[i]->coded.frame;
+    off[i] = bytes;
+    pool_at[i] = pool;
+    bytes += pad256(geo[i].total);
+    nchunks += imgs[i]->coded.chunks_len;
+    pool += imgs[i]->coded.bytes_len;
+  }
+  if (nchunks > 0x7fffffffu) { err = "tiff batch: more chunks than a launch has workgroups"; return OCR_ERR_ARG; }
+  // the batch's chunks, the long streams first, so that they do not form the tail
+  std::vector<TiffFaxDesc> cd;
+  cd.reserve(nchunks);
+  for (int i = 0; i < count; ++i) {
+    const ocr_tiff_coded& c = imgs[i]->coded;
+    for (size_t k = 0; k < c.chunks_len; ++k)
+      cd.push_back(TiffFaxDesc{pool_at[i] + c.chunks[k].byte_off, off[i] + k * geo[i].chunk_bytes, c.chunks[k].byte_len, c.chunks[k].rows,
+                               (uint32_t)geo[i].chunk_bytes, (uint32_t)c.frame.tile_width, (uint32_t)c.compression, imgs[i]->t4_options});
+  }
+  std::stable_sort(cd.begin(), cd.end(), [](const TiffFaxDesc& a, const TiffFaxDesc& b) { return a.byte_len > b.byte_len; });
+  L.nfax = (uint32_t)cd.size();
+  const size_t at_pool = pad256(cd.size() * sizeof(TiffFaxDesc)), coded_bytes = at_pool + pad256(pool);
+  L.bytes = coded_bytes;
+  if (!sc.data.ensure(bytes + 256, err) || !sc.coded.ensure(coded_bytes + 256, err) || !sc.id.ensure((size_t)count, err)) return OCR_ERR_DEVICE;
+  if (!sc.stage.reserve(coded_bytes, err)) return OCR_ERR_DEVICE;
+  if (!cd.empty()) memcpy(sc.stage.p, cd.data(), cd.size() * sizeof(TiffFaxDesc));
+  parallel_copy((size_t)count, pool, [&](size_t i) { if (imgs[i]->coded.bytes_len) memcpy(sc.stage.p + at_pool + pool_at[i], imgs[i]->coded.bytes, imgs[i]->coded.bytes_len); });
+  L.fax = (const TiffFaxDesc*)sc.coded.p;
+  L.pool = sc.coded.p + at_pool;
+  const std::vector<TiffImageDesc> id = describe(frames.data(), count, geo, off, dst, sc.data.p, L);
+  if (!sc.stage.upload(sc.coded.p, coded_bytes, s, err) ||
+      hipMemcpyAsync(sc.id.p, id.data(), id.size() * sizeof(TiffImageDesc), hipMemcpyHostToDevice, s) != hipSuccess) {
+    err = "tiff fax chunks upload failed";
+    return OCR_ERR_DEVICE;
+  }
+  tiff_fax_relaunch(sc, L, s);
+  if (hipGetLastError() != hipSuccess) { err = "tiff fax expansion kernel failed to launch"; return OCR_ERR_DEVICE; }
+  if (pixels) {
+    tiff_relaunch(sc, L, s);
+    if (hipGetLastError() != hipSuccess) { err = "tiff pixel kernels failed to launch"; return OCR_ERR_DEVICE; }
+  }
+  if (launched) *launched = L;
+  return OCR_OK;
+}
+
 const char* tiff_deflate_fault(const ocr_tiff_coded& c) {
   TiffGeometry g;
   return tiff_deflate_fault_of(c, g);
@@ -346,7 +425,53 @@ struct TiffDeflateRoute : TiffCodedRoute {
   static hipError_t middle(Scratch& sc, const Launch& L) { return tiff_inflate_relaunch(sc, L, nullptr) == OCR_OK ? hipSuccess : hipErrorUnknown; }
 };
 
+// the fax route: upload, the fax expansion, pixel stage
+struct TiffFaxRoute {
+  using Frame = ocr_tiff_fax;
+  using Scratch = TiffScratch;
+  using Launch = TiffLaunch;
+  static const char* fault(const Frame& c) { return tiff_fax_fault(c); }
+  static int rows(const Frame& c) { return c.coded.frame.height; }
+  static int cols(const Frame& c) { return c.coded.frame.width; }
+  static int decode(const Frame* const* fax, int count, uint8_t* const* dst, Scratch& sc, std::string& err, Launch* L) {
+    return tiff_fax_decode_async(fax, count, dst, sc, nullptr, err, L);
+  }
+  static uint8_t* uploaded(Scratch& sc, const Launch&) { return sc.coded.p; }
+  static hipError_t middle(Scratch& sc, const Launch& L) { tiff_fax_relaunch(sc, L, nullptr); return hipGetLastError(); }
+  static void pixels(Scratch& sc, const Launch& L) { tiff_relaunch(sc, L, nullptr); }
+};
+
 }  // namespace
+
+extern "C" int ocr_tiff_unfax(const ocr_tiff_fax* fax, int device_id, uint8_t* out, size_t cap) {
+  if (!fax || !out) return fail(OCR_ERR_ARG, "null argument");
+  TiffGeometry g;
+  if (const char* fault = tiff_fax_fault_of(*fax, g)) return fail(OCR_ERR_ARG, fault);
+  if (g.total > cap) return fail(OCR_ERR_CAPACITY, "output buffer too small");
+  int rc = ocr_rt_init(device_id);
+  if (rc) return rc;
+  TiffScratch sc;
+  std::string err;
+  rc = tiff_fax_decode_async(&fax, 1, nullptr, sc, nullptr, err, nullptr, false);
+  if (rc) return fail(rc, err);
+  CAPI_HIP(hipStreamSynchronize(nullptr));
+  CAPI_HIP(g_memcpy(out, sc.data.p, g.total, hipMemcpyDeviceToHost));
+  return OCR_OK;
+}
+
+extern "C" int ocr_tiff_decode_fax(const ocr_tiff_fax* fax, int device_id, uint8_t* bgr, size_t cap) {
+  return decode_frame<TiffFaxRoute>(fax, device_id, bgr, cap);
+}
+
+extern "C" int ocr_tiff_time_fax(const ocr_tiff_fax* fax, int device_id, int iters, double ms[3]) {
+  if (!fax || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
+  return time_frames3<TiffFaxRoute>(&fax, 1, device_id, iters, ms);
+}
+
+extern "C" int ocr_tiff_time_fax_batch(const ocr_tiff_fax* const* fax, int count, int device_id, int iters, double ms[3]) {
+  if (!fax || count < 1 || !ms || iters <= 0) return fail(OCR_ERR_ARG, "null argument");
+  return time_frames3<TiffFaxRoute>(fax, count, device_id, iters, ms);
+}
 
 extern "C" int ocr_tiff_inflate(const ocr_tiff_coded* coded, int device_id, uint8_t* out, size_t cap, uint32_t* produced) {
   if (!coded || !out) return fail(OCR_ERR_ARG, "null argument");

@@ -20,7 +20,7 @@ struct FrameScratch {
   JpegScratch jpeg;
   PngScratch png;
   RawScratch raw;
-  TiffScratch tiff, tiff_coded, tiff_deflate;
+  TiffScratch tiff, tiff_coded, tiff_deflate, tiff_fax;
   WebpScratch webp;
   Vp8Scratch vp8;
   J2kScratch j2k, j2k_coded;
@@ -49,6 +49,7 @@ inline void jpeg_size(const void* frame, int& rows, int& cols) {
   cols = jpeg_out_cols(*(const ocr_jpeg_frame*)frame);
 }
 static_assert(offsetof(ocr_tiff_coded, frame) == 0 && offsetof(ocr_j2k_coded, frame) == 0, "a coded descriptor starts with its frame");
+static_assert(offsetof(ocr_tiff_fax, coded) == 0, "a fax descriptor starts with its coded frame, and that with its frame");
 
 template <class F, class S, class L, int (*Decode)(const F* const*, int, uint8_t* const*, S&, hipStream_t, std::string&, L*), S FrameScratch::*Sc>
 static int decode(const void* const* frames, int count, uint8_t* const* dst, FrameScratch& sc, hipStream_t s, std::string& err, const int*) {
@@ -62,6 +63,9 @@ inline int tiff_coded_decode(const void* const* frames, int count, uint8_t* cons
 }
 inline int tiff_deflate_decode(const void* const* frames, int count, uint8_t* const* dst, FrameScratch& sc, hipStream_t s, std::string& err, const int* ids) {
   return tiff_deflate_decode_async((const ocr_tiff_coded* const*)frames, count, dst, sc.tiff_deflate, s, err, nullptr, true, nullptr, ids);
+}
+inline int tiff_fax_decode(const void* const* frames, int count, uint8_t* const* dst, FrameScratch& sc, hipStream_t s, std::string& err, const int*) {
+  return tiff_fax_decode_async((const ocr_tiff_fax* const*)frames, count, dst, sc.tiff_fax, s, err);
 }
 
 }  // namespace frame_kinds
@@ -85,9 +89,10 @@ inline const FrameKind kFrameKinds[] = {
     /* J2K_CODED */ {frame_kinds::fault<ocr_j2k_coded, j2k_coded_fault>, frame_kinds::size<ocr_j2k_frame>, frame_kinds::j2k_coded_decode},
     /* TIFF_CODED */ {frame_kinds::fault<ocr_tiff_coded, tiff_coded_fault>, frame_kinds::size<ocr_tiff_frame>, frame_kinds::tiff_coded_decode},
     /* TIFF_DEFLATE */ {frame_kinds::fault<ocr_tiff_coded, tiff_deflate_fault>, frame_kinds::size<ocr_tiff_frame>, frame_kinds::tiff_deflate_decode},
+    /* TIFF_FAX */ {frame_kinds::fault<ocr_tiff_fax, tiff_fax_fault>, frame_kinds::size<ocr_tiff_frame>, frame_kinds::tiff_fax_decode},
 };
 constexpr int kFrameKindCount = (int)(sizeof kFrameKinds / sizeof kFrameKinds[0]);
-static_assert(kFrameKindCount == OCR_FRAME_TIFF_DEFLATE + 1 && OCR_FRAME_JPEG == 0 && OCR_FRAME_PNG == 1 && OCR_FRAME_RAW == 2 && OCR_FRAME_TIFF == 3 &&
+static_assert(kFrameKindCount == OCR_FRAME_TIFF_FAX + 1 && OCR_FRAME_TIFF_DEFLATE == 9 && OCR_FRAME_JPEG == 0 && OCR_FRAME_PNG == 1 && OCR_FRAME_RAW == 2 && OCR_FRAME_TIFF == 3 &&
                   OCR_FRAME_WEBP == 4 && OCR_FRAME_VP8 == 5 && OCR_FRAME_J2K == 6 && OCR_FRAME_J2K_CODED == 7 && OCR_FRAME_TIFF_CODED == 8,
               "kFrameKinds is in the order of ocr_frame_kind");
 
@@ -95,6 +100,7 @@ static_assert(kFrameKindCount == OCR_FRAME_TIFF_DEFLATE + 1 && OCR_FRAME_JPEG ==
 // refuse a stream (it waits for its inflate verdicts), and it does so before anything else is enqueued; the others in
 // the order of the enum.
 constexpr int kFrameLaunchOrder[kFrameKindCount] = {OCR_FRAME_TIFF_DEFLATE, OCR_FRAME_JPEG, OCR_FRAME_PNG, OCR_FRAME_RAW,       OCR_FRAME_TIFF,
-                                                    OCR_FRAME_WEBP,         OCR_FRAME_VP8,  OCR_FRAME_J2K, OCR_FRAME_J2K_CODED, OCR_FRAME_TIFF_CODED};
+                                                    OCR_FRAME_WEBP,         OCR_FRAME_VP8,  OCR_FRAME_J2K, OCR_FRAME_J2K_CODED, OCR_FRAME_TIFF_CODED,
+                                                    OCR_FRAME_TIFF_FAX};
 
 }  // namespace ocr

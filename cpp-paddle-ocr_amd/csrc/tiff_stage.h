@@ -6,6 +6,7 @@
 #include "image_stage.h"
 #include "kernels_tiff.h"
 #include "kernels_inflate.h"
+#include "kernels_tiff_fax.h"
 #include "kernels_tiff_lzw.h"
 
 namespace ocr {
@@ -31,6 +32,9 @@ struct TiffLaunch {
   // a Deflate batch: the streams the inflate launch goes over (device), instead of chunks / lzw / runs
   const InflateDesc* streams = nullptr;
   uint32_t nstreams = 0;
+  // a fax batch: the chunks the fax expansion goes over (device), instead of either
+  const TiffFaxDesc* fax = nullptr;
+  uint32_t nfax = 0;
 };
 // why a frame is refused, nullptr when it is sound: a kernel only ever sees descriptors that passed
 const char* tiff_frame_fault(const ocr_tiff_frame& f);
@@ -57,6 +61,13 @@ void tiff_expand_relaunch(const TiffScratch& sc, const TiffLaunch& L, hipStream_
 const char* tiff_deflate_fault(const ocr_tiff_coded& c);
 int tiff_deflate_decode_async(const ocr_tiff_coded* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
                               TiffLaunch* launched = nullptr, bool pixels = true, uint32_t* const* produced = nullptr, const int* ids = nullptr);
+// Fax frames (ocr_tiff_fax: Compression 2, 3, 4, 32771).  tiff_fax_fault: the frame, what the coding asks of it, the records,
+// the walk of every stream (tiff::fax_fault_of), the device bounds and the widest chunk (kTiffFaxMaxWidth).
+// tiff_fax_decode_async as tiff_coded_decode_async, with the fax expansion (tiff_fax_relaunch) in the expansion's place.
+const char* tiff_fax_fault(const ocr_tiff_fax& c);
+int tiff_fax_decode_async(const ocr_tiff_fax* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
+                          TiffLaunch* launched = nullptr, bool pixels = true);
+void tiff_fax_relaunch(const TiffScratch& sc, const TiffLaunch& L, hipStream_t s);
 // the inflate launch and its read-back again (ocr_tiff_time_deflate)
 int tiff_inflate_relaunch(TiffScratch& sc, const TiffLaunch& L, hipStream_t s);  // (after a tiff_deflate_decode_async of the batch)
 

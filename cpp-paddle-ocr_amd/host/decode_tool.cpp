@@ -34,6 +34,11 @@
 // OCR_FRAME_TIFF_DEFLATE) and by --stage for "coded:<file>"; --time on such a file adds "coded_upload_ms", "inflate_stage_ms"
 // (the inflate launch with the read-back of its counts), "coded_pixel_stage_ms" (ocr_tiff_time_deflate / _batch) and
 // "host_inflate_ms_per_image" (tiff::inflate_all: zlib on one host thread).
+// A CCITT fax TIFF (Compression 2, 3, 4, 32771) goes coded under OCR_DEVICE_TIFF=4 (--device / --frame / --stage:
+// ocr_tiff_decode_fax, OCR_FRAME_TIFF_FAX) and by --stage for "coded:<file>"; --time on such a file adds "coded_upload_ms",
+// "unfax_stage_ms", "coded_pixel_stage_ms" (ocr_tiff_time_fax / _batch), "host_scan_ms_per_image" (tiff::fax_fault: the walk of
+// every stream, which both routes pay) and "host_unfax_ms_per_image" (tiff::unfax_all on one host thread, which the coded
+// route saves).
 // --time <iters> <tiff file> [<batch>]: ocr_tiff_time / ocr_tiff_time_batch (upload of the expanded
 // chunks, pixel stage), "host_pixels_ms" (tiff::pixels on one host thread), "bytes_in" / "bytes_out" (what the kernel reads and
 // writes) and "copy_ms": a plain copy kernel that reads and writes as many bytes in all (ocr_dev_copy_time), timed in the same run.
@@ -214,6 +219,27 @@ static int time_device(int iters, const char* in, int batch) {
       printf(", \"compression\": %d, \"chunks\": %zu, \"coded_bytes\": %zu, \"coded_upload_ms\": %.5f, \"expand_stage_ms\": %.5f, \"coded_pixel_stage_ms\": %.5f, "
              "\"host_scan_ms_per_image\": %.5f, \"host_expand_ms_per_image\": %.5f",
              c->compression, c->chunks.size(), c->bytes.size(), cms[0], cms[1], cms[2], scan_ms, expand_ms);
+    } else if (PaddleOCR::tiff::parse_fax(bytes.data(), bytes.size(), *c) && c->frame.device_ok && c->frame.tile_width <= PaddleOCR::tiff::kMaxFaxDeviceWidth) {
+      // the fax route: upload of the coded chunks, the fax expansion and the pixel stage on the device, against the walk of
+      // every stream (both routes) and tiff::unfax_all (the =1 route) per image on one host thread
+      im.tiff_fax = c;
+      const ocr_tiff_fax cd = im.tiff_fax_frame();
+      double cms[3];
+      if (!time_copies(cd, n, iters, ocr_tiff_time_fax, ocr_tiff_time_fax_batch, cms)) return 1;
+      PaddleOCR::tiff::Geometry g;
+      const int reps = iters < 3 ? 3 : iters;
+      auto t1 = std::chrono::steady_clock::now();
+      bool sound = true;
+      for (int i = 0; i < reps; ++i) sound = sound && !PaddleOCR::tiff::fax_fault(*c, g);
+      const double scan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() / reps;
+      PaddleOCR::tiff::Frame ef;
+      t1 = std::chrono::steady_clock::now();
+      for (int i = 0; i < reps; ++i) sound = sound && PaddleOCR::tiff::unfax_all(*c, ef);
+      const double unfax_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() / reps;
+      if (!sound) { fprintf(stderr, "host expansion failed\n"); return 1; }
+      printf(", \"compression\": %d, \"chunks\": %zu, \"coded_bytes\": %zu, \"coded_upload_ms\": %.5f, \"unfax_stage_ms\": %.5f, \"coded_pixel_stage_ms\": %.5f, "
+             "\"host_scan_ms_per_image\": %.5f, \"host_unfax_ms_per_image\": %.5f",
+             c->compression, c->chunks.size(), c->bytes.size(), cms[0], cms[1], cms[2], scan_ms, unfax_ms);
     } else if (PaddleOCR::tiff::parse_deflate(bytes.data(), bytes.size(), *c) && c->frame.device_ok) {
       // the Deflate route: upload of the coded chunks, the inflate launch with its read-back and the pixel stage on the device,
       // against tiff::inflate_all - zlib on one thread - per image
@@ -345,6 +371,13 @@ static int stage_batches(const std::string& model_dir, int nargs, char** args, b
             b.frames.add(b.ims[i]);
             continue;
           }
+          if (route == PaddleOCR::tiff::kFaxRoute && PaddleOCR::tiff::parse_fax(bytes.data(), bytes.size(), *t) && t->frame.device_ok &&
+              t->frame.tile_width <= PaddleOCR::tiff::kMaxFaxDeviceWidth) {  // OCR_FRAME_TIFF_FAX
+            b.ims[i].rows = t->frame.height; b.ims[i].cols = t->frame.width;
+            b.ims[i].tiff_fax = t;
+            b.frames.add(b.ims[i]);
+            continue;
+          }
           if (route != PaddleOCR::tiff::kCoded || !t->frame.device_ok) {
             fprintf(stderr, "decode failed: %s\n", b.in[i].c_str());
             return 1;
@@ -409,6 +442,11 @@ static int decode_one(bool device, bool frame, const char* in, const char* outp)
     const ocr_tiff_coded d = im.tiff_deflate_frame();
     im.pixels.resize((size_t)d.frame.height * d.frame.width * 3);
     if (ocr_tiff_decode_deflate(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
+  } else
+  if (im.device_decodable() && im.tiff_fax) {
+    const ocr_tiff_fax d = im.tiff_fax_frame();
+    im.pixels.resize((size_t)d.coded.frame.height * d.coded.frame.width * 3);
+    if (ocr_tiff_decode_fax(&d, 0, im.pixels.data(), im.pixels.size()) != OCR_OK) { fprintf(stderr, "device decode failed: %s: %s\n", in, ocr_last_error()); return 1; }
   } else
   if (im.device_decodable() && im.tiff_coded) {
     const ocr_tiff_coded d = im.tiff_coded_frame();

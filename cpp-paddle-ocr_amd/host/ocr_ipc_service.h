@@ -217,7 +217,11 @@ inline bool decode_bmp(const std::vector<uint8_t>& d, Image& im, bool device_pix
   return d.size() >= 2 && d[0] == 'B' && d[1] == 'M' && decode_raw(d, im, device_pixels, force_device);
 }
 // TIFF as cv::imdecode(IMREAD_COLOR) returns it (tiff_decode.h: classic TIFF, strips and tiles, uncompressed / PackBits / LZW /
-// Deflate, the sample forms libtiff's RGBA interface reads).  device_pixels / force_device as for BMP and PNM; the switch is
+// Deflate / CCITT fax - Modified Huffman, Group 3, Group 4 -, the sample forms libtiff's RGBA interface reads).  A CCITT file is
+// expanded on this host thread (ccitt_decode.h) under =0 .. =3, and the expanded 1-bit frame then goes where the switch sends
+// such frames; =4 is =3 and hands CCITT files within the device bounds (and at most tiff::kMaxFaxDeviceWidth pixels a chunk)
+// over coded too (tiff::parse_fax, which walks every stream with the decoder's verdict: Image::tiff_fax, OCR_FRAME_TIFF_FAX).
+// A damaged fax stream refuses the file under every value alike, and *why says which rule of the coding did.  device_pixels / force_device as for BMP and PNM; the switch is
 // OCR_DEVICE_TIFF, read once: =1 stops after the chunks are expanded and leaves predictor, conversion and placement to the
 // worker (frames within the device stage's bounds, tiff::Frame::device_ok), =2 stops before the expansion already and leaves
 // the chunks' LZW / PackBits streams to the worker as well (tiff::parse_coded, which still scans every stream; Deflate files and
@@ -226,31 +230,43 @@ inline bool decode_bmp(const std::vector<uint8_t>& d, Image& im, bool device_pix
 // staging and the worker's fallback, one request per image, gives that file the host's refusal through Image::materialise),
 // =0 or unset finishes every file on this host thread.
 constexpr bool TIFF_DEVICE_DEFAULT = false;
-inline int tiff_device_mode() {  // 0 host, 1 expanded chunks to the device, 2 coded chunks to the device, 3 Deflate chunks too
+inline int tiff_device_mode() {  // 0 host, 1 expanded chunks to the device, 2 coded chunks to the device, 3 Deflate chunks too, 4 fax chunks too
   static const char* env = getenv("OCR_DEVICE_TIFF");
-  return env && env[0] ? (env[0] == '0' ? 0 : (env[0] == '2' || env[0] == '3') && !env[1] ? env[0] - '0' : 1) : (TIFF_DEVICE_DEFAULT ? 1 : 0);
+  return env && env[0] ? (env[0] == '0' ? 0 : (env[0] == '2' || env[0] == '3' || env[0] == '4') && !env[1] ? env[0] - '0' : 1) : (TIFF_DEVICE_DEFAULT ? 1 : 0);
 }
 inline bool tiff_device_enabled() { return tiff_device_mode() != 0; }
 inline bool is_tiff(const uint8_t* d, size_t n) {
   return n >= 4 && ((d[0] == 'I' && d[1] == 'I' && d[2] == 42 && d[3] == 0) || (d[0] == 'M' && d[1] == 'M' && d[2] == 0 && d[3] == 42));
 }
-inline bool decode_tiff(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false) {
+inline bool decode_tiff(const std::vector<uint8_t>& d, Image& im, bool device_pixels = false, bool force_device = false, const char** why = nullptr) {
   if (!is_tiff(d.data(), d.size())) return false;
   auto f = std::make_shared<tiff::Frame>();
   bool parsed = false;
-  if (device_pixels && tiff_device_mode() >= 2) {
+  const int mode = tiff_device_mode();
+  if (device_pixels && mode >= 2) {
     auto c = std::make_shared<tiff::Coded>();
-    bool deflate = false;  // =3: the container is read once, whatever the compression
-    const tiff::Route route = tiff_device_mode() == 3 ? tiff::parse_any(d.data(), d.size(), *c, deflate) : tiff::parse_coded(d.data(), d.size(), *c);
-    if (route == tiff::kRefused) return false;
+    bool deflate = false;  // the container is read once, whatever the compression; fax streams are walked once: here for =4, else by unfax_all
+    const char* fax_why = nullptr;
+    const tiff::Route route = tiff::parse_any(d.data(), d.size(), *c, deflate, mode >= 4, &fax_why);
+    if (route == tiff::kRefused) { if (why && fax_why) *why = fax_why; return false; }
     if (deflate) {
-      if (c->frame.device_ok) {
+      if (mode >= 3 && c->frame.device_ok) {
         im.pixels.clear();
         im.rows = c->frame.height; im.cols = c->frame.width;
         im.tiff_deflate = std::move(c);
         return true;
       }
       if (!tiff::inflate_all(*c, *f)) return false;  // (beyond the device bounds: the =1 route, from the container already read)
+      parsed = true;
+    } else
+    if (route == tiff::kFaxRoute) {
+      if (mode >= 4 && c->frame.device_ok && c->frame.tile_width <= tiff::kMaxFaxDeviceWidth) {
+        im.pixels.clear();
+        im.rows = c->frame.height; im.cols = c->frame.width;
+        im.tiff_fax = std::move(c);
+        return true;
+      }
+      if (!tiff::unfax_all(*c, *f, &fax_why)) { if (why && fax_why) *why = fax_why; return false; }  // (the =1 route, from the container already read)
       parsed = true;
     } else
     if (route == tiff::kCoded) {
@@ -264,7 +280,10 @@ inline bool decode_tiff(const std::vector<uint8_t>& d, Image& im, bool device_pi
       parsed = true;
     }
   }
-  if (!parsed && !tiff::parse(d.data(), d.size(), *f)) return false;
+  if (!parsed) {
+    const char* fax_why = nullptr;
+    if (!tiff::parse(d.data(), d.size(), *f, &fax_why)) { if (why && fax_why) *why = fax_why; return false; }
+  }
   im.pixels.clear();
   im.rows = f->height; im.cols = f->width;
   if (device_pixels && f->device_ok && (force_device || tiff_device_enabled())) { im.tiff = std::move(f); return true; }
@@ -427,7 +446,7 @@ inline bool decode_jpeg(const std::vector<uint8_t>& d, Image& im, bool device_pi
 inline bool decode_image(const std::vector<uint8_t>& bytes, Image& im, bool device_pixels = false, bool force_device = false, const char** why = nullptr) {
   return decode_png(bytes, im, device_pixels, force_device) || decode_jpeg(bytes, im, device_pixels) ||
          decode_ppm(bytes, im, device_pixels, force_device) || decode_bmp(bytes, im, device_pixels, force_device) ||
-         decode_tiff(bytes, im, device_pixels, force_device) || decode_webp(bytes, im, device_pixels, force_device, why) ||
+         decode_tiff(bytes, im, device_pixels, force_device, why) || decode_webp(bytes, im, device_pixels, force_device, why) ||
          decode_j2k(bytes, im, device_pixels, force_device, why);
 }
 inline bool read_file(const std::string& path, std::vector<uint8_t>& out) {

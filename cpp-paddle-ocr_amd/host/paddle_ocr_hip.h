@@ -74,6 +74,9 @@ struct Image {
   // stream is faulty - of all kinds this one alone can, the others were checked before they got here - so the worker calls it
   // per request and fails that request alone; where the device refused, the worker asks it and the host's answer stands
   std::shared_ptr<tiff::Coded> tiff_deflate;
+  // a CCITT fax TIFF whose container alone has been parsed and whose streams have been walked (tiff::parse_fax): the worker
+  // expands the chunks on the device, then goes on as for tiff (ocr_pipe_stage_batch, OCR_FRAME_TIFF_FAX)
+  std::shared_ptr<tiff::Coded> tiff_fax;
   // a lossless WebP whose entropy-coded image has been decoded (prefix codes, LZ77, colour cache): the worker undoes the
   // transforms on the device (ocr_pipe_stage_batch)
   std::shared_ptr<webp::Frame> webp;
@@ -94,8 +97,8 @@ struct Image {
     }
   }
   ImageView view() const { return ImageView{pixels.data(), rows, cols, (size_t)cols * 3}; }
-  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8 && !j2k && !j2k_coded && !tiff_coded && !tiff_deflate; }
-  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8 || j2k || j2k_coded || tiff_coded || tiff_deflate); }
+  bool empty() const { return pixels.empty() && !jpeg && !png && !raw && !tiff && !webp && !vp8 && !j2k && !j2k_coded && !tiff_coded && !tiff_deflate && !tiff_fax; }
+  bool device_decodable() const { return pixels.empty() && (jpeg || png || raw || tiff || webp || vp8 || j2k || j2k_coded || tiff_coded || tiff_deflate || tiff_fax); }
   void materialise() {  // the pixel half of the JPEG / PNG / BMP / PNM / TIFF / WebP on the host
     if (!device_decodable()) return;
     if (j2k_coded) {
@@ -123,6 +126,12 @@ struct Image {
       tiff::Frame f;
       if (!tiff::inflate_all(*tiff_deflate, f) || !tiff::pixels(f, pixels)) throw std::runtime_error("TIFF conversion failed");
       tiff_deflate.reset();
+      return;
+    }
+    if (tiff_fax) {
+      tiff::Frame f;
+      if (!tiff::unfax_all(*tiff_fax, f) || !tiff::pixels(f, pixels)) throw std::runtime_error("TIFF conversion failed");
+      tiff_fax.reset();
       return;
     }
     if (tiff_coded) {
@@ -171,6 +180,13 @@ struct Image {
   }
   ocr_tiff_coded tiff_coded_frame() const { return coded_frame_of(*tiff_coded); }      // only when tiff_coded
   ocr_tiff_coded tiff_deflate_frame() const { return coded_frame_of(*tiff_deflate); }  // only when tiff_deflate
+  ocr_tiff_fax tiff_fax_frame() const {  // only when tiff_fax
+    ocr_tiff_fax d;
+    memset(&d, 0, sizeof d);
+    d.coded = coded_frame_of(*tiff_fax);
+    d.t4_options = tiff_fax->t4_options;
+    return d;
+  }
   static ocr_tiff_coded coded_frame_of(const tiff::Coded& c) {
     static_assert(sizeof(tiff::Chunk) == sizeof(ocr_tiff_chunk), "tiff::Chunk is ocr_tiff_chunk");
     const tiff::Frame& f = c.frame;
@@ -268,6 +284,7 @@ struct DeviceFrames {
   std::deque<ocr_j2k_frame> kf;
   std::deque<ocr_j2k_coded> kcf;
   std::deque<ocr_tiff_coded> tcf, tdf;
+  std::deque<ocr_tiff_fax> tff;
   std::vector<ocr_coded_frame> list;
   template <class D>
   void push(std::deque<D>& q, int kind, const D& d) {
@@ -280,6 +297,7 @@ struct DeviceFrames {
     else if (im.vp8) push(vf, OCR_FRAME_VP8, im.vp8_frame());
     else if (im.webp) push(wf, OCR_FRAME_WEBP, im.webp_frame());
     else if (im.tiff_deflate) push(tdf, OCR_FRAME_TIFF_DEFLATE, im.tiff_deflate_frame());
+    else if (im.tiff_fax) push(tff, OCR_FRAME_TIFF_FAX, im.tiff_fax_frame());
     else if (im.tiff_coded) push(tcf, OCR_FRAME_TIFF_CODED, im.tiff_coded_frame());
     else if (im.tiff) push(tf, OCR_FRAME_TIFF, im.tiff_frame());
     else if (im.raw) push(rf, OCR_FRAME_RAW, im.raw_frame());

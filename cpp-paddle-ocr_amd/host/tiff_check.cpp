@@ -16,7 +16,7 @@
 //   status 1 for a refused file, 3 for one that takes the other route (Deflate).
 // tiff_check --expand <in> <out>: tiff::expand over Codeds of that form, one after another; out: Frame::data of each (nothing
 //   for a refused one: the exit status is 1 then) - what the device expansion is compared with.  Prints "ok" or "refused" per frame.
-// tiff_check --why <file> [...]: per file "<file>: ok", "refused" or "other route" (parse_coded's answer).
+// tiff_check --why <file> [...]: per file "<file>: ok", "refused", "other route" or - a sound CCITT file - "fax" (parse_coded's answer).
 // tiff_check --extents <streams> <out>: streams: repeated [u32 compression (5 or 32773), u32 need, u32 length][the bytes];
 //   out: per stream two bytes, the verdict of lzw_extent / packbits_extent and that of unlzw / unpack_bits for the same need.
 // tiff_check --route-deflate <file> <out> [...]: tiff::parse_deflate; out: the Coded in the form of --coded.  Exit status 1 for a
@@ -25,6 +25,14 @@
 //   produced][need bytes: what zlib wrote, zeros behind] - tiff::detail::inflate_count, the host's verdict the device's inflate
 //   kernel is held to (and the form of inflate_check).  Prints "<streams> <good>".
 // tiff_check --inflate-all <in> <out>: tiff::inflate_all over Codeds of that form; out and what is printed as --expand.
+// tiff_check --route-fax <file> <out> [...]: tiff::parse_fax; out: the Coded in the form of --coded with [u32 T4Options] behind the
+//   compression.  Exit status 1 for a file that is refused or is not a CCITT one; its reason goes to stderr.
+// tiff_check --unfax <in> <out>: tiff::unfax_all over Codeds of that form; out as --expand; prints "ok" or "refused: <reason>" per
+//   frame - what the device's fax expansion is compared with.
+// tiff_check --fax-why <file> [...]: per file "<file>: <parse_fax's answer> | <parse's answer>", an answer being "ok", the reason
+//   a rule of the coding refused the file with, or "refused" (the container did).
+// tiff_check --fax-scan <streams> <out>: streams: repeated [u32 compression, T4Options, width, rows, length][the bytes]; out: per
+//   stream two bytes, the verdict of ccitt::walk as the scan (no output) and as the decoder, into a block of exactly rows * row bytes.
 #include <dirent.h>
 
 #include <cstdio>
@@ -83,14 +91,17 @@ static int pixels_of_frames(const char* in, const char* outp) {
   return rc;
 }
 
-static const char* const kRouteName[] = {"refused", "ok", "other route"};
+static const char* const kRouteName[] = {"refused", "ok", "other route", "fax"};
 
-static int coded_of_file(const char* in, const char* outp, bool deflate = false) {
+static int coded_of_file(const char* in, const char* outp, bool deflate = false, bool fax = false) {
   std::unique_ptr<uint8_t[]> buf;
   size_t n = 0;
   if (!read_exact(in, buf, n)) { fprintf(stderr, "cannot read %s\n", in); return 2; }
   tiff::Coded c;
-  if (deflate) {
+  if (fax) {
+    const char* why = nullptr;
+    if (!tiff::parse_fax(buf.get(), n, c, &why)) { fprintf(stderr, "refused: %s: %s\n", why ? why : "the container", in); return 1; }
+  } else if (deflate) {
     if (!tiff::parse_deflate(buf.get(), n, c)) { fprintf(stderr, "refused: %s\n", in); return 1; }
   } else {
     const tiff::Route route = tiff::parse_coded(buf.get(), n, c);
@@ -105,6 +116,7 @@ static int coded_of_file(const char* in, const char* outp, bool deflate = false)
   fwrite(head, 1, sizeof head, o);
   fwrite(f.palette, 1, 1024, o);
   fwrite(&comp, 1, 4, o);
+  if (fax) fwrite(&c.t4_options, 1, 4, o);
   fwrite(&nchunks, 1, 8, o);
   for (const tiff::Chunk& k : c.chunks) { fwrite(&k.byte_off, 1, 8, o); fwrite(&k.byte_len, 1, 4, o); fwrite(&k.rows, 1, 4, o); }
   fwrite(&len, 1, 8, o);
@@ -114,7 +126,7 @@ static int coded_of_file(const char* in, const char* outp, bool deflate = false)
   return 0;
 }
 
-static int expand_codeds(const char* in, const char* outp, bool deflate = false) {
+static int expand_codeds(const char* in, const char* outp, bool deflate = false, bool fax = false) {
   FILE* f = fopen(in, "rb");
   FILE* o = fopen(outp, "wb");
   if (!f || !o) return 2;
@@ -125,7 +137,8 @@ static int expand_codeds(const char* in, const char* outp, bool deflate = false)
     tiff::Coded c;
     const size_t got = fread(head, 1, sizeof head, f);
     if (got == 0) break;
-    if (got != sizeof head || fread(c.frame.palette, 1, 1024, f) != 1024 || fread(&comp, 1, 4, f) != 4 || fread(&nchunks, 1, 8, f) != 8) return 2;
+    if (got != sizeof head || fread(c.frame.palette, 1, 1024, f) != 1024 || fread(&comp, 1, 4, f) != 4 || (fax && fread(&c.t4_options, 1, 4, f) != 4) ||
+        fread(&nchunks, 1, 8, f) != 8) return 2;
     tiff::Frame& fr = c.frame;
     fr.width = head[0]; fr.height = head[1]; fr.photometric = head[2]; fr.bits = head[3]; fr.samples = head[4];
     fr.planar = head[5]; fr.predictor = head[6]; fr.big_endian = head[7]; fr.premultiply = head[8];
@@ -142,6 +155,13 @@ static int expand_codeds(const char* in, const char* outp, bool deflate = false)
     c.bytes.assign(pool.get(), pool.get() + len);
     c.bytes.shrink_to_fit();
     tiff::Frame out;
+    if (fax) {
+      const char* why = nullptr;
+      if (!tiff::unfax_all(c, out, &why)) { rc = 1; printf("refused: %s\n", why ? why : "?"); continue; }
+      printf("ok\n");
+      fwrite(out.data.data(), 1, out.data.size(), o);
+      continue;
+    }
     if (!(deflate ? tiff::inflate_all(c, out) : tiff::expand(c, out))) { rc = 1; printf("refused\n"); continue; }
     printf("ok\n");
     fwrite(out.data.data(), 1, out.data.size(), o);
@@ -166,6 +186,28 @@ static int extents_of_streams(const char* in, const char* outp) {
     uint8_t verdict[2];
     if (head[0] == 5) { verdict[0] = tiff::detail::lzw_extent(s.get(), len, need); verdict[1] = tiff::detail::unlzw(s.get(), len, out.get(), need); }
     else { verdict[0] = tiff::detail::packbits_extent(s.get(), len, need); verdict[1] = tiff::detail::unpack_bits(s.get(), len, out.get(), need); }
+    fwrite(verdict, 1, 2, o);
+  }
+  fclose(f);
+  fclose(o);
+  return 0;
+}
+
+static int fax_scan_streams(const char* in, const char* outp) {
+  FILE* f = fopen(in, "rb");
+  FILE* o = fopen(outp, "wb");
+  if (!f || !o) return 2;
+  for (;;) {
+    uint32_t head[5];
+    const size_t got = fread(head, 1, sizeof head, f);
+    if (got == 0) break;
+    if (got != sizeof head || head[2] < 1 || head[2] > (1u << 20) || head[3] > (1u << 16) || head[4] > (1u << 26)) return 2;
+    const size_t len = head[4], row_bytes = (head[2] + 7) / 8, need = row_bytes * head[3];
+    std::unique_ptr<uint8_t[]> s(new uint8_t[len ? len : 1]), out(new uint8_t[need ? need : 1]);  // exactly their sizes
+    if (fread(s.get(), 1, len, f) != len) return 2;
+    memset(out.get(), 0, need);
+    const uint8_t verdict[2] = {!ccitt::walk(s.get(), len, (int)head[0], head[1], head[2], head[3], nullptr, 0),
+                                !ccitt::walk(s.get(), len, (int)head[0], head[1], head[2], head[3], out.get(), row_bytes)};
     fwrite(verdict, 1, 2, o);
   }
   fclose(f);
@@ -249,6 +291,26 @@ int main(int argc, char** argv) {
       if (const int rc = coded_of_file(argv[i], argv[i + 1], true)) return rc;
     return 0;
   }
+  if (mode == "--route-fax" && argc >= 4 && argc % 2 == 0) {
+    for (int i = 2; i < argc; i += 2)
+      if (const int rc = coded_of_file(argv[i], argv[i + 1], false, true)) return rc;
+    return 0;
+  }
+  if (mode == "--unfax" && argc == 4) return expand_codeds(argv[2], argv[3], false, true);
+  if (mode == "--fax-scan" && argc == 4) return fax_scan_streams(argv[2], argv[3]);
+  if (mode == "--fax-why" && argc >= 3) {
+    for (int i = 2; i < argc; ++i) {
+      std::unique_ptr<uint8_t[]> buf;
+      size_t n = 0;
+      if (!read_exact(argv[i], buf, n)) { fprintf(stderr, "cannot read %s\n", argv[i]); return 2; }
+      tiff::Coded c;
+      tiff::Frame frame;
+      const char *scan = nullptr, *full = nullptr;
+      const bool a = tiff::parse_fax(buf.get(), n, c, &scan), b = tiff::parse(buf.get(), n, frame, &full);
+      printf("%s: %s | %s\n", argv[i], a ? "ok" : scan ? scan : "refused", b ? "ok" : full ? full : "refused");
+    }
+    return 0;
+  }
   if (mode == "--extents" && argc == 4) return extents_of_streams(argv[2], argv[3]);
   if (mode == "--why" && argc >= 3) {
     for (int i = 2; i < argc; ++i) {
@@ -274,6 +336,7 @@ int main(int argc, char** argv) {
     return 0;
   }
   fprintf(stderr, "usage: tiff_check --decode <file> <out> [...] | --pixels <descriptors> <out> | --reject <dir> | --chunks <file> <out> [...] | --coded <file> <out> [...] | --expand <codeds> <out> | "
-                  "--why <file> [...] | --extents <streams> <out> | --route-deflate <file> <out> [...] | --inflate <streams> <out> | --inflate-all <codeds> <out>\n");
+                  "--why <file> [...] | --extents <streams> <out> | --route-deflate <file> <out> [...] | --inflate <streams> <out> | --inflate-all <codeds> <out> | "
+                  "--route-fax <file> <out> [...] | --unfax <codeds> <out> | --fax-why <file> [...] | --fax-scan <streams> <out>\n");
   return 2;
 }

@@ -32,14 +32,20 @@
 //     with the reduced a; 1 (associated) and 0 (unspecified): the colour as stored.  Alpha is then dropped
 //   - CMYK 8 bits chunky: (255 - c) * (255 - k) / 255, rounded down; InkSet absent or 1; samples beyond the four skipped
 //   - 16-bit words are read in the file's byte order, and the predictor's sum runs on those words
-// Orientation is ignored: rows are taken as stored (UNPINNED).  YCbCr, CIELab, masks, CCITT and
-// JPEG compression are refused.
+//   - Compression 2, 32771 (Modified Huffman RLE), 3 (T.4 / Group 3, 1-D and 2-D) and 4 (T.6 / Group 4): bilevel fax pages,
+//     through ccitt_decode.h, which states what is decoded.  1 bit, 1 sample, photometric 0 or 1, no predictor; T4Options
+//     absent means 0.  The chunks come out as 1-bit rows, white 0 and black 1 whatever the photometric says, and go the way of
+//     1-bit grey.  A damaged stream refuses the file with a reason (fax_why) - stricter than libtiff, which patches such rows
+//     with white and warns, as for LZW above; uncompressed mode (T4Options / T6Options bit 1) is refused, as libtiff does
+// Orientation is ignored: rows are taken as stored (UNPINNED).  YCbCr, CIELab, masks and JPEG compression
+// are refused.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
+#include "ccitt_decode.h"
 #include "png_decode.h"
 
 namespace PaddleOCR {
@@ -52,6 +58,7 @@ constexpr int kMaxSamples = 16;                 // per pixel
 // unit of its work is found by division - so the bound is on what a header can make it walk: chunks at their nominal size.
 constexpr size_t kMaxDeviceChunks = 1u << 20;
 constexpr size_t kMaxDeviceBytes = (size_t)1 << 29;
+constexpr int kMaxFaxDeviceWidth = 8192;  // pixels of a CCITT chunk row that the device expansion takes (csrc/kernels_tiff_fax.h)
 
 struct Frame {  // ocr_tiff_frame of include/ocr_hip.h, field for field
   int width = 0, height = 0;
@@ -120,8 +127,10 @@ struct Coded {
   int compression = 1;        // 1, 5 (LZW) or 32773 (PackBits); 8 or 32946 (Deflate) from parse_deflate alone
   std::vector<Chunk> chunks;  // in the order Frame::data has them: plane by plane, row of chunks by row of chunks
   std::vector<uint8_t> bytes; // the coded chunks one after another, MSB first (FillOrder 2 is undone)
+  uint32_t t4_options = 0;    // a fax frame (compression 2, 3, 4 or 32771, from parse_fax alone): T4Options of Compression 3, else 0
 };
-enum Route { kRefused = 0, kCoded = 1, kOtherRoute = 2 };  // of parse_coded; kOtherRoute: Deflate, which goes through parse()
+// of parse_coded; kOtherRoute: Deflate, which goes through parse(); kFaxRoute: a sound CCITT file, which parse_fax() hands over
+enum Route { kRefused = 0, kCoded = 1, kOtherRoute = 2, kFaxRoute = 3 };
 
 namespace detail {
 
@@ -290,6 +299,8 @@ struct Head {
   Reader r{nullptr, 0, false};
   Geometry g;
   uint32_t comp = 1, fill = 1;
+  uint32_t t4 = 0;            // T4Options of a Compression 3 file
+  const char* why = nullptr;  // a CCITT file that is refused for a rule of its coding: which
   bool tiled = false;
   size_t chunks = 0;
   Tag offs, counts;
@@ -314,8 +325,8 @@ inline bool parse_head(const uint8_t* d, size_t n, Frame& f, Head& hd) {
   if (ifd < 8 || ifd > n - 2) return false;
   const size_t entries = r.u16(ifd);
   if ((n - ifd - 2) / 12 < entries) return false;
-  enum { W, H, BPS, COMP, PHOTO, FILL, OFFS, SPP, RPS, COUNTS, PLANAR, PRED, CMAP, TW, TL, TOFFS, TCOUNTS, EXTRA, FORMAT, INK, kTags };
-  static const uint16_t ids[kTags] = {256, 257, 258, 259, 262, 266, 273, 277, 278, 279, 284, 317, 320, 322, 323, 324, 325, 338, 339, 332};
+  enum { W, H, BPS, COMP, PHOTO, FILL, OFFS, SPP, RPS, COUNTS, PLANAR, PRED, CMAP, TW, TL, TOFFS, TCOUNTS, EXTRA, FORMAT, INK, T4OPT, T6OPT, kTags };
+  static const uint16_t ids[kTags] = {256, 257, 258, 259, 262, 266, 273, 277, 278, 279, 284, 317, 320, 322, 323, 324, 325, 338, 339, 332, 292, 293};
   Tag tag[kTags];
   for (size_t e = 0; e < entries; ++e) {
     const size_t at = ifd + 2 + 12 * e;
@@ -341,7 +352,16 @@ inline bool parse_head(const uint8_t* d, size_t n, Frame& f, Head& hd) {
   const uint32_t spp = one(SPP, 1), comp = one(COMP, 1), photo = one(PHOTO, 0), fill = one(FILL, 1), planar = one(PLANAR, 1);
   uint32_t pred = one(PRED, 1);
   if (spp < 1 || spp > (uint32_t)kMaxSamples || (fill != 1 && fill != 2) || (planar != 1 && planar != 2)) return false;
-  if (comp != 1 && comp != 5 && comp != 8 && comp != 32946 && comp != 32773) return false;
+  const bool fax = ccitt::is_fax((int)comp);
+  if (comp != 1 && comp != 5 && comp != 8 && comp != 32946 && comp != 32773 && !fax) return false;
+  if (fax) {  // the rules of the coding that the container shows
+    if (pred == 2) { hd.why = "fax: CCITT coding takes no predictor"; return false; }
+    if ((tag[BPS].present && (tag[BPS].count != 1 || value(r, tag[BPS], 0) != 1)) || spp != 1) { hd.why = "fax: CCITT coding needs 1 bit per sample and 1 sample per pixel"; return false; }
+    if (photo > 1) { hd.why = "fax: CCITT coding needs photometric 0 or 1"; return false; }
+    if ((comp == 3 && (one(T4OPT, 0) & 2)) || (comp == 4 && (one(T6OPT, 0) & 2))) { hd.why = ccitt::kUncompressed; return false; }
+    if (comp == 3 && (one(T4OPT, 0) & ~7u)) { hd.why = "fax: T4Options has bits beyond 0 .. 2"; return false; }
+    hd.t4 = comp == 3 ? one(T4OPT, 0) : 0;
+  }
   if (comp == 1 || comp == 32773) pred = 1;  // (the tag belongs to the LZW and Deflate codecs: libtiff does not read it here)
   if (pred != 1 && pred != 2) return false;
   uint32_t bits = 1;
@@ -406,7 +426,8 @@ inline bool parse_head(const uint8_t* d, size_t n, Frame& f, Head& hd) {
     const size_t rows = cy + 1 == (size_t)g.down && !tiled ? (size_t)h - cy * f.tile_height : (size_t)f.tile_height;
     if (comp == 1 && len < rows * g.row_bytes) return false;
     // no codec here expands beyond 2800 to 1 (LZW: a 12-bit code for a string of 4094 bytes at most; Deflate 1032, PackBits 64)
-    if (comp != 1 && rows * g.row_bytes / 2800 > len) return false;
+    // a fax row takes a bit at least (a V0 code)
+    if (fax ? rows / 8 > len : comp != 1 && rows * g.row_bytes / 2800 > len) return false;
     coded += len;
   }
   if (comp != 1 && coded == 0) return false;
@@ -450,7 +471,9 @@ inline const char* coded_fault(const Coded& c, Geometry& g) {
 
 // The expansion: every chunk of a coded frame to its nominal size, as Frame::data holds them.  The records are checked here,
 // the streams by the expanders themselves; false where coded_fault() would have refused.
+inline bool unfax_all(const Coded& c, Frame& f, const char** why);
 inline bool expand(const Coded& c, Frame& f) {
+  if (ccitt::is_fax(c.compression)) return unfax_all(c, f, nullptr);  // a frame of parse_fax()
   Geometry g;
   if (!c.frame.data.empty() || detail::structure_fault(c.frame, c.compression, c.chunks.data(), c.chunks.size(), c.bytes.size(), g)) { f = Frame(); return false; }
   f = c.frame;
@@ -499,6 +522,79 @@ inline bool gather(const uint8_t* d, const Head& h, Coded& c, bool scan) {
 }
 }  // namespace detail
 
+// The fax route (Compression 2, 3, 4 and 32771), reached by names of its own.  The rules of a fax frame over its parts
+// (csrc/capi_tiff.hip runs the same text on its side of the ABI): fault(), what the coding asks of the frame, the records, and
+// ccitt::walk over every chunk's stream with no output - the decoder's own verdict, found on the host, because the device
+// expander cannot refuse a file.  nullptr when it is sound.
+inline const char* fax_structure_fault(const Frame& f, int compression, uint32_t t4, const Chunk* chunks, size_t nchunks, size_t pool, Geometry& g) {
+  if (const char* why = fault(f, g)) return why;
+  if (!ccitt::is_fax(compression)) return "fax: compression must be 2, 3, 4 or 32771 (CCITT)";
+  if (f.bits != 1 || f.samples != 1) return "fax: CCITT coding needs 1 bit per sample and 1 sample per pixel";
+  if (f.photometric > 1) return "fax: CCITT coding needs photometric 0 or 1";
+  if (f.predictor != 1) return "fax: CCITT coding takes no predictor";
+  if (t4 & 2) return ccitt::kUncompressed;
+  if ((t4 & ~7u) || (compression != 3 && t4)) return "fax: T4Options has bits beyond 0 .. 2, or belongs to another coding than Compression 3";
+  if (nchunks != (size_t)g.across * g.down * g.planes || (nchunks && !chunks)) return "coded: as many chunk records as the geometry has chunks";
+  for (size_t c = 0; c < nchunks; ++c) {
+    if (chunks[c].rows < 1 || chunks[c].rows > (uint32_t)f.tile_height) return "coded: a chunk's rows must be 1 .. tile_height";
+    if (chunks[c].byte_off > pool || pool - chunks[c].byte_off < chunks[c].byte_len) return "coded: a chunk's bytes lie outside the pool";
+  }
+  return nullptr;
+}
+inline const char* fax_fault_of(const Frame& f, int compression, uint32_t t4, const Chunk* chunks, size_t nchunks, const uint8_t* bytes, size_t pool, Geometry& g) {
+  if (const char* why = fax_structure_fault(f, compression, t4, chunks, nchunks, pool, g)) return why;
+  if (pool && !bytes) return "coded: the byte pool is missing";
+  for (size_t c = 0; c < nchunks; ++c)
+    if (const char* why = ccitt::walk(bytes + chunks[c].byte_off, chunks[c].byte_len, compression, t4, (uint32_t)f.tile_width, chunks[c].rows, nullptr, 0)) return why;
+  return nullptr;
+}
+inline const char* fax_fault(const Coded& c, Geometry& g) {
+  if (!c.frame.data.empty()) return "coded: a coded frame carries no expanded chunks";
+  return fax_fault_of(c.frame, c.compression, c.t4_options, c.chunks.data(), c.chunks.size(), c.bytes.data(), c.bytes.size(), g);
+}
+// The host expansion of a fax frame: what parse() gives for the file.  false, with the reason at *why, where fax_fault() would
+// have refused: the records are checked here, the streams by the decoder itself.
+inline bool unfax_all(const Coded& c, Frame& f, const char** why = nullptr) {
+  Geometry g;
+  const char* w = !c.frame.data.empty() ? "coded: a coded frame carries no expanded chunks"
+                                        : fax_structure_fault(c.frame, c.compression, c.t4_options, c.chunks.data(), c.chunks.size(), c.bytes.size(), g);
+  if (!w) {
+    f = c.frame;
+    for (size_t k = 0; k < c.chunks.size() && !w; ++k) {
+      f.data.resize((k + 1) * g.chunk_bytes, 0);  // (chunk by chunk, as parse() grows it; rows of a strip the image does not have stay zero)
+      w = ccitt::walk(c.bytes.data() + c.chunks[k].byte_off, c.chunks[k].byte_len, c.compression, c.t4_options, (uint32_t)f.tile_width, c.chunks[k].rows,
+                      f.data.data() + k * g.chunk_bytes, g.row_bytes);
+    }
+  }
+  if (why) *why = w;
+  if (w) { f = Frame(); return false; }
+  f.device_ok = c.chunks.size() <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
+  return true;
+}
+namespace detail {
+inline bool gather_fax(const uint8_t* d, const Head& h, Coded& c, bool scan, const char** why) {
+  gather_bytes(d, h, c);
+  c.t4_options = h.t4;
+  Geometry g;
+  const char* w = scan ? fax_fault(c, g) : fax_structure_fault(c.frame, c.compression, c.t4_options, c.chunks.data(), c.chunks.size(), c.bytes.size(), g);
+  if (why) *why = w;
+  if (w) return false;
+  c.frame.device_ok = h.chunks <= kMaxDeviceChunks && g.total <= kMaxDeviceBytes;
+  return true;
+}
+}  // namespace detail
+// The container alone of a CCITT file: one Chunk per strip or tile, the coding and the T4 options, every stream scanned with the
+// decoder's verdict - so that true means unfax_all(), on the host or on the device, has what it needs.  false: not such a
+// file, or a refused one; *why then says which rule of the coding refused it (nullptr: the container did, or it is no fax file).
+inline bool parse_fax(const uint8_t* d, size_t n, Coded& c, const char** why = nullptr) {
+  c = Coded();
+  if (why) *why = nullptr;
+  detail::Head h;
+  if (!detail::parse_head(d, n, c.frame, h)) { if (why) *why = h.why; c = Coded(); return false; }
+  if (!ccitt::is_fax((int)h.comp) || !detail::gather_fax(d, h, c, true, why)) { c = Coded(); return false; }
+  return true;
+}
+
 // The container alone, for the files whose expansion the device can take: Compression 1, 5 and 32773.  Every chunk's stream
 // is scanned (coded_fault), so that kCoded means expand() - on the host or on the device - has what it needs.  Deflate answers
 // kOtherRoute: parse() is the way.
@@ -506,6 +602,11 @@ inline Route parse_coded(const uint8_t* d, size_t n, Coded& c) {
   c = Coded();
   detail::Head h;
   if (!detail::parse_head(d, n, c.frame, h)) { c = Coded(); return kRefused; }
+  if (ccitt::is_fax((int)h.comp)) {  // a sound CCITT file: parse_fax() is the way; an unsound one is refused here already
+    const bool ok = detail::gather_fax(d, h, c, true, nullptr);
+    c = Coded();
+    return ok ? kFaxRoute : kRefused;
+  }
   if (h.comp != 1 && h.comp != 5 && h.comp != 32773) { c = Coded(); return kOtherRoute; }
   if (!detail::gather(d, h, c, true)) { c = Coded(); return kRefused; }
   return kCoded;
@@ -530,11 +631,19 @@ inline bool parse_deflate(const uint8_t* d, size_t n, Coded& c) {
   return true;
 }
 // parse_coded() and parse_deflate() behind one reading of the container: kCoded with `deflate` false is parse_coded()'s answer,
-// kCoded with `deflate` true parse_deflate()'s; kOtherRoute does not occur.
-inline Route parse_any(const uint8_t* d, size_t n, Coded& c, bool& deflate) {
+// kCoded with `deflate` true parse_deflate()'s; kFaxRoute is parse_fax()'s true, with the fax frame in c - with scan_fax false its
+// streams have not been walked, for a caller that goes on to unfax_all(), which gives the same verdict; kOtherRoute does not
+// occur.  why: as parse_fax's.
+inline Route parse_any(const uint8_t* d, size_t n, Coded& c, bool& deflate, bool scan_fax = true, const char** why = nullptr) {
   c = Coded();
+  if (why) *why = nullptr;
   detail::Head h;
-  if (!detail::parse_head(d, n, c.frame, h)) { c = Coded(); return kRefused; }
+  if (!detail::parse_head(d, n, c.frame, h)) { if (why) *why = h.why; c = Coded(); return kRefused; }
+  if (ccitt::is_fax((int)h.comp)) {
+    deflate = false;
+    if (!detail::gather_fax(d, h, c, scan_fax, why)) { c = Coded(); return kRefused; }
+    return kFaxRoute;
+  }
   deflate = h.comp == 8 || h.comp == 32946;
   if (!deflate) {
     if (!detail::gather(d, h, c, true)) { c = Coded(); return kRefused; }
@@ -560,10 +669,17 @@ inline bool inflate_all(const Coded& c, Frame& f) {
 }
 
 // The container and the expansion: everything but the pixels.  false = not a TIFF file, or one that is refused.
-inline bool parse(const uint8_t* d, size_t n, Frame& f) {
+inline bool parse(const uint8_t* d, size_t n, Frame& f, const char** why = nullptr) {
   using namespace detail;
   Head h;
-  if (!parse_head(d, n, f, h)) return false;
+  if (why) *why = nullptr;
+  if (!parse_head(d, n, f, h)) { if (why) *why = h.why; return false; }
+  if (ccitt::is_fax((int)h.comp)) {
+    Coded c;  // parse_fax + unfax_all, less the scan: the decoder refuses what its scan refuses
+    c.frame = f;
+    if (!gather_fax(d, h, c, false, why) || !unfax_all(c, f, why)) { f = Frame(); return false; }
+    return true;
+  }
   if (h.comp == 1 || h.comp == 5 || h.comp == 32773) {
     Coded c;  // parse_coded + expand, less the scan: unlzw / unpack_bits refuse what lzw_extent / packbits_extent refuse
     c.frame = f;

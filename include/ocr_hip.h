@@ -466,6 +466,26 @@ int ocr_tiff_decode_deflate(const ocr_tiff_coded* coded, int device_id, uint8_t*
  * ms[2] = the pixel stage's kernels; ocr_tiff_time_deflate_batch: `count` frames as ONE batch. */
 int ocr_tiff_time_deflate(const ocr_tiff_coded* coded, int device_id, int iters, double ms[3]);
 int ocr_tiff_time_deflate_batch(const ocr_tiff_coded* const* coded, int count, int device_id, int iters, double ms[3]);
+/* CCITT fax TIFFs (Compression 2 and 32771: Modified Huffman RLE; 3: T.4 / Group 3; 4: T.6 / Group 4) through entry points
+ * of their own: the caller stops before the expansion (host/tiff_decode.h, tiff::parse_fax) and hands over the frame - 1 bit,
+ * 1 sample, photometric 0 or 1 - with one record per strip or tile, the coding and the T4 options.  One chunk is expanded by
+ * one wavefront (csrc/kernels_tiff_fax.hip) into device scratch, to the bytes of tiff::unfax_all: rows of 1-bit pixels, white 0
+ * and black 1, which the 1-bit grey pixel stage takes.  Every field and every stream is checked on the host before anything
+ * is launched (tiff::fax_fault_of, which walks each chunk's codes with the decoder's own verdict: OCR_ERR_ARG, ocr_last_error
+ * says which rule, nothing launched, the output untouched).  A chunk wider than 8192 pixels and a frame beyond the bounds of
+ * ocr_tiff_coded are refused here - tiff::unfax_all and ocr_tiff_decode take them. */
+typedef struct ocr_tiff_fax {
+  ocr_tiff_coded coded;  /* compression 2, 3, 4 or 32771 */
+  uint32_t t4_options;   /* T4Options of Compression 3 (bit 0: two-dimensional; bit 2: fill bits), else 0 */
+} ocr_tiff_fax;
+/* the expansion alone, out as ocr_tiff_expand's */
+int ocr_tiff_unfax(const ocr_tiff_fax* fax, int device_id, uint8_t* out, size_t cap);
+/* the expansion, then the launches of ocr_tiff_decode, on one stream with no host round trip in between */
+int ocr_tiff_decode_fax(const ocr_tiff_fax* fax, int device_id, uint8_t* bgr, size_t cap_bytes);
+/* measurement aid (decode_tool --time): ms[0] = the upload, ms[1] = the expansion, ms[2] = the pixel stage's kernels;
+ * ocr_tiff_time_fax_batch: `count` frames as ONE batch. */
+int ocr_tiff_time_fax(const ocr_tiff_fax* fax, int device_id, int iters, double ms[3]);
+int ocr_tiff_time_fax_batch(const ocr_tiff_fax* const* fax, int count, int device_id, int iters, double ms[3]);
 /* Lossless WebP inputs with the pixel half of the decoder on the device: the caller parses the container and does what is
  * serial (prefix codes, LZ77, the colour cache: host/webp_decode.h, webp::parse); the inverse transforms - spatial predictor,
  * cross-colour, add-green, palette with pixel bundling - run on the copy stream straight into the slot.  The pixels are
@@ -603,10 +623,10 @@ int ocr_j2k_time_coded_batch(const ocr_j2k_coded* const* coded, int count, int d
 /* A batch as a tagged list: image i is frames[i].frame, a descriptor of the type frames[i].kind names - JPEG, PNG, raw, TIFF,
  * WebP, VP8 and JPEG 2000 frames (coefficient form and coded form) and coded TIFF frames in any mix.  ocr_pipe_stage_frames and the three entry points it lists stay as equivalents for the kinds they know:
  * all five validate their own argument list and stage through the same code, with the same bytes in the slot. */
-typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5, OCR_FRAME_J2K = 6, OCR_FRAME_J2K_CODED = 7, OCR_FRAME_TIFF_CODED = 8, OCR_FRAME_TIFF_DEFLATE = 9 } ocr_frame_kind;
+typedef enum ocr_frame_kind { OCR_FRAME_JPEG = 0, OCR_FRAME_PNG = 1, OCR_FRAME_RAW = 2, OCR_FRAME_TIFF = 3, OCR_FRAME_WEBP = 4, OCR_FRAME_VP8 = 5, OCR_FRAME_J2K = 6, OCR_FRAME_J2K_CODED = 7, OCR_FRAME_TIFF_CODED = 8, OCR_FRAME_TIFF_DEFLATE = 9, OCR_FRAME_TIFF_FAX = 10 } ocr_frame_kind;
 typedef struct ocr_coded_frame {
   int kind;           /* ocr_frame_kind */
-  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame, ocr_vp8_frame, ocr_j2k_frame, ocr_j2k_coded or ocr_tiff_coded (TIFF_CODED and TIFF_DEFLATE) */
+  const void* frame;  /* ocr_jpeg_frame, ocr_png_frame, ocr_raw_frame, ocr_tiff_frame, ocr_webp_frame, ocr_vp8_frame, ocr_j2k_frame, ocr_j2k_coded, ocr_tiff_coded (TIFF_CODED and TIFF_DEFLATE) or ocr_tiff_fax */
 } ocr_coded_frame;
 int ocr_pipe_stage_batch(ocr_pipe* h, int slot, const ocr_coded_frame* frames, int count);
 const char* ocr_pipe_label(ocr_pipe* h, int id);
