@@ -1212,6 +1212,32 @@ FRAME_TIFF_DEFLATE = 9
 FRAME_TIFF_FAX = 10
 
 
+def _fill_tiff_frame(f, width, height, photometric, bits, samples, tile, planar, predictor, big_endian, premultiply, palette):
+    """the fields of an ocr_tiff_frame but its data"""
+    f.width, f.height, f.photometric, f.bits_per_sample, f.samples_per_pixel = width, height, photometric, bits, samples
+    f.planar, f.predictor, f.big_endian, f.premultiply = planar, predictor, int(big_endian), premultiply
+    f.tile_width, f.tile_height = tile if tile else (width, height)
+    if palette is not None:
+        flat = np.ascontiguousarray(palette, np.uint8).reshape(-1)
+        C.memmove(f.palette, flat.ctypes.data, min(1024, len(flat)))
+
+
+def _tiff_expansion_alone(name, coded, device_id, fill, counts=False):
+    """ocr_tiff_expand / ocr_tiff_inflate / ocr_tiff_unfax of a TiffCoded or TiffFax: the chunks as tiff::parse fills Frame::data
+    (uint8 array, pre-filled with `fill`) - with counts (ocr_tiff_inflate): and the bytes each chunk's stream gave; OcrError
+    where the call refuses (err.out: the buffer as the call left it)"""
+    L = lib()
+    fn = getattr(L, name)
+    fn.argtypes = [C.POINTER(type(coded.c)), C.c_int, C.c_void_p, C.c_size_t] + ([C.c_void_p] if counts else [])
+    n = coded.nominal()
+    out = np.full(n if 0 < n <= 1 << 30 else 1, fill, np.uint8)
+    produced = np.zeros(max(1, len(coded.chunks)), np.uint32)
+    rc = fn(C.byref(coded.c), device_id, out.ctypes.data, out.size, *([produced.ctypes.data] if counts else []))
+    if rc != 0:
+        _raise(L, rc, out)
+    return (out, produced[:len(coded.chunks)]) if counts else out
+
+
 class TiffFrame:
     """an ocr_tiff_frame over Python-owned memory.  chunks: the expanded chunks at their nominal size (bytes or uint8 array);
     tile: (width, height) of a chunk, None for one strip; palette: (n, 4) B,G,R,x or None.  Fields of .c may be changed before
@@ -1220,12 +1246,7 @@ class TiffFrame:
     def __init__(self, width, height, photometric, bits, samples, chunks, tile=None, planar=1, predictor=1, big_endian=0, premultiply=0, palette=None):
         self._data = np.frombuffer(bytes(chunks), np.uint8).copy() if not isinstance(chunks, np.ndarray) else np.ascontiguousarray(chunks, np.uint8).reshape(-1).copy()
         c = ocr_tiff_frame()
-        c.width, c.height, c.photometric, c.bits_per_sample, c.samples_per_pixel = width, height, photometric, bits, samples
-        c.planar, c.predictor, c.big_endian, c.premultiply = planar, predictor, int(big_endian), premultiply
-        c.tile_width, c.tile_height = tile if tile else (width, height)
-        if palette is not None:
-            flat = np.ascontiguousarray(palette, np.uint8).reshape(-1)
-            C.memmove(c.palette, flat.ctypes.data, min(1024, len(flat)))
+        _fill_tiff_frame(c, width, height, photometric, bits, samples, tile, planar, predictor, big_endian, premultiply, palette)
         c.data, c.data_len = self._data.ctypes.data, len(self._data)
         self.c = c
 
@@ -1253,14 +1274,8 @@ class TiffCoded:
         self.chunks = np.array(chunks, TIFF_CHUNK).reshape(-1)
         self.data = np.frombuffer(bytes(data), np.uint8).copy() if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8).reshape(-1).copy()
         c = ocr_tiff_coded()
-        f = c.frame
-        f.width, f.height, f.photometric, f.bits_per_sample, f.samples_per_pixel = width, height, photometric, bits, samples
-        f.planar, f.predictor, f.big_endian, f.premultiply = planar, predictor, int(big_endian), premultiply
-        f.tile_width, f.tile_height = tile if tile else (width, height)
-        if palette is not None:
-            flat = np.ascontiguousarray(palette, np.uint8).reshape(-1)
-            C.memmove(f.palette, flat.ctypes.data, min(1024, len(flat)))
-        f.data, f.data_len = None, 0
+        _fill_tiff_frame(c.frame, width, height, photometric, bits, samples, tile, planar, predictor, big_endian, premultiply, palette)
+        c.frame.data, c.frame.data_len = None, 0
         c.compression = compression
         c.chunks, c.chunks_len = self.chunks.ctypes.data if len(self.chunks) else None, len(self.chunks)
         c.bytes, c.bytes_len = self.data.ctypes.data if len(self.data) else None, len(self.data)
@@ -1277,14 +1292,7 @@ class TiffCoded:
 
     def expand(self, device_id=0, fill=0):
         """ocr_tiff_expand: the chunks as tiff::parse fills Frame::data (uint8 array); OcrError where the call refuses"""
-        L = lib()
-        L.ocr_tiff_expand.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_void_p, C.c_size_t]
-        n = self.nominal()
-        out = np.full(n if 0 < n <= 1 << 30 else 1, fill, np.uint8)
-        rc = L.ocr_tiff_expand(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            _raise(L, rc, out)
-        return out
+        return _tiff_expansion_alone("ocr_tiff_expand", self, device_id, fill)
 
     def decode(self, device_id=0, fill=0):
         """ocr_tiff_decode_coded: the (height, width, 3) BGR image; OcrError where the call refuses (err.out: the buffer as the
@@ -1299,15 +1307,7 @@ class TiffCoded:
     def inflate(self, device_id=0, fill=0):
         """ocr_tiff_inflate: (the chunks as tiff::parse fills Frame::data, the bytes each chunk's stream gave); OcrError where
         the call refuses (err.out: the buffer as the call left it, pre-filled with `fill`)"""
-        L = lib()
-        L.ocr_tiff_inflate.argtypes = [C.POINTER(ocr_tiff_coded), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        n = self.nominal()
-        out = np.full(n if 0 < n <= 1 << 30 else 1, fill, np.uint8)
-        produced = np.zeros(max(1, len(self.chunks)), np.uint32)
-        rc = L.ocr_tiff_inflate(C.byref(self.c), device_id, out.ctypes.data, out.size, produced.ctypes.data)
-        if rc != 0:
-            _raise(L, rc, out)
-        return out, produced[:len(self.chunks)]
+        return _tiff_expansion_alone("ocr_tiff_inflate", self, device_id, fill, counts=True)
 
     def decode_deflate(self, device_id=0, fill=0):
         """ocr_tiff_decode_deflate: the (height, width, 3) BGR image; OcrError where the call refuses (err.out as for decode)"""
@@ -1369,14 +1369,7 @@ class TiffFax:
     def unfax(self, device_id=0, fill=0):
         """ocr_tiff_unfax: the chunks as tiff::parse fills Frame::data (uint8 array, pre-filled with `fill`); OcrError where the
         call refuses (err.out: the buffer as the call left it)"""
-        L = lib()
-        L.ocr_tiff_unfax.argtypes = [C.POINTER(ocr_tiff_fax), C.c_int, C.c_void_p, C.c_size_t]
-        n = self.nominal()
-        out = np.full(n if 0 < n <= 1 << 30 else 1, fill, np.uint8)
-        rc = L.ocr_tiff_unfax(C.byref(self.c), device_id, out.ctypes.data, out.size)
-        if rc != 0:
-            _raise(L, rc, out)
-        return out
+        return _tiff_expansion_alone("ocr_tiff_unfax", self, device_id, fill)
 
     def decode(self, device_id=0, fill=0):
         """ocr_tiff_decode_fax: the (height, width, 3) BGR image; OcrError where the call refuses (err.out as for unfax)"""

@@ -58,14 +58,12 @@ static int decode(const void* const* frames, int count, uint8_t* const* dst, Fra
 inline int j2k_coded_decode(const void* const* frames, int count, uint8_t* const* dst, FrameScratch& sc, hipStream_t s, std::string& err, const int*) {
   return j2k_coded_decode_async((const ocr_j2k_coded* const*)frames, count, dst, sc.j2k_coded, s, err);
 }
-inline int tiff_coded_decode(const void* const* frames, int count, uint8_t* const* dst, FrameScratch& sc, hipStream_t s, std::string& err, const int*) {
-  return tiff_coded_decode_async((const ocr_tiff_coded* const*)frames, count, dst, sc.tiff_coded, s, err);
-}
-inline int tiff_deflate_decode(const void* const* frames, int count, uint8_t* const* dst, FrameScratch& sc, hipStream_t s, std::string& err, const int* ids) {
-  return tiff_deflate_decode_async((const ocr_tiff_coded* const*)frames, count, dst, sc.tiff_deflate, s, err, nullptr, true, nullptr, ids);
-}
-inline int tiff_fax_decode(const void* const* frames, int count, uint8_t* const* dst, FrameScratch& sc, hipStream_t s, std::string& err, const int*) {
-  return tiff_fax_decode_async((const ocr_tiff_fax* const*)frames, count, dst, sc.tiff_fax, s, err);
+// the coded TIFF routes: one staging function over the route; ids reach the one route that names a frame in a refusal (Deflate)
+template <TiffRouteKind R>
+static const char* tiff_route_fault(const void* frame) { return tiff_coded_fault(R, *(const ocr_tiff_coded*)frame); }
+template <TiffRouteKind R, TiffScratch FrameScratch::*Sc>
+static int tiff_route_decode(const void* const* frames, int count, uint8_t* const* dst, FrameScratch& sc, hipStream_t s, std::string& err, const int* ids) {
+  return tiff_coded_decode_async(R, (const ocr_tiff_coded* const*)frames, count, dst, sc.*Sc, s, err, nullptr, true, nullptr, ids);
 }
 
 }  // namespace frame_kinds
@@ -87,9 +85,12 @@ inline const FrameKind kFrameKinds[] = {
     /* J2K */ {frame_kinds::fault<ocr_j2k_frame, j2k_frame_fault>, frame_kinds::size<ocr_j2k_frame>,
                frame_kinds::decode<ocr_j2k_frame, J2kScratch, J2kLaunch, j2k_decode_async, &FrameScratch::j2k>},
     /* J2K_CODED */ {frame_kinds::fault<ocr_j2k_coded, j2k_coded_fault>, frame_kinds::size<ocr_j2k_frame>, frame_kinds::j2k_coded_decode},
-    /* TIFF_CODED */ {frame_kinds::fault<ocr_tiff_coded, tiff_coded_fault>, frame_kinds::size<ocr_tiff_frame>, frame_kinds::tiff_coded_decode},
-    /* TIFF_DEFLATE */ {frame_kinds::fault<ocr_tiff_coded, tiff_deflate_fault>, frame_kinds::size<ocr_tiff_frame>, frame_kinds::tiff_deflate_decode},
-    /* TIFF_FAX */ {frame_kinds::fault<ocr_tiff_fax, tiff_fax_fault>, frame_kinds::size<ocr_tiff_frame>, frame_kinds::tiff_fax_decode},
+    /* TIFF_CODED */ {frame_kinds::tiff_route_fault<tiff_plan::kCoded>, frame_kinds::size<ocr_tiff_frame>,
+                      frame_kinds::tiff_route_decode<tiff_plan::kCoded, &FrameScratch::tiff_coded>},
+    /* TIFF_DEFLATE */ {frame_kinds::tiff_route_fault<tiff_plan::kDeflate>, frame_kinds::size<ocr_tiff_frame>,
+                        frame_kinds::tiff_route_decode<tiff_plan::kDeflate, &FrameScratch::tiff_deflate>},
+    /* TIFF_FAX */ {frame_kinds::tiff_route_fault<tiff_plan::kFax>, frame_kinds::size<ocr_tiff_frame>,
+                    frame_kinds::tiff_route_decode<tiff_plan::kFax, &FrameScratch::tiff_fax>},
 };
 constexpr int kFrameKindCount = (int)(sizeof kFrameKinds / sizeof kFrameKinds[0]);
 static_assert(kFrameKindCount == OCR_FRAME_TIFF_FAX + 1 && OCR_FRAME_TIFF_DEFLATE == 9 && OCR_FRAME_JPEG == 0 && OCR_FRAME_PNG == 1 && OCR_FRAME_RAW == 2 && OCR_FRAME_TIFF == 3 &&

@@ -4,17 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tiff_desc.h"  // InflateDesc
+
 namespace ocr {
 
 constexpr int kInflateWave = 64;  // a stream belongs to one wavefront, and a workgroup is one wavefront
-
-struct InflateDesc {   // a stream of the batch; nobody has looked at its bytes
-  uint64_t src;        // into the batch's byte pool
-  uint64_t dst;        // into the batch's output
-  uint32_t byte_len;   // coded bytes
-  uint32_t need;       // the bytes the stream must give: what is asked of it, and no more is written
-  uint32_t nominal;    // >= need: what is written, zeros behind what the stream gave
-};
 
 // One workgroup a stream, in the order of the list.  Reads pool[src .. src + byte_len) and writes out[dst .. dst + nominal) and
 // produced[i] per stream and nothing else, whatever the bytes are.  produced[i]: the bytes that came out before the first fault,

@@ -1,4 +1,5 @@
-// Expanded TIFF chunks -> device pixels for a batch of images (host side of kernels_tiff.hip).
+// Expanded TIFF chunks -> device pixels for a batch of images (host side of kernels_tiff.hip), and the coded routes in front
+// of it: what is arithmetic about a batch is tiff_plan.h, the device calls around it are capi_tiff.hip.
 #pragma once
 #include <string>
 #include <vector>
@@ -8,8 +9,11 @@
 #include "kernels_inflate.h"
 #include "kernels_tiff_fax.h"
 #include "kernels_tiff_lzw.h"
+#include "tiff_plan.h"
 
 namespace ocr {
+
+using TiffRouteKind = tiff_plan::Route;  // kCoded, kDeflate, kFax
 
 struct TiffScratch {
   DevBuf<uint8_t> data;
@@ -20,21 +24,15 @@ struct TiffScratch {
   PinnedStage counts;  // the same on the host, pinned: the read-back is then a plain asynchronous copy
   const uint32_t* produced_host() const { return (const uint32_t*)counts.p; }
 };
-// what a batch launched, for a caller that repeats it (ocr_tiff_time): id[first[k]] .. + count[k] are the frames of kind k
-struct TiffLaunch {
-  int first[kTiffKinds] = {}, count[kTiffKinds] = {};
-  unsigned long long units[kTiffKinds] = {};
+// what a batch launched, for a caller that repeats it (ocr_tiff_time): the frames of each kind (tiff_plan::Kinds)
+struct TiffLaunch : tiff_plan::Kinds {
   size_t bytes = 0;  // of the upload
-  // a coded batch: what the expansion launches over (device)
-  const TiffChunkDesc* chunks = nullptr;
-  uint32_t lzw = 0, runs = 0;
+  // a coded batch: what its route's expansion launches over (device) - records of the route's type, the first `lzw` of a
+  // kCoded batch its LZW chunks
+  TiffRouteKind route = tiff_plan::kCoded;
+  const void* records = nullptr;
+  uint32_t nrecords = 0, lzw = 0;
   const uint8_t* pool = nullptr;
-  // a Deflate batch: the streams the inflate launch goes over (device), instead of chunks / lzw / runs
-  const InflateDesc* streams = nullptr;
-  uint32_t nstreams = 0;
-  // a fax batch: the chunks the fax expansion goes over (device), instead of either
-  const TiffFaxDesc* fax = nullptr;
-  uint32_t nfax = 0;
 };
 // why a frame is refused, nullptr when it is sound: a kernel only ever sees descriptors that passed
 const char* tiff_frame_fault(const ocr_tiff_frame& f);
@@ -43,32 +41,22 @@ const char* tiff_frame_fault(const ocr_tiff_frame& f);
 int tiff_decode_async(const ocr_tiff_frame* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
                       TiffLaunch* launched = nullptr);
 void tiff_relaunch(const TiffScratch& sc, const TiffLaunch& L, hipStream_t s);
-// The same for coded frames (ocr_tiff_coded): chunk records and bytes are uploaded, the expansion fills the chunks in device
-// scratch (tiff_expand_relaunch), then the pixel kernels run (tiff_relaunch) - all on `s`.  `pixels` false: the expansion
-// alone, dst unused; frame i's chunks then lie in sc.data in the order of the batch, each frame padded to 256 bytes.
-const char* tiff_coded_fault(const ocr_tiff_coded& c);
-int tiff_coded_decode_async(const ocr_tiff_coded* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
-                            TiffLaunch* launched = nullptr, bool pixels = true);
-void tiff_expand_relaunch(const TiffScratch& sc, const TiffLaunch& L, hipStream_t s);
-// Deflate frames (ocr_tiff_coded with compression 8 or 32946).  tiff_deflate_fault checks the frame and the chunk records - the
-// rules of a coded frame with that compression set and the same device bounds - and looks at no stream: the inflate kernel gives
-// a verdict per chunk.  tiff_deflate_decode_async, all on `s`: uploads the records and the pool, runs the inflate launch into
-// sc.data, copies the per-chunk counts back and WAITS for that copy (4 bytes a chunk: the one host round trip of this route),
-// and launches the pixel kernels only where every chunk gave the bytes its rows need; otherwise OCR_ERR_ARG "deflate: a
-// chunk's stream does not hold the bytes its rows need (frame F, chunk C)" - F is ids[i] where ids is given, else i - and no
-// pixel kernel is launched for the batch.  `pixels` false: the inflate launch and the read-back alone, no refusal; produced:
-// count pointers (or null), each to chunks_len words in the frame's chunk order.
-const char* tiff_deflate_fault(const ocr_tiff_coded& c);
-int tiff_deflate_decode_async(const ocr_tiff_coded* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
-                              TiffLaunch* launched = nullptr, bool pixels = true, uint32_t* const* produced = nullptr, const int* ids = nullptr);
-// Fax frames (ocr_tiff_fax: Compression 2, 3, 4, 32771).  tiff_fax_fault: the frame, what the coding asks of it, the records,
-// the walk of every stream (tiff::fax_fault_of), the device bounds and the widest chunk (kTiffFaxMaxWidth).
-// tiff_fax_decode_async as tiff_coded_decode_async, with the fax expansion (tiff_fax_relaunch) in the expansion's place.
-const char* tiff_fax_fault(const ocr_tiff_fax& c);
-int tiff_fax_decode_async(const ocr_tiff_fax* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s, std::string& err,
-                          TiffLaunch* launched = nullptr, bool pixels = true);
-void tiff_fax_relaunch(const TiffScratch& sc, const TiffLaunch& L, hipStream_t s);
-// the inflate launch and its read-back again (ocr_tiff_time_deflate)
-int tiff_inflate_relaunch(TiffScratch& sc, const TiffLaunch& L, hipStream_t s);  // (after a tiff_deflate_decode_async of the batch)
+// why a coded frame of `route` is refused (tiff_plan::coded_fault), nullptr when it is sound
+const char* tiff_coded_fault(TiffRouteKind route, const ocr_tiff_coded& c);
+// The same for the coded frames of a route (a kFax batch: each the first member of an ocr_tiff_fax): tiff_plan::coded_fault
+// per frame, then chunk records and bytes are uploaded, the route's expansion fills the chunks in device scratch
+// (tiff_middle_relaunch), then the pixel kernels run (tiff_relaunch) - all on `s`.  `pixels` false: the expansion alone, dst
+// unused; frame i's chunks then lie in sc.data in the order of the batch, each frame padded to 256 bytes.
+// kDeflate looks at no stream on the host: after the inflate launch it copies the per-chunk counts back and WAITS for that copy
+// (4 bytes a chunk: the one host round trip of the coded routes), and launches the pixel kernels only where every chunk gave
+// the bytes its rows need; otherwise OCR_ERR_ARG "deflate: a chunk's stream does not hold the bytes its rows need (frame F,
+// chunk C)" - F is ids[i] where ids is given, else i - and no pixel kernel is launched for the batch.  `pixels` false: no
+// refusal.  produced (kDeflate): count pointers (or null), each to chunks_len words in the frame's chunk order.
+int tiff_coded_decode_async(TiffRouteKind route, const ocr_tiff_coded* const* imgs, int count, uint8_t* const* dst, TiffScratch& sc, hipStream_t s,
+                            std::string& err, TiffLaunch* launched = nullptr, bool pixels = true, uint32_t* const* produced = nullptr,
+                            const int* ids = nullptr);
+// what runs between upload and pixel stage, again (after a tiff_coded_decode_async of the batch): the expansion of L.route;
+// kDeflate: with the read-back of its counts, which it waits for
+hipError_t tiff_middle_relaunch(TiffScratch& sc, const TiffLaunch& L, hipStream_t s);
 
 }  // namespace ocr

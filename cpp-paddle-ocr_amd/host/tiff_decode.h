@@ -435,17 +435,23 @@ inline bool parse_head(const uint8_t* d, size_t n, Frame& f, Head& hd) {
   return true;
 }
 
-inline const char* structure_fault(const Frame& f, int compression, const Chunk* chunks, size_t nchunks, size_t pool, Geometry& g, bool deflate = false) {
-  if (const char* why = fault(f, g)) return why;
-  if (deflate) {
-    if (compression != 8 && compression != 32946) return "deflate: compression must be 8 or 32946 (Deflate)";
-  } else if (compression != 1 && compression != 5 && compression != 32773) return "coded: compression must be 1 (none), 5 (LZW) or 32773 (PackBits)";
+// the chunk records of a frame whose geometry is g: as many as the geometry has chunks, each with rows the chunk can hold and
+// bytes inside the pool
+inline const char* records_fault(const Frame& f, const Geometry& g, const Chunk* chunks, size_t nchunks, size_t pool) {
   if (nchunks != (size_t)g.across * g.down * g.planes || (nchunks && !chunks)) return "coded: as many chunk records as the geometry has chunks";
   for (size_t c = 0; c < nchunks; ++c) {
     if (chunks[c].rows < 1 || chunks[c].rows > (uint32_t)f.tile_height) return "coded: a chunk's rows must be 1 .. tile_height";
     if (chunks[c].byte_off > pool || pool - chunks[c].byte_off < chunks[c].byte_len) return "coded: a chunk's bytes lie outside the pool";
   }
   return nullptr;
+}
+
+inline const char* structure_fault(const Frame& f, int compression, const Chunk* chunks, size_t nchunks, size_t pool, Geometry& g, bool deflate = false) {
+  if (const char* why = fault(f, g)) return why;
+  if (deflate) {
+    if (compression != 8 && compression != 32946) return "deflate: compression must be 8 or 32946 (Deflate)";
+  } else if (compression != 1 && compression != 5 && compression != 32773) return "coded: compression must be 1 (none), 5 (LZW) or 32773 (PackBits)";
+  return records_fault(f, g, chunks, nchunks, pool);
 }
 
 }  // namespace detail
@@ -534,12 +540,7 @@ inline const char* fax_structure_fault(const Frame& f, int compression, uint32_t
   if (f.predictor != 1) return "fax: CCITT coding takes no predictor";
   if (t4 & 2) return ccitt::kUncompressed;
   if ((t4 & ~7u) || (compression != 3 && t4)) return "fax: T4Options has bits beyond 0 .. 2, or belongs to another coding than Compression 3";
-  if (nchunks != (size_t)g.across * g.down * g.planes || (nchunks && !chunks)) return "coded: as many chunk records as the geometry has chunks";
-  for (size_t c = 0; c < nchunks; ++c) {
-    if (chunks[c].rows < 1 || chunks[c].rows > (uint32_t)f.tile_height) return "coded: a chunk's rows must be 1 .. tile_height";
-    if (chunks[c].byte_off > pool || pool - chunks[c].byte_off < chunks[c].byte_len) return "coded: a chunk's bytes lie outside the pool";
-  }
-  return nullptr;
+  return detail::records_fault(f, g, chunks, nchunks, pool);
 }
 inline const char* fax_fault_of(const Frame& f, int compression, uint32_t t4, const Chunk* chunks, size_t nchunks, const uint8_t* bytes, size_t pool, Geometry& g) {
   if (const char* why = fax_structure_fault(f, compression, t4, chunks, nchunks, pool, g)) return why;
